@@ -107,6 +107,10 @@ def parse():
     ap.add_argument("--steps", type=int, default=None,
                     help="timed steps (default: 200 x ~1 ms for the render workload, 100 for stress, 3 x 1.2 s for full)")
     ap.add_argument("--warmup", type=int, default=None)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32): the "
+                         "RGBA frames and, for render / stress, the decoded Gaussians; a fixed seeded sample of frames "
+                         "when the whole shard exceeds 64 MB")
     ap.add_argument("--frames", type=int, default=250, help="frames per GPU per step (shard size)")
     ap.add_argument("--gaussians", type=int, default=10000)
     ap.add_argument("--image", type=int, default=512)
@@ -130,7 +134,12 @@ def parse():
                          "full = configs[2]: synthetic audio tokens -> AudioTriplaneNet (autoregressive) -> SMPL-X "
                          "decoder -> LBS -> decode -> rasterize; stress = configs[4] per GPU: triplane 128^2 x 512 "
                          "channels, 50 000 Gaussians, 1024x1024, decode + LBS + rasterize (32 frames per step)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def renderer_config(args, device, with_decoder=False):
@@ -755,6 +764,8 @@ def run_full_workload(args, device, world, rank, dist):
     total = sum(s[0] for s in status)
     assert not any(s[1] for s in status), "rasterizer workspace overflowed inside the timed region"
     assert gather is None or not gather.overflowed(), "exchange wire buffer overflowed inside the timed region"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"rgba": rgba})
     result = {
         "metric": "rendered frames/sec @512x512, 10k Gaussians (audio -> Wav2Vec2 -> AudioTriplaneNet -> SMPL-X LBS -> "
                   "decode -> rasterize)",
@@ -866,6 +877,31 @@ def cpu_baseline_and_parity(renderer, cfg, tokens, smpl, cam, step_outputs, n_fr
     return base, parity
 
 
+DUMP_BUDGET_BYTES = 60 * 2 ** 20  # under the 64 MB cap with room for the .npy headers
+
+
+def dump_outputs(directory, arrays, seed=0):
+    """Write `arrays` ({name: tensor [F, ...]}, sharing the leading frame axis) as directory/<name>.npy in float32.
+    When they do not fit in DUMP_BUDGET_BYTES together, the same fixed seeded subset of frames (ascending) is written
+    for every array; when one frame alone does not fit, a fixed seeded sample of that frame's elements is."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    F = next(iter(arrays.values())).shape[0]
+    frame_bytes = sum(4 * a[0].numel() for a in arrays.values())
+    g = torch.Generator().manual_seed(seed)
+    keep = max(1, min(F, DUMP_BUDGET_BYTES // max(1, frame_bytes)))
+    frames = torch.randperm(F, generator=g)[:keep].sort().values
+    for name, a in arrays.items():
+        a = a.detach()[frames.to(a.device)].float()
+        if keep == 1 and frame_bytes > DUMP_BUDGET_BYTES:
+            flat = a.reshape(-1)
+            n = max(1, flat.numel() * DUMP_BUDGET_BYTES // frame_bytes)
+            idx = torch.randperm(flat.numel(), generator=g)[:n].sort().values
+            a = flat[idx.to(a.device)]
+        np.save(os.path.join(directory, f"{name}.npy"), a.cpu().numpy())
+
+
 def emit(result):
     """The one JSON line of the contract, on the process's original stdout."""
     os.write(JSON_FD, (json.dumps(result) + "\n").encode())
@@ -899,6 +935,7 @@ def main():
         else:
             dist.init_process_group(backend)
 
+    torch.manual_seed(0)  # module initialisers draw from the default generator: identical inputs in every run
     if args.steps is None:
         args.steps = {"render": 200, "stress": 100, "full": 3}[args.workload]
     if args.warmup is None:
@@ -1036,6 +1073,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MIN)
         exchange_ok = bool(t.item())
         assert exchange_ok, "the all-gathered clip does not match the frames the ranks rendered"
+    if args.dump_outputs and rank == 0:  # what the last timed step returned: frames + the Gaussians they were drawn from
+        g = renderer.unpack_gaussians(stages[0])
+        dump_outputs(args.dump_outputs, {"rgba": out[0], **{f"gaussians_{k}": g[k] for k in
+                                                             ("xyz", "rot", "scale", "opacity", "color")}})
 
     # blend-kernel time per step = sum over the step's frame groups (one launch each)
     blend_ms = sorted(sum(s.elapsed_ms(e) for s, e in step_events) for step_events in events)
