@@ -43,6 +43,14 @@ class RasterArgs(ctypes.Structure):
     ]
 
 
+class DecodeSource(ctypes.Structure):
+    _fields_ = [
+        ("resolution", ctypes.c_int32), ("num_verts", ctypes.c_int32),
+        ("proj", ctypes.c_void_p), ("vertices", ctypes.c_void_p), ("idx4", ctypes.c_void_p), ("transl", ctypes.c_void_p),
+        ("radius", ctypes.c_float), ("head_w_point", ctypes.c_void_p),
+    ]
+
+
 class BodyTables(ctypes.Structure):
     _fields_ = [
         ("num_verts", ctypes.c_int32), ("num_joints", ctypes.c_int32), ("num_coeffs", ctypes.c_int32),
@@ -86,6 +94,8 @@ SIGNATURES = {
     "amav_rasterize_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                          ctypes.c_int64]),
     "amav_rasterize_forward": (ctypes.c_int, [ctypes.POINTER(RasterArgs), ctypes.c_void_p]),
+    "amav_rasterize_decode_forward": (ctypes.c_int, [ctypes.POINTER(RasterArgs), ctypes.POINTER(DecodeSource),
+                                                     ctypes.c_void_p]),
     "amav_rasterize_status": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
                                              ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32),
                                              ctypes.c_void_p]),

@@ -34,6 +34,7 @@
 #include <cstdlib>
 
 #include "amav_common.h"
+#include "decode_quad.h"
 
 namespace amav {
 namespace raster {
@@ -134,6 +135,19 @@ struct Params {
     int stash;   // fused binning: the binning records of the frame also go to LDS (8 B each) for the key scatter
     int slices;  // few-frame shards: blocks per frame of slice_count_kernel / slice_scatter_kernel (bin_slices)
     Buffers buf;
+    // decoding binning block (bin_kernel<true, true, true>, amav_rasterize_decode_forward): the triplane decode inputs
+    // (amav_triplane_sample_decode_indexed's) and where the packed records go (= the means3d views' buffer)
+    struct {
+        const float4 *proj;     // [F][3][R*R][4]
+        const float *vertices;  // [F][V][3]
+        const int *idx4;        // [N][4]
+        const float *transl;    // [F][3] or NULL
+        const float4 *wpoint;   // [16][1]
+        float4 *out;            // [F][N][4]
+        float radius;
+        int R, V;
+        int rec_lds;  // byte offset of the record buffer in the block's LDS
+    } dec;
 };
 
 __device__ __forceinline__ const float *at(const amav_attr &a, int f, int i) {
@@ -406,7 +420,10 @@ __global__ __launch_bounds__(256) void preprocess_kernel(Params p) {
 // grid = F blocks of 1024 threads; dynamic LDS = (2*T + 48 + 3*8*(kBuckets+1)) ints: counts[T], cursor[T], classes, scratch[48]
 // kFused: the block also projects its frame's Gaussians (shards of >= kFusedMinFrames frames: every CU has a frame, and
 // the projection's memory traffic hides under the counting); otherwise preprocess_kernel has done that for all frames.
-template <bool kFused, bool kPacked>
+// kDecode (with kFused, kPacked and the stash): the block also DECODES its frame's Gaussians from the triplane (p.dec),
+// in the quad form of decode_quad.h on half of its waves while the other half projects, writes their packed records and
+// hands them to the projection through an LDS ring (+ 64 KiB at p.dec.rec_lds) instead of reading them back.
+template <bool kFused, bool kPacked, bool kDecode = false>
 __global__ __launch_bounds__(1024) void bin_kernel(Params p) {
     extern __shared__ int bin_lds[];
     int *counts = bin_lds;
@@ -425,6 +442,7 @@ __global__ __launch_bounds__(1024) void bin_kernel(Params p) {
 #endif
     AMAV_BIN_STAMP(0);
     for (int t = threadIdx.x; t < p.T; t += blockDim.x) counts[t] = 0;
+    if (kDecode && threadIdx.x < 4) scratch[40 + threadIdx.x] = 0;  // the decode ring's counters
     __syncthreads();
 
     // phase 1: count instances per tile (LDS atomics)
@@ -464,21 +482,115 @@ __global__ __launch_bounds__(1024) void bin_kernel(Params p) {
             if (p.stash && real)  // tile box (8 bits per bound) + depth bits: what the key scatter needs, without a reload
                 stash[i] = make_uint2((rd.x & 0xff) | ((rd.x >> 16) << 8) | ((rd.y & 0xff) << 16) | ((rd.y >> 16) << 24), rd.z);
             const size_t gi = real ? (size_t)f * p.N + i : (size_t)p.F * p.N + threadIdx.x;  // spare slots: carve()
-            p.buf.rectd[gi] = rd;
+            if (!kDecode) p.buf.rectd[gi] = rd;  // the decoding block always has the stash: nobody reads them
             float4 *dst = p.buf.geom + gi * 3;
             dst[0] = g[0], dst[1] = g[1], dst[2] = g[2];
         };
-        GaussRec a0 = load_gaussian<kPacked>(p, f, min((int)threadIdx.x, p.N - 1));
-        GaussRec a1 = load_gaussian<kPacked>(p, f, min((int)threadIdx.x + B, p.N - 1));
-        for (int base = 0; base < p.N; base += 2 * B) {  // block-uniform trip count
-            const int i = base + threadIdx.x;
-            GaussRec n0 = load_gaussian<kPacked>(p, f, min(i + 2 * B, p.N - 1));
-            GaussRec n1 = load_gaussian<kPacked>(p, f, min(i + 3 * B, p.N - 1));
-            project(a0, i);
-            project(a1, i + B);
-            pin(n0);
-            pin(n1);
-            a0 = n0, a1 = n1;
+        if (kDecode) {
+            // Wave-specialised: waves 0-7 DECODE (latency-bound: subdivision index -> posed vertex -> twelve tap
+            // gathers from the L2-resident projected planes), waves 8-15 PROJECT and count (VALU-bound), at the same
+            // time on the same SIMDs.  They meet in a two-slot LDS ring of 512 records per slot (quarter-major:
+            // conflict-free for the quads' writes and the projection lanes' four 16-byte reads), with LDS counters
+            // instead of block barriers (barriers kept all sixteen waves in one phase: 227 us for the launch, about the
+            // two separate kernels' sum).  The decoding waves issue no global store -- their gathers never wait for
+            // store acknowledgements -- and request the indices two groups and the vertices one group ahead.  The
+            // projecting waves store the packed record and the blend record.
+            constexpr int kRounds = 4, kSlot = kRounds * 128, kWaves = 8;
+            float4 *recs = reinterpret_cast<float4 *>(reinterpret_cast<char *>(bin_lds) + p.dec.rec_lds);  // [2][4][kSlot]
+            int *filled = scratch + 40, *drained = scratch + 42;  // per slot: waves done writing / reading it (monotonic)
+            const int N = p.N, groups = (N + kSlot - 1) / kSlot;
+            bool stuck = false;
+            // wave-uniform wait for an LDS counter; bounded, so that a broken hand-off reports instead of hanging
+            auto wait_ge = [&](int *c, int v) {
+                for (int n = 0; __hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < v; ++n) {
+                    if (n > (1 << 22)) {
+                        stuck = true;
+                        break;
+                    }
+                    __builtin_amdgcn_s_sleep(1);
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            };
+            auto signal = [&](int *c) {
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // this wave's LDS accesses of the slot are done
+                if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(c, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            };
+            if (threadIdx.x < kWaves * 64) {
+                const int q = threadIdx.x & 3, slot = threadIdx.x >> 2;  // 128 points per round
+                const int R = p.dec.R;
+                const float4 *pl0 = p.dec.proj + (size_t)f * 3 * R * R * 4 + q;
+                const float *vf = p.dec.vertices + (size_t)f * p.dec.V * 3;
+                const float4 wp[4] = {p.dec.wpoint[q * 4], p.dec.wpoint[q * 4 + 1], p.dec.wpoint[q * 4 + 2], p.dec.wpoint[q * 4 + 3]};
+                float tx = 0.f, ty = 0.f, tz = 0.f;
+                if (p.dec.transl && q == 0) tx = p.dec.transl[f * 3], ty = p.dec.transl[f * 3 + 1], tz = p.dec.transl[f * 3 + 2];
+                // this lane's base vertex of point n (clamped: lanes past the end decode the last point, nobody stores it)
+                auto index_of = [&](int n) { return p.dec.idx4[(size_t)min(n, N - 1) * 4 + q]; };
+                int idx[kRounds];
+                float v[kRounds][3];
+#pragma unroll
+                for (int r = 0; r < kRounds; ++r) idx[r] = index_of(r * 128 + slot);
+#pragma unroll
+                for (int r = 0; r < kRounds; ++r) {
+                    const float *vp = vf + (size_t)idx[r] * 3;
+                    v[r][0] = vp[0], v[r][1] = vp[1], v[r][2] = vp[2];
+                }
+#pragma unroll
+                for (int r = 0; r < kRounds; ++r) idx[r] = index_of(kSlot + r * 128 + slot);
+                for (int k = 0; k < groups; ++k) {  // block-uniform trip count
+                    const int s = k & 1;
+                    float4 *ring = recs + s * 4 * kSlot + q * kSlot;
+                    wait_ge(&drained[s], kWaves * (k >> 1));  // the projection of group k - 2 has read the slot
+#pragma unroll
+                    for (int r = 0; r < kRounds; ++r) {
+                        float p0, p1, p2;
+                        decode::quad_point(v[r][0], v[r][1], v[r][2], p0, p1, p2);
+                        const decode::QuadTaps t = decode::quad_taps(p0, p1, p2, p.dec.radius, R, q);
+                        float4 tv[12];
+#pragma unroll
+                        for (int j = 0; j < 12; ++j) tv[j] = pl0[t.off[j]];
+                        ring[r * 128 + slot] = decode::quad_record(tv, t.w, wp, p0, p1, p2, tx, ty, tz, q);
+                    }
+                    signal(&filled[s]);
+#pragma unroll
+                    for (int r = 0; r < kRounds; ++r) {
+                        const float *vp = vf + (size_t)idx[r] * 3;
+                        v[r][0] = vp[0], v[r][1] = vp[1], v[r][2] = vp[2];
+                    }
+#pragma unroll
+                    for (int r = 0; r < kRounds; ++r) idx[r] = index_of((k + 2) * kSlot + r * 128 + slot);
+                }
+            } else {
+                const int j = threadIdx.x - kWaves * 64;
+                float4 *outf = p.dec.out + (size_t)f * N * 4;
+                for (int k = 0; k < groups; ++k) {
+                    const int s = k & 1;
+                    const float4 *ring = recs + s * 4 * kSlot + j;
+                    wait_ge(&filled[s], kWaves * ((k >> 1) + 1));  // the decode of group k has written the slot
+                    GaussRec rec;
+                    rec.r0 = ring[0], rec.r1 = ring[kSlot], rec.r2 = ring[2 * kSlot], rec.r3 = ring[3 * kSlot];
+                    signal(&drained[s]);
+                    const int i = k * kSlot + j;
+                    if (i < N) {
+                        float4 *o = outf + (size_t)i * 4;
+                        o[0] = rec.r0, o[1] = rec.r1, o[2] = rec.r2, o[3] = rec.r3;
+                    }
+                    project(rec, i);
+                }
+            }
+            if (stuck) atomicExch(&p.buf.status->overflow, 1);  // never expected: the caller sees a failed launch
+        } else {
+            GaussRec a0 = load_gaussian<kPacked>(p, f, min((int)threadIdx.x, p.N - 1));
+            GaussRec a1 = load_gaussian<kPacked>(p, f, min((int)threadIdx.x + B, p.N - 1));
+            for (int base = 0; base < p.N; base += 2 * B) {  // block-uniform trip count
+                const int i = base + threadIdx.x;
+                GaussRec n0 = load_gaussian<kPacked>(p, f, min(i + 2 * B, p.N - 1));
+                GaussRec n1 = load_gaussian<kPacked>(p, f, min(i + 3 * B, p.N - 1));
+                project(a0, i);
+                project(a1, i + B);
+                pin(n0);
+                pin(n1);
+                a0 = n0, a1 = n1;
+            }
         }
         int upstream_total;
         block_exclusive_scan(upstream, scratch, &upstream_total);
@@ -1851,7 +1963,9 @@ extern "C" size_t amav_rasterize_workspace_bytes(int F, int N, int H, int W, int
     return bytes;
 }
 
-extern "C" int amav_rasterize_forward(const amav_raster_args *a, void *stream_) {
+// amav_rasterize_forward, and with d != NULL amav_rasterize_decode_forward (the packed records are decoded first: inside
+// the binning block where it can, else by amav_triplane_sample_decode_indexed's launch ahead of the usual sequence)
+static int rasterize_forward(const amav_raster_args *a, const amav_decode_source *d, void *stream_) {
     AMAV_REQUIRE(a != nullptr, "amav_rasterize_forward: args is NULL");
     AMAV_REQUIRE(a->num_frames > 0 && a->num_gaussians > 0 && a->height > 0 && a->width > 0,
                  "amav_rasterize_forward: bad sizes F=%d N=%d H=%d W=%d", a->num_frames, a->num_gaussians, a->height,
@@ -1874,10 +1988,14 @@ extern "C" int amav_rasterize_forward(const amav_raster_args *a, void *stream_) 
     // fused binning: room in LDS for the frame's binning records (8 B each), tile bounds in 8 bits, no radii output
     // (the scatter pass writes those from the full records)
     const bool stash = bin_lds + 8 + (size_t)N * 8 <= 160 * 1024 && gx <= 255 && gy <= 255 && a->out_radii == nullptr;
+    // decoding binning block: + 64 KiB of LDS behind the stash for the decode ring (2 slots x 512 records)
+    const size_t rec_lds = align_up(bin_lds + (size_t)N * 8, 16);
+    const bool fits_decode = stash && rec_lds + 1024 * 64 <= 160 * 1024;
     const long long cap_per_frame = a->instance_capacity / F;
     AMAV_REQUIRE(cap_per_frame < (1ll << 31), "amav_rasterize_forward: per-frame instance capacity overflows int32");
     size_t need = 0;
     Params p;
+    p.dec = {};
     p.buf = carve(a->workspace, F, N, gx, gy, cap_per_frame * F, &need);
     if (a->workspace_bytes < need)
         return fail(AMAV_ERR_WORKSPACE, "amav_rasterize_forward: workspace %zu < required %zu", a->workspace_bytes, need);
@@ -1917,13 +2035,15 @@ extern "C" int amav_rasterize_forward(const amav_raster_args *a, void *stream_) 
     }
 
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    static const hipError_t attr[5] = {
+    static const hipError_t attr[6] = {
         hipFuncSetAttribute(reinterpret_cast<const void *>(&slice_count_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
         hipFuncSetAttribute(reinterpret_cast<const void *>(&slice_scatter_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
         hipFuncSetAttribute(reinterpret_cast<const void *>(&bin_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
         hipFuncSetAttribute(reinterpret_cast<const void *>(&bin_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&bin_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)};
-    if (attr[0] != hipSuccess || attr[1] != hipSuccess || attr[2] != hipSuccess || attr[3] != hipSuccess || attr[4] != hipSuccess)
+        hipFuncSetAttribute(reinterpret_cast<const void *>(&bin_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
+        hipFuncSetAttribute(reinterpret_cast<const void *>(&bin_kernel<true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)};
+    if (attr[0] != hipSuccess || attr[1] != hipSuccess || attr[2] != hipSuccess || attr[3] != hipSuccess || attr[4] != hipSuccess ||
+        attr[5] != hipSuccess)
         return fail(AMAV_ERR_LAUNCH, "amav_rasterize_forward: cannot raise the dynamic LDS limit");
     // packed-record fast path: the attributes are the xyz|opacity|rot|scale|color views of one [.., 16] buffer
     const float *b0 = a->means3d.ptr;
@@ -1935,6 +2055,35 @@ extern "C" int amav_rasterize_forward(const amav_raster_args *a, void *stream_) 
                         a->rotations.frame_stride == a->means3d.frame_stride &&
                         a->scales.frame_stride == a->means3d.frame_stride &&
                         a->colors.frame_stride == a->means3d.frame_stride;
+    // decode source: the attributes must be the packed views of one contiguous [F, N, 16] buffer, the decode's output
+    const bool decode_fused = d && F >= kFusedMinFrames && fits_decode;
+    if (d) {
+        AMAV_REQUIRE(packed && a->means3d.frame_stride == (int64_t)N * 16,
+                     "amav_rasterize_decode_forward: the Gaussian attributes must view one contiguous packed [F, N, 16] buffer");
+        AMAV_REQUIRE(d->resolution > 0 && d->num_verts > 0 && d->radius > 0.0f,
+                     "amav_rasterize_decode_forward: bad decode source (R=%d V=%d radius=%g)", d->resolution, d->num_verts,
+                     (double)d->radius);
+        AMAV_REQUIRE(d->proj && d->vertices && d->idx4 && d->head_w_point,
+                     "amav_rasterize_decode_forward: NULL decode input");
+        AMAV_REQUIRE(((reinterpret_cast<uintptr_t>(d->proj) | reinterpret_cast<uintptr_t>(d->idx4) |
+                       reinterpret_cast<uintptr_t>(d->head_w_point)) & 15) == 0,
+                     "amav_rasterize_decode_forward: proj/idx4/head_w_point not 16-B aligned");
+        p.dec.proj = reinterpret_cast<const float4 *>(d->proj);
+        p.dec.vertices = d->vertices;
+        p.dec.idx4 = d->idx4;
+        p.dec.transl = d->transl;
+        p.dec.wpoint = reinterpret_cast<const float4 *>(d->head_w_point);
+        p.dec.out = reinterpret_cast<float4 *>(const_cast<float *>(b0));
+        p.dec.radius = d->radius;
+        p.dec.R = d->resolution, p.dec.V = d->num_verts;
+        p.dec.rec_lds = (int)rec_lds;
+        if (!decode_fused) {  // the two launches: decode, then the rasterizer as amav_rasterize_forward runs it
+            const int rc = amav_triplane_sample_decode_indexed(F, N, d->resolution, d->num_verts, d->proj, d->vertices,
+                                                               d->idx4, d->transl, d->radius, d->head_w_point,
+                                                               const_cast<float *>(b0), stream);
+            if (rc != AMAV_OK) return rc;
+        }
+    }
     if (zero_async(p.buf.status, sizeof(Status), stream) != hipSuccess)
         return fail(AMAV_ERR_LAUNCH, "amav_rasterize_forward: status clear failed");
     if (p.wire_header && zero_async(p.wire_header, (size_t)kWireHeaderInts * 4, stream) != hipSuccess)
@@ -1954,7 +2103,9 @@ extern "C" int amav_rasterize_forward(const amav_raster_args *a, void *stream_) 
         slice_count_kernel<<<slice_grid, 1024, (size_t)T * sizeof(int), stream>>>(p);
         bin_kernel<false, false><<<F, 1024, bin_lds, stream>>>(p);
         slice_scatter_kernel<<<slice_grid, 1024, (size_t)T * sizeof(int), stream>>>(p);
-    } else if (packed)
+    } else if (decode_fused)
+        bin_kernel<true, true, true><<<F, 1024, rec_lds + 1024 * 64, stream>>>(p);
+    else if (packed)
         bin_kernel<true, true><<<F, 1024, bin_lds + (stash ? 8 + (size_t)N * 8 : 0), stream>>>(p);
     else
         bin_kernel<true, false><<<F, 1024, bin_lds + (stash ? 8 + (size_t)N * 8 : 0), stream>>>(p);
@@ -1968,6 +2119,13 @@ extern "C" int amav_rasterize_forward(const amav_raster_args *a, void *stream_) 
         render_kernel<false><<<blocks, 64, 0, stream>>>(p);
     if (a->profile_stop_event) (void)hipEventRecord(static_cast<hipEvent_t>(a->profile_stop_event), stream);
     return check_launch("amav_rasterize_forward");
+}
+
+extern "C" int amav_rasterize_forward(const amav_raster_args *a, void *stream) { return rasterize_forward(a, nullptr, stream); }
+
+extern "C" int amav_rasterize_decode_forward(const amav_raster_args *a, const amav_decode_source *d, void *stream) {
+    AMAV_REQUIRE(d != nullptr, "amav_rasterize_decode_forward: decode source is NULL");
+    return rasterize_forward(a, d, stream);
 }
 
 namespace amav {

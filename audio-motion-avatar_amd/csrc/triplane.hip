@@ -20,6 +20,7 @@
 #include <cstdlib>
 
 #include "amav_common.h"
+#include "decode_quad.h"
 
 namespace amav {
 namespace triplane {
@@ -181,20 +182,10 @@ __device__ __forceinline__ Taps make_taps(float gx, float gy, int R) {
     return t;
 }
 
-// Lane group of 4 per point; lane q owns projected channels 4q..4q+3:
+// Lane group of 4 per point; lane q owns projected channels 4q..4q+3 (decode_quad.h):
 //   q0 = (xyz_offset, opacity), q1 = rotation, q2 = (scaling, pad), q3 = (shs, pad)
 // kIndexed: the point is gathered from the posed vertices through the baked subdivision table (lbs.hip gather_kernel
 // fused in: 1/2 (1/2 (v[a0]+v[b0]) + 1/2 (v[a1]+v[b1])), the same operation order, so the same bits).
-template <int K>
-__device__ __forceinline__ float quad_bcast(float v) {  // value of lane K of this lane's quad
-    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), K * 0x55, 0xf, 0xf, true));
-}
-
-template <int K>
-__device__ __forceinline__ int quad_bcast_i(int v) {
-    return __builtin_amdgcn_mov_dpp(v, K * 0x55, 0xf, 0xf, true);
-}
-
 template <bool kIndexed>
 __global__ __launch_bounds__(256) void sample_decode_kernel(int F, int N, int R, int V,
                                                             const float *__restrict__ proj,
@@ -219,80 +210,23 @@ __global__ __launch_bounds__(256) void sample_decode_kernel(int F, int N, int R,
         const int4 id = idx4[n];
         const int mine = q == 0 ? id.x : (q == 1 ? id.y : (q == 2 ? id.z : id.w));
         const float *vp = points + ((size_t)f * V + mine) * 3;
-        const float v0 = vp[0], v1 = vp[1], v2 = vp[2];
-        p0 = ((quad_bcast<0>(v0) + quad_bcast<1>(v0)) * 0.5f + (quad_bcast<2>(v0) + quad_bcast<3>(v0)) * 0.5f) * 0.5f;
-        p1 = ((quad_bcast<0>(v1) + quad_bcast<1>(v1)) * 0.5f + (quad_bcast<2>(v1) + quad_bcast<3>(v1)) * 0.5f) * 0.5f;
-        p2 = ((quad_bcast<0>(v2) + quad_bcast<1>(v2)) * 0.5f + (quad_bcast<2>(v2) + quad_bcast<3>(v2)) * 0.5f) * 0.5f;
+        decode::quad_point(vp[0], vp[1], vp[2], p0, p1, p2);
     } else {
         const float *pp = points + ((size_t)f * N + n) * 3;
         p0 = pp[0], p1 = pp[1], p2 = pp[2];
     }
-    const float u0 = fminf(fmaxf(p0 / radius, -1.0f), 1.0f);  // IEEE division, as torch: the taps depend on it
-    const float u1 = fminf(fmaxf(p1 / radius, -1.0f), 1.0f);
-    const float u2 = fminf(fmaxf(p2 / radius, -1.0f), 1.0f);
-    const int RR = R * R;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    // The four lanes of a point need the same twelve taps.  Lane q < 3 works out plane q's four (texel, weight)
-    // pairs -- branch-free: an out-of-range texel (zero padding) is a clamped address with weight 0 -- and the quad
-    // trades them by DPP; then every lane issues its twelve 16-byte loads back to back.
-    // plane 0 <- (x, y), plane 1 <- (x, z), plane 2 <- (y, z); grid x indexes W, grid y indexes H
-    int my_off[4];
-    float my_w[4];
-    {
-        const Taps t = make_taps(q == 2 ? u1 : u0, q == 0 ? u1 : u2, R);
-#pragma unroll
-        for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-            for (int dx = 0; dx < 2; ++dx) {
-                const int ix = t.ix0 + dx, iy = t.iy0 + dy;
-                const bool in = ix >= 0 && ix < R && iy >= 0 && iy < R;
-                const int cx = min(max(ix, 0), R - 1), cy = min(max(iy, 0), R - 1);
-                my_w[dy * 2 + dx] = in ? (dx ? t.wx1 : t.wx0) * (dy ? t.wy1 : t.wy0) : 0.0f;
-                my_off[dy * 2 + dx] = (cy * R + cx) * 4;  // in float4 units
-            }
-    }
+    // The four lanes of a point need the same twelve taps: traded inside the quad, then every lane issues its twelve
+    // 16-byte loads back to back.
+    const decode::QuadTaps t = decode::quad_taps(p0, p1, p2, radius, R, q);
     float4 tv[12];
-    float tw[12];
-    const float4 *pl0 = reinterpret_cast<const float4 *>(proj + ((size_t)f * 3 * RR) * 16) + q;
+    const float4 *pl0 = reinterpret_cast<const float4 *>(proj + ((size_t)f * 3 * R * R) * 16) + q;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        tw[k] = quad_bcast<0>(my_w[k]), tw[4 + k] = quad_bcast<1>(my_w[k]), tw[8 + k] = quad_bcast<2>(my_w[k]);
-        tv[k] = pl0[quad_bcast_i<0>(my_off[k])];
-        tv[4 + k] = pl0[(size_t)RR * 4 + quad_bcast_i<1>(my_off[k])];
-        tv[8 + k] = pl0[(size_t)RR * 8 + quad_bcast_i<2>(my_off[k])];
-    }
-#pragma unroll
-    for (int k = 0; k < 12; ++k) {  // plane, then dy, then dx
-        const float w = tw[k];
-        const float4 v = tv[k];
-        acc.x += w * v.x, acc.y += w * v.y, acc.z += w * v.z, acc.w += w * v.w;
-    }
-    // + W_xyz p + bias  (wpoint [16][4]: 3 xyz weights, bias)
-    const float4 *wp = reinterpret_cast<const float4 *>(wpoint) + q * 4;
-    const float4 w0 = wp[0], w1 = wp[1], w2 = wp[2], w3 = wp[3];
-    acc.x += w0.x * p0 + w0.y * p1 + w0.z * p2 + w0.w;
-    acc.y += w1.x * p0 + w1.y * p1 + w1.z * p2 + w1.w;
-    acc.z += w2.x * p0 + w2.y * p1 + w2.z * p2 + w2.w;
-    acc.w += w3.x * p0 + w3.y * p1 + w3.z * p2 + w3.w;
-
-    float4 rec;
-    if (q == 0) {
-        float tx = 0.f, ty = 0.f, tz = 0.f;
-        if (transl) tx = transl[f * 3], ty = transl[f * 3 + 1], tz = transl[f * 3 + 2];
-        rec = make_float4(p0 + acc.x + tx, p1 + acc.y + ty, p2 + acc.z + tz, acc.w);
-    } else if (q == 1) {
-        // F.normalize(dim=-1): v / max(||v||, 1e-12).  Hardware sqrt / reciprocal (1 ulp): the four lane roles of a
-        // quad run one after the other, so the IEEE division and exp sequences were a third of the kernel's issue slots
-        const float nrm = fmaxf(__fsqrt_rn(acc.x * acc.x + acc.y * acc.y + acc.z * acc.z + acc.w * acc.w), 1e-12f);
-        const float inv = __frcp_rn(nrm);
-        rec = make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv);
-    } else if (q == 2) {
-        rec = make_float4(acc.x, acc.y, acc.z, 0.0f);
-    } else {
-        rec = make_float4(__frcp_rn(1.0f + __expf(-acc.x)), __frcp_rn(1.0f + __expf(-acc.y)),
-                          __frcp_rn(1.0f + __expf(-acc.z)), 0.0f);
-    }
-    reinterpret_cast<float4 *>(out)[((size_t)f * N + n) * 4 + q] = rec;
+    for (int k = 0; k < 12; ++k) tv[k] = pl0[t.off[k]];
+    const float4 *wq = reinterpret_cast<const float4 *>(wpoint) + q * 4;
+    const float4 wp[4] = {wq[0], wq[1], wq[2], wq[3]};
+    float tx = 0.f, ty = 0.f, tz = 0.f;
+    if (transl && q == 0) tx = transl[f * 3], ty = transl[f * 3 + 1], tz = transl[f * 3 + 2];
+    reinterpret_cast<float4 *>(out)[((size_t)f * N + n) * 4 + q] = decode::quad_record(tv, t.w, wp, p0, p1, p2, tx, ty, tz, q);
 }
 
 // Plain sample_from_triplane: grid (N, F), lanes along the 3C output channels (coalesced writes).

@@ -3,11 +3,12 @@
 Every function requires CUDA(HIP) float32 tensors and raises on anything else: there is no CPU path.
 """
 import ctypes
+import os
 
 import torch
 
 from . import _lib
-from ._lib import AmavError, Attr, BodyTables, PoseParts, RasterArgs, check
+from ._lib import AmavError, Attr, BodyTables, DecodeSource, PoseParts, RasterArgs, check
 
 SCALE_BIAS = 3.9    # src/models/renderer.py:428
 OPACITY_BIAS = 0.0  # src/models/renderer.py:429
@@ -149,10 +150,16 @@ def default_instance_capacity(num_frames, num_gaussians, per_gaussian=16):
     return int(num_frames) * int(num_gaussians) * per_gaussian
 
 
+def decode_bin_enabled():
+    """AMAV_DECODE_BIN (default 1): rasterize(decode=...) decodes inside the rasterizer's binning block where that
+    applies (amav_rasterize_decode_forward); 0 = the decode and the rasterizer as two launches."""
+    return os.environ.get("AMAV_DECODE_BIN", "1") != "0"
+
+
 def rasterize(means3d, rotations, scales, opacities, colors, viewmatrix, projmatrix, tanfov, height, width,
               bg=(1.0, 1.0, 1.0), apply_activations=False, scale_modifier=1.0, antialiasing=False, clamp_output=False,
               want_inv_depth=False, want_radii=False, workspace=None, check_overflow=True, out_rgba=None,
-              profile_events=None, wire=None):
+              profile_events=None, wire=None, decode=None, fuse_decode=None):
     """Batched tile rasterizer.  Gaussian attributes are [F,N,*] (frame stride 0 = shared across frames).
 
     Returns dict(rgba [F,H,W,4], inv_depth [F,H,W] | None, radii [F,N] | None, workspace).
@@ -161,6 +168,9 @@ def rasterize(means3d, rotations, scales, opacities, colors, viewmatrix, projmat
     `wire`: (uint8 buffer, capacity in tiles) -- the rasterizer also writes the frame exchange's tile-sparse wire buffer
     (include/amav.h, amav_raster_args.wire; needs clamp_output): what frames_pack_tiles would produce from these frames
     with the tile counts as hint, without the extra pass.
+    `decode`: a decode_source() whose `out` buffer the five attributes view.  The packed records are decoded into it
+    first: with fuse_decode (None = decode_bin_enabled()) by the rasterizer's own launch (amav_rasterize_decode_forward,
+    again on an overflow retry), else by triplane_sample_decode_indexed ahead of it.  Same records and frames either way.
     """
     a_m, means3d = _attr(means3d, "means3d", 3)
     a_r, rotations = _attr(rotations, "rotations", 4)
@@ -188,6 +198,16 @@ def rasterize(means3d, rotations, scales, opacities, colors, viewmatrix, projmat
         workspace = RasterWorkspace(F, N, H, W, default_instance_capacity(F, N), dev)
     elif workspace.key != (F, N, H, W):
         raise AmavError(f"workspace was sized for {workspace.key}, call is {(F, N, H, W)}")
+
+    fused = False
+    if decode is not None:
+        if means3d.data_ptr() != decode["out"].data_ptr():
+            raise AmavError("rasterize: with decode=..., the Gaussian attributes must be views of decode['out']")
+        fused = decode_bin_enabled() if fuse_decode is None else bool(fuse_decode)
+        if not fused:
+            d = decode
+            triplane_sample_decode_indexed(d["proj"], d["vertices"], d["idx4"], d["transl"], d["radius"],
+                                           d["head_w_point"], out=d["out"])
 
     def launch(ws):
         args = RasterArgs()
@@ -217,7 +237,11 @@ def rasterize(means3d, rotations, scales, opacities, colors, viewmatrix, projmat
             ev = PROFILE_EVENTS.pop(0)
         if ev is not None:
             args.profile_start_event, args.profile_stop_event = ev[0].handle, ev[1].handle
-        check(_lib.lib().amav_rasterize_forward(ctypes.byref(args), _stream()), "amav_rasterize_forward")
+        if fused:
+            check(_lib.lib().amav_rasterize_decode_forward(ctypes.byref(args), ctypes.byref(decode["struct"]), _stream()),
+                  "amav_rasterize_decode_forward")
+        else:
+            check(_lib.lib().amav_rasterize_forward(ctypes.byref(args), _stream()), "amav_rasterize_forward")
 
     launch(workspace)
     if check_overflow:
@@ -565,6 +589,29 @@ def triplane_sample_decode_indexed(proj, vertices, idx4, transl, radius, head_w_
                                                          float(radius), head_w_point.data_ptr(), out.data_ptr(),
                                                          _stream()), "amav_triplane_sample_decode_indexed")
     return out
+
+
+def decode_source(proj, vertices, idx4, transl, radius, head_w_point, out=None):
+    """The inputs of triplane_sample_decode_indexed, checked and held for rasterize(decode=...), which decodes them into
+    `out` (packed [F,N,16], allocated here if None) as part of the rasterizer's launch sequence."""
+    proj = _contig(proj, "proj")
+    vertices = _contig(vertices, "vertices")
+    idx4 = _contig(idx4, "idx4", torch.int32)
+    head_w_point = _contig(head_w_point, "head_w_point")
+    F, _, R, _, _ = proj.shape
+    if vertices.shape[0] != F:
+        raise AmavError(f"vertices has {vertices.shape[0]} frames, proj has {F}")
+    V, N = vertices.shape[1], idx4.shape[0]
+    if transl is not None:
+        transl = _contig(transl.reshape(F, 3), "transl")
+    out = _decode_out(out, F, N, proj.device)
+    st = DecodeSource()
+    st.resolution, st.num_verts = R, V
+    st.proj, st.vertices, st.idx4 = proj.data_ptr(), vertices.data_ptr(), idx4.data_ptr()
+    st.transl = transl.data_ptr() if transl is not None else None
+    st.radius, st.head_w_point = float(radius), head_w_point.data_ptr()
+    return dict(proj=proj, vertices=vertices, idx4=idx4, transl=transl, radius=float(radius), head_w_point=head_w_point,
+                out=out, struct=st)
 
 
 def triplane_sample_features(planes, points, radius):

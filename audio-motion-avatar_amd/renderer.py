@@ -187,7 +187,8 @@ class Renderer(nn.Module):
         proj = ops.triplane_project(triplane_tokens, w_plane, self._plane_resolution(triplane_tokens))
         return ops.triplane_sample_decode(proj, points, transl, self.cfg.radius, w_point)
 
-    def gaussians_from_tokens(self, triplane_tokens, smpl_params, out=None, side_work=None, window_plan=None):
+    def gaussians_from_tokens(self, triplane_tokens, smpl_params, out=None, side_work=None, window_plan=None,
+                              defer_decode=False):
         """renderer.py:127-181 as one fused stage: tokens [F,C,3R^2] + SMPL-X params -> packed Gaussians [F,N,16].
 
         Everything is enqueued on the calling stream: camera set-up (`side_work`, an optional callable whose result is
@@ -196,6 +197,9 @@ class Renderer(nn.Module):
         1.137 ms per 250-frame step -- and a fork/join graph only hid the hipMemsetAsync replay fault described in
         DESIGN.md section 1.)  `window_plan`: the windowed upsampler's plan for exactly these frames (mask [F,g,g] per
         plane); refined points that leave it raise _WindowTooSmall.
+        `defer_decode`: for the densified decode (no point refiner), do not launch the sampling kernel but return its
+        inputs (ops.decode_source, for ops.rasterize(decode=...)) as a last value; `packed` is filled by the rasterizer.
+        Other configurations decode here and return None in that place.
         """
         F = triplane_tokens.shape[0]
         w_plane, w_point = self._head_weights()
@@ -211,6 +215,7 @@ class Renderer(nn.Module):
             region = (ops.points_bbox(points_like), self.cfg.radius) if self.project_sampled_region else None
             return ops.triplane_project(triplane_tokens, w_plane, R, region=region)
 
+        source = None
         if hasattr(self, "point_encoder"):
             if self.cfg.densify_smplx_verts:
                 vertices = ops.points_gather(vertices, self._gather_idx)
@@ -219,15 +224,21 @@ class Renderer(nn.Module):
                     window_plan, points, self.cfg.triplane_resolution, self.cfg.radius):
                 raise _WindowTooSmall()
             packed = ops.triplane_sample_decode(project(points), points, transl, self.cfg.radius, w_point, out=out)
+        elif self.cfg.densify_smplx_verts and defer_decode:
+            source = ops.decode_source(project(vertices), vertices, self._gather_idx, transl, self.cfg.radius, w_point,
+                                       out=out)
+            packed = source["out"]
         elif self.cfg.densify_smplx_verts:
             packed = ops.triplane_sample_decode_indexed(project(vertices), vertices, self._gather_idx, transl,
                                                         self.cfg.radius, w_point, out=out)
         else:
             packed = ops.triplane_sample_decode(project(vertices), vertices, transl, self.cfg.radius, w_point, out=out)
+        if defer_decode:
+            return (packed, source) if side_work is None else (packed, side_result, source)
         return packed if side_work is None else (packed, side_result)
 
     def render_tokens(self, triplane_tokens, smpl_params, cam_params, chunks=1, workspaces=None, check_overflow=True,
-                      bg_color=None, window_plan=None, wire=None):
+                      bg_color=None, window_plan=None, wire=None, fuse_decode=None):
         """tokens [F,C,3R^2] + SMPL-X params [B,T,...] (B*T = F) + cameras -> (rgba [F,H,W,4], packed [F,N,16]).
 
         The body of forward() after the SMPL-X decoder.  With `chunks` > 1 the frames are split into that many
@@ -238,6 +249,9 @@ class Renderer(nn.Module):
         `window_plan`: see gaussians_from_tokens (covers all F frames; every frame group checks its own slice of it).
         `wire`: (uint8 buffer, capacity in tiles) -- the rasterizer writes the exchange's wire buffer of these F frames
         itself (ops.rasterize; dist.FrameAllGather.wire_target()); one frame group only.
+        `fuse_decode` (None = ops.decode_bin_enabled(), AMAV_DECODE_BIN): with one frame group and the densified decode,
+        the triplane decode runs inside the rasterizer's binning block (ops.rasterize(decode=...)); False = its own
+        launch.  Same records and frames either way.
         """
         F = triplane_tokens.shape[0]
         H, W = int(self.cfg.image_size[0]), int(self.cfg.image_size[1])
@@ -257,6 +271,7 @@ class Renderer(nn.Module):
         cur = torch.cuda.current_stream()
         while len(self._chunk_streams) < chunks - 1:
             self._chunk_streams.append(torch.cuda.Stream(device=dev))
+        fuse = chunks == 1 and (ops.decode_bin_enabled() if fuse_decode is None else bool(fuse_decode))
         used = []
         try:
             for ci, (s, e) in enumerate(bounds):
@@ -269,13 +284,15 @@ class Renderer(nn.Module):
                     Kc, Ec = K[s:e].float(), E[s:e].float()
                     plan = None if window_plan is None else [
                         dict(w, mask=None if w["mask"] is None else w["mask"][s:e]) for w in window_plan]
-                    packed, camera = self.gaussians_from_tokens(
+                    res = self.gaussians_from_tokens(
                         triplane_tokens[s:e], sub, out=packed_all[s:e],
-                        side_work=lambda: ops.camera_from_intrinsics(Kc, Ec, H, W), window_plan=plan)
+                        side_work=lambda: ops.camera_from_intrinsics(Kc, Ec, H, W), window_plan=plan, defer_decode=fuse)
+                    packed, camera, source = res if fuse else (*res, None)
                     g = self.unpack_gaussians(packed)
                     out = render_batch(g, K[s:e].unsqueeze(0), E[s:e].unsqueeze(0), self.cfg, bg_color,
                                        workspace=workspaces[ci], check_overflow=check_overflow, out_rgba=rgba[s:e],
-                                       return_workspace=True, camera=camera[:3], wire=wire)
+                                       return_workspace=True, camera=camera[:3], wire=wire, decode=source,
+                                       fuse_decode=fuse)
                     workspaces[ci] = out[1]
         finally:  # also on _WindowTooSmall from a later frame group: the side streams' work is joined before a re-render
             for st in used:
@@ -678,12 +695,15 @@ def render_multi_view(gaussians, K, E, args, bg_color=None, debug=False):
 
 
 def render_batch(gaussians, K, E, args, bg_color=None, debug=False, return_alpha=False, workspace=None,
-                 check_overflow=True, return_rgba=False, out_rgba=None, return_workspace=False, camera=None, wire=None):
+                 check_overflow=True, return_rgba=False, out_rgba=None, return_workspace=False, camera=None, wire=None,
+                 decode=None, fuse_decode=None):
     """renderer.py:447-479: gaussians dict [(B*T),N,*], K [B,T,3,3], E [B,T,4,4] -> images [B,T,H,W,3] in [0,1].
 
     One camera launch + one rasterizer launch sequence for all B*T frames.  The returned image is a view of the
     kernel's RGBA output ([..., :3]); `return_alpha=True` also returns alpha [B,T,H,W] (= 1 - final transmittance);
     `return_rgba=True` returns the contiguous [B,T,H,W,4] buffer itself.
+    `decode`, `fuse_decode`: ops.decode_source whose `out` the Gaussians view, decoded as part of the rasterizer's launch
+    sequence (ops.rasterize).
     """
     if not getattr(args, "rgb", True):
         raise NotImplementedError("args.rgb=False selects the reference's SH branch (renderer.py:540-545), which "
@@ -700,13 +720,16 @@ def render_batch(gaussians, K, E, args, bg_color=None, debug=False, return_alpha
         raise AmavError(f"render_batch: {xyz.shape[0]} Gaussian sets for B*T = {B * T} cameras")
     bg = [1.0, 1.0, 1.0] if bg_color is None else [float(c) for c in bg_color]
     activate = True
+    if debug and decode is not None:
+        raise AmavError("render_batch: debug replaces the attributes; decode the Gaussians first")
     if debug:  # renderer.py:535-537
         scale = torch.full_like(scale, 0.01)
         opacity = torch.full_like(opacity, 0.1)
         color = color.clamp(0.0, 1.0)
         activate = False
     out = ops.rasterize(xyz, rot, scale, opacity, color, view, proj, tanfov, H, W, bg=bg, apply_activations=activate,
-                        clamp_output=True, workspace=workspace, check_overflow=check_overflow, out_rgba=out_rgba, wire=wire)
+                        clamp_output=True, workspace=workspace, check_overflow=check_overflow, out_rgba=out_rgba, wire=wire,
+                        decode=decode, fuse_decode=fuse_decode)
     rgba = out["rgba"].view(B, T, H, W, 4)
     if return_workspace:
         return rgba, out["workspace"]

@@ -135,6 +135,24 @@ int amav_rasterize_forward(const amav_raster_args *args, void *stream);
 int amav_rasterize_status(const void *workspace, int64_t *total_instances, int64_t *max_frame_instances,
                           int32_t *overflow, void *stream);
 
+/* amav_triplane_sample_decode_indexed + amav_rasterize_forward in one call: the packed Gaussian records are decoded
+ * from the inputs below into the buffer the attributes of `args` view -- which must be the packed views
+ * (xyz|opacity|rot|scale|color at float offsets 0, 3, 4, 8, 12, element stride 16) of ONE contiguous [F,N,16] buffer,
+ * 16-B aligned -- and then rasterised.  Same records, frames, instance counts and workspace as the two calls.  For
+ * shards of many frames whose binning block keeps its records in LDS (no out_radii, images up to 255 x 255 tiles, N
+ * small enough) the decode runs inside the per-frame binning block and the records are not read back; otherwise the
+ * two launches are enqueued.  No allocation and no host synchronisation (HIP-graph capturable). */
+typedef struct amav_decode_source {
+    int32_t resolution, num_verts;  /* R of the projected planes, V of the posed vertices */
+    const float *proj;              /* [F,3,R,R,16] from amav_triplane_project(_region), 16-B aligned */
+    const float *vertices;          /* [F,V,3] posed vertices */
+    const int32_t *idx4;            /* [N,4] subdivision table, 16-B aligned */
+    const float *transl;            /* [F,3] or NULL */
+    float radius;
+    const float *head_w_point;      /* [16,4], 16-B aligned */
+} amav_decode_source;
+int amav_rasterize_decode_forward(const amav_raster_args *args, const amav_decode_source *src, void *stream);
+
 /* Rendered frames -> on-wire format of the multi-GPU exchange: fp32 RGBA [pixels,4] -> uint8 RGB [pixels,3] with the
  * reference's own quantisation (src/main2.py:351: (frame * 255).astype(uint8), truncating). num_pixels % 4 == 0. */
 int amav_frames_to_rgb8(int64_t num_pixels, const float *rgba_dev, uint8_t *out_rgb8_dev, void *stream);
