@@ -43,6 +43,15 @@ class RasterArgs(ctypes.Structure):
     ]
 
 
+class RasterBackwardArgs(ctypes.Structure):
+    _fields_ = [
+        ("grad_rgba", ctypes.c_void_p), ("grad_means3d", ctypes.c_void_p), ("grad_rotations", ctypes.c_void_p),
+        ("grad_scales", ctypes.c_void_p), ("grad_opacities", ctypes.c_void_p), ("grad_colors", ctypes.c_void_p),
+        ("max_frame_instances", ctypes.c_int64), ("scratch", ctypes.c_void_p), ("scratch_bytes", ctypes.c_size_t),
+        ("debug_alpha", ctypes.c_void_p),
+    ]
+
+
 class DecodeSource(ctypes.Structure):
     _fields_ = [
         ("resolution", ctypes.c_int32), ("num_verts", ctypes.c_int32),
@@ -99,6 +108,9 @@ SIGNATURES = {
     "amav_rasterize_status": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
                                              ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32),
                                              ctypes.c_void_p]),
+    "amav_rasterize_backward_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
+    "amav_rasterize_backward": (ctypes.c_int, [ctypes.POINTER(RasterArgs), ctypes.POINTER(RasterBackwardArgs),
+                                               ctypes.c_void_p]),
     "amav_frames_to_rgb8": (ctypes.c_int, [ctypes.c_int64, c_float_p, ctypes.c_void_p, ctypes.c_void_p]),
     "amav_add_layernorm": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int64, c_float_p, c_float_p, c_float_p,
                                           c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_float, c_float_p,

@@ -35,6 +35,7 @@
 
 #include "amav_common.h"
 #include "decode_quad.h"
+#include "raster_workspace.h"
 
 namespace amav {
 namespace raster {
@@ -2137,6 +2138,20 @@ __global__ __launch_bounds__(256) void tile_counts_kernel(int F, int T, const St
     const int f = i / T, t = i - f * T;
     const int *off = tile_off + (size_t)f * (T + 1);
     out[i] = st->overflow ? 1 : off[t + 1] - off[t];  // after an overflow nothing is known: every tile "may be drawn"
+}
+
+WorkspaceView workspace_view(void *workspace, int F, int N, int H, int W, long long instance_capacity) {
+    const int gx = (W + kTile - 1) / kTile, gy = (H + kTile - 1) / kTile;
+    const long long cap_per_frame = instance_capacity / F;
+    size_t bytes = 0;
+    const Buffers b = carve(workspace, F, N, gx, gy, cap_per_frame * F, &bytes);
+    WorkspaceView v;
+    v.geom = b.geom, v.rectd = b.rectd, v.tile_off = b.tile_off, v.keys = b.keys, v.sorted = b.sorted;
+    v.overflow = workspace ? &b.status->overflow : nullptr;
+    v.cap_per_frame = cap_per_frame;
+    v.sort_cap = kSortCap;
+    v.bytes = bytes;
+    return v;
 }
 }  // namespace raster
 }  // namespace amav

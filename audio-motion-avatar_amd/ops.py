@@ -8,7 +8,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import AmavError, Attr, BodyTables, DecodeSource, PoseParts, RasterArgs, check
+from ._lib import AmavError, Attr, BodyTables, DecodeSource, PoseParts, RasterArgs, RasterBackwardArgs, check
 
 SCALE_BIAS = 3.9    # src/models/renderer.py:428
 OPACITY_BIAS = 0.0  # src/models/renderer.py:429
@@ -252,7 +252,132 @@ def rasterize(means3d, rotations, scales, opacities, colors, viewmatrix, projmat
             total, max_frame, over = workspace.status_full()
             if over:
                 raise AmavError(f"rasterizer overflowed twice (instances={total}, fullest frame {max_frame})")
+        # the largest per-frame instance count: what rasterize_backward sizes its partial sums by
+        return dict(rgba=out_rgba, inv_depth=inv_depth, radii=radii, workspace=workspace, max_frame=max_frame)
     return dict(rgba=out_rgba, inv_depth=inv_depth, radii=radii, workspace=workspace)
+
+
+def rasterize_backward(means3d, rotations, scales, opacities, colors, viewmatrix, projmatrix, tanfov, height, width,
+                       grad_rgba, workspace, max_frame, bg=(1.0, 1.0, 1.0), apply_activations=False, scale_modifier=1.0,
+                       want_alpha=False):
+    """Gradients of the rasterizer (amav_rasterize_backward) for the LAST rasterize() on `workspace`, which must have run
+    on these inputs with clamp_output=False and check_overflow=True (`max_frame` = its result's "max_frame").
+
+    grad_rgba = dL/d rgba [F,H,W,4].  Returns dict(means3d, rotations, scales, opacities, colors): dense [F,N,width]
+    gradients (a frame-stride-0 input gets one row per frame), and with want_alpha the replay's 1 - T_final [F,H,W]
+    ("alpha"; bit-identical to the forward's alpha channel).  No host sync.
+    """
+    a_m, means3d = _attr(means3d, "means3d", 3)
+    a_r, rotations = _attr(rotations, "rotations", 4)
+    a_s, scales = _attr(scales, "scales", 3)
+    a_o, opacities = _attr(opacities, "opacities", 1)
+    a_c, colors = _attr(colors, "colors", 3)
+    F, N = means3d.shape[0], means3d.shape[1]
+    H, W = int(height), int(width)
+    if workspace.key != (F, N, H, W):
+        raise AmavError(f"workspace was sized for {workspace.key}, call is {(F, N, H, W)}")
+    viewmatrix = _contig(viewmatrix.reshape(F, 16), "viewmatrix")
+    projmatrix = _contig(projmatrix.reshape(F, 16), "projmatrix")
+    tanfov = _contig(tanfov.reshape(F, 2), "tanfov")
+    grad_rgba = _contig(grad_rgba, "grad_rgba")
+    if tuple(grad_rgba.shape) != (F, H, W, 4):
+        raise AmavError(f"grad_rgba must be [F,H,W,4] = {(F, H, W, 4)}, got {tuple(grad_rgba.shape)}")
+    dev = means3d.device
+    grads = {k: torch.empty(F, N, w, device=dev) for k, w in
+             (("means3d", 3), ("rotations", 4), ("scales", 3), ("opacities", 1), ("colors", 3))}
+    alpha = torch.empty(F, H, W, device=dev) if want_alpha else None
+    nbytes = _lib.lib().amav_rasterize_backward_bytes(F, N, int(max_frame))
+    if nbytes == 0:
+        raise AmavError(f"amav_rasterize_backward_bytes rejected F={F} N={N} max_frame={max_frame}")
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+    args = RasterArgs()
+    args.num_frames, args.num_gaussians, args.height, args.width = F, N, H, W
+    args.means3d, args.rotations, args.scales, args.opacities, args.colors = a_m, a_r, a_s, a_o, a_c
+    args.viewmatrix, args.projmatrix, args.tanfov = viewmatrix.data_ptr(), projmatrix.data_ptr(), tanfov.data_ptr()
+    args.bg = (ctypes.c_float * 3)(*[float(b) for b in bg])
+    args.scale_modifier = float(scale_modifier)
+    args.apply_activations = int(bool(apply_activations))
+    args.scale_bias, args.scale_max, args.opacity_bias = SCALE_BIAS, SCALE_MAX, OPACITY_BIAS
+    args.workspace, args.workspace_bytes = workspace.buffer.data_ptr(), workspace.buffer.numel()
+    args.instance_capacity = workspace.capacity
+    b = RasterBackwardArgs()
+    b.grad_rgba = grad_rgba.data_ptr()
+    b.grad_means3d, b.grad_rotations = grads["means3d"].data_ptr(), grads["rotations"].data_ptr()
+    b.grad_scales, b.grad_opacities = grads["scales"].data_ptr(), grads["opacities"].data_ptr()
+    b.grad_colors = grads["colors"].data_ptr()
+    b.max_frame_instances = int(max_frame)
+    b.scratch, b.scratch_bytes = scratch.data_ptr(), nbytes
+    b.debug_alpha = alpha.data_ptr() if alpha is not None else None
+    check(_lib.lib().amav_rasterize_backward(ctypes.byref(args), ctypes.byref(b), _stream()), "amav_rasterize_backward")
+    if want_alpha:
+        grads["alpha"] = alpha
+    return grads
+
+
+class _Rasterize(torch.autograd.Function):
+    """rasterize() with diff_gaussian_rasterization's backward.  The Function owns its workspace and keeps it in ctx:
+    the backward reads the forward's tile lists and blend records from it, which a later forward must not overwrite."""
+
+    @staticmethod
+    def forward(ctx, means3d, rotations, scales, opacities, colors, viewmatrix, projmatrix, tanfov, settings):
+        s = settings
+        F, N = means3d.shape[0], means3d.shape[1]
+        ws = RasterWorkspace(F, N, s["height"], s["width"], default_instance_capacity(F, N), means3d.device)
+        out = rasterize(means3d, rotations, scales, opacities, colors, viewmatrix, projmatrix, tanfov, s["height"],
+                        s["width"], bg=s["bg"], apply_activations=s["apply_activations"],
+                        scale_modifier=s["scale_modifier"], clamp_output=False, want_inv_depth=s["want_inv_depth"],
+                        want_radii=s["want_radii"], workspace=ws, check_overflow=True)
+        ctx.workspace, ctx.max_frame, ctx.settings = out["workspace"], out["max_frame"], s
+        ctx.save_for_backward(means3d, rotations, scales, opacities, colors, viewmatrix, projmatrix, tanfov)
+        empty = means3d.new_empty(0)
+        inv_depth = out["inv_depth"] if out["inv_depth"] is not None else empty
+        radii = out["radii"] if out["radii"] is not None else empty.to(torch.int32)
+        ctx.mark_non_differentiable(inv_depth, radii)
+        return out["rgba"], inv_depth, radii
+
+    @staticmethod
+    def backward(ctx, grad_rgba, _grad_inv_depth, _grad_radii):
+        means3d, rotations, scales, opacities, colors, viewmatrix, projmatrix, tanfov = ctx.saved_tensors
+        s = ctx.settings
+        if grad_rgba is None:
+            grad_rgba = torch.zeros(means3d.shape[0], s["height"], s["width"], 4, device=means3d.device)
+        g = rasterize_backward(means3d, rotations, scales, opacities, colors, viewmatrix, projmatrix, tanfov,
+                               s["height"], s["width"], grad_rgba.float(), ctx.workspace, ctx.max_frame, bg=s["bg"],
+                               apply_activations=s["apply_activations"], scale_modifier=s["scale_modifier"])
+        need = ctx.needs_input_grad
+        out = [g[k] if need[i] else None for i, k in enumerate(("means3d", "rotations", "scales", "opacities", "colors"))]
+        return (*out, None, None, None, None)
+
+
+def rasterize_differentiable(means3d, rotations, scales, opacities, colors, viewmatrix, projmatrix, tanfov, height,
+                             width, bg=(1.0, 1.0, 1.0), apply_activations=False, scale_modifier=1.0, antialiasing=False,
+                             clamp_output=False, want_inv_depth=False, want_radii=False, workspace=None, **unsupported):
+    """rasterize() as a torch.autograd.Function: the rgba output (RGB and alpha) is differentiable with respect to the
+    five Gaussian attributes (amav_rasterize_backward); inv_depth and radii are not, nor are the camera and `bg`.
+
+    The images equal rasterize()'s with the same arguments bit for bit: the kernel runs unclamped and clamp_output is
+    applied here with torch.clamp (exact either way), so the clamp's backward is torch's.  The call owns its workspace
+    (no `workspace=`) and synchronises once for the overflow check.  Not differentiable, and refused:
+    antialiasing, and rasterize()'s `decode` / `wire` / `out_rgba` / `profile_events` arguments.
+    """
+    if workspace is not None:
+        raise NotImplementedError("rasterize_differentiable owns its workspace (the backward reads the forward's); "
+                                  "do not pass workspace=")
+    if antialiasing:
+        raise NotImplementedError("the rasterizer has no backward for antialiasing=True")
+    bad = sorted(k for k, v in unsupported.items() if v is not None)
+    if bad:
+        raise NotImplementedError(f"rasterize_differentiable does not support {', '.join(bad)}")
+    settings = dict(height=int(height), width=int(width), bg=tuple(float(b) for b in bg),
+                    apply_activations=bool(apply_activations), scale_modifier=float(scale_modifier),
+                    want_inv_depth=bool(want_inv_depth), want_radii=bool(want_radii))
+    rgba, inv_depth, radii = _Rasterize.apply(means3d, rotations, scales, opacities, colors, viewmatrix, projmatrix,
+                                                 tanfov, settings)
+    if clamp_output:
+        rgba = torch.cat([rgba[..., :3].clamp(0.0, 1.0), rgba[..., 3:]], dim=-1)
+    return dict(rgba=rgba, inv_depth=inv_depth if want_inv_depth else None, radii=radii if want_radii else None,
+                workspace=None)
 
 
 def frames_to_rgb8(rgba, out=None):

@@ -681,6 +681,12 @@ def _flat(t, width):
     return t.reshape(-1, t.shape[-2], width).float()
 
 
+def _needs_grad(*tensors):
+    """The differentiable rasterizer is taken only when autograd would record it; otherwise the inference path runs
+    exactly as before."""
+    return torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
+
+
 def render_multi_view(gaussians, K, E, args, bg_color=None, debug=False):
     """renderer.py:431-445: one Gaussian set per batch item, T cameras.  The views share the Gaussians through a
     zero frame stride instead of the reference's expand + reshape copy."""
@@ -702,6 +708,9 @@ def render_batch(gaussians, K, E, args, bg_color=None, debug=False, return_alpha
     One camera launch + one rasterizer launch sequence for all B*T frames.  The returned image is a view of the
     kernel's RGBA output ([..., :3]); `return_alpha=True` also returns alpha [B,T,H,W] (= 1 - final transmittance);
     `return_rgba=True` returns the contiguous [B,T,H,W,4] buffer itself.
+    Differentiable: when grad mode is on and a Gaussian attribute requires grad, the images (RGB and alpha) carry the
+    rasterizer's backward (ops.rasterize_differentiable; bit-identical images).  `workspace`, `out_rgba`, `wire`,
+    `decode` and `return_workspace` are refused then.
     `decode`, `fuse_decode`: ops.decode_source whose `out` the Gaussians view, decoded as part of the rasterizer's launch
     sequence (ops.rasterize).
     """
@@ -727,6 +736,20 @@ def render_batch(gaussians, K, E, args, bg_color=None, debug=False, return_alpha
         opacity = torch.full_like(opacity, 0.1)
         color = color.clamp(0.0, 1.0)
         activate = False
+    if _needs_grad(xyz, rot, scale, opacity, color):
+        # differentiable path (ops.rasterize_differentiable): same images, owns its workspace
+        refused = [n for n, v in (("workspace", workspace), ("out_rgba", out_rgba), ("wire", wire), ("decode", decode))
+                   if v is not None] + (["return_workspace"] if return_workspace else [])
+        if refused:
+            raise NotImplementedError(f"render_batch: {', '.join(refused)} cannot be combined with gradients")
+        out = ops.rasterize_differentiable(xyz, rot, scale, opacity, color, view, proj, tanfov, H, W, bg=bg,
+                                           apply_activations=activate, clamp_output=True)
+        rgba = out["rgba"].view(B, T, H, W, 4)
+        if return_rgba:
+            return rgba
+        if return_alpha:
+            return rgba[..., :3], rgba[..., 3]
+        return rgba[..., :3]
     out = ops.rasterize(xyz, rot, scale, opacity, color, view, proj, tanfov, H, W, bg=bg, apply_activations=activate,
                         clamp_output=True, workspace=workspace, check_overflow=check_overflow, out_rgba=out_rgba, wire=wire,
                         decode=decode, fuse_decode=fuse_decode)
@@ -762,7 +785,11 @@ class GaussianRasterizationSettings:
 
 class GaussianRasterizer(nn.Module):
     """`GaussianRasterizer(raster_settings)(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-    cov3D_precomp)` -> (color [3,H,W], radii [N] int32, inv_depth [1,H,W]); inputs already activated."""
+    cov3D_precomp)` -> (color [3,H,W], radii [N] int32, inv_depth [1,H,W]); inputs already activated.
+
+    Differentiable in means3D, rotations, scales, opacities and colors_precomp when grad mode is on and one of them
+    requires grad (ops.rasterize_differentiable).  inv_depth and radii carry no gradient, and means2D is not used:
+    its .grad stays None (no screen-space densification statistics)."""
 
     def __init__(self, raster_settings):
         super().__init__()
@@ -777,6 +804,17 @@ class GaussianRasterizer(nn.Module):
         if cov3D_precomp is not None or scales is None or rotations is None:
             raise NotImplementedError("cov3D_precomp is not supported (the reference passes None, renderer.py:566)")
         dev = means3D.device
+        if _needs_grad(means3D, rotations, scales, opacities, colors_precomp):
+            if s.antialiasing:
+                raise NotImplementedError("the rasterizer has no backward for antialiasing=True")
+            out = ops.rasterize_differentiable(
+                means3D[None].float(), rotations[None].float(), scales[None].float(), opacities.reshape(1, -1, 1).float(),
+                colors_precomp[None].float(), s.viewmatrix.reshape(1, 16).float(), s.projmatrix.reshape(1, 16).float(),
+                torch.tensor([[s.tanfovx, s.tanfovy]], device=dev), s.image_height, s.image_width,
+                bg=[float(b) for b in s.bg.detach().cpu().tolist()], scale_modifier=s.scale_modifier,
+                want_inv_depth=True, want_radii=True)
+            color = out["rgba"][0, :, :, :3].permute(2, 0, 1)
+            return color, out["radii"][0], out["inv_depth"]
         out = ops.rasterize(means3D[None].float(), rotations[None].float(), scales[None].float(),
                             opacities.reshape(1, -1, 1).float(), colors_precomp[None].float(),
                             s.viewmatrix.reshape(1, 16).float(), s.projmatrix.reshape(1, 16).float(),

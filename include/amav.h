@@ -135,6 +135,35 @@ int amav_rasterize_forward(const amav_raster_args *args, void *stream);
 int amav_rasterize_status(const void *workspace, int64_t *total_instances, int64_t *max_frame_instances,
                           int32_t *overflow, void *stream);
 
+/* Gaussian tile rasterizer, backward: diff_gaussian_rasterization's backward (the reference's stage-2 training,
+ * src/models/lightning_model_wrapper.py:132-156) for the forward that `fwd` describes, which must be the LAST
+ * amav_rasterize_forward on fwd->workspace, with the same inputs, sizes and settings (the backward reads its tile
+ * lists and blend records).  Not supported: antialiasing, a decoding or wire forward.
+ * Gradients of the five Gaussian inputs, dense [F,N,width] fp32 (frame stride 0 inputs get one row per frame; the
+ * caller sums them).  grad_rgba is dL/d out_rgba [F,H,W,4] of an UNCLAMPED forward (clamp_output = 0): alpha is
+ * differentiable, inv_depth and the background are not.  The min(0.99, .) clamp of alpha is passed through (upstream's
+ * convention); the tanfov clamp of the view-space mean and the activations (apply_activations) are differentiated as
+ * torch autograd does.  Deterministic: no float atomics, bitwise the same gradients from run to run.
+ * scratch: amav_rasterize_backward_bytes(F, N, max_frame_instances) bytes, max_frame_instances = the largest per-frame
+ * instance count amav_rasterize_status reported for that forward (a larger value is fine).  A forward that overflowed
+ * (max_frame_instances > instance_capacity / F) is refused.  No host synchronisation. */
+typedef struct amav_raster_backward_args {
+    const float *grad_rgba;        /* device [F,H,W,4] */
+    float *grad_means3d;           /* device [F,N,3] */
+    float *grad_rotations;         /* device [F,N,4] */
+    float *grad_scales;            /* device [F,N,3] */
+    float *grad_opacities;         /* device [F,N,1] */
+    float *grad_colors;            /* device [F,N,3] */
+    int64_t max_frame_instances;   /* from amav_rasterize_status after the forward */
+    void *scratch;
+    size_t scratch_bytes;
+    /* optional, device [F,H,W]: 1 - T_final of the backward's replay of the blend (equals the forward's alpha channel
+     * bit for bit); NULL = off */
+    float *debug_alpha;
+} amav_raster_backward_args;
+size_t amav_rasterize_backward_bytes(int num_frames, int num_gaussians, int64_t max_frame_instances);
+int amav_rasterize_backward(const amav_raster_args *fwd, const amav_raster_backward_args *bwd, void *stream);
+
 /* amav_triplane_sample_decode_indexed + amav_rasterize_forward in one call: the packed Gaussian records are decoded
  * from the inputs below into the buffer the attributes of `args` view -- which must be the packed views
  * (xyz|opacity|rot|scale|color at float offsets 0, 3, 4, 8, 12, element stride 16) of ONE contiguous [F,N,16] buffer,
