@@ -52,6 +52,19 @@ class RasterBackwardArgs(ctypes.Structure):
     ]
 
 
+class TriplaneDecodeBackwardArgs(ctypes.Structure):
+    _fields_ = [
+        ("num_frames", ctypes.c_int32), ("num_points", ctypes.c_int32), ("channels", ctypes.c_int32),
+        ("resolution", ctypes.c_int32), ("radius", ctypes.c_float),
+        ("tokens", ctypes.c_void_p), ("tokens_frame_stride", ctypes.c_int64),
+        ("head_w_plane", ctypes.c_void_p), ("head_w_point", ctypes.c_void_p), ("points", ctypes.c_void_p),
+        ("proj", ctypes.c_void_p), ("boxes", ctypes.c_void_p), ("grad_records", ctypes.c_void_p),
+        ("grad_tokens", ctypes.c_void_p), ("grad_head_w_plane", ctypes.c_void_p), ("grad_head_w_point", ctypes.c_void_p),
+        ("grad_points", ctypes.c_void_p), ("grad_transl", ctypes.c_void_p),
+        ("scratch", ctypes.c_void_p), ("scratch_bytes", ctypes.c_size_t),
+    ]
+
+
 class DecodeSource(ctypes.Structure):
     _fields_ = [
         ("resolution", ctypes.c_int32), ("num_verts", ctypes.c_int32),
@@ -192,6 +205,8 @@ SIGNATURES = {
     "amav_triplane_sample_decode_indexed": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                            c_float_p, c_float_p, ctypes.c_void_p, c_float_p,
                                                            ctypes.c_float, c_float_p, c_float_p, ctypes.c_void_p]),
+    "amav_triplane_decode_backward_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "amav_triplane_decode_backward": (ctypes.c_int, [ctypes.POINTER(TriplaneDecodeBackwardArgs), ctypes.c_void_p]),
     "amav_triplane_sample_features": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                      c_float_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                                      c_float_p, ctypes.c_float, c_float_p, ctypes.c_void_p]),

@@ -21,6 +21,7 @@
 
 #include "amav_common.h"
 #include "decode_quad.h"
+#include "triplane_region.h"
 
 namespace amav {
 namespace triplane {
@@ -30,29 +31,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // grid: (ceil(R*R/4 / 256), 3, F); each thread projects 4 consecutive texels of one plane.  The plane's [C][16] weight
 // block is staged in LDS once per workgroup and read back as broadcasts (as scalar loads its 16 KB per plane thrash
 // the 16 KB scalar cache when workgroups of different planes share a CU, putting an L2 round trip in every iteration).
-// The texels of plane `plane` that bilinear taps of points inside the box [lo, hi] (world space) can touch, with
-// sample_decode_kernel's own arithmetic (u = clamp(p / radius), pixel = ((u + 1) R - 1) / 2, taps floor and floor + 1,
-// out-of-range taps read the clamped address): every step is monotonic in p, so the taps of any point of the box --
-// in particular of any point the subdivision table averages from vertices inside it -- lie in the returned rectangle
-// [x0, x1] x [y0, y1] (inclusive, already clamped to the plane).
-struct TexelRect {
-    int x0, x1, y0, y1;
-};
-__device__ __forceinline__ int tap_floor(float p, float radius, int R) {
-    const float u = fminf(fmaxf(p / radius, -1.0f), 1.0f);
-    return (int)floorf(((u + 1.0f) * (float)R - 1.0f) * 0.5f);
-}
-__device__ __forceinline__ TexelRect region_of(const float *__restrict__ box, int plane, float radius, int R) {
-    // plane 0 <- (x, y), plane 1 <- (x, z), plane 2 <- (y, z); grid x indexes W, grid y indexes H
-    const int ax = plane == 2 ? 1 : 0, ay = plane == 0 ? 1 : 2;
-    TexelRect r;
-    r.x0 = min(max(tap_floor(box[ax], radius, R), 0), R - 1);
-    r.x1 = min(max(tap_floor(box[3 + ax], radius, R) + 1, 0), R - 1);
-    r.y0 = min(max(tap_floor(box[ay], radius, R), 0), R - 1);
-    r.y1 = min(max(tap_floor(box[3 + ay], radius, R) + 1, 0), R - 1);
-    return r;
-}
-
 // `boxes` (NULL = all texels): per frame the bounding box {min xyz, max xyz} of the points that will be sampled
 // (amav_points_bbox); texel quads outside the frame's region_of() are neither read nor written -- the body covers a
 // fifth to a third of each plane, and the slab is the largest stream of the whole path.

@@ -8,7 +8,8 @@ import os
 import torch
 
 from . import _lib
-from ._lib import AmavError, Attr, BodyTables, DecodeSource, PoseParts, RasterArgs, RasterBackwardArgs, check
+from ._lib import (AmavError, Attr, BodyTables, DecodeSource, PoseParts, RasterArgs, RasterBackwardArgs,
+                   TriplaneDecodeBackwardArgs, check)
 
 SCALE_BIAS = 3.9    # src/models/renderer.py:428
 OPACITY_BIAS = 0.0  # src/models/renderer.py:429
@@ -604,23 +605,34 @@ def points_gather(vertices, idx4):
 
 
 # ------------------------------------------------------------------------------------------------------- triplane
-def pack_head_weights(weights: dict, channels: int, device):
+def pack_head_weights(weights: dict, channels: int, device, differentiable=False):
     """The five head Linear layers (renderer.py:51-55) -> (head_w_plane [3,C,16], head_w_point [16,4]).
 
     `weights` maps 'xyz_layer' | 'rotation_layer' | 'scaling_layer' | 'opacity_layer' | 'shs_layer' to
     (weight [out, 3C+3], bias [out]).  Output channel order = packed record layout (include/amav.h).
+    differentiable=True: the same values, built from the layers' tensors without detach() (autograd carries the packed
+    weights' gradients back to the layers).
     """
     C = channels
     rows = {"xyz_layer": (0, 3), "opacity_layer": (3, 1), "rotation_layer": (4, 4), "scaling_layer": (8, 3),
             "shs_layer": (12, 3)}
-    Wcat = torch.zeros(16, 3 * C + 3, device=device)
-    bias = torch.zeros(16, device=device)
     for name, (o, n) in rows.items():
-        w, b = weights[name]
+        w = weights[name][0]
         if tuple(w.shape) != (n, 3 * C + 3):
             raise AmavError(f"{name}.weight has shape {tuple(w.shape)}, expected {(n, 3 * C + 3)}")
-        Wcat[o:o + n] = w.detach().to(device=device, dtype=torch.float32)
-        bias[o:o + n] = b.detach().to(device=device, dtype=torch.float32)
+    if differentiable:
+        zw, zb = torch.zeros(1, 3 * C + 3, device=device), torch.zeros(1, device=device)
+        parts = [(weights[k][0], weights[k][1]) for k in ("xyz_layer", "opacity_layer", "rotation_layer", "scaling_layer")]
+        parts += [(zw, zb), (weights["shs_layer"][0], weights["shs_layer"][1]), (zw, zb)]  # record rows 11, 15: pad
+        Wcat = torch.cat([w.to(device=device, dtype=torch.float32) for w, _ in parts])
+        bias = torch.cat([b.to(device=device, dtype=torch.float32) for _, b in parts])
+    else:
+        Wcat = torch.zeros(16, 3 * C + 3, device=device)
+        bias = torch.zeros(16, device=device)
+        for name, (o, n) in rows.items():
+            w, b = weights[name]
+            Wcat[o:o + n] = w.detach().to(device=device, dtype=torch.float32)
+            bias[o:o + n] = b.detach().to(device=device, dtype=torch.float32)
     w_plane = Wcat[:, 3:].reshape(16, 3, C).permute(1, 2, 0).contiguous()  # [3, C, 16]
     w_point = torch.cat([Wcat[:, :3], bias[:, None]], dim=1).contiguous()   # [16, 4]
     return w_plane, w_point
@@ -737,6 +749,99 @@ def decode_source(proj, vertices, idx4, transl, radius, head_w_point, out=None):
     st.radius, st.head_w_point = float(radius), head_w_point.data_ptr()
     return dict(proj=proj, vertices=vertices, idx4=idx4, transl=transl, radius=float(radius), head_w_point=head_w_point,
                 out=out, struct=st)
+
+
+def triplane_decode_backward(tokens, head_w_plane, head_w_point, points, proj, grad_records, radius, boxes=None,
+                             want_points=True, want_transl=True):
+    """Gradients of triplane_project(tokens, head_w_plane, R, region=(boxes, radius) or None) followed by
+    triplane_sample_decode(proj, points, transl, radius, head_w_point) (amav_triplane_decode_backward).
+
+    `proj` is that forward's output, kept; grad_records = dL/d records [F,N,16].  Returns dict(tokens [F,C,3R^2],
+    head_w_plane [3,C,16], head_w_point [16,4], points [F,N,3] or None, transl [F,3] or None).  With boxes, the slab is
+    read only inside the projected rectangles and d tokens is exactly 0 outside them.  Deterministic; no host sync.
+    """
+    _need(tokens, "tokens")
+    if tokens.dim() != 3 or tokens.stride(2) != 1 or tokens.stride(1) != tokens.shape[2]:
+        tokens = tokens.contiguous()
+    F, C, S = tokens.shape
+    proj = _contig(proj, "proj")
+    R = int(proj.shape[2])
+    if tuple(proj.shape) != (F, 3, R, R, 16) or S != 3 * R * R:
+        raise AmavError(f"proj {tuple(proj.shape)} does not match tokens {tuple(tokens.shape)}")
+    head_w_plane = _contig(head_w_plane, "head_w_plane")
+    head_w_point = _contig(head_w_point, "head_w_point")
+    points = _contig(points, "points")
+    grad_records = _contig(grad_records, "grad_records")
+    N = int(points.shape[1])
+    if tuple(head_w_plane.shape) != (3, C, 16) or tuple(head_w_point.shape) != (16, 4):
+        raise AmavError(f"head weights {tuple(head_w_plane.shape)}, {tuple(head_w_point.shape)} != (3,{C},16), (16,4)")
+    if tuple(points.shape) != (F, N, 3) or tuple(grad_records.shape) != (F, N, GAUSS_STRIDE):
+        raise AmavError(f"points {tuple(points.shape)} / grad_records {tuple(grad_records.shape)} do not match F={F}")
+    if boxes is not None:
+        boxes = _contig(boxes, "boxes")
+        if tuple(boxes.shape) != (F, 6):
+            raise AmavError(f"boxes {tuple(boxes.shape)} != {(F, 6)}")
+    dev = tokens.device
+    out = dict(tokens=torch.empty(F, C, S, device=dev), head_w_plane=torch.empty(3, C, 16, device=dev),
+               head_w_point=torch.empty(16, 4, device=dev),
+               points=torch.empty(F, N, 3, device=dev) if want_points else None,
+               transl=torch.empty(F, 3, device=dev) if want_transl else None)
+    nbytes = _lib.lib().amav_triplane_decode_backward_bytes(F, N, C, R)
+    if nbytes == 0:
+        raise AmavError(f"amav_triplane_decode_backward_bytes rejected F={F} N={N} C={C} R={R}")
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    a = TriplaneDecodeBackwardArgs()
+    a.num_frames, a.num_points, a.channels, a.resolution, a.radius = F, N, C, R, float(radius)
+    a.tokens, a.tokens_frame_stride = tokens.data_ptr(), tokens.stride(0)
+    a.head_w_plane, a.head_w_point = head_w_plane.data_ptr(), head_w_point.data_ptr()
+    a.points, a.proj = points.data_ptr(), proj.data_ptr()
+    a.boxes = boxes.data_ptr() if boxes is not None else None
+    a.grad_records = grad_records.data_ptr()
+    a.grad_tokens, a.grad_head_w_plane = out["tokens"].data_ptr(), out["head_w_plane"].data_ptr()
+    a.grad_head_w_point = out["head_w_point"].data_ptr()
+    a.grad_points = out["points"].data_ptr() if want_points else None
+    a.grad_transl = out["transl"].data_ptr() if want_transl else None
+    a.scratch, a.scratch_bytes = scratch.data_ptr(), nbytes
+    check(_lib.lib().amav_triplane_decode_backward(ctypes.byref(a), _stream()), "amav_triplane_decode_backward")
+    return out
+
+
+class _TriplaneDecode(torch.autograd.Function):
+    """triplane_project (region) + triplane_sample_decode with amav_triplane_decode_backward as the backward.  The
+    projected planes and region boxes of the forward are kept for it."""
+
+    @staticmethod
+    def forward(ctx, tokens, w_plane, w_point, points, transl, settings):
+        R, radius = settings["resolution"], settings["radius"]
+        boxes = points_bbox(points) if settings["region"] else None
+        proj = triplane_project(tokens, w_plane, R, region=(boxes, radius) if boxes is not None else None)
+        out = triplane_sample_decode(proj, points, transl, radius, w_point)
+        ctx.settings, ctx.has_transl = settings, transl is not None
+        ctx.save_for_backward(tokens, w_plane, w_point, points, proj, boxes)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_records):
+        tokens, w_plane, w_point, points, proj, boxes = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        g = triplane_decode_backward(tokens, w_plane, w_point, points, proj, grad_records.float(),
+                                     ctx.settings["radius"], boxes=boxes, want_points=need[3],
+                                     want_transl=ctx.has_transl and need[4])
+        return (g["tokens"] if need[0] else None, g["head_w_plane"] if need[1] else None,
+                g["head_w_point"] if need[2] else None, g["points"] if need[3] else None,
+                g["transl"] if ctx.has_transl and need[4] else None, None)
+
+
+def triplane_decode_differentiable(tokens, w_plane, w_point, points, transl, resolution, radius, region=True):
+    """The fused triplane decode as a torch.autograd.Function: tokens [F,C,3R^2], head weights (pack_head_weights,
+    differentiable=True), points [F,N,3], transl [F,3] or None -> packed records [F,N,16], equal bit for bit to
+    triplane_project(region) + triplane_sample_decode.  Gradients reach tokens, both weight blocks, points and transl
+    (amav_triplane_decode_backward).  region=True projects (and differentiates) only the texels the points can sample."""
+    F = tokens.shape[0]
+    if transl is not None:
+        transl = transl.reshape(F, 3)
+    settings = dict(resolution=int(resolution), radius=float(radius), region=bool(region))
+    return _TriplaneDecode.apply(tokens, w_plane, w_point, points, transl, settings)
 
 
 def triplane_sample_features(planes, points, radius):

@@ -163,16 +163,45 @@ class Renderer(nn.Module):
             refined[s:s + step] = pts + offsets.view(pts.shape)
         return refined
 
-    def _head_weights(self):
+    def _head_layers(self):
         gd = self.gaussian_decoder
-        layers = dict(xyz_layer=gd.xyz_layer, rotation_layer=gd.rotation_layer, scaling_layer=gd.scaling_layer,
-                      opacity_layer=gd.opacity_layer, shs_layer=gd.shs_layer)
+        return dict(xyz_layer=gd.xyz_layer, rotation_layer=gd.rotation_layer, scaling_layer=gd.scaling_layer,
+                    opacity_layer=gd.opacity_layer, shs_layer=gd.shs_layer)
+
+    def _head_weights(self, differentiable=False):
+        layers = self._head_layers()
+        device = self.gaussian_decoder.xyz_layer.weight.device
+        if differentiable:  # packed from the live parameters on every call: never the detached cache
+            return ops.pack_head_weights({k: (l.weight, l.bias) for k, l in layers.items()},
+                                         self.cfg.triplane_feature_dim, device, differentiable=True)
         version = tuple((ops.tensor_version(l.weight), ops.tensor_version(l.bias), l.weight.data_ptr()) for l in layers.values())
         if self._packed is None or self._packed[0] != version:
             heads = {k: (l.weight, l.bias) for k, l in layers.items()}
-            self._packed = (version, ops.pack_head_weights(heads, self.cfg.triplane_feature_dim,
-                                                           gd.xyz_layer.weight.device))
+            self._packed = (version, ops.pack_head_weights(heads, self.cfg.triplane_feature_dim, device))
         return self._packed[1]
+
+    def _wants_grad(self, *tensors):
+        """Gradients are recorded through the decode when grad mode is on and the tokens, a head parameter or transl
+        (among `tensors`) requires grad; otherwise every call runs the inference path exactly as before."""
+        if not torch.is_grad_enabled():
+            return False
+        return any(t is not None and t.requires_grad for t in tensors) or any(
+            p.requires_grad for p in self.gaussian_decoder.parameters())
+
+    def _refuse_under_grad(self, smpl_params):
+        """Configurations with no backward are refused rather than silently dropping gradient."""
+        if hasattr(self, "point_encoder"):
+            raise NotImplementedError("Renderer: the point refiner has no backward; disable gradients "
+                                      "(torch.no_grad()) or use no_point_refiner=True")
+        bad = sorted(k for k, v in smpl_params.items() if k != "transl" and isinstance(v, torch.Tensor) and v.requires_grad)
+        if bad:
+            raise NotImplementedError(f"Renderer: SMPL-X parameters {', '.join(bad)} require grad, but LBS has no "
+                                      "backward (only transl is differentiable)")
+
+    def _differentiable_decode(self, triplane_tokens, points, transl, region):
+        w_plane, w_point = self._head_weights(differentiable=True)
+        return ops.triplane_decode_differentiable(triplane_tokens, w_plane, w_point, points, transl,
+                                                  self._plane_resolution(triplane_tokens), self.cfg.radius, region=region)
 
     def _plane_resolution(self, triplane_tokens):
         """Resolution of the planes inside a token slab [F,C,3 R^2] (R grows 2^num_upsample_blocks when upsampled)."""
@@ -182,7 +211,10 @@ class Renderer(nn.Module):
         return r
 
     def decode_gaussians(self, triplane_tokens, points, transl):
-        """Fused renderer.py:136-181: tokens [F,C,3R^2], points [F,N,3], transl [F,3] -> packed [F,N,16]."""
+        """Fused renderer.py:136-181: tokens [F,C,3R^2], points [F,N,3], transl [F,3] -> packed [F,N,16].
+        Differentiable in the tokens, the heads, points and transl when grad mode is on and one of them requires grad."""
+        if self._wants_grad(triplane_tokens, points, transl):
+            return self._differentiable_decode(triplane_tokens, points, transl, region=False)
         w_plane, w_point = self._head_weights()
         proj = ops.triplane_project(triplane_tokens, w_plane, self._plane_resolution(triplane_tokens))
         return ops.triplane_sample_decode(proj, points, transl, self.cfg.radius, w_point)
@@ -200,8 +232,23 @@ class Renderer(nn.Module):
         `defer_decode`: for the densified decode (no point refiner), do not launch the sampling kernel but return its
         inputs (ops.decode_source, for ops.rasterize(decode=...)) as a last value; `packed` is filled by the rasterizer.
         Other configurations decode here and return None in that place.
+        Differentiable (ops.triplane_decode_differentiable; the same records) when grad mode is on and the tokens, a
+        head parameter or transl requires grad; `out`, `window_plan`, `defer_decode`, the point refiner and SMPL-X
+        parameters other than transl that require grad are refused then (NotImplementedError).
         """
         F = triplane_tokens.shape[0]
+        if self._wants_grad(triplane_tokens, smpl_params["transl"]):
+            self._refuse_under_grad(smpl_params)
+            refused = [n for n, v in (("out", out), ("window_plan", window_plan)) if v is not None] + (
+                ["defer_decode"] if defer_decode else [])
+            if refused:
+                raise NotImplementedError(f"gaussians_from_tokens: {', '.join(refused)} cannot be combined with gradients")
+            side_result = side_work() if side_work is not None else None
+            with torch.no_grad():
+                points = self.get_smpl_vertices(smpl_params)  # gather = the indexed decode's own points, bit for bit
+            packed = self._differentiable_decode(triplane_tokens, points, smpl_params["transl"].reshape(F, 3).float(),
+                                                 region=self.project_sampled_region)
+            return packed if side_work is None else (packed, side_result)
         w_plane, w_point = self._head_weights()
         R = self._plane_resolution(triplane_tokens)
         side_result = side_work() if side_work is not None else None
@@ -259,6 +306,19 @@ class Renderer(nn.Module):
         K = cam_params["intrinsic"].reshape(F, 3, 3)
         E = cam_params["extrinsic"].reshape(F, 4, 4)
         chunks = max(1, min(int(chunks), F))
+        if self._wants_grad(triplane_tokens, smpl_params["transl"]):
+            # differentiable: separate decode launch, one frame group, then render_batch's differentiable rasterizer
+            refused = [n for n, v in (("workspaces", workspaces), ("wire", wire), ("window_plan", window_plan))
+                       if v is not None] + (["chunks > 1"] if chunks > 1 else []) + (["fuse_decode"] if fuse_decode else [])
+            if refused:
+                raise NotImplementedError(f"render_tokens: {', '.join(refused)} cannot be combined with gradients")
+            Kc, Ec = K.float(), E.float()
+            packed, camera = self.gaussians_from_tokens(
+                triplane_tokens, {k: v.unsqueeze(0) for k, v in flat.items()},
+                side_work=lambda: ops.camera_from_intrinsics(Kc, Ec, H, W))
+            rgba = render_batch(self.unpack_gaussians(packed), K.unsqueeze(0), E.unsqueeze(0), self.cfg, bg_color,
+                                return_rgba=True, camera=camera[:3])
+            return rgba.reshape(F, H, W, 4), packed
         if wire is not None and chunks != 1:
             raise AmavError("render_tokens: the wire buffer covers the whole shard; use chunks=1 with it")
         bounds = [(F * i // chunks, F * (i + 1) // chunks) for i in range(chunks)]
@@ -356,6 +416,9 @@ class Renderer(nn.Module):
             raise AmavError("Renderer.forward: no SMPL-X parameters (predict_smplx_params is off and no smpl_params_gt)")
 
         chunks = int(getattr(self.cfg, "pipeline_chunks", 1)) if B * T >= 32 else 1
+        grad = self._wants_grad(tokens, smpl_params["transl"])
+        if grad:
+            chunks = 1  # the differentiable path renders the frames as one group
         window_plan = None
         if getattr(self.cfg, "upsample_triplane", False):  # renderer.py:94-99 (library convolutions, 8(f) row 2)
             up, R = self.triplane_upsampler, self.cfg.triplane_resolution
@@ -365,6 +428,9 @@ class Renderer(nn.Module):
                 # point refiner folds its BatchNorms as eval too.  This package is inference-only.
                 raise AmavError("Renderer.forward: the triplane upsampler is in training mode; its BatchNorm layers are "
                                 "evaluated with running statistics only -- call .eval() on the module first")
+            if grad:
+                raise NotImplementedError("Renderer.forward: the triplane upsampler has no backward; disable gradients "
+                                          "(torch.no_grad()) or upsample_triplane=False")
             coarse = tokens
             if getattr(self.cfg, "upsample_windows", True):
                 # only the texels the body's points can sample are upsampled (TriplaneUpsampler, "windowed evaluation")

@@ -328,6 +328,44 @@ int amav_triplane_sample_decode_indexed(int num_frames, int num_points, int reso
                                         const float *proj_dev, const float *vertices_dev, const int32_t *idx_dev,
                                         const float *transl_dev, float radius, const float *head_w_point_dev,
                                         float *out_gaussians_dev, void *stream);
+/* Triplane decode, backward: gradients of the packed records that amav_triplane_project(_region) +
+ * amav_triplane_sample_decode produced (the reference's stage-2 training reaches the five gaussian_decoder heads and the
+ * triplane tokens through them, src/models/renderer.py:136-181), given grad_records = dL/d records [F,N,16].  The
+ * padding channels 11 and 15 take no gradient; F.normalize (eps 1e-12) and the sigmoid are differentiated as torch
+ * autograd does, and so are clamp(p / radius) and grid_sample (bilinear, align_corners=False, zero padding) for the points.
+ *   tokens, proj, boxes, radius, head weights, points: exactly those of the forward (proj is its output, kept).
+ *   Region contract: with boxes (R % 4 == 0) only the rectangle of each frame's plane the forward projected is read from
+ *   the slab -- the unprojected texels may hold anything, NaN included -- and grad_tokens is written everywhere, exact
+ *   zeros outside it; nothing from outside reaches grad_head_w_plane.
+ *   Outputs: grad_tokens [F,C,3R^2] contiguous, grad_head_w_plane [3,C,16], grad_head_w_point [16,4] (overwritten,
+ *   not accumulated); grad_points [F,N,3] and grad_transl [F,3] optional (NULL = not wanted).
+ * Deterministic: no float atomics; every sum has a fixed order, so gradients are bitwise the same from run to run, and
+ * grad_tokens, grad_points and grad_transl of a frame do not depend on the other frames of the call (each texel sums its
+ * taps in point order).  scratch: amav_triplane_decode_backward_bytes(F, N, C, R) bytes, 16-B aligned (0 = bad sizes).
+ * Refused with an error code before any launch: NULL pointers, sizes <= 0, F > 65535, C > 1024 (the plane's weights
+ * are staged in 64 KiB of LDS), radius <= 0, misaligned buffers, a tokens frame stride below C 3R^2, scratch too small.
+ * No allocation and no host synchronisation. */
+typedef struct amav_triplane_decode_backward_args {
+    int32_t num_frames, num_points, channels, resolution;
+    float radius;
+    const float *tokens;            /* [F,C,3R^2], unit stride along texels, frame stride below */
+    int64_t tokens_frame_stride;    /* floats */
+    const float *head_w_plane;      /* [3,C,16], 16-B aligned */
+    const float *head_w_point;      /* [16,4], 16-B aligned */
+    const float *points;            /* [F,N,3] */
+    const float *proj;              /* [F,3,R,R,16] of the forward, 16-B aligned */
+    const float *boxes;             /* [F,6] given to amav_triplane_project_region, or NULL (whole planes) */
+    const float *grad_records;      /* [F,N,16], 16-B aligned */
+    float *grad_tokens;             /* [F,C,3R^2], 16-B aligned */
+    float *grad_head_w_plane;       /* [3,C,16] */
+    float *grad_head_w_point;       /* [16,4] */
+    float *grad_points;             /* [F,N,3] or NULL */
+    float *grad_transl;             /* [F,3] or NULL */
+    void *scratch;
+    size_t scratch_bytes;
+} amav_triplane_decode_backward_args;
+size_t amav_triplane_decode_backward_bytes(int num_frames, int num_points, int channels, int resolution);
+int amav_triplane_decode_backward(const amav_triplane_decode_backward_args *args, void *stream);
 /* Plain Renderer.sample_from_triplane (renderer.py:292-317): element (f,p,c,h,w) of the planes lives at
  * planes[f*frame_stride + p*plane_stride + c*chan_stride + h*R + w] (so both the [F,3,C,R,R] tensor and the
  * [F,C,(3 R R)] token layout are addressable); points [F,N,3] -> features [F,N,3C] in (plane, channel) order. */
