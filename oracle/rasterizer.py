@@ -114,10 +114,18 @@ def preprocess_torch(means3d, rotations, scales, opacities, view, proj, tanfovx,
                 visible=visible, opacity=opacities.reshape(-1))
 
 
-def rasterize_torch(means3d, rotations, scales, opacities, colors, view, proj, tanfovx, tanfovy, bg, H, W):
+def rasterize_torch(means3d, rotations, scales, opacities, colors, view, proj, tanfovx, tanfovy, bg, H, W,
+                    scale_modifier=1.0, alpha_clamp_grad="torch"):
     """Brute-force restatement: Gaussians in global (depth, index) order, all pixels at once; a pixel only sees a
-    Gaussian when its 16x16 tile lies inside the Gaussian's tile rectangle."""
-    g = preprocess_torch(means3d, rotations, scales, opacities, view, proj, tanfovx, tanfovy, H, W)
+    Gaussian when its 16x16 tile lies inside the Gaussian's tile rectangle.
+
+    alpha_clamp_grad: the derivative of alpha = min(0.99, opacity * exp(power)).  "torch" is torch.clamp's (zero where
+    the cap engages); "upstream" keeps the capped value but passes the gradient straight through, as
+    diff_gaussian_rasterization's backward (and amav_rasterize_backward) do.  Values agree to rounding (exactly
+    wherever the cap does not engage)."""
+    if alpha_clamp_grad not in ("torch", "upstream"):
+        raise ValueError(f"alpha_clamp_grad must be 'torch' or 'upstream', got {alpha_clamp_grad!r}")
+    g = preprocess_torch(means3d, rotations, scales, opacities, view, proj, tanfovx, tanfovy, H, W, scale_modifier)
     dt = means3d.dtype
     ys, xs = torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij")
     tx, ty = xs // 16, ys // 16
@@ -134,7 +142,10 @@ def rasterize_torch(means3d, rotations, scales, opacities, colors, view, proj, t
         dx, dy = g["xy"][i, 0] - xf, g["xy"][i, 1] - yf
         A, B, Cc = g["conic"][i]
         power = -0.5 * (A * dx * dx + Cc * dy * dy) - B * dx * dy
-        alpha = torch.clamp(g["opacity"][i] * torch.exp(power), max=0.99)
+        raw = g["opacity"][i] * torch.exp(power)
+        alpha = torch.clamp(raw, max=0.99)
+        if alpha_clamp_grad == "upstream":
+            alpha = raw + (alpha - raw).detach()
         ok = in_rect & ~done & (power <= 0) & (alpha >= 1.0 / 255.0)
         test_T = T * (1 - alpha)
         newly_done = ok & (test_T < 0.0001)

@@ -4,7 +4,8 @@ through Renderer.
 Accuracy is checked against torch autograd, in float64 on the CPU, of the oracle's restatement of the reference
 (oracle.triplane: tokens_to_planes -> sample_from_triplane -> gaussian_heads -> construct_gaussians).  The derivative
 of bilinear sampling jumps where a point crosses a texel centre and where p / radius crosses the clamp at +-1, so the
-points are kept 1e-3 texel away from both (fp32 and fp64 then take the same branch).  Bound, chosen and not measured:
+random points are kept 1e-3 texel away from both (fp32 and fp64 then take the same branch); test_gradients_at_kinks
+puts points exactly on them, at dyadic coordinates that both precisions compute exactly.  Bound, chosen and not measured:
 max|g - g_ref| <= 1e-4 max|g_ref| per tensor; the measured ratios are printed.
 """
 import math
@@ -31,7 +32,8 @@ def _points(g, F, N, R, radius, spread=1.15):
     return (u * radius).float()
 
 
-def make_case(F, N, C, R, seed, radius=1.4, spread=1.15):
+def make_case(F, N, C, R, seed, radius=1.4, spread=1.15, exact=None):
+    """`exact` [F, M, 3]: points placed first as given (not nudged); the other N - M are drawn by _points."""
     g = torch.Generator().manual_seed(seed)
     tokens = torch.randn(F, C, 3 * R * R, generator=g)
     # raw head outputs of order one whatever C; the rotation's norm stays away from 0, where F.normalize's backward
@@ -40,7 +42,9 @@ def make_case(F, N, C, R, seed, radius=1.4, spread=1.15):
     heads = {k: (torch.randn(n, 3 * C + 3, generator=g) * std, torch.randn(n, generator=g) * 0.3)
              for k, n in LAYERS.items()}
     heads["rotation_layer"][1][0] += 2.0
-    points = _points(g, F, N, R, radius, spread)
+    points = _points(g, F, N - (0 if exact is None else exact.shape[1]), R, radius, spread)
+    if exact is not None:
+        points = torch.cat([exact.float(), points], 1)
     transl = torch.randn(F, 3, generator=g) * 0.1
     grec = torch.randn(F, N, 16, generator=g)
     grec[..., PAD] = 0.0
@@ -166,6 +170,131 @@ def test_deterministic_and_independent_of_frame_slicing():
         part = _backward_once(case, s, s + 25, proj, boxes, wpl, wpt)
         for k in ("tokens", "points", "transl"):
             assert torch.equal(part[k], a[k][s:s + 25]), (k, s)
+
+
+def _compare(label, got, ref):
+    """max|g - g_ref| / max|g_ref| per tensor, printed, each within TOL."""
+    ratios = {}
+    for k, r in ref.items():
+        scale = float(r.abs().max())
+        assert torch.isfinite(got[k]).all(), f"{label}: {k} not finite"
+        ratios[k] = float((got[k].double() - r).abs().max()) / max(scale, 1e-30)
+    print(f"\n{label} max|g - g_ref| / max|g_ref|: " + ", ".join(f"{k} {v:.1e}" for k, v in ratios.items()))
+    bad = {k: v for k, v in ratios.items() if not v <= TOL}
+    assert not bad, bad
+    return ratios
+
+
+# Shapes the default cases do not reach: R % 4 != 0 (no region; R = 5, 7: R^2 % 4 != 0, dtokens_kernel's scalar form;
+# R = 6: its vector form with quads that straddle rows), C % 64 != 0 above 64 (dwplane_kernel's partial last block),
+# C % 4 != 0, C = 1, C = 1024 (the ABI's largest), N = 1, N just past a 256-point block, N not a multiple of 64.
+EDGE_SHAPES = [(2, 300, 16, 5), (2, 300, 16, 6), (2, 300, 16, 7), (2, 400, 1, 16), (2, 400, 3, 8), (2, 500, 100, 16),
+               (2, 500, 200, 32), (2, 300, 1024, 16), (3, 1, 8, 8), (2, 257, 32, 16), (2, 321, 40, 12)]
+
+
+@pytest.mark.parametrize("F,N,C,R", EDGE_SHAPES)
+def test_gradients_at_edge_shapes(F, N, C, R):
+    assert R % 4 != 0 or C % 64 != 0 or C % 4 != 0 or C == 1024 or N % 64 != 0
+    case = make_case(F, N, C, R, seed=F * 7919 + N * 31 + C * 7 + R)
+    ref, ref_rec = reference_grads(case)
+    got, rec = gpu_grads(case, region=True)
+    assert (rec - ref_rec.float()).abs().max() < 1e-3
+    _compare(f"F={F} N={N} C={C} R={R}", got, ref)
+    flat, rec_flat = gpu_grads(case, region=False)
+    if R % 4 != 0:  # amav_triplane_project_region ignores boxes there: the same launches, the same bits
+        assert torch.equal(rec_flat, rec)
+        for k in got:
+            assert torch.equal(flat[k], got[k]), k
+    else:
+        _compare(f"F={F} N={N} C={C} R={R} no region", flat, ref)
+
+
+def _kink_points(F, R, g):
+    """Points on the derivative's kinks, exactly: p / radius (radius 2) on texel centres ((2k + 1) / R - 1), on +-1 and
+    beyond +-1 (+-1.25), each coordinate drawn from those values (dyadic: fp32 and fp64 take the same branch)."""
+    centres = [(2 * k + 1) / R - 1 for k in range(R)]
+    values = torch.tensor(centres + [-1.0, 1.0, -1.0, 1.0, -1.25, 1.25], dtype=torch.float64)
+    idx = torch.randint(0, len(values), (F, 6 * R, 3), generator=g)
+    return values[idx] * 2.0
+
+
+def test_gradients_at_kinks():
+    F, N, C, R, radius = 2, 400, 16, 16, 2.0
+    g = torch.Generator().manual_seed(551)
+    exact = _kink_points(F, R, g)
+    case = make_case(F, N, C, R, seed=552, radius=radius, exact=exact)
+    u = case["points"][:, :exact.shape[1]].double() / radius
+    assert torch.equal(case["points"][:, :exact.shape[1]].double(), exact)
+    pix = ((u.clamp(-1, 1) + 1) * R - 1) / 2
+    assert (pix == pix.round()).sum() > 200 and (u.abs() == 1).sum() > 50 and (u.abs() > 1).sum() > 20
+    ref, ref_rec = reference_grads(case)
+    got, rec = gpu_grads(case)
+    assert (rec - ref_rec.float()).abs().max() < 1e-3
+    _compare("kinks", got, ref)
+
+
+def test_zero_rotation_head():
+    """The reference's zero-initialised gaussian_decoder: the raw quaternion is exactly 0 and F.normalize takes its
+    eps branch (dv = g / 1e-12); every gradient, the amplified ones included, against fp64 autograd."""
+    F, N, C, R = 2, 600, 32, 16
+    case = make_case(F, N, C, R, seed=561)
+    w, b = case["heads"]["rotation_layer"]
+    case["heads"]["rotation_layer"] = (torch.zeros_like(w), torch.zeros_like(b))
+    ref, ref_rec = reference_grads(case)
+    assert (ref_rec[..., 4:8] == 0).all()
+    assert ref["rotation_layer.bias"].abs().max() > 1e9  # the eps branch really ran
+    got, rec = gpu_grads(case)
+    assert (rec[..., 4:8] == 0).all()
+    _compare("zero rotation head", got, ref)
+
+
+def test_token_frame_stride_is_passed_through(monkeypatch):
+    """tokens as a view whose frame stride exceeds C 3R^2: ops hands the view's pointer and stride to the library (no
+    copy), and the gradients equal those of a contiguous copy bit for bit."""
+    from audio_motion_avatar_amd import _lib, ops
+
+    F, N, C, R = 3, 500, 24, 16
+    S = 3 * R * R
+    case = make_case(F, N, C, R, seed=571)
+    lib = _lib.lib()
+    seen = []
+    for name in ("amav_triplane_project_region", "amav_triplane_decode_backward"):
+        orig = getattr(lib, name)
+
+        def spy(*args, _orig=orig, _name=name):
+            if _name == "amav_triplane_project_region":
+                seen.append((_name, args[3], args[4]))
+            else:
+                a = args[0]._obj
+                seen.append((_name, a.tokens, a.tokens_frame_stride))
+            return _orig(*args)
+
+        monkeypatch.setattr(lib, name, spy)
+    for pad in (4, 1):  # 16-B aligned frames, and not (the forward's scalar path)
+        slab = torch.zeros(F, C * S + pad)
+        slab[:, :C * S] = case["tokens"].reshape(F, C * S)
+        slab = slab.cuda().requires_grad_()
+        tokens = slab[:, :C * S].view(F, C, S)
+        assert tokens.stride(0) == C * S + pad
+        c = lambda t: t.cuda().clone().requires_grad_()  # noqa: E731
+        pts, tr = c(case["points"]), c(case["transl"])
+        heads = {k: (c(w), c(b)) for k, (w, b) in case["heads"].items()}
+        wpl, wpt = ops.pack_head_weights(heads, C, "cuda", differentiable=True)
+        seen.clear()
+        rec = ops.triplane_decode_differentiable(tokens, wpl, wpt, pts, tr, R, case["radius"])
+        (rec * case["grec"].cuda()).sum().backward()
+        assert [s[0] for s in seen] == ["amav_triplane_project_region", "amav_triplane_decode_backward"]
+        for name, ptr, stride in seen:
+            assert ptr == tokens.data_ptr() and stride == C * S + pad, name
+        want, want_rec = gpu_grads(case)
+        assert torch.equal(rec.detach().cpu(), want_rec)
+        assert torch.equal(slab.grad[:, :C * S].reshape(F, C, S).cpu(), want["tokens"])
+        assert (slab.grad[:, C * S:] == 0).all()
+        got = dict(points=pts.grad, transl=tr.grad)
+        for k, (w, b) in heads.items():
+            got[k + ".weight"], got[k + ".bias"] = w.grad, b.grad
+        for k, v in got.items():
+            assert torch.equal(v.cpu(), want[k]), (pad, k)
 
 
 # ---- Renderer ------------------------------------------------------------------------------------------------------

@@ -153,3 +153,89 @@ def test_render_batch_restatement_shapes_and_activation():
     assert img.shape == (1, 2, 48, 48, 3) and img.min() >= 0 and img.max() <= 1
     dbg = R.render_batch(gauss, K, E, (48, 48), debug=True)   # scales 0.01, opacity 0.1 (renderer.py:535-537)
     assert not torch.equal(img, dbg)
+
+
+def _torch_frame(s, f=0, **kw):
+    """rasterize_torch of frame f of a random_scene in fp64, with leaf tensors for autograd."""
+    p = {k: s[k][f].double().clone().requires_grad_() for k in ("xyz", "rot", "scale", "opacity", "color")}
+    view, proj, tx, ty, _ = camera.camera_setup(s["K"][f].double(), s["E"][f].double(), s["H"], s["W"])
+    out = R.rasterize_torch(p["xyz"], p["rot"], p["scale"], p["opacity"], p["color"], view, proj, tx, ty,
+                            kw.pop("bg", (0.1, 0.6, 0.9)), s["H"], s["W"], **kw)
+    return p, out, (view, proj, tx, ty)
+
+
+def _grads(p, out, seed):
+    g = torch.Generator().manual_seed(seed)
+    w = torch.randn(out["color"].shape, generator=g, dtype=torch.float64)
+    wa = torch.randn(out["alpha"].shape, generator=g, dtype=torch.float64)
+    loss = (out["color"] * w).sum() + (out["alpha"] * wa).sum()
+    return dict(zip(p, torch.autograd.grad(loss, list(p.values()))))
+
+
+def test_alpha_clamp_grad_upstream_equals_torch_below_the_cap():
+    s = random_scene(31, 200, 40, 56, 1)
+    s["opacity"] = s["opacity"].clamp(max=0.95)  # alpha = opacity * exp(power) <= 0.95: the cap never engages
+    p0, o0, _ = _torch_frame(s)
+    p1, o1, _ = _torch_frame(s, alpha_clamp_grad="upstream")
+    for k in ("color", "alpha", "inv_depth", "radii"):
+        assert torch.equal(o0[k], o1[k]), k
+    g0, g1 = _grads(p0, o0, 32), _grads(p1, o1, 32)
+    for k in g0:
+        assert g0[k].abs().max() > 0 and torch.equal(g0[k], g1[k]), k
+    with pytest.raises(ValueError):
+        _torch_frame(s, alpha_clamp_grad="none")
+
+
+def test_alpha_clamp_grad_upstream_passes_the_capped_gradient_through():
+    """One opaque Gaussian (opacity 0.999): where opacity * exp(power) > 0.99 the values agree, torch's gradient of the
+    opacity through those pixels is zero and upstream's is not; elsewhere the two are the same."""
+    o = dict(xyz=[[0.0, 0.0, 2.5]], scale=[[1.5, 1.5, 1.5]], opacity=[0.999], color=[[0.2, 0.5, 0.8]])
+    view, proj, tx, ty, _ = camera.camera_setup(K64, torch.eye(4, dtype=torch.float64), 64, 64)
+    outs, gops = [], []
+    for mode in ("torch", "upstream"):
+        op = torch.tensor([[0.999]], dtype=torch.float64, requires_grad=True)
+        out = R.rasterize_torch(torch.tensor(o["xyz"], dtype=torch.float64), torch.tensor([[1.0, 0, 0, 0]],
+                                dtype=torch.float64), torch.tensor(o["scale"], dtype=torch.float64), op,
+                                torch.tensor(o["color"], dtype=torch.float64), view, proj, tx, ty, (1, 1, 1), 64, 64,
+                                alpha_clamp_grad=mode)
+        outs.append(out)
+        gops.append(torch.autograd.grad(out["alpha"].sum(), op)[0].item())
+    capped = (outs[0]["alpha"] >= 0.99 - 1e-12)
+    assert capped.sum() > 10
+    assert (outs[0]["alpha"] - outs[1]["alpha"]).abs().max() < 1e-15
+    assert (outs[0]["color"] - outs[1]["color"]).abs().max() < 1e-15
+    # d sum(alpha) / d opacity: upstream adds exactly exp(power) for every capped pixel
+    xs = torch.arange(64, dtype=torch.float64)
+    g = R.preprocess_torch(torch.tensor(o["xyz"], dtype=torch.float64), torch.tensor([[1.0, 0, 0, 0]],
+                           dtype=torch.float64), torch.tensor(o["scale"], dtype=torch.float64),
+                           torch.tensor([[0.999]], dtype=torch.float64), view, proj, tx, ty, 64, 64)
+    dx, dy = g["xy"][0, 0] - xs[None, :], g["xy"][0, 1] - xs[:, None]
+    A, B, Cc = g["conic"][0]
+    e = torch.exp(-0.5 * (A * dx * dx + Cc * dy * dy) - B * dx * dy)
+    assert gops[1] - gops[0] == pytest.approx(float(e[capped].sum()), rel=1e-9)
+
+
+@pytest.mark.parametrize("s", [0.6, 1.7])
+def test_scale_modifier_equals_scaled_scales(s):
+    sc = random_scene(33, 150, 48, 64, 1)
+    p0, o0, _ = _torch_frame(sc, scale_modifier=s)
+    scaled = dict(sc, scale=sc["scale"].double() * s)  # the modifier multiplies in fp64 too
+    p1, o1, _ = _torch_frame(scaled)
+    for k in ("color", "alpha", "inv_depth", "radii"):
+        assert torch.equal(o0[k], o1[k]), k
+    assert not torch.equal(o0["radii"], _torch_frame(sc)[1]["radii"])  # the modifier does change the scene
+    g0, g1 = _grads(p0, o0, 34), _grads(p1, o1, 34)
+    torch.testing.assert_close(g0["scale"], g1["scale"] * s, rtol=1e-12, atol=0)
+    for k in ("xyz", "rot", "opacity", "color"):
+        torch.testing.assert_close(g0[k], g1[k], rtol=1e-12, atol=1e-15)
+
+
+@pytest.mark.parametrize("s", [0.6, 1.7])
+def test_scale_modifier_torch_restatement_matches_c_oracle(s):
+    sc = random_scene(35, 200, 48, 64, 1)
+    _, t, (view, proj, tx, ty) = _torch_frame(sc, scale_modifier=s)
+    c = R.rasterize_c(sc["xyz"][0], sc["rot"][0], sc["scale"][0], sc["opacity"][0], sc["color"][0], view, proj, tx, ty,
+                      (0.1, 0.6, 0.9), 48, 64, scale_modifier=s, dtype=np.float64)
+    assert np.abs(c["color"] - t["color"].detach().numpy()).max() < 1e-12
+    assert np.abs(c["alpha"] - t["alpha"].detach().numpy()).max() < 1e-12
+    assert np.array_equal(c["radii"], t["radii"].numpy())

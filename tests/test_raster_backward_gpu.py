@@ -4,7 +4,8 @@ brute-force restatement oracle.rasterizer.rasterize_torch in float64 on the CPU.
 Decision flips between fp32 and fp64 are removed without widening a tolerance: the output gradient dL/d rgba is drawn
 at random and zeroed on the pixels the fp32 C oracle flags `unstable` (a blend decision within rounding of a threshold).
 Every gradient term is proportional to its pixel's incoming gradient, so flagged pixels contribute nothing.  Opacities
-stay <= 0.95, so the 0.99 clamp (passed through upstream, zeroed by torch) never engages, and the GPU forward's radii
+stay <= 0.95, so the 0.99 clamp (passed through upstream, zeroed by torch) never engages -- except in the tests that
+engage it on purpose and compare with rasterize_torch(alpha_clamp_grad="upstream") -- and the GPU forward's radii
 must equal the reference's, which (with unflagged pixels) makes both sides blend the same Gaussians per tile.
 
 Tolerance.  The backward recovers the colour behind Gaussian j front to back, as (C_total - C_through_j) + T_final bg
@@ -34,19 +35,20 @@ def scene_of(seed, N, H, W, F=1, **kw):
     return s
 
 
-def grad_out(scene, seed, bg=(1.0, 1.0, 1.0)):
+def grad_out(scene, seed, bg=(1.0, 1.0, 1.0), **settings):
     """Random dL/d rgba [F,H,W,4], zero on the pixels the fp32 oracle flags."""
     g = torch.Generator().manual_seed(seed)
     F, H, W = scene["xyz"].shape[0], scene["H"], scene["W"]
     go = torch.randn(F, H, W, 4, generator=g)
-    for f, r in enumerate(oracle_frames(scene, np.float32, bg=bg)):
+    for f, r in enumerate(oracle_frames(scene, np.float32, bg=bg, **settings)):
         go[f][torch.from_numpy(r["unstable"] != 0)] = 0.0
     return go
 
 
-def reference(scene, go, bg=(1.0, 1.0, 1.0), activations=False, clamp=False, raw=None):
+def reference(scene, go, bg=(1.0, 1.0, 1.0), activations=False, clamp=False, raw=None, scale_modifier=1.0,
+              alpha_clamp_grad="torch"):
     """fp64 CPU autograd of rasterize_torch (with torch's activations and output clamp when asked) -> gradients of
-    the five attributes [F,N,*] and the radii [F,N]."""
+    the five attributes [F,N,*] and the radii [F,N].  A frame in which no Gaussian is drawn has zero gradients."""
     from oracle import camera
     from oracle.rasterizer import rasterize_torch
 
@@ -63,14 +65,17 @@ def reference(scene, go, bg=(1.0, 1.0, 1.0), activations=False, clamp=False, raw
             c = torch.clamp(c, 0.0, 1.0)
         view, proj, tx, ty, _ = camera.camera_setup(scene["K"][f].double(), scene["E"][f].double(), scene["H"],
                                                     scene["W"])
-        out = rasterize_torch(p["xyz"], p["rot"], s, o, c, view, proj, tx, ty, bg, scene["H"], scene["W"])
+        out = rasterize_torch(p["xyz"], p["rot"], s, o, c, view, proj, tx, ty, bg, scene["H"], scene["W"],
+                              scale_modifier=scale_modifier, alpha_clamp_grad=alpha_clamp_grad)
         rgb = out["color"].permute(1, 2, 0)
         if clamp:
             rgb = rgb.clamp(0.0, 1.0)
         loss = (rgb * go[f, ..., :3].double()).sum() + (out["alpha"] * go[f, ..., 3].double()).sum()
-        gs = torch.autograd.grad(loss, [p[k] for k in NAMES])
-        for k, g in zip(NAMES, gs):
-            grads[k][f] = g
+        if loss.requires_grad:
+            gs = torch.autograd.grad(loss, [p[k] for k in NAMES], allow_unused=True)
+            for k, g in zip(NAMES, gs):
+                if g is not None:
+                    grads[k][f] = g
         radii.append(out["radii"])
     return grads, torch.stack(radii)
 
@@ -380,3 +385,285 @@ def test_refusals():
     # without gradients the inference paths are untouched: antialiasing still renders
     with torch.no_grad():
         aa(**{k: v.detach() for k, v in leaf.items()})
+
+
+# ---- branches the default scenes do not reach ----------------------------------------------------------------------
+def _rot(ax, ay):
+    """Extrinsic [4,4] rotating by ax about x, then ay about y."""
+    cx, sx, cy, sy = np.cos(ax), np.sin(ax), np.cos(ay), np.sin(ay)
+    Rx = torch.tensor([[1, 0, 0], [0, cx, -sx], [0, sx, cx]], dtype=torch.float64)
+    Ry = torch.tensor([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]], dtype=torch.float64)
+    E = torch.eye(4, dtype=torch.float64)
+    E[:3, :3] = Ry @ Rx
+    return E
+
+
+def _to_world(view_pts, E):
+    """View-space points [N,3] -> world space for the extrinsic E (view = E[:3,:3] x + E[:3,3])."""
+    return ((view_pts.double() - E[:3, 3]) @ E[:3, :3]).float()
+
+
+def _gaussians(g, n, scale, spread_opacity=True):
+    rot = torch.nn.functional.normalize(torch.randn(n, 4, generator=g), dim=-1)
+    sc = torch.exp(torch.randn(n, 3, generator=g) * 0.3 + float(np.log(scale)))
+    op = torch.sigmoid(torch.randn(n, 1, generator=g) * 1.5).clamp(max=0.95)
+    return rot, sc, op, torch.rand(n, 3, generator=g)
+
+
+def clamp_scene(seed, H=48, W=96, focal=80.0):
+    """Two frames, rotated extrinsics, a 2:1 image (limx = 1.3 tanfovx = 0.78, limy = 0.39): 150 large Gaussians
+    whose view-space |vx / tz| or |vy / tz| lies 2-50 % beyond the clamp, 60 just inside it (2-10 %), 60 central."""
+    g = torch.Generator().manual_seed(seed)
+    limx, limy = 1.3 * W / (2 * focal), 1.3 * H / (2 * focal)
+    u = lambda n, a, b: torch.rand(n, generator=g) * (b - a) + a  # noqa: E731
+    sign = lambda n: torch.where(torch.rand(n, generator=g) < 0.5, -1.0, 1.0)  # noqa: E731
+    F, n_out, n_in, n_mid = 2, 150, 60, 60
+    N = n_out + n_in + n_mid
+    scene = {k: [] for k in NAMES}
+    Es = []
+    for f in range(F):
+        E = _rot(0.15 + 0.1 * f, -0.3 + 0.5 * f)
+        E[:3, 3] = torch.tensor([0.05, -0.03, 0.1 * f], dtype=torch.float64)
+        rx, ry = u(N, -0.9, 0.9) * limx, u(N, -0.9, 0.9) * limy
+        axis = torch.randint(0, 3, (n_out,), generator=g)  # 0: x clamped, 1: y clamped, 2: both
+        out_x, out_y = axis != 1, axis != 0
+        rx[:n_out] = torch.where(out_x, sign(n_out) * u(n_out, 1.02, 1.5) * limx, rx[:n_out])
+        ry[:n_out] = torch.where(out_y, sign(n_out) * u(n_out, 1.02, 1.5) * limy, ry[:n_out])
+        ins = slice(n_out, n_out + n_in)
+        rx[ins] = sign(n_in) * u(n_in, 0.90, 0.98) * limx
+        ry[ins] = torch.where(torch.rand(n_in, generator=g) < 0.5, sign(n_in) * u(n_in, 0.90, 0.98) * limy, ry[ins])
+        rx[n_out + n_in:], ry[n_out + n_in:] = u(n_mid, -0.7, 0.7) * limx, u(n_mid, -0.7, 0.7) * limy
+        tz = u(N, 1.8, 3.2)
+        scene["xyz"].append(_to_world(torch.stack([rx * tz, ry * tz, tz], 1), E))
+        parts = [_gaussians(g, n_out, 0.3), _gaussians(g, n_in, 0.08), _gaussians(g, n_mid, 0.06)]
+        for i, k in enumerate(("rot", "scale", "opacity", "color")):
+            scene[k].append(torch.cat([p[i] for p in parts]))
+        Es.append(E.float())
+    scene = {k: torch.stack(v) for k, v in scene.items()}
+    K = torch.tensor([[focal, 0, W / 2], [0, focal, H / 2], [0, 0, 1.0]]).repeat(F, 1, 1)
+    scene.update(K=K, E=torch.stack(Es), H=H, W=W)
+    return scene
+
+
+def _view_ratios(scene):
+    """fp64 |vx / tz| / limx and |vy / tz| / limy per Gaussian [F,N] (the clamp engages above 1)."""
+    F, H, W = scene["xyz"].shape[0], scene["H"], scene["W"]
+    out = []
+    for f in range(F):
+        E, K = scene["E"][f].double(), scene["K"][f].double()
+        v = scene["xyz"][f].double() @ E[:3, :3].T + E[:3, 3]
+        limx, limy = 1.3 * W / (2 * K[0, 0]), 1.3 * H / (2 * K[1, 1])
+        out.append(((v[:, 0] / v[:, 2]).abs() / limx, (v[:, 1] / v[:, 2]).abs() / limy))
+    return torch.stack([o[0] for o in out]), torch.stack([o[1] for o in out])
+
+
+def test_offscreen_clamp():
+    """View-space means beyond 1.3 tanfov (the clamp of tx, ty: d/dvx = 0 there, d/dtz picks up g_tx * clamp)."""
+    scene = clamp_scene(461)
+    go = grad_out(scene, 462)
+    got, out = hip_grads(scene, go)
+    ref, ref_radii = reference(scene, go)
+    assert torch.equal(out["radii"].cpu().long(), ref_radii.long())
+    qx, qy = _view_ratios(scene)
+    clamped = (qx > 1.0) | (qy > 1.0)
+    assert not (((qx - 1).abs() < 0.02) | ((qy - 1).abs() < 0.02)).any()  # every mean 2 % or more from the boundary
+    drawn = ref_radii > 0
+    live = ref["xyz"].abs().amax(-1) > 0
+    n_clamped, n_inside = int((clamped & drawn & live).sum()), int((~clamped & (qx > 0.9) & drawn & live).sum())
+    print(f"clamp: {n_clamped} clamped Gaussians drawn ({int((qx > 1).sum())} in x, {int((qy > 1).sum())} in y), "
+          f"{n_inside} just inside")
+    assert n_clamped >= 100 and int((clamped & (qx > 1) & drawn).sum()) > 30 and int((clamped & (qy > 1) & drawn).sum()) > 30
+    assert n_inside >= 30
+    check_grads("off-screen clamp", got, ref)
+    # the clamped Gaussians' own gradients against their own scale (they are not swamped by the central ones)
+    sel = clamped & drawn
+    check_grads("off-screen clamp, clamped only", {k: v * sel[..., None] for k, v in got.items()},
+                {k: v * sel[..., None] for k, v in ref.items()})
+
+
+@pytest.mark.parametrize("modifier", [0.6, 1.7])
+def test_scale_modifier(modifier):
+    scene = scene_of(471, 300, 56, 72, 2)
+    go = grad_out(scene, 472, scale_modifier=modifier)
+    got, out = hip_grads(scene, go, scale_modifier=modifier)
+    ref, ref_radii = reference(scene, go, scale_modifier=modifier)
+    assert torch.equal(out["radii"].cpu().long(), ref_radii.long())
+    check_grads(f"scale_modifier {modifier}", got, ref)
+
+
+@pytest.mark.parametrize("bg", [(0.1, 0.6, 0.9), (0.0, 0.0, 0.0)])
+def test_background_colour(bg):
+    """T_final bg enters every Gaussian's colour-behind term, channel by channel."""
+    scene = scene_of(481, 300, 50, 70, 2)
+    go = grad_out(scene, 482, bg=bg)
+    got, out = hip_grads(scene, go, bg=bg)
+    ref, ref_radii = reference(scene, go, bg=bg)
+    assert torch.equal(out["radii"].cpu().long(), ref_radii.long())
+    check_grads(f"bg {bg}", got, ref)
+
+
+def test_opacity_above_the_cap():
+    """Opacities in (0.99, 1): alpha = min(0.99, opacity exp(power)) is capped near every centre, and the backward
+    passes the gradient straight through the cap (diff_gaussian_rasterization's convention)."""
+    scene = scene_of(491, 250, 50, 70, 2)
+    g = torch.Generator().manual_seed(492)
+    scene["opacity"] = 0.991 + 0.008 * torch.rand(scene["opacity"].shape, generator=g)
+    go = grad_out(scene, 493)
+    got, out = hip_grads(scene, go)
+    ref, ref_radii = reference(scene, go, alpha_clamp_grad="upstream")
+    assert torch.equal(out["radii"].cpu().long(), ref_radii.long())
+    torch_ref, _ = reference(scene, go)  # the convention matters here: torch's clamp gradient is another answer
+    assert (torch_ref["opacity"] - ref["opacity"]).abs().max() > 1e-2 * ref["opacity"].abs().max()
+    check_grads("opacity > 0.99", got, ref)
+
+
+def test_render_batch_activations_at_their_caps():
+    """render_batch(apply activations): sigmoid(raw opacity) above 0.99, raw scales on both sides of the 0.1 cap
+    (exp(s - 3.9) = 0.1 at s = 1.597), colours outside [0, 1]."""
+    from audio_motion_avatar_amd import ops, renderer
+
+    g = torch.Generator().manual_seed(501)
+    N, H, W = 500, 72, 88
+    u = lambda *s, a, b: torch.rand(*s, generator=g) * (b - a) + a  # noqa: E731
+    scale = torch.randn(1, N, 3, generator=g) * 0.5
+    scale[:, :60] = u(1, 60, 3, a=1.70, b=2.20)  # capped: exp(s - 3.9) in [0.111, 0.183]
+    scale[:, 60:120] = u(1, 60, 3, a=0.90, b=1.45)  # below the cap: [0.050, 0.086]
+    opacity = torch.randn(1, N, 1, generator=g)
+    opacity[:, ::3] = u(1, (N + 2) // 3, 1, a=4.8, b=7.0)  # sigmoid in [0.9918, 0.9991]
+    raw = dict(xyz=torch.randn(1, N, 3, generator=g) * 0.3 + torch.tensor([0, 0, 2.4]),
+               rot=torch.nn.functional.normalize(torch.randn(1, N, 4, generator=g), dim=-1),
+               scale=scale, opacity=opacity, color=torch.rand(1, N, 3, generator=g) * 1.6 - 0.3)
+    assert (raw["color"] < 0).any() and (raw["color"] > 1).any()
+    K = torch.tensor([[[88.0, 0, 44], [0, 88.0, 36], [0, 0, 1]]])
+    E = torch.eye(4)[None]
+    bg = (0.2, 0.5, 0.8)
+    act = dict(xyz=raw["xyz"], rot=raw["rot"], scale=torch.min(torch.exp(raw["scale"] - 3.9), torch.tensor(0.1)),
+               opacity=torch.sigmoid(raw["opacity"]), color=raw["color"].clamp(0, 1), K=K, E=E, H=H, W=W)
+    assert (act["opacity"] > 0.99).sum() > 100
+    go = grad_out(act, 502, bg=bg)
+    ref, ref_radii = reference(act, go, bg=bg, activations=True, clamp=True, raw=raw, alpha_clamp_grad="upstream")
+    p = {k: raw[k].cuda().requires_grad_() for k in NAMES}
+    args = types.SimpleNamespace(image_size=(H, W), rgb=True)
+    rgb, alpha = renderer.render_batch(p, K[None].cuda(), E[None].cuda(), args, bg_color=bg, return_alpha=True)
+    (torch.cat([rgb, alpha[..., None]], -1)[0] * go.cuda()).sum().backward()
+    got = {k: p[k].grad.cpu() for k in NAMES}
+    check_grads("render_batch at the caps", got, ref)
+    radii = ops.rasterize(*[raw[k].cuda() for k in NAMES], *ops.camera_from_intrinsics(K.cuda(), E.cuda(), H, W)[:3], H, W,
+                          apply_activations=True, want_radii=True)["radii"].cpu()
+    assert torch.equal(radii.long(), ref_radii.long())
+    drawn = ref_radii[0] > 0
+    capped = drawn[:60, None] & torch.ones(60, 3, dtype=torch.bool)
+    assert capped.sum() > 30 and (got["scale"][0, :60][capped] == 0).all()  # capped scales: no gradient
+    assert (ref["scale"][0, 60:120][drawn[60:120]].abs().amax(-1) > 0).float().mean() > 0.8
+
+
+def _culled_scene(seed, H=48, W=64):
+    """Three frames of 400: frame 0 = 300 drawn + 100 culled, frame 1 = all culled, frame 2 = 400 drawn.  Culled:
+    behind the camera (tz in [-2, -0.5]), in front of the near plane (tz in [0.03, 0.17]), or small and far outside
+    the image (|vx / tz| >= 2.5 tanfovx), so that no tile of the image is in their rectangle."""
+    g = torch.Generator().manual_seed(seed)
+    F, N = 3, 400
+    s = scene_of(seed, N, H, W, F)
+    s["E"] = torch.eye(4).repeat(F, 1, 1)  # view space = world space
+    tanx = W / (2 * float(s["K"][0, 0, 0]))
+    u = lambda n, a, b: torch.rand(n, generator=g) * (b - a) + a  # noqa: E731
+    kind = torch.full((F, N), -1)
+    kind[0, 300:] = torch.arange(100) % 3
+    kind[1] = torch.arange(N) % 3
+    for f in range(F):
+        for k in range(3):
+            m = kind[f] == k
+            n = int(m.sum())
+            if k == 0:
+                tz = u(n, -2.0, -0.5)
+            elif k == 1:
+                tz = u(n, 0.03, 0.17)
+            else:
+                tz = u(n, 1.5, 3.0)
+            rx = torch.where(torch.rand(n, generator=g) < 0.5, -1.0, 1.0) * u(n, 2.5, 4.0) * tanx if k == 2 \
+                else u(n, -0.3, 0.3)
+            s["xyz"][f, m] = torch.stack([rx * tz, u(n, -0.2, 0.2) * tz, tz], 1)
+            if k == 2:
+                s["scale"][f, m] = 0.01
+    return s, kind
+
+
+def test_culled_gaussians_and_empty_frame_have_exact_zero_gradients():
+    scene, kind = _culled_scene(511)
+    culled = kind >= 0
+    go = grad_out(scene, 512)
+    got, out = hip_grads(scene, go)
+    ref, ref_radii = reference(scene, go)
+    radii = out["radii"].cpu()
+    assert torch.equal(radii.long(), ref_radii.long())
+    assert (radii[culled] == 0).all() and (radii[0, ~culled[0]] > 0).sum() > 100 and (radii[2] > 0).sum() > 200
+    for k in range(3):
+        assert (kind == k).sum() >= 30
+    for k in NAMES:
+        v = got[k][culled]
+        assert torch.isfinite(got[k]).all(), k
+        assert (v == 0).all() and not torch.signbit(v).any(), f"{k}: culled Gaussians got a gradient"
+        assert (ref[k][culled] == 0).all(), k
+    # the empty frame: only the background, all gradients +0.0, next to drawn frames
+    assert torch.equal(out["rgba"][1].detach().cpu(), torch.tensor([1.0, 1.0, 1.0, 0.0]).expand(48, 64, 4))
+    keep = [0, 2]
+    check_grads("culled + empty frame", {k: v[keep] for k, v in got.items()}, {k: v[keep] for k, v in ref.items()})
+
+
+def test_every_frame_empty():
+    """max_frame = 0: no instance anywhere; the backward runs and returns +0.0 everywhere."""
+    from audio_motion_avatar_amd import ops
+
+    scene = scene_of(521, 60, 32, 48, 2)
+    scene["xyz"][..., 2] = -1.0  # all behind the camera
+    p = {k: scene[k].cuda().requires_grad_() for k in NAMES}
+    view, proj, tanfov = camera(scene)
+    fwd = ops.rasterize(*[scene[k].cuda() for k in NAMES], view, proj, tanfov, 32, 48, check_overflow=True)
+    assert fwd["max_frame"] == 0
+    out = ops.rasterize_differentiable(*[p[k] for k in NAMES], view, proj, tanfov, 32, 48, bg=(0.1, 0.6, 0.9))
+    assert torch.equal(out["rgba"].detach().cpu(), torch.tensor([0.1, 0.6, 0.9, 0.0]).expand(2, 32, 48, 4))
+    (out["rgba"] * torch.randn(2, 32, 48, 4, generator=torch.Generator().manual_seed(522)).cuda()).sum().backward()
+    for k in NAMES:
+        v = p[k].grad
+        assert v is not None and (v == 0).all() and not torch.signbit(v).any(), k
+
+
+def test_single_gaussian():
+    scene = scene_of(531, 1, 40, 56, 2)
+    scene["xyz"][:, 0] = torch.tensor([[0.05, -0.03, 2.5], [-0.08, 0.04, 2.2]])
+    scene["scale"][:, 0] = torch.tensor([[0.06, 0.03, 0.04], [0.02, 0.05, 0.03]])
+    go = grad_out(scene, 532)
+    got, out = hip_grads(scene, go)
+    ref, ref_radii = reference(scene, go)
+    assert torch.equal(out["radii"].cpu().long(), ref_radii.long()) and (ref_radii > 0).all()
+    check_grads("N=1", got, ref)
+
+
+def test_strided_record_inputs():
+    """The five attributes as column views of one [F,N,16] record tensor (ops.REC_* layout, as Renderer feeds them):
+    the same gradients, bit for bit, as contiguous copies, and the reference's."""
+    from audio_motion_avatar_amd import ops
+
+    scene = scene_of(541, 400, 56, 72, 2)
+    go = grad_out(scene, 542)
+    F, N = 2, 400
+    rec = torch.zeros(F, N, 16)
+    cols = {"xyz": (ops.REC_XYZ, 3), "opacity": (ops.REC_OPACITY, 1), "rot": (ops.REC_ROT, 4),
+            "scale": (ops.REC_SCALE, 3), "color": (ops.REC_COLOR, 3)}
+    for k, (o, w) in cols.items():
+        rec[..., o:o + w] = scene[k]
+    leaf = rec.cuda().requires_grad_()
+    views = {k: leaf[..., o:o + w] for k, (o, w) in cols.items()}
+    assert all(v.stride(1) == 16 and not v.is_contiguous() for v in views.values())
+    view, proj, tanfov = camera(scene)
+    out = ops.rasterize_differentiable(*[views[k] for k in NAMES], view, proj, tanfov, 56, 72)
+    (out["rgba"] * go.cuda()).sum().backward()
+    got = {k: leaf.grad[..., o:o + w].cpu() for k, (o, w) in cols.items()}
+    contiguous, out_c = hip_grads(scene, go)
+    assert torch.equal(out["rgba"].detach(), out_c["rgba"].detach())
+    for k in NAMES:
+        assert torch.equal(got[k], contiguous[k]), k
+    pad = leaf.grad[..., [11, 15]]
+    assert (pad == 0).all()
+    ref, _ = reference(scene, go)
+    check_grads("strided records", got, ref)

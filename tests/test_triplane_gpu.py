@@ -173,3 +173,61 @@ def test_projection_of_the_sampled_region_gives_the_same_gaussians(F, N, C, R, s
     assert not torch.isnan(part[0]).any()
     with pytest.raises(ops.AmavError):
         ops.triplane_project(tok, w_plane, R, region=(boxes[:, :5], radius))
+
+
+@pytest.mark.parametrize("C", [512, 768])
+def test_region_projection_with_many_channels_matches_oracle(C):
+    """C >= 512 with boxes: amav_triplane_project_region's 8-channel-group launch (the region path for wide slabs).
+    The texels it writes equal the full projection's bit for bit, and region projection + sample_decode matches the
+    oracle at the usual bound."""
+    from audio_motion_avatar_amd import ops
+    from oracle import triplane as orc
+
+    F, N, R, radius = 2, 1500, 32, 1.4
+    tokens, _, transl, params = make_case(C + 5, F, N, C, R)
+    g = torch.Generator().manual_seed(C)
+    points = torch.randn(F, 1, 3, generator=g) * 0.2 + torch.randn(F, N, 3, generator=g) * torch.tensor([0.12, 0.2, 0.06])
+    heads = {n: (params[f"gaussian_decoder.{n}.weight"], params[f"gaussian_decoder.{n}.bias"])
+             for n in ("xyz_layer", "rotation_layer", "scaling_layer", "opacity_layer", "shs_layer")}
+    w_plane, w_point = ops.pack_head_weights(heads, C, "cuda")
+    tok, pts = tokens.cuda(), points.cuda()
+    boxes = ops.points_bbox(pts)
+    part = torch.full((F, 3, R, R, 16), float("nan"), device="cuda")
+    ops.triplane_project(tok, w_plane, R, region=(boxes, radius), out=part)
+    full = ops.triplane_project(tok, w_plane, R)
+    written = ~torch.isnan(part[..., 0])
+    assert 0.02 < written.float().mean() < 0.7  # a real part of each plane
+    assert torch.equal(part[written], full[written])
+    rec = ops.triplane_sample_decode(part, pts, transl.cuda(), radius, w_point).cpu()
+    assert torch.isfinite(rec).all()  # every tap the points take lies in the written rectangle
+    planes = orc.tokens_to_planes(tokens[None], R)
+    ref = orc.decode_gaussians(params, planes, points, transl, radius)
+    ref64 = orc.decode_gaussians({k: v.double() for k, v in params.items()}, planes.double(), points.double(),
+                                 transl.double(), radius)
+    got = dict(xyz=rec[..., 0:3], opacity=rec[..., 3:4], rot=rec[..., 4:8], scale=rec[..., 8:11],
+               color=rec[..., 12:15])
+    for k, v in got.items():
+        err, err64 = (v - ref[k]).abs().max().item(), (v.double() - ref64[k]).abs().max().item()
+        own = (ref[k].double() - ref64[k]).abs().max().item()
+        print(f"region C={C} {k}: |rec - oracle| {err:.1e}, |rec - fp64| {err64:.1e} (oracle's own {own:.1e})")
+        assert err <= 2e-5, k
+        assert err64 <= max(2e-5, 4 * own), k
+
+
+@pytest.mark.parametrize("C,R", [(64, 5), (64, 6), (512, 6), (512, 10)])
+def test_region_is_ignored_when_r_is_not_a_multiple_of_4(C, R):
+    """R % 4 != 0: the rectangle cannot be walked in row quads, so boxes are ignored and every texel is projected,
+    equal to the call without boxes."""
+    from audio_motion_avatar_amd import ops
+
+    assert R % 4 != 0
+    F, N = 2, 300
+    tokens, points, _, params = make_case(R * 13 + C, F, N, C, R)
+    points = points * 0.2  # a small box: a real region would leave most of the plane unwritten
+    heads = {n: (params[f"gaussian_decoder.{n}.weight"], params[f"gaussian_decoder.{n}.bias"])
+             for n in ("xyz_layer", "rotation_layer", "scaling_layer", "opacity_layer", "shs_layer")}
+    w_plane, _ = ops.pack_head_weights(heads, C, "cuda")
+    tok = tokens.cuda()
+    part = torch.full((F, 3, R, R, 16), float("nan"), device="cuda")
+    ops.triplane_project(tok, w_plane, R, region=(ops.points_bbox(points.cuda()), 1.4), out=part)
+    assert torch.equal(part, ops.triplane_project(tok, w_plane, R))
