@@ -92,6 +92,15 @@ class PoseParts(ctypes.Structure):
     ]
 
 
+
+class LbsBackwardArgs(ctypes.Structure):
+    _fields_ = [
+        ("num_frames", ctypes.c_int32), ("tables", ctypes.POINTER(BodyTables)), ("parts", ctypes.POINTER(PoseParts)),
+        ("grad_vertices", ctypes.c_void_p), ("grad_full_pose", ctypes.c_void_p), ("grad_coeffs", ctypes.c_void_p),
+        ("skin_offsets", ctypes.c_void_p), ("skin_verts", ctypes.c_void_p), ("skin_weights", ctypes.c_void_p),
+        ("scratch", ctypes.c_void_p), ("scratch_bytes", ctypes.c_size_t),
+    ]
+
 # name -> (restype, argtypes); every symbol include/amav.h declares
 SIGNATURES = {
     "amav_version": (ctypes.c_char_p, []),
@@ -194,6 +203,10 @@ SIGNATURES = {
                                               c_float_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "amav_points_gather": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_float_p, ctypes.c_void_p,
                                           c_float_p, ctypes.c_void_p]),
+    "amav_lbs_backward_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.POINTER(BodyTables)]),
+    "amav_lbs_backward": (ctypes.c_int, [ctypes.POINTER(LbsBackwardArgs), ctypes.c_void_p]),
+    "amav_points_gather_backward": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_float_p, ctypes.c_void_p,
+                                                   ctypes.c_void_p, c_float_p, ctypes.c_void_p]),
     "amav_points_bbox": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_float_p, c_float_p, ctypes.c_void_p]),
     "amav_triplane_project_region": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_float_p, ctypes.c_int64,
                                                     c_float_p, c_float_p, c_float_p, ctypes.c_float, ctypes.c_void_p]),

@@ -240,6 +240,21 @@ def build_subdivision_table(faces: np.ndarray, num_verts: int, levels: int) -> n
     return np.concatenate([keep, mids], axis=0).astype(np.int32)
 
 
+def build_skin_transpose(skin_idx: np.ndarray, skin_w: np.ndarray, num_joints: int):
+    """The skinning table [V, k] (ids, weights) transposed for the LBS backward (csrc/lbs_backward.hip): offsets
+    [J+1] int32, then for every joint its vertices in ascending order (int32) and their weights (float32).  The zero
+    weights that pad skin_idx are left out."""
+    V, k = skin_idx.shape
+    nz = skin_w.reshape(-1) != 0
+    joint = skin_idx.reshape(-1)[nz].astype(np.int64)
+    vert = np.repeat(np.arange(V, dtype=np.int64), k)[nz]
+    order = np.lexsort((vert, joint))  # joint-major, ascending vertex
+    offsets = np.zeros(num_joints + 1, np.int64)
+    np.cumsum(np.bincount(joint, minlength=num_joints), out=offsets[1:])
+    return (offsets.astype(np.int32), vert[order].astype(np.int32),
+            skin_w.reshape(-1)[nz][order].astype(np.float32))
+
+
 class _BodyOutput:
     """`.vertices`, and `.full_pose` (smplx's output field; nothing on the path reads it) assembled on first use."""
 
@@ -299,6 +314,10 @@ class BodyModel(torch.nn.Module):
         self.register_buffer("_parents32", torch.as_tensor(self.parents.astype(np.int32)), persistent=False)
         self.register_buffer("_skin_idx", torch.as_tensor(skin_idx), persistent=False)
         self.register_buffer("_skin_w", torch.as_tensor(skin_w), persistent=False)
+        t_off, t_verts, t_w = build_skin_transpose(skin_idx, skin_w, J)
+        self.register_buffer("_skin_t_offsets", torch.as_tensor(t_off), persistent=False)
+        self.register_buffer("_skin_t_verts", torch.as_tensor(t_verts), persistent=False)
+        self.register_buffer("_skin_t_weights", torch.as_tensor(t_w), persistent=False)
         self.to(device)
 
     # ---- construction -------------------------------------------------------------------------------------------
@@ -325,7 +344,9 @@ class BodyModel(torch.nn.Module):
     # ---- tables for the C ABI ----------------------------------------------------------------------------------
     def device_tables(self) -> dict:
         tables = dict(v_template=self.v_template, blend=self._blend, j_template=self._j_template, j_dirs=self._j_dirs,
-                      parents=self._parents32, skin_idx=self._skin_idx, skin_w=self._skin_w)
+                      parents=self._parents32, skin_idx=self._skin_idx, skin_w=self._skin_w,
+                      skin_t_offsets=self._skin_t_offsets, skin_t_verts=self._skin_t_verts,
+                      skin_t_weights=self._skin_t_weights)
         if self._blend.is_cuda:
             # the blend table as two fp16 parts for the 16-bit matrix pipe (csrc/lbs.hip, skin_f16_kernel), built once
             # per device placement of the table
@@ -356,14 +377,19 @@ class BodyModel(torch.nn.Module):
         """Same keyword call as renderer.py:261-272; returns an object with `.vertices` [B,V,3] (and, computed on
         demand, smplx's `.full_pose`).  float32 arguments go to the joint-chain kernel as they are (it concatenates on
         load and adds pose_mean: smplx's torch.cat + add + torch.cat were three launches); other dtypes are assembled
-        with torch first, in their own dtype as smplx does."""
+        with torch first, in their own dtype as smplx does.  When grad mode is on and one of the nine tensors requires
+        grad, the same kernels run inside an autograd Function (ops.lbs_differentiable; the same vertices bit for bit)
+        whose backward is amav_lbs_backward."""
         B = global_orient.shape[0]
         pose = [global_orient.reshape(B, 3), body_pose.reshape(B, 63), jaw_pose.reshape(B, 3), leye_pose.reshape(B, 3),
                 reye_pose.reshape(B, 3), left_hand_pose.reshape(B, 45), right_hand_pose.reshape(B, 45)]
         coeff = [betas.reshape(B, -1), expression.reshape(B, -1)]
+        grad = torch.is_grad_enabled() and any(t.requires_grad for t in pose + coeff)
         if all(p.dtype == torch.float32 and (p.shape[1] == 1 or p.stride(1) == 1) for p in pose + coeff):
-            verts = ops.lbs_forward_parts(self.device_tables(), pose, coeff, pose_mean=self.pose_mean)
+            verts = (ops.lbs_differentiable if grad else ops.lbs_forward_parts)(self.device_tables(), pose, coeff,
+                                                                                pose_mean=self.pose_mean)
         else:
             fp = (torch.cat(pose, dim=1) + self.pose_mean).float()
-            verts = ops.lbs_forward(self.device_tables(), fp, torch.cat(coeff, dim=1).float())
+            verts = (ops.lbs_differentiable_full if grad else ops.lbs_forward)(self.device_tables(), fp,
+                                                                               torch.cat(coeff, dim=1).float())
         return _BodyOutput(verts, lambda: (torch.cat(pose, dim=1) + self.pose_mean).float())

@@ -66,6 +66,9 @@ class RendererConfig:
     subset_order: str = "random"      # "spatial": the same subset, stored along a Z-order curve of the rest pose
     body_seed: int = 42               # seed of the synthetic body used when smplx_model_path is absent
     pipeline_chunks: int = 1          # >1: frame groups on separate HIP streams (measured slower on MI355X: 1.53 -> 1.79 ms)
+    # training: gradients of a rendered-image loss reach the SMPL-X parameters (and an SMPLXDecoder that predicts them)
+    # through the LBS backward; off = SMPL-X parameters other than transl that require grad are refused
+    differentiable_smplx: bool = False
 
 
 @dataclass

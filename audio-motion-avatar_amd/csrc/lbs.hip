@@ -25,7 +25,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "amav_common.h"
+#include "lbs_common.h"
 
 #ifndef AMAV_LBS_ABLATE
 #define AMAV_LBS_ABLATE 0  /* diagnostic builds only (tools/ablate_lbs.sh) */
@@ -33,16 +33,6 @@
 
 namespace amav {
 namespace lbs {
-
-constexpr int kMaxJoints = 64;
-
-struct Tables {
-    int V, J, NC, KW, KB;  // KB = NC + (J-1)*9 blend rows
-    const float *v_template, *blend, *j_template, *j_dirs;
-    const int *parents, *skin_idx;
-    const float *skin_w;
-    const void *blend_split;  // fp16 x 2 form of `blend` (amav_lbs_prepare_blend_split) or NULL
-};
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
@@ -57,20 +47,6 @@ __device__ __forceinline__ void split2(float x, _Float16 &a, _Float16 &b) {
     b = (_Float16)__builtin_fmaf((float)a, -1.0f, x);
 }
 static inline int k16_of(int KB) { return (KB + 31) / 32 * 32; }  // table rows padded to whole 32-row chunks
-
-constexpr int kMaxFeatures = 64 + (kMaxJoints - 1) * 9;  // KB <= num_coeffs + (J - 1) * 9
-
-// Where the pose and the shape / expression coefficients of a frame come from: the keyword arguments of the SMPL-X
-// call as the caller holds them (global_orient, body_pose, jaw_pose, ... / betas, expression: renderer.py:261-272),
-// concatenated on load -- smplx's torch.cat + `full_pose += pose_mean` + torch.cat were three launches of ~16 us each
-// in front of a 12 us kernel.  One part each = an assembled full_pose / coefficient matrix.
-struct PoseSource {
-    int nparts, ncparts;
-    int first[8], cfirst[4];        // first joint / coefficient of every part
-    const float *part[8], *cpart[4];
-    long long stride[8], cstride[4];  // floats between frames
-    const float *mean;              // [J*3] added to the concatenated pose, or NULL
-};
 
 // One 64-lane block per frame (kSplit: per padded frame).  kSplit = the feature row of the frame goes straight into the
 // fp16 x 2 operand layout of skin_f16_kernel (featH, fscale) instead of the fp32 matrix featT.
@@ -322,12 +298,7 @@ __global__ __launch_bounds__(256) void skin_kernel(Tables t, int F, int Fpad, in
 //   feats  : featT[k][frame] rows straight from L2 (0.5 MB, hot), one chunk ahead in registers; rows past KB are zero
 //            (host pads featT), so the last chunk needs no special case.
 // The frame groups of a vertex tile are adjacent in block order and share an XCD (as in skin_kernel).
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr int kMfmaWaves = 4;                    // frame tiles (of 32) per block
-constexpr int kMfmaKC = 32;                      // table rows per staged chunk
-constexpr int kMfmaChunk4 = kMfmaKC * 96 / 4;    // float4 per chunk (768)
-constexpr int kMfmaKPad = 2 * kMfmaKC;           // zero rows appended to featT on this path
-
+// (f32x16 and the kMfma* constants: lbs_common.h)
 __global__ __launch_bounds__(64 * kMfmaWaves, 3) void skin_mfma_kernel(Tables t, int F, int Fpad, int ntiles,
                                                                     const float *__restrict__ featT,
                                                                     const float *__restrict__ A,
@@ -663,7 +634,7 @@ static int frame_pad(int F, int FT) { return FT ? (F + FT - 1) / FT * FT : (F + 
 using namespace amav;
 using namespace amav::lbs;
 
-static int validate_tables(const amav_body_tables *t, const char *who) {
+int amav::lbs::validate_tables(const amav_body_tables *t, const char *who) {
     AMAV_REQUIRE(t != nullptr, "%s: tables is NULL", who);
     AMAV_REQUIRE(t->num_verts > 0 && t->num_joints > 0 && t->num_joints <= kMaxJoints, "%s: bad V=%d J=%d", who,
                  t->num_verts, t->num_joints);
@@ -673,6 +644,48 @@ static int validate_tables(const amav_body_tables *t, const char *who) {
                  "%s: NULL table", who);
     AMAV_REQUIRE((reinterpret_cast<uintptr_t>(t->blend) & 15) == 0, "%s: blend table not 16-byte aligned", who);
     return AMAV_OK;
+}
+
+Tables amav::lbs::make_tables(const amav_body_tables *tb) {
+    Tables t;
+    t.V = tb->num_verts, t.J = tb->num_joints, t.NC = tb->num_coeffs, t.KW = tb->skin_k;
+    t.KB = t.NC + (t.J - 1) * 9;
+    t.v_template = tb->v_template, t.blend = tb->blend, t.j_template = tb->j_template, t.j_dirs = tb->j_dirs;
+    t.parents = tb->parents, t.skin_idx = tb->skin_idx, t.skin_w = tb->skin_w, t.blend_split = tb->blend_split;
+    return t;
+}
+
+int amav::lbs::pose_source(const amav_pose_parts *pp, const amav_body_tables *tb, PoseSource *out, const char *who) {
+    PoseSource &src = *out;
+    AMAV_REQUIRE(pp->num_pose_parts >= 1 && pp->num_pose_parts <= 8 && pp->num_coeff_parts >= 1 && pp->num_coeff_parts <= 4,
+                 "%s: %d pose parts (1..8), %d coefficient parts (1..4)", who, pp->num_pose_parts, pp->num_coeff_parts);
+    int joints = 0, ncoef = 0;
+    for (int q = 0; q < 8; ++q) {
+        const bool used = q < pp->num_pose_parts;
+        AMAV_REQUIRE(!used || (pp->pose[q] && pp->pose_joints[q] > 0 && pp->pose_stride[q] >= 3ll * pp->pose_joints[q]),
+                     "%s: pose part %d: NULL, no joints, or frame stride %lld < 3 * %d", who, q,
+                     (long long)pp->pose_stride[q], pp->pose_joints[q]);
+        src.first[q] = joints, src.part[q] = used ? pp->pose[q] : nullptr, src.stride[q] = used ? pp->pose_stride[q] : 0;
+        if (used) joints += pp->pose_joints[q];
+    }
+    for (int q = 0; q < 4; ++q) {
+        const bool used = q < pp->num_coeff_parts;
+        AMAV_REQUIRE(!used || (pp->coeff[q] && pp->coeff_count[q] > 0 && pp->coeff_stride[q] >= pp->coeff_count[q]),
+                     "%s: coefficient part %d: NULL, empty, or frame stride %lld < %d", who, q,
+                     (long long)pp->coeff_stride[q], pp->coeff_count[q]);
+        src.cfirst[q] = ncoef, src.cpart[q] = used ? pp->coeff[q] : nullptr, src.cstride[q] = used ? pp->coeff_stride[q] : 0;
+        if (used) ncoef += pp->coeff_count[q];
+    }
+    AMAV_REQUIRE(joints == tb->num_joints && ncoef == tb->num_coeffs,
+                 "%s: the parts hold %d joints / %d coefficients, the tables %d / %d", who, joints, ncoef,
+                 tb->num_joints, tb->num_coeffs);
+    src.nparts = pp->num_pose_parts, src.ncparts = pp->num_coeff_parts, src.mean = pp->pose_mean;
+    return AMAV_OK;
+}
+
+void amav::lbs::launch_joint_chain(const Tables &t, int F, int Fpad, const PoseSource &src, float *featT, float *A,
+                                   hipStream_t stream) {
+    joint_chain_kernel<false><<<F, 64, 0, stream>>>(t, F, Fpad, src, featT, A, 0, nullptr, nullptr, nullptr);
 }
 
 // AMAV_LBS=f32 keeps the fp32 MFMA kernel even when the tables carry a split blend table
@@ -746,41 +759,13 @@ extern "C" int amav_lbs_forward_parts(int F, const amav_body_tables *tb, const a
     if (int rc = validate_tables(tb, "amav_lbs_forward")) return rc;
     AMAV_REQUIRE(pp && out_vertices && workspace, "amav_lbs_forward: NULL pointer");
     PoseSource src;
-    {
-        AMAV_REQUIRE(pp->num_pose_parts >= 1 && pp->num_pose_parts <= 8 && pp->num_coeff_parts >= 1 && pp->num_coeff_parts <= 4,
-                     "amav_lbs_forward: %d pose parts (1..8), %d coefficient parts (1..4)", pp->num_pose_parts, pp->num_coeff_parts);
-        int joints = 0, ncoef = 0;
-        for (int q = 0; q < 8; ++q) {
-            const bool used = q < pp->num_pose_parts;
-            AMAV_REQUIRE(!used || (pp->pose[q] && pp->pose_joints[q] > 0 && pp->pose_stride[q] >= 3ll * pp->pose_joints[q]),
-                         "amav_lbs_forward: pose part %d: NULL, no joints, or frame stride %lld < 3 * %d", q,
-                         (long long)pp->pose_stride[q], pp->pose_joints[q]);
-            src.first[q] = joints, src.part[q] = used ? pp->pose[q] : nullptr, src.stride[q] = used ? pp->pose_stride[q] : 0;
-            if (used) joints += pp->pose_joints[q];
-        }
-        for (int q = 0; q < 4; ++q) {
-            const bool used = q < pp->num_coeff_parts;
-            AMAV_REQUIRE(!used || (pp->coeff[q] && pp->coeff_count[q] > 0 && pp->coeff_stride[q] >= pp->coeff_count[q]),
-                         "amav_lbs_forward: coefficient part %d: NULL, empty, or frame stride %lld < %d", q,
-                         (long long)pp->coeff_stride[q], pp->coeff_count[q]);
-            src.cfirst[q] = ncoef, src.cpart[q] = used ? pp->coeff[q] : nullptr, src.cstride[q] = used ? pp->coeff_stride[q] : 0;
-            if (used) ncoef += pp->coeff_count[q];
-        }
-        AMAV_REQUIRE(joints == tb->num_joints && ncoef == tb->num_coeffs,
-                     "amav_lbs_forward: the parts hold %d joints / %d coefficients, the tables %d / %d", joints, ncoef,
-                     tb->num_joints, tb->num_coeffs);
-        src.nparts = pp->num_pose_parts, src.ncparts = pp->num_coeff_parts, src.mean = pp->pose_mean;
-    }
+    if (int rc = pose_source(pp, tb, &src, "amav_lbs_forward")) return rc;
     float *featT = nullptr, *A = nullptr, *fscale = nullptr;
     _Float16 *featH = nullptr;
     const size_t need = lbs_ws(F, tb, &featT, &A, workspace, &featH, &fscale);
     if (workspace_bytes < need)
         return fail(AMAV_ERR_WORKSPACE, "amav_lbs_forward: workspace %zu < required %zu", workspace_bytes, need);
-    Tables t;
-    t.V = tb->num_verts, t.J = tb->num_joints, t.NC = tb->num_coeffs, t.KW = tb->skin_k;
-    t.KB = t.NC + (t.J - 1) * 9;
-    t.v_template = tb->v_template, t.blend = tb->blend, t.j_template = tb->j_template, t.j_dirs = tb->j_dirs;
-    t.parents = tb->parents, t.skin_idx = tb->skin_idx, t.skin_w = tb->skin_w, t.blend_split = tb->blend_split;
+    const Tables t = make_tables(tb);
     const int FT = frame_tile(F, t.KB);
     const int Fpad = frame_pad(F, FT);
     hipStream_t stream = static_cast<hipStream_t>(stream_);

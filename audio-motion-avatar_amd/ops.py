@@ -8,8 +8,8 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (AmavError, Attr, BodyTables, DecodeSource, PoseParts, RasterArgs, RasterBackwardArgs,
-                   TriplaneDecodeBackwardArgs, check)
+from ._lib import (AmavError, Attr, BodyTables, DecodeSource, LbsBackwardArgs, PoseParts, RasterArgs,
+                   RasterBackwardArgs, TriplaneDecodeBackwardArgs, check)
 
 SCALE_BIAS = 3.9    # src/models/renderer.py:428
 OPACITY_BIAS = 0.0  # src/models/renderer.py:429
@@ -539,12 +539,8 @@ def lbs_forward(tables: dict, full_pose, coeffs, want_transforms=False):
     return (verts, A) if want_transforms else verts
 
 
-def lbs_forward_parts(tables: dict, pose_parts, coeff_parts, pose_mean=None, want_transforms=False):
-    """lbs_forward with the pose / coefficients as the SMPL-X call's keyword arguments hold them (renderer.py:261-272):
-    `pose_parts` = float32 tensors [F, joints_p * 3] (rows may be strided, elements contiguous) concatenated in order,
-    `coeff_parts` likewise (betas, expression), `pose_mean` [J*3] is added to the concatenated pose (smplx's
-    full_pose += pose_mean).  No torch.cat / add launches: the joint-chain kernel reads the parts."""
-    ts = body_tables_struct(tables)
+def _pose_parts(ts, pose_parts, coeff_parts, pose_mean):
+    """-> (amav_pose_parts, tensors it points into, F) for the SMPL-X call's pose / coefficient parts."""
     F = int(pose_parts[0].shape[0])
     pp = PoseParts()
     keep = []
@@ -579,6 +575,17 @@ def lbs_forward_parts(tables: dict, pose_parts, coeff_parts, pose_mean=None, wan
         if pose_mean.numel() != ts.num_joints * 3:
             raise AmavError(f"lbs: pose_mean has {pose_mean.numel()} entries, expected {ts.num_joints * 3}")
         pp.pose_mean = pose_mean.data_ptr()
+        keep.append(pose_mean)
+    return pp, keep, F
+
+
+def lbs_forward_parts(tables: dict, pose_parts, coeff_parts, pose_mean=None, want_transforms=False):
+    """lbs_forward with the pose / coefficients as the SMPL-X call's keyword arguments hold them (renderer.py:261-272):
+    `pose_parts` = float32 tensors [F, joints_p * 3] (rows may be strided, elements contiguous) concatenated in order,
+    `coeff_parts` likewise (betas, expression), `pose_mean` [J*3] is added to the concatenated pose (smplx's
+    full_pose += pose_mean).  No torch.cat / add launches: the joint-chain kernel reads the parts."""
+    ts = body_tables_struct(tables)
+    pp, keep, F = _pose_parts(ts, pose_parts, coeff_parts, pose_mean)
     dev = keep[0].device
     nbytes = _lib.lib().amav_lbs_workspace_bytes(F, ctypes.byref(ts))
     if nbytes == 0:
@@ -592,6 +599,85 @@ def lbs_forward_parts(tables: dict, pose_parts, coeff_parts, pose_mean=None, wan
     return (verts, A) if want_transforms else verts
 
 
+def lbs_backward(tables: dict, pose_parts, coeff_parts, grad_vertices, pose_mean=None):
+    """Gradients of lbs_forward_parts(tables, pose_parts, coeff_parts, pose_mean) (amav_lbs_backward), given
+    grad_vertices = dL/d vertices [F,V,3] -> (grad_full_pose [F, J*3], grad_coeffs [F, n_coeff]): the gradient of the
+    concatenated pose (and of every pose part's columns: pose_mean passes it through) and of betas + expression.
+    `tables` needs the transposed skin table (skin_t_offsets / skin_t_verts / skin_t_weights, from
+    body_model.BodyModel.device_tables()).  For lbs_forward(full_pose, coeffs): pose_parts=[full_pose],
+    coeff_parts=[coeffs].  Deterministic, bitwise independent of how frames are split; no host sync."""
+    ts = body_tables_struct(tables)
+    pp, keep, F = _pose_parts(ts, pose_parts, coeff_parts, pose_mean)
+    grad_vertices = _contig(grad_vertices, "grad_vertices")
+    if tuple(grad_vertices.shape) != (F, ts.num_verts, 3):
+        raise AmavError(f"lbs_backward: grad_vertices {tuple(grad_vertices.shape)} != {(F, ts.num_verts, 3)}")
+    if any(k not in tables for k in ("skin_t_offsets", "skin_t_verts", "skin_t_weights")):
+        raise AmavError("lbs_backward: the tables lack the transposed skin table (BodyModel.device_tables())")
+    dev = grad_vertices.device
+    nbytes = _lib.lib().amav_lbs_backward_bytes(F, ctypes.byref(ts))
+    if nbytes == 0:
+        raise AmavError("amav_lbs_backward_bytes rejected the tables: " + _lib.lib().amav_last_error().decode())
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    gpose = torch.empty(F, ts.num_joints * 3, device=dev)
+    gcoef = torch.empty(F, ts.num_coeffs, device=dev)
+    skin = [_contig(tables["skin_t_offsets"], "skin_t_offsets", torch.int32),
+            _contig(tables["skin_t_verts"], "skin_t_verts", torch.int32),
+            _contig(tables["skin_t_weights"], "skin_t_weights")]
+    if skin[0].numel() != ts.num_joints + 1:
+        raise AmavError(f"lbs_backward: skin_t_offsets has {skin[0].numel()} entries, expected {ts.num_joints + 1}")
+    a = LbsBackwardArgs()
+    a.num_frames, a.tables, a.parts = F, ctypes.pointer(ts), ctypes.pointer(pp)
+    a.grad_vertices, a.grad_full_pose, a.grad_coeffs = grad_vertices.data_ptr(), gpose.data_ptr(), gcoef.data_ptr()
+    a.skin_offsets, a.skin_verts, a.skin_weights = (x.data_ptr() for x in skin)
+    a.scratch, a.scratch_bytes = scratch.data_ptr(), nbytes
+    check(_lib.lib().amav_lbs_backward(ctypes.byref(a), _stream()), "amav_lbs_backward")
+    return gpose, gcoef
+
+
+class _LBSParts(torch.autograd.Function):
+    """lbs_forward_parts with amav_lbs_backward as the backward: each part's gradient is its columns of the full-pose /
+    coefficient gradient (autograd sums a broadcast part over the frames and scatters a strided view)."""
+
+    @staticmethod
+    def forward(ctx, settings, *parts):
+        n = settings["num_pose_parts"]
+        tables, mean = settings["tables"], settings["pose_mean"]
+        verts = lbs_forward_parts(tables, list(parts[:n]), list(parts[n:]), pose_mean=mean)
+        ctx.settings = settings
+        ctx.save_for_backward(*parts)
+        return verts
+
+    @staticmethod
+    def backward(ctx, grad_vertices):
+        parts = ctx.saved_tensors
+        n = ctx.settings["num_pose_parts"]
+        if not any(ctx.needs_input_grad[1:]):
+            return (None,) * (1 + len(parts))
+        gpose, gcoef = lbs_backward(ctx.settings["tables"], list(parts[:n]), list(parts[n:]), grad_vertices.float(),
+                                    pose_mean=ctx.settings["pose_mean"])
+        out, col, ccol = [None], 0, 0
+        for q, p in enumerate(parts):
+            w = int(p.shape[1])
+            if q < n:
+                g, col = gpose[:, col:col + w], col + w
+            else:
+                g, ccol = gcoef[:, ccol:ccol + w], ccol + w
+            out.append(g if ctx.needs_input_grad[1 + q] else None)
+        return tuple(out)
+
+
+def lbs_differentiable(tables: dict, pose_parts, coeff_parts, pose_mean=None):
+    """lbs_forward_parts as a torch.autograd.Function: the same vertices bit for bit, with gradients to every part
+    (amav_lbs_backward).  `tables` from BodyModel.device_tables() (it carries the transposed skin table)."""
+    settings = dict(tables=tables, pose_mean=pose_mean, num_pose_parts=len(pose_parts))
+    return _LBSParts.apply(settings, *pose_parts, *coeff_parts)
+
+
+def lbs_differentiable_full(tables: dict, full_pose, coeffs):
+    """lbs_forward(full_pose [F, J*3], coeffs [F, n_coeff]) as a torch.autograd.Function (pose_mean already added)."""
+    return lbs_differentiable(tables, [full_pose], [coeffs])
+
+
 def points_gather(vertices, idx4):
     """vertices [F,V,3], idx4 [N,4] int32 -> points [F,N,3] (baked subdivision + subset, renderer.py:276-288)."""
     vertices = _contig(vertices, "vertices")
@@ -602,6 +688,60 @@ def points_gather(vertices, idx4):
     check(_lib.lib().amav_points_gather(F, V, N, vertices.data_ptr(), idx4.data_ptr(), out.data_ptr(), _stream()),
           "amav_points_gather")
     return out
+
+
+def points_gather_csr(idx4, num_verts):
+    """The gather table transposed (host-built once, like body_model.build_subdivision_table): idx4 [N,4] ->
+    (offsets int32 [V+1], entries int32 [4N]) on idx4's device: for every vertex the ids of the points whose slots name
+    it, ascending, once per slot.  Raises on ids outside [0, num_verts)."""
+    import numpy as np
+
+    ids = torch.as_tensor(idx4).detach().cpu().numpy().astype(np.int64).reshape(-1)
+    if ids.size and (ids.min() < 0 or ids.max() >= num_verts):
+        raise AmavError(f"points_gather_csr: vertex ids outside [0, {num_verts})")
+    n = ids.size // 4
+    order = np.argsort(ids, kind="stable")  # stable over the point-major slots: ascending point id per vertex
+    entries = np.repeat(np.arange(n, dtype=np.int64), 4)[order]
+    offsets = np.zeros(num_verts + 1, np.int64)
+    np.cumsum(np.bincount(ids, minlength=num_verts), out=offsets[1:])
+    dev = idx4.device if isinstance(idx4, torch.Tensor) else "cpu"
+    return (torch.as_tensor(offsets.astype(np.int32)).to(dev), torch.as_tensor(entries.astype(np.int32)).to(dev))
+
+
+def points_gather_backward(grad_points, csr, num_verts):
+    """grad_points [F,N,3] -> grad_vertices [F,V,3] (amav_points_gather_backward; `csr` = points_gather_csr(idx4, V)).
+    A vertex no point names gets exactly 0."""
+    grad_points = _contig(grad_points, "grad_points")
+    offsets = _contig(csr[0], "csr offsets", torch.int32)
+    entries = _contig(csr[1], "csr entries", torch.int32)
+    F, N, _ = grad_points.shape
+    if offsets.numel() != num_verts + 1 or entries.numel() != 4 * N:
+        raise AmavError(f"points_gather_backward: table of {offsets.numel() - 1} vertices / {entries.numel()} entries "
+                        f"does not match V={num_verts}, N={N}")
+    out = torch.empty(F, num_verts, 3, device=grad_points.device)
+    check(_lib.lib().amav_points_gather_backward(F, num_verts, N, grad_points.data_ptr(), offsets.data_ptr(),
+                                                 entries.data_ptr(), out.data_ptr(), _stream()),
+          "amav_points_gather_backward")
+    return out
+
+
+class _PointsGather(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, vertices, idx4, csr_offsets, csr_entries):
+        ctx.csr, ctx.num_verts = (csr_offsets, csr_entries), int(vertices.shape[1])
+        return points_gather(vertices, idx4)
+
+    @staticmethod
+    def backward(ctx, grad_points):
+        return points_gather_backward(grad_points.float(), ctx.csr, ctx.num_verts), None, None, None
+
+
+def points_gather_differentiable(vertices, idx4, csr=None):
+    """points_gather as a torch.autograd.Function (the same points bit for bit); csr = points_gather_csr(idx4, V),
+    built here (one host copy of idx4) when not given."""
+    if csr is None:
+        csr = points_gather_csr(idx4, int(vertices.shape[1]))
+    return _PointsGather.apply(vertices, idx4, csr[0], csr[1])
 
 
 # ------------------------------------------------------------------------------------------------------- triplane

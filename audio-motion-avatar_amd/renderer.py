@@ -121,6 +121,10 @@ class Renderer(nn.Module):
             idx = idx[_morton_order(self.smplx_model.v_template.detach().cpu(), torch.as_tensor(table)[idx])]
         self.subset_index = idx  # ids into the densified vertex list (kept for tests)
         self.register_buffer("_gather_idx", torch.as_tensor(table)[idx].contiguous(), persistent=False)
+        # the gather transposed, for its backward (differentiable_smplx)
+        offsets, entries = ops.points_gather_csr(self._gather_idx, self.smplx_model.num_verts)
+        self.register_buffer("_gather_csr_offsets", offsets, persistent=False)
+        self.register_buffer("_gather_csr_entries", entries, persistent=False)
 
     def _posed_vertices(self, smpl_params):
         B, T = smpl_params["global_orient"].shape[:2]
@@ -134,6 +138,9 @@ class Renderer(nn.Module):
         """renderer.py:245-290: SMPL-X LBS for all B*T frames, then densify + subset.  -> [B*T, N, 3]"""
         vertices = self._posed_vertices(smpl_params)
         if self.cfg.densify_smplx_verts:
+            if vertices.requires_grad:  # BodyModel's differentiable path (grad mode on, an SMPL-X tensor requires grad)
+                return ops.points_gather_differentiable(vertices, self._gather_idx,
+                                                        (self._gather_csr_offsets, self._gather_csr_entries))
             vertices = ops.points_gather(vertices, self._gather_idx)
         return vertices
 
@@ -180,11 +187,17 @@ class Renderer(nn.Module):
             self._packed = (version, ops.pack_head_weights(heads, self.cfg.triplane_feature_dim, device))
         return self._packed[1]
 
-    def _wants_grad(self, *tensors):
+    def _differentiable_smplx(self):
+        return bool(getattr(self.cfg, "differentiable_smplx", False))
+
+    def _wants_grad(self, *tensors, smpl_params=None):
         """Gradients are recorded through the decode when grad mode is on and the tokens, a head parameter or transl
-        (among `tensors`) requires grad; otherwise every call runs the inference path exactly as before."""
+        (among `tensors`) requires grad -- with cfg.differentiable_smplx, also any tensor of `smpl_params`; otherwise
+        every call runs the inference path exactly as before."""
         if not torch.is_grad_enabled():
             return False
+        if smpl_params is not None and self._differentiable_smplx():
+            tensors = tensors + tuple(v for v in smpl_params.values() if isinstance(v, torch.Tensor))
         return any(t is not None and t.requires_grad for t in tensors) or any(
             p.requires_grad for p in self.gaussian_decoder.parameters())
 
@@ -193,10 +206,13 @@ class Renderer(nn.Module):
         if hasattr(self, "point_encoder"):
             raise NotImplementedError("Renderer: the point refiner has no backward; disable gradients "
                                       "(torch.no_grad()) or use no_point_refiner=True")
+        if self._differentiable_smplx():
+            return
         bad = sorted(k for k, v in smpl_params.items() if k != "transl" and isinstance(v, torch.Tensor) and v.requires_grad)
         if bad:
             raise NotImplementedError(f"Renderer: SMPL-X parameters {', '.join(bad)} require grad, but LBS has no "
-                                      "backward (only transl is differentiable)")
+                                      "backward (only transl is differentiable; set differentiable_smplx=True in the "
+                                      "renderer config to train through LBS)")
 
     def _differentiable_decode(self, triplane_tokens, points, transl, region):
         w_plane, w_point = self._head_weights(differentiable=True)
@@ -233,19 +249,22 @@ class Renderer(nn.Module):
         inputs (ops.decode_source, for ops.rasterize(decode=...)) as a last value; `packed` is filled by the rasterizer.
         Other configurations decode here and return None in that place.
         Differentiable (ops.triplane_decode_differentiable; the same records) when grad mode is on and the tokens, a
-        head parameter or transl requires grad; `out`, `window_plan`, `defer_decode`, the point refiner and SMPL-X
-        parameters other than transl that require grad are refused then (NotImplementedError).
+        head parameter or transl requires grad (with cfg.differentiable_smplx: any SMPL-X parameter, whose gradient then
+        comes from the gather and LBS backwards); `out`, `window_plan`, `defer_decode`, the point refiner and -- without
+        that flag -- SMPL-X parameters other than transl that require grad are refused then (NotImplementedError).
         """
         F = triplane_tokens.shape[0]
-        if self._wants_grad(triplane_tokens, smpl_params["transl"]):
+        if self._wants_grad(triplane_tokens, smpl_params["transl"], smpl_params=smpl_params):
             self._refuse_under_grad(smpl_params)
             refused = [n for n, v in (("out", out), ("window_plan", window_plan)) if v is not None] + (
                 ["defer_decode"] if defer_decode else [])
             if refused:
                 raise NotImplementedError(f"gaussians_from_tokens: {', '.join(refused)} cannot be combined with gradients")
             side_result = side_work() if side_work is not None else None
-            with torch.no_grad():
-                points = self.get_smpl_vertices(smpl_params)  # gather = the indexed decode's own points, bit for bit
+            # gather = the indexed decode's own points, bit for bit; with differentiable_smplx they carry gradients to
+            # the SMPL-X parameters that require grad (BodyModel + points_gather_differentiable)
+            with torch.set_grad_enabled(self._differentiable_smplx()):
+                points = self.get_smpl_vertices(smpl_params)
             packed = self._differentiable_decode(triplane_tokens, points, smpl_params["transl"].reshape(F, 3).float(),
                                                  region=self.project_sampled_region)
             return packed if side_work is None else (packed, side_result)
@@ -306,7 +325,7 @@ class Renderer(nn.Module):
         K = cam_params["intrinsic"].reshape(F, 3, 3)
         E = cam_params["extrinsic"].reshape(F, 4, 4)
         chunks = max(1, min(int(chunks), F))
-        if self._wants_grad(triplane_tokens, smpl_params["transl"]):
+        if self._wants_grad(triplane_tokens, smpl_params["transl"], smpl_params=smpl_params):
             # differentiable: separate decode launch, one frame group, then render_batch's differentiable rasterizer
             refused = [n for n, v in (("workspaces", workspaces), ("wire", wire), ("window_plan", window_plan))
                        if v is not None] + (["chunks > 1"] if chunks > 1 else []) + (["fuse_decode"] if fuse_decode else [])
@@ -416,7 +435,7 @@ class Renderer(nn.Module):
             raise AmavError("Renderer.forward: no SMPL-X parameters (predict_smplx_params is off and no smpl_params_gt)")
 
         chunks = int(getattr(self.cfg, "pipeline_chunks", 1)) if B * T >= 32 else 1
-        grad = self._wants_grad(tokens, smpl_params["transl"])
+        grad = self._wants_grad(tokens, smpl_params["transl"], smpl_params=smpl_params)
         if grad:
             chunks = 1  # the differentiable path renders the frames as one group
         window_plan = None

@@ -289,6 +289,43 @@ int amav_lbs_forward_parts(int num_frames, const amav_body_tables *tables, const
 int amav_points_gather(int num_frames, int num_verts, int num_points, const float *vertices_dev,
                        const int32_t *idx_dev, float *out_points_dev, void *stream);
 
+/* SMPL-X LBS, backward: given grad_vertices = dL/d vertices [F,V,3] of amav_lbs_forward_parts (or amav_lbs_forward: one
+ * pose part, one coefficient part, no pose_mean), the gradients of the concatenated pose and coefficients:
+ *   grad_full_pose [F, J*3] (the pose_mean term passes the gradient through: it is also the gradient of every pose part's
+ *   columns) and grad_coeffs [F, n_coeff] (betas, then expression).  Both contiguous, overwritten.
+ * The derivative is that of the forward as oracle.lbs.lbs states it (Rodrigues with angle = ||r + 1e-8||, the kinematic
+ * chain, the pose-corrective and shape blend, the skinning), whichever forward kernel produced the vertices.
+ * skin_offsets [J+1] / skin_verts / skin_weights [skin_offsets[J]]: the skinning weights transposed -- for every joint
+ * its vertices in ascending order with their non-zero weights (body_model.build_skin_transpose).
+ * Deterministic: no float atomics; every sum has a fixed order that depends on V, J and the tables only, so gradients
+ * are bitwise the same from run to run and a frame's gradients do not depend on the other frames of the call.
+ * scratch: amav_lbs_backward_bytes(F, tables) bytes, 16-B aligned (0 = bad arguments).  Refused with an error code
+ * before any launch: NULL pointers, F <= 0, bad tables, parts that do not add up to J joints and n_coeff coefficients,
+ * scratch too small or misaligned.  No allocation and no host synchronisation. */
+typedef struct amav_lbs_backward_args {
+    int32_t num_frames;
+    const amav_body_tables *tables;
+    const amav_pose_parts *parts;   /* exactly those of the forward */
+    const float *grad_vertices;     /* [F,V,3] contiguous */
+    float *grad_full_pose;          /* [F,J*3] */
+    float *grad_coeffs;             /* [F,n_coeff] */
+    const int32_t *skin_offsets;    /* [J+1] */
+    const int32_t *skin_verts;      /* [skin_offsets[J]] */
+    const float *skin_weights;      /* [skin_offsets[J]] */
+    void *scratch;
+    size_t scratch_bytes;
+} amav_lbs_backward_args;
+size_t amav_lbs_backward_bytes(int num_frames, const amav_body_tables *tables);
+int amav_lbs_backward(const amav_lbs_backward_args *args, void *stream);
+
+/* amav_points_gather, backward: grad_vertices [F,V,3] (overwritten) from grad_points [F,N,3].  Every slot of idx[n]
+ * carries 1/4 of point n's gradient to its vertex.  csr_offsets [V+1] / csr_entries [4N]: the gather table transposed --
+ * for every vertex the ids of the points whose slots name it, ascending, once per slot (ops.points_gather_csr); a vertex
+ * no point names gets exactly +0.  One thread per (frame, vertex) sums in that order: deterministic, no atomics. */
+int amav_points_gather_backward(int num_frames, int num_verts, int num_points, const float *grad_points_dev,
+                                const int32_t *csr_offsets_dev, const int32_t *csr_entries_dev,
+                                float *grad_vertices_dev, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Triplane decode: F.grid_sample x 3 planes + the five Gaussian heads + construct_gaussians
  * (src/models/renderer.py:136,158,165-181,292-346), restructured for HBM: because the heads are linear in the
