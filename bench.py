@@ -14,8 +14,12 @@ checks that its block of the reassembled clip equals the frames it rendered (`co
 Other workloads: --workload full (BASELINE configs[2]/[3]: the autoregressive audio net in front), --workload stress
 (configs[4] per GPU).  stdout carries exactly the one JSON line (RCCL's banner and everything else go to stderr).
 
-Extra objects on the JSON line: `roofline` (the blend kernel, timed live with HIP events around the kernel on its
-own stream), `cpu_baseline` (the CPU oracle = a port, timed on this box's host cores on a bounded sample of the
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs, the JSON line with
+`roofline` (render / stress: the blend kernel, timed live with HIP events around the kernel on its own stream inside the
+timed steps).  Everything else it measures or checks comes with --full, after the timed region: the render / stress
+workloads first run one eager step through `Renderer.forward` and check that the pinned-workspace step equals it;
+`roofline_project` (stress) and `roofline` (full workload: the self-attention kernel), each timed in runs of its own;
+`cpu_baseline` (the CPU oracle = a port, timed on this box's host cores on a bounded sample of the
 same workload), `parity` (GPU vs oracle on that sample; all-pixel maxima and counts, and a `pass` flag: the process
 exits non-zero after printing the line when it is false) and -- default workload at N = 1 only -- `full_path`: a few
 250-frame steps of BASELINE configs[2] (the audio-driven path the >= 30 frames/s/GPU target is quoted on) run after
@@ -114,15 +118,22 @@ def parse():
     ap.add_argument("--frames", type=int, default=250, help="frames per GPU per step (shard size)")
     ap.add_argument("--gaussians", type=int, default=10000)
     ap.add_argument("--image", type=int, default=512)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: before the warm-up the "
+                         "Renderer.forward check; after the timed region the CPU baseline and parity against the oracle, "
+                         "rooflines timed in runs of their own and (default workload) the full_path, point_refiner, "
+                         "reference_defaults and stress objects; the --no-* options below leave parts of it out")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline` and `parity`")
     ap.add_argument("--no-full-path", action="store_true",
-                    help="default workload only: skip the `full_path` object (a few steps of configs[2] after the timed region)")
+                    help="default workload with --full: skip the `full_path` object (a few steps of configs[2] after the "
+                         "timed region)")
     ap.add_argument("--no-refiner", action="store_true",
-                    help="default workload only: skip the `point_refiner` object (PTv3 refiner, SURVEY 8(f) row 2)")
+                    help="default workload with --full: skip the `point_refiner` object (PTv3 refiner, SURVEY 8(f) row 2)")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="default workload only: skip the `reference_defaults` and `stress` objects")
-    ap.add_argument("--full-steps", type=int, default=2, help="steps (250-frame clips) of the `full_path` measurement")
-    ap.add_argument("--cpu-frames", type=int, default=8, help="frames of the workload timed on the CPU oracle")
+                    help="default workload with --full: skip the `reference_defaults` and `stress` objects")
+    ap.add_argument("--full-steps", type=int, default=2,
+                    help="with --full: steps (250-frame clips) of the `full_path` measurement")
+    ap.add_argument("--cpu-frames", type=int, default=8, help="with --full: frames of the workload timed on the CPU oracle")
     ap.add_argument("--chunks", type=int, default=1,
                     help="frame groups pipelined on separate HIP streams (1 is fastest; 2 costs 17 percent more time, 4 costs 56 percent)")
     ap.add_argument("--exchange", choices=["collective", "direct"], default=os.environ.get("AMAV_EXCHANGE", "collective"),
@@ -779,9 +790,10 @@ def run_full_workload(args, device, world, rank, dist):
                    "weights": "random init (transformer.proj_out scaled by 0.02 so the AR chain stays bounded)",
                    "instances_per_step": int(total), "output_finite": bool(torch.isfinite(rgba).all()),
                    "exchange": exchange_description(gather)},
-        "roofline": fp.attention_roofline(),
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        result["roofline"] = fp.attention_roofline()
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"], result["parity"] = fp.cpu_baseline_and_parity()
     if rank == 0:
         emit(result)
@@ -972,9 +984,10 @@ def main():
         stages[:] = [packed, rgba]
         return rgba.unsqueeze(0)
 
-    # one eager step: validates the drop-in entry point end to end and sizes the workspace
+    # the pinned step sizes the workspace; with --full an eager step through Renderer.forward first validates the
+    # drop-in entry point end to end
     with torch.no_grad():
-        ref_img = renderer(tokens, cam, smpl_tokens, smpl)[0]
+        ref_img = renderer(tokens, cam, smpl_tokens, smpl)[0] if args.full else None
         rgba = step()
         torch.cuda.synchronize()
         for ci, ws in enumerate(workspaces):
@@ -984,7 +997,7 @@ def main():
                 workspaces[ci] = ops.RasterWorkspace(fc, n, h, w, int(fc * max_frame * 1.25), device)
         rgba = step()
         assert not any(ws.status()[1] for ws in workspaces)
-        assert torch.equal(ref_img, rgba[..., :3]), "pinned-workspace step differs from Renderer.forward"
+        assert ref_img is None or torch.equal(ref_img, rgba[..., :3]), "pinned-workspace step differs from Renderer.forward"
         if gather is not None:
             # sizes the wire buffers (host sync + MAX all-reduce, outside the timed region)
             gather.calibrate(rgba, tile_hint=workspaces[0].tile_counts() if len(workspaces) == 1 else None)
@@ -1114,22 +1127,22 @@ def main():
                      "avg_launch_ms": blend_avg_ms, "algorithmic_bytes_per_launch": blend_bytes,
                      "issue": pmc_issue_fractions("render_kernel") if (F, N, H) == (250, 10000, 512) else None},
     }
-    if args.workload == "stress":  # the stage that dominates this configuration is the slab projection (HBM stream)
+    if args.full and args.workload == "stress":  # the stage that dominates this configuration: the slab projection
         with torch.no_grad():
             result["roofline_project"] = project_roofline(renderer, cfg, tokens[0], smpl, F)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         base, parity = cpu_baseline_and_parity(renderer, cfg, tokens, smpl, cam, stages, args.cpu_frames)
         result["cpu_baseline"] = base
         result["parity"] = parity
-    if rank == 0 and world == 1 and args.workload == "render" and not args.no_full_path:
+    if args.full and rank == 0 and world == 1 and args.workload == "render" and not args.no_full_path:
         torch.cuda.empty_cache()
         result["full_path"], fp = measure_full_path(args, device, rank, args.full_steps, 1, not args.no_cpu_baseline)
         result["full_path_exact_fp32"] = measure_full_path_exact_fp32(fp, result["full_path"], 1, not args.no_cpu_baseline)
         del fp
-    if rank == 0 and world == 1 and args.workload == "render" and not args.no_refiner and N == 10000:
+    if args.full and rank == 0 and world == 1 and args.workload == "render" and not args.no_refiner and N == 10000:
         torch.cuda.empty_cache()
         result["point_refiner"] = measure_point_refiner(args, device, not args.no_cpu_baseline)
-    if rank == 0 and world == 1 and args.workload == "render" and not args.no_extra_configs:
+    if args.full and rank == 0 and world == 1 and args.workload == "render" and not args.no_extra_configs:
         torch.cuda.empty_cache()
         result["reference_defaults"] = measure_reference_defaults(args, device, not args.no_cpu_baseline)
         fpath = result.get("full_path")
