@@ -35,6 +35,7 @@
 
 #include "amav_common.h"
 #include "decode_quad.h"
+#include "raster_project.h"
 #include "raster_workspace.h"
 
 namespace amav {
@@ -46,13 +47,11 @@ namespace raster {
 #ifndef AMAV_ABLATE
 #define AMAV_ABLATE 0  /* diagnostic builds of the blend kernel only (tools/): never set in the product */
 #endif
-constexpr int kTile = AMAV_TILE;
 constexpr int kRenderWavesPerSimd = 4;  // blend kernel: one-wave workgroups resident per SIMD (register cap)
 constexpr int kFusedMinFrames = 96;  // binning: shards below this project their Gaussians in a launch of their own
 constexpr int kSortCap = 512;      // keys a wave sorts in its LDS slice (4 KiB); longer lists go to sort_big
 constexpr int kBigLdsCap = 2048;   // keys a sort_big block sorts in LDS (16 KiB); longer lists are sorted in place
 constexpr int kBigBlocks = 1280;
-constexpr float kLog2e = 1.4426950408889634f;
 
 constexpr int kQueues = 8;    // one work queue per XCD (frame f feeds queue f % 8, so an XCD's L2 sees whole frames)
 constexpr int kBuckets = 17;  // list-length classes: bucket 0 = longer than 512, then 481..512, ..., 1..32
@@ -151,10 +150,6 @@ struct Params {
     } dec;
 };
 
-__device__ __forceinline__ const float *at(const amav_attr &a, int f, int i) {
-    return a.ptr + (long long)f * a.frame_stride + (long long)i * a.elem_stride;
-}
-
 // The value of `x`, opaque to the optimiser: what is derived from the result cannot be hoisted out of the enclosing loop.
 // The persistent kernels below are one long loop around a lot of inlined code; left alone, the compiler hoists every
 // lane-derived address and predicate out of it and then spills them (90 registers to scratch, whose reloads are
@@ -237,25 +232,22 @@ __device__ __forceinline__ uint4 preprocess_one(const Params &p, const GaussRec 
     uint4 rd = make_uint4(0u, 0u, 0u, 0u);
     const float4 rec0 = rec.r0, rec1 = rec.r1, rec2 = rec.r2, rec3 = rec.r3;
     const float px3 = rec0.x, py3 = rec0.y, pz3 = rec0.z;
-    const float vx = vm[0] * px3 + vm[4] * py3 + vm[8] * pz3 + vm[12];
-    const float vy = vm[1] * px3 + vm[5] * py3 + vm[9] * pz3 + vm[13];
-    const float vz = vm[2] * px3 + vm[6] * py3 + vm[10] * pz3 + vm[14];
+    const ViewPoint v = view_point(vm, px3, py3, pz3);
+    const float vx = v.x, vy = v.y, vz = v.z;
     if (!(vz > 0.2f)) return rd;
-    const float hx_ = pm[0] * px3 + pm[4] * py3 + pm[8] * pz3 + pm[12];
-    const float hy_ = pm[1] * px3 + pm[5] * py3 + pm[9] * pz3 + pm[13];
-    const float hw = pm[3] * px3 + pm[7] * py3 + pm[11] * pz3 + pm[15];
-    const float pw = 1.0f / (hw + 0.0000001f);
-    const float ppx = hx_ * pw, ppy = hy_ * pw;
+    const ClipPoint cp = clip_point(pm, px3, py3, pz3);
+    const float ppx = cp.ppx, ppy = cp.ppy;
 
     const float r = rec1.x, x = rec1.y, y = rec1.z, z = rec1.w;
     float s0 = rec2.x, s1 = rec2.y, s2 = rec2.z;
     float opacity = rec0.w;
     float c0 = rec3.x, c1 = rec3.y, c2 = rec3.z;
     if (p.apply_activations) {
-        s0 = fminf(expf(s0 - p.scale_bias), p.scale_max);
-        s1 = fminf(expf(s1 - p.scale_bias), p.scale_max);
-        s2 = fminf(expf(s2 - p.scale_bias), p.scale_max);
-        opacity = 1.0f / (1.0f + expf(-(opacity - p.opacity_bias)));
+        float e;
+        s0 = scale_act(s0, p.scale_bias, p.scale_max, e);
+        s1 = scale_act(s1, p.scale_bias, p.scale_max, e);
+        s2 = scale_act(s2, p.scale_bias, p.scale_max, e);
+        opacity = opacity_act(opacity, p.opacity_bias);
         c0 = fminf(fmaxf(c0, 0.0f), 1.0f);
         c1 = fminf(fmaxf(c1, 0.0f), 1.0f);
         c2 = fminf(fmaxf(c2, 0.0f), 1.0f);
@@ -264,19 +256,7 @@ __device__ __forceinline__ uint4 preprocess_one(const Params &p, const GaussRec 
     s1 *= p.scale_modifier;
     s2 *= p.scale_modifier;
 
-    // Sigma3D = R diag(s)^2 R^T
-    const float R00 = 1.f - 2.f * (y * y + z * z), R01 = 2.f * (x * y - r * z), R02 = 2.f * (x * z + r * y);
-    const float R10 = 2.f * (x * y + r * z), R11 = 1.f - 2.f * (x * x + z * z), R12 = 2.f * (y * z - r * x);
-    const float R20 = 2.f * (x * z - r * y), R21 = 2.f * (y * z + r * x), R22 = 1.f - 2.f * (x * x + y * y);
-    const float M00 = s0 * R00, M01 = s0 * R10, M02 = s0 * R20;
-    const float M10 = s1 * R01, M11 = s1 * R11, M12 = s1 * R21;
-    const float M20 = s2 * R02, M21 = s2 * R12, M22 = s2 * R22;
-    const float S00 = M00 * M00 + M10 * M10 + M20 * M20;
-    const float S01 = M00 * M01 + M10 * M11 + M20 * M21;
-    const float S02 = M00 * M02 + M10 * M12 + M20 * M22;
-    const float S11 = M01 * M01 + M11 * M11 + M21 * M21;
-    const float S12 = M01 * M02 + M11 * M12 + M21 * M22;
-    const float S22 = M02 * M02 + M12 * M12 + M22 * M22;
+    const Cov3 cv = cov3d(r, x, y, z, s0, s1, s2);
 
     // EWA splat: cov2D = (J Wv) Sigma (J Wv)^T
     const float focal_x = (float)p.W / (2.0f * tanx), focal_y = (float)p.H / (2.0f * tany);
@@ -292,15 +272,10 @@ __device__ __forceinline__ uint4 preprocess_one(const Params &p, const GaussRec 
         T0[b] = J00 * vm[b * 4 + 0] + J02 * vm[b * 4 + 2];
         T1[b] = J11 * vm[b * 4 + 1] + J12 * vm[b * 4 + 2];
     }
-    const float U00 = S00 * T0[0] + S01 * T0[1] + S02 * T0[2];
-    const float U01 = S01 * T0[0] + S11 * T0[1] + S12 * T0[2];
-    const float U02 = S02 * T0[0] + S12 * T0[1] + S22 * T0[2];
-    const float U10 = S00 * T1[0] + S01 * T1[1] + S02 * T1[2];
-    const float U11 = S01 * T1[0] + S11 * T1[1] + S12 * T1[2];
-    const float U12 = S02 * T1[0] + S12 * T1[1] + S22 * T1[2];
-    float ca = T0[0] * U00 + T0[1] * U01 + T0[2] * U02;
-    const float cb = T0[0] * U10 + T0[1] * U11 + T0[2] * U12;
-    float cc = T1[0] * U10 + T1[1] * U11 + T1[2] * U12;
+    const Cov2 cov = cov2d(cv.S, T0, T1);
+    float ca = cov.ca;
+    const float cb = cov.cb;
+    float cc = cov.cc;
 
     const float det_cov = ca * cc - cb * cb;
     ca += 0.3f;
@@ -310,7 +285,7 @@ __device__ __forceinline__ uint4 preprocess_one(const Params &p, const GaussRec 
     if (p.antialiasing) h_scale = sqrtf(fmaxf(0.000025f, det_cov / det));
     // upstream skips det == 0.  det < 0 cannot happen for a real covariance (J W Sigma W^T J^T is positive
     // semi-definite and 0.3 is added to its diagonal); a record that gets there by overflow / NaN inputs is dropped too
-    // (upstream would blend an indefinite form), which is what lets the blend kernel use the square-root form below.
+    // (upstream would blend an indefinite form), which is what lets the blend kernel use the square-root form (conic).
     if (!(det > 0.0f)) return rd;
     const float det_inv = 1.0f / det;
     const float mid = 0.5f * (ca + cc);
@@ -347,18 +322,9 @@ __device__ __forceinline__ uint4 preprocess_one(const Params &p, const GaussRec 
     if (cx1 <= cx0 || cy1 <= cy0) cx0 = cx1 = cy0 = cy1 = 0;
     rd = make_uint4((unsigned)cx0 | ((unsigned)cy0 << 16), (unsigned)cx1 | ((unsigned)cy1 << 16), __float_as_uint(vz),
                     (unsigned)(int)my_radius);
-    // The blend needs log2(alpha) = log2(op) + log2(e) * power, power = -1/2 (A dx^2 + C dy^2) - B dx dy with the conic
-    // (A, B, C) = (cc, -cb, ca) / det.  The quadratic form is stored as its Cholesky factor: with k = log2(e) / 2,
-    //     -log2(e) * power = (a dx + b dy)^2 + (c dy)^2,   a = sqrt(k A), b = k B / a, c = sqrt(k (C - B^2 / A)) = sqrt(k / cc)
-    // (A C - B^2 = 1 / det).  A sum of squares is >= 0 in floating point too, so upstream's "power > 0 -> skip" guard
-    // (which only ever fires on rounding noise of ITS three-term form) has nothing left to catch, and the blend kernel
-    // evaluates log2(alpha) in five fused multiply-adds (blend_px).
-    const float kk = 0.5f * kLog2e;
-    const float qa = sqrtf(kk * (cc * det_inv));
-    const float qb = -(kk * (cb * det_inv)) / qa;
-    const float qc = sqrtf(kk / cc);
-    g[0] = make_float4(pix_x, pix_y, qa, qb);
-    g[1] = make_float4(qc, log2f(op), c0, c1);
+    const Conic q = conic(cb, cc, det_inv);  // the quadratic form as its Cholesky factor
+    g[0] = make_float4(pix_x, pix_y, q.qa, q.qb);
+    g[1] = make_float4(q.qc, log2f(op), c0, c1);
     g[2] = make_float4(c2, 1.0f / vz, bx, by);
     return rd;
 }
@@ -1757,18 +1723,12 @@ __global__ __launch_bounds__(64, kRenderWavesPerSimd) void render_kernel(Params 
                     // quadrant mask of this ln's Gaussian: which live 8x8 quadrants its alpha >= 1/255 box can reach
                     int qm = 0;
                     if (base + ln < n) {
-                        const bool hx0 = (g0.x + g2.z >= X0f) & (g0.x - g2.z <= X0f + 7.f);
-                        const bool hx1 = (g0.x + g2.z >= X0f + 8.f) & (g0.x - g2.z <= X0f + 15.f);
-                        const bool hy0 = (g0.y + g2.w >= Y0f) & (g0.y - g2.w <= Y0f + 7.f);
-                        const bool hy1 = (g0.y + g2.w >= Y0f + 8.f) & (g0.y - g2.w <= Y0f + 15.f);
-                        qm = (int)(hx0 & hy0) | ((int)(hx1 & hy0) << 1) | ((int)(hx0 & hy1) << 2) | ((int)(hx1 & hy1) << 3);
-                        qm &= qalive;
+                        qm = quad_mask(g0, g2, X0f, Y0f) & qalive;
                     }
-                    // every ln stages its record at its own (= sorted) slot, moved into the tile's frame:
-                    // u = qa (x - px) + qb (y - py) = k0 - qa lx - qb ly with k0 = qa (x - X0) + qb (y - Y0); v likewise
+                    // every ln stages its record at its own (= sorted) slot, moved into the tile's frame (tile_k)
                     if (qm != 0) {
-                        const float rx = g0.x - X0f, ry = g0.y - Y0f;
-                        L.geo[ln] = make_float4(fmaf(g0.z, rx, g0.w * ry), g1.x * ry, g0.z, g0.w);
+                        const float2 k = tile_k(g0, g1, X0f, Y0f);
+                        L.geo[ln] = make_float4(k.x, k.y, g0.z, g0.w);
                         *reinterpret_cast<float2 *>(&L.geo2[ln]) = make_float2(g1.x, g1.y);
                         L.col[ln] = make_float4(g1.z, g1.w, g2.x, g2.y);
                     }

@@ -27,17 +27,20 @@
 #include <cstddef>
 
 #include "amav_common.h"
+#include "raster_project.h"
 #include "raster_workspace.h"
 
 namespace amav {
 namespace raster_bwd {
 
-constexpr int kTile = AMAV_TILE;
+using raster::at;
+using raster::kLog2e;
+using raster::kTile;
+
 constexpr int kChunk = 64;       // Gaussians staged per round
 constexpr int kLocalSort = 512;  // lists up to this length are sorted by the block (the forward's kSortCap)
 constexpr int kComp = 9;         // per-instance partials: dx, dy, dqa, dqb, dqc, dL, dr, dg, db
 constexpr float kLn2 = 0.6931471805599453f;
-constexpr float kLog2e = 1.4426950408889634f;
 
 struct Params {
     int F, N, H, W, gx, gy, T;
@@ -55,10 +58,6 @@ struct Params {
     int *seg;                   // [F*N] first slot of each Gaussian inside its frame
     float *slots;               // [F][S][kComp]
 };
-
-__device__ __forceinline__ const float *at(const amav_attr &a, int f, int i) {
-    return a.ptr + (long long)f * a.frame_stride + (long long)i * a.elem_stride;
-}
 
 __device__ __forceinline__ int rect_area(uint4 rd) {
     if (rd.w == 0u) return 0;
@@ -208,16 +207,12 @@ __global__ __launch_bounds__(256) void tile_grad_kernel(Params p) {
             if (k < n) {
                 const unsigned id = local ? L.order[k] : sorted[k];
                 const float4 g0 = geom[(size_t)id * 3], g1 = geom[(size_t)id * 3 + 1], g2 = geom[(size_t)id * 3 + 2];
-                // the forward's staging: k0 = qa (x - X0) + qb (y - Y0) (one fma), k1 = qc (y - Y0)
-                const float rx = g0.x - X0f, ry = g0.y - Y0f;
-                L.geo[tid] = make_float4(fmaf(g0.z, rx, g0.w * ry), g1.x * ry, g0.z, g0.w);
+                // the forward's staging (raster_project.h)
+                const float2 k = raster::tile_k(g0, g1, X0f, Y0f);
+                L.geo[tid] = make_float4(k.x, k.y, g0.z, g0.w);
                 L.geo2[tid] = make_float4(g1.x, g1.y, g0.x, g0.y);
                 L.col[tid] = make_float4(g1.z, g1.w, g2.x, 0.f);
-                const bool hx0 = (g0.x + g2.z >= X0f) & (g0.x - g2.z <= X0f + 7.f);
-                const bool hx1 = (g0.x + g2.z >= X0f + 8.f) & (g0.x - g2.z <= X0f + 15.f);
-                const bool hy0 = (g0.y + g2.w >= Y0f) & (g0.y - g2.w <= Y0f + 7.f);
-                const bool hy1 = (g0.y + g2.w >= Y0f + 8.f) & (g0.y - g2.w <= Y0f + 15.f);
-                L.qmask[tid] = (int)(hx0 & hy0) | ((int)(hx1 & hy0) << 1) | ((int)(hx0 & hy1) << 2) | ((int)(hx1 & hy1) << 3);
+                L.qmask[tid] = raster::quad_mask(g0, g2, X0f, Y0f);
                 const uint4 rd = rectd[id];
                 const int cx0 = rd.x & 0xffff, cy0 = rd.x >> 16, cx1 = rd.y & 0xffff;
                 L.slot[tid] = seg[id] + (ty - cy0) * (cx1 - cx0) + (tx - cx0);
@@ -365,19 +360,16 @@ __global__ __launch_bounds__(256) void gauss_grad_kernel(Params p) {
         for (int k = 0; k < kComp; ++k) d[k] += sl[(size_t)s * kComp + k];
     const float g_px = d[0], g_py = d[1], g_qa = d[2], g_qb = d[3], g_qc = d[4], g_L = d[5];
 
-    // ---- the forward's projection, recomputed in preprocess_one's operation order
+    // ---- the forward's projection: preprocess_one's stages (raster_project.h); J is restated in its operation order
     const float *vm = p.view + f * 16, *pm = p.proj + f * 16;
     const float tanx = p.tanfov[2 * f], tany = p.tanfov[2 * f + 1];
     const float *m_ = at(p.means3d, f, i), *q_ = at(p.rotations, f, i), *s_ = at(p.scales, f, i);
     const float *c_ = at(p.colors, f, i);
     const float px3 = m_[0], py3 = m_[1], pz3 = m_[2];
-    const float vx = vm[0] * px3 + vm[4] * py3 + vm[8] * pz3 + vm[12];
-    const float vy = vm[1] * px3 + vm[5] * py3 + vm[9] * pz3 + vm[13];
-    const float vz = vm[2] * px3 + vm[6] * py3 + vm[10] * pz3 + vm[14];
-    const float hx_ = pm[0] * px3 + pm[4] * py3 + pm[8] * pz3 + pm[12];
-    const float hy_ = pm[1] * px3 + pm[5] * py3 + pm[9] * pz3 + pm[13];
-    const float hw = pm[3] * px3 + pm[7] * py3 + pm[11] * pz3 + pm[15];
-    const float pw = 1.0f / (hw + 0.0000001f);
+    const raster::ViewPoint vp = raster::view_point(vm, px3, py3, pz3);
+    const float vx = vp.x, vy = vp.y, vz = vp.z;
+    const raster::ClipPoint cp = raster::clip_point(pm, px3, py3, pz3);
+    const float hx_ = cp.hx, hy_ = cp.hy, pw = cp.pw;
     const float r = q_[0], x = q_[1], y = q_[2], z = q_[3];
     const float sraw[3] = {s_[0], s_[1], s_[2]};
     float sact[3], sexp[3];
@@ -386,23 +378,13 @@ __global__ __launch_bounds__(256) void gauss_grad_kernel(Params p) {
     const float craw[3] = {c_[0], c_[1], c_[2]};
     for (int k = 0; k < 3; ++k) sact[k] = sraw[k], sexp[k] = 0.f;
     if (p.apply_activations) {
-        for (int k = 0; k < 3; ++k) {
-            sexp[k] = expf(sraw[k] - p.scale_bias);
-            sact[k] = fminf(sexp[k], p.scale_max);
-        }
-        opacity = 1.0f / (1.0f + expf(-(oraw - p.opacity_bias)));
+        for (int k = 0; k < 3; ++k) sact[k] = raster::scale_act(sraw[k], p.scale_bias, p.scale_max, sexp[k]);
+        opacity = raster::opacity_act(oraw, p.opacity_bias);
     }
     const float s0 = sact[0] * p.scale_modifier, s1 = sact[1] * p.scale_modifier, s2 = sact[2] * p.scale_modifier;
-    const float Rm[3][3] = {{1.f - 2.f * (y * y + z * z), 2.f * (x * y - r * z), 2.f * (x * z + r * y)},
-                            {2.f * (x * y + r * z), 1.f - 2.f * (x * x + z * z), 2.f * (y * z - r * x)},
-                            {2.f * (x * z - r * y), 2.f * (y * z + r * x), 1.f - 2.f * (x * x + y * y)}};
+    const raster::Cov3 cv = raster::cov3d(r, x, y, z, s0, s1, s2);
+    const float(&Rm)[3][3] = cv.R, (&M)[3][3] = cv.M, (&S)[3][3] = cv.S;  // M[k][a] = s_k R[a][k]; Sigma = M^T M
     const float sv[3] = {s0, s1, s2};
-    float M[3][3];  // M[k][a] = s_k R[a][k]; Sigma = M^T M
-    for (int k = 0; k < 3; ++k)
-        for (int a = 0; a < 3; ++a) M[k][a] = sv[k] * Rm[a][k];
-    float S[3][3];
-    for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) S[a][b] = M[0][a] * M[0][b] + M[1][a] * M[1][b] + M[2][a] * M[2][b];
     const float focal_x = (float)p.W / (2.0f * tanx), focal_y = (float)p.H / (2.0f * tany);
     const float limx = 1.3f * tanx, limy = 1.3f * tany;
     const float tz = vz;
@@ -416,21 +398,14 @@ __global__ __launch_bounds__(256) void gauss_grad_kernel(Params p) {
         T0[b] = J00 * vm[b * 4 + 0] + J02 * vm[b * 4 + 2];
         T1[b] = J11 * vm[b * 4 + 1] + J12 * vm[b * 4 + 2];
     }
-    float ST0[3], ST1[3];  // Sigma T0, Sigma T1
-    for (int a = 0; a < 3; ++a) {
-        ST0[a] = S[a][0] * T0[0] + S[a][1] * T0[1] + S[a][2] * T0[2];
-        ST1[a] = S[a][0] * T1[0] + S[a][1] * T1[1] + S[a][2] * T1[2];
-    }
-    const float ca = T0[0] * ST0[0] + T0[1] * ST0[1] + T0[2] * ST0[2] + 0.3f;
-    const float cb = T0[0] * ST1[0] + T0[1] * ST1[1] + T0[2] * ST1[2];
-    const float cc = T1[0] * ST1[0] + T1[1] * ST1[1] + T1[2] * ST1[2] + 0.3f;
+    const raster::Cov2 cov = raster::cov2d(S, T0, T1);
+    const float(&ST0)[3] = cov.ST0, (&ST1)[3] = cov.ST1;  // Sigma T0, Sigma T1
+    const float ca = cov.ca + 0.3f, cb = cov.cb, cc = cov.cc + 0.3f;
     const float det = ca * cc - cb * cb;
     const float det_inv = 1.0f / det;
     const float kk = 0.5f * kLog2e;
-    const float A = cc * det_inv;
-    const float qa = sqrtf(kk * A);
-    const float qb = -(kk * (cb * det_inv)) / qa;
-    const float qc = sqrtf(kk / cc);
+    const raster::Conic q = raster::conic(cb, cc, det_inv);
+    const float A = q.A, qa = q.qa, qb = q.qb, qc = q.qc;
 
     // ---- Cholesky form -> conic (A, B) -> 2D covariance (the +0.3 dilation has derivative 1)
     const float gA = g_qa * (kk / (2.0f * qa)) - g_qb * (qb / (2.0f * A));

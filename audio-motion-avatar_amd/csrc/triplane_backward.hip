@@ -4,7 +4,7 @@
 // the [N, 3C] feature tensor never exists here either.  Five launches, no float atomics, no host synchronisation:
 //
 //   point_kernel      one thread per (frame, point), blocks never straddle frames.  Recomputes the sixteen raw head
-//                     outputs with the forward's exact arithmetic (its twelve taps of the kept projected planes), takes
+//                     outputs with the forward's own functions (decode_quad.h: the twelve taps, group_raw), takes
 //                     the epilogue's backward (F.normalize with its eps branch, s (1 - s) of the sigmoid) -> gRaw
 //                     [F,N,16] (scratch); dPoints = direct xyz term + W_xyz^T gRaw + the bilinear weights' derivative
 //                     (torch grid_sampler's backward, zero padding, through clamp(p / radius)); fixed-order block
@@ -29,10 +29,19 @@
 #include <cstddef>
 
 #include "amav_common.h"
+#include "decode_quad.h"
 #include "triplane_region.h"
 
 namespace amav {
 namespace triplane_bwd {
+
+// the forward's tap and record arithmetic
+using decode::clamp_unit;
+using decode::group_raw;
+using decode::normalize4;
+using decode::plane_taps;
+using decode::PlaneTaps;
+using decode::sigmoid;
 
 constexpr int kTileTexels = 256;  // texels of G one texel_kernel wave keeps in LDS (16 KB)
 constexpr int kPointBlock = 256;  // points per point_kernel block
@@ -50,24 +59,6 @@ __device__ __forceinline__ triplane::TexelRect backward_rect(const float *__rest
     }
     return r;
 }
-
-// One plane's bilinear taps, decode_quad.h's quad_taps arithmetic (the same operations in the same order, so the same
-// texels and weights): tap (dy, dx) is texel (ix0 + dx, iy0 + dy), weight wx[dx] * wy[dy], zero padding outside.
-struct PlaneTaps {
-    int ix0, iy0;
-    float wx0, wx1, wy0, wy1;
-};
-__device__ __forceinline__ PlaneTaps plane_taps(float gx, float gy, int R) {
-#pragma clang fp contract(off)
-    const float sx = fmaf(gx + 1.0f, (float)R, -1.0f), sy = fmaf(gy + 1.0f, (float)R, -1.0f);  // 2 * pixel
-    const float fx = floorf(sx * 0.5f), fy = floorf(sy * 0.5f);
-    PlaneTaps t;
-    t.ix0 = (int)fx, t.iy0 = (int)fy;
-    t.wx1 = fmaf(sx, 0.5f, -fx), t.wx0 = fmaf(-sx, 0.5f, fx + 1.0f);
-    t.wy1 = fmaf(sy, 0.5f, -fy), t.wy0 = fmaf(-sy, 0.5f, fy + 1.0f);
-    return t;
-}
-__device__ __forceinline__ float clamp_unit(float p, float radius) { return fminf(fmaxf(p / radius, -1.0f), 1.0f); }
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -90,7 +81,7 @@ __global__ __launch_bounds__(256) void point_kernel(int N, int R, const float *_
     const float p[3] = {points[pt * 3], points[pt * 3 + 1], points[pt * 3 + 2]};
     const float4 *g4 = reinterpret_cast<const float4 *>(grec) + pt * 4;
     const float u[3] = {clamp_unit(p[0], radius), clamp_unit(p[1], radius), clamp_unit(p[2], radius)};
-    // the twelve taps (plane, dy, dx) as the forward forms them: clamped address, weight 0 outside the plane
+    // the twelve taps (plane, dy, dx) as the forward forms them (decode_quad.h)
     PlaneTaps pt3[3];
     int off[12];
     float w[12];
@@ -99,15 +90,10 @@ __global__ __launch_bounds__(256) void point_kernel(int N, int R, const float *_
     for (int pl = 0; pl < 3; ++pl) {
         pt3[pl] = plane_taps(pl == 2 ? u[1] : u[0], pl == 0 ? u[1] : u[2], R);
 #pragma unroll
-        for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-            for (int dx = 0; dx < 2; ++dx) {
-                const int k = pl * 4 + dy * 2 + dx, x = pt3[pl].ix0 + dx, y = pt3[pl].iy0 + dy;
-                in[k] = x >= 0 && x < R && y >= 0 && y < R;
-                const int cx = min(max(x, 0), R - 1), cy = min(max(y, 0), R - 1);
-                w[k] = in[k] ? (dx ? pt3[pl].wx1 : pt3[pl].wx0) * (dy ? pt3[pl].wy1 : pt3[pl].wy0) : 0.0f;
-                off[k] = (pl * R * R + cy * R + cx) * 4;  // float4 units from the frame's plane 0
-            }
+        for (int k = 0; k < 4; ++k) {
+            in[pl * 4 + k] = pt3[pl].in[k], w[pl * 4 + k] = pt3[pl].w[k];
+            off[pl * 4 + k] = pl * R * R * 4 + pt3[pl].off[k];  // float4 units from the frame's plane 0
+        }
     }
     const float4 *pl0 = reinterpret_cast<const float4 *>(proj + (size_t)f * 3 * R * R * 16);
     const float4 *wq = reinterpret_cast<const float4 *>(wpoint);
@@ -119,29 +105,19 @@ __global__ __launch_bounds__(256) void point_kernel(int N, int R, const float *_
     // one group of four channels (one quad lane of the forward) at a time: twelve float4 taps live, not 48
 #pragma unroll 1
     for (int q = 0; q < 4; ++q) {
-        // raw channels 4q..4q+3 exactly as quad_record accumulates them
+        // raw channels 4q..4q+3 as quad_record forms them
         float4 tv[12];
 #pragma unroll
         for (int k = 0; k < 12; ++k) tv[k] = pl0[off[k] + q];
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int k = 0; k < 12; ++k) {
-            const float4 v = tv[k];
-            acc.x = fmaf(v.x, w[k], acc.x), acc.y = fmaf(v.y, w[k], acc.y);
-            acc.z = fmaf(v.z, w[k], acc.z), acc.w = fmaf(v.w, w[k], acc.w);
-        }
-        const float4 w0 = wq[q * 4], w1 = wq[q * 4 + 1], w2 = wq[q * 4 + 2], w3 = wq[q * 4 + 3];
-        acc.x += fmaf(w0.z, p[2], fmaf(w0.y, p[1], w0.x * p[0])) + w0.w;
-        acc.y += fmaf(w1.z, p[2], fmaf(w1.x, p[0], w1.y * p[1])) + w1.w;
-        acc.z += fmaf(w2.z, p[2], fmaf(w2.y, p[1], w2.x * p[0])) + w2.w;
-        acc.w += fmaf(w3.z, p[2], fmaf(w3.x, p[0], w3.y * p[1])) + w3.w;
+        const float4 wrow[4] = {wq[q * 4], wq[q * 4 + 1], wq[q * 4 + 2], wq[q * 4 + 3]};
+        const float4 acc = group_raw(tv, w, wrow, p[0], p[1], p[2]);
         const float4 gq = g4[q];
         float d[4] = {gq.x, gq.y, gq.z, gq.w};
         if (q == 1) {
             // y = v / max(|v|, 1e-12): dv = (g - y (y . g)) / |v| above eps, g / eps below (torch's clamp_min branch)
-            const float nrm_raw = __fsqrt_rn(acc.x * acc.x + acc.y * acc.y + acc.z * acc.z + acc.w * acc.w);
-            const float inv = __frcp_rn(fmaxf(nrm_raw, 1e-12f));
-            const float y[4] = {acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv};
+            float nrm_raw, inv;
+            const float4 y4 = normalize4(acc, nrm_raw, inv);
+            const float y[4] = {y4.x, y4.y, y4.z, y4.w};
             const float dot = d[0] * y[0] + d[1] * y[1] + d[2] * y[2] + d[3] * y[3];
 #pragma unroll
             for (int e = 0; e < 4; ++e) d[e] = nrm_raw >= 1e-12f ? (d[e] - y[e] * dot) * inv : d[e] * inv;
@@ -151,7 +127,7 @@ __global__ __launch_bounds__(256) void point_kernel(int N, int R, const float *_
             const float a[3] = {acc.x, acc.y, acc.z};
 #pragma unroll
             for (int e = 0; e < 3; ++e) {
-                const float s = __frcp_rn(1.0f + __expf(-a[e]));
+                const float s = sigmoid(a[e]);
                 d[e] = d[e] * (s * (1.0f - s));
             }
             d[3] = 0.0f;  // pad
@@ -162,7 +138,6 @@ __global__ __launch_bounds__(256) void point_kernel(int N, int R, const float *_
 #pragma unroll
         for (int k = 0; k < 12; ++k)
             vt[k] = fmaf(tv[k].w, d[3], fmaf(tv[k].z, d[2], fmaf(tv[k].y, d[1], fmaf(tv[k].x, d[0], vt[k]))));
-        const float4 wrow[4] = {w0, w1, w2, w3};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             dpw[0] = fmaf(d[e], wrow[e].x, dpw[0]), dpw[1] = fmaf(d[e], wrow[e].y, dpw[1]);
