@@ -200,12 +200,24 @@ __global__ __launch_bounds__(256, 3) void selfattn_kernel(const float *__restric
 
 // One thread per (b, head, query, 4 consecutive d): merge the nsplit partial softmax states.  kSplitOut: the result goes
 // out as the fp16 x 2 operand of the projection that follows (rows of [h2 | h1 | h1], K = H * 64 each, x 2^scale_exp =
-// h1 + h2: exactly what split_operand_f16_kernel makes of the fp32 result, without the pass over it).
+// h1 + h2: exactly what split_operand_f16_kernel makes of the fp32 result, without the pass over it).  kLse: the row's
+// log-sum-exp also goes to lse [B, H, S] (natural units; the partial states are selfattn_f16_kernel's, whose sums carry
+// the 2^14 of its probabilities: amav_selfattn_forward_lse).
 typedef _Float16 c_f16x4 __attribute__((ext_vector_type(4)));
-template <bool kSplitOut>
+constexpr float kLn2 = 0.69314718055994531f;
+// combine_kernel's lse argument: an empty struct when kLse is off, so that the kernel the inference path runs keeps its
+// argument layout (its implicit arguments, read for blockDim, would move 8 bytes behind a pointer) and its code
+template <bool kLse>
+struct LseOut {
+    float *p;
+};
+template <>
+struct LseOut<false> {};
+template <bool kSplitOut, bool kLse = false>
 __global__ __launch_bounds__(256) void combine_kernel(const float *__restrict__ part, float *__restrict__ out, int B,
                                                       int H, int S, int nsplit, long long out_row_stride,
-                                                      _Float16 *__restrict__ out_split, float prescale) {
+                                                      _Float16 *__restrict__ out_split, float prescale,
+                                                      LseOut<kLse> lse = {}) {
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const int d4 = (int)(gid & 15);
     const long long row = gid >> 4;  // (b * H + head) * S + query
@@ -223,6 +235,9 @@ __global__ __launch_bounds__(256) void combine_kernel(const float *__restrict__ 
     }
     const float inv = 1.0f / l;
     const int qi = (int)(row % S), head = (int)((row / S) % H), b = (int)(row / ((long long)S * H));
+    if constexpr (kLse) {
+        if (d4 == 0) lse.p[row] = kLn2 * (m + log2f(l) - 14.0f);
+    }
     if (kSplitOut) {
         const float v[4] = {o0 * inv, o1 * inv, o2 * inv, o3 * inv};
         c_f16x4 p1, p2;
@@ -675,12 +690,17 @@ __device__ unsigned long long amav_attn_stamp_totals[8];
 #define AMAV_STAMP_FLUSH
 #endif
 
+// kLse (amav_selfattn_forward_lse): with one key slice, the row's log-sum-exp also goes to lse [B, H, S] in natural
+// units, ln 2 (m + log2 l - 14) -- m and l are in the log2 domain and l carries the 2^14 of P'; with nsplit > 1
+// combine_kernel<., true> writes it.
+template <bool kLse = false>
 __global__ __launch_bounds__(256, 3) void selfattn_f16_kernel(const float *__restrict__ q, const _Float16 *__restrict__ Kp,
                                                            const _Float16 *__restrict__ Vt, float *__restrict__ out,
                                                            int S, int Spad, long long row_stride,
                                                            long long out_row_stride, float scale_log2e, int nsplit,
                                                            float *__restrict__ part, const unsigned *__restrict__ hdr,
-                                                           Magnitudes given, int H, int B, int q_tiles) {
+                                                           Magnitudes given, int H, int B, int q_tiles,
+                                                           float *__restrict__ lse = nullptr) {
     __shared__ _Float16 Ks[2][kBN * kLdK];  // [part][key][d]
     __shared__ _Float16 Vs[2][kD * kLdK];   // [part][d][key, in the group order of split_kv_f16_kernel]
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -858,6 +878,7 @@ __global__ __launch_bounds__(256, 3) void selfattn_f16_kernel(const float *__res
     }
     const float inv = unv / l_tot;
     if (q0 + r < S) {
+        if (kLse && hh == 0) lse[bh * S + q0 + r] = kLn2 * (m_run + log2f(l_tot) - 14.0f);
         float *orow = out + ((size_t)b * S + q0 + r) * out_row_stride + head * kD;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -949,10 +970,36 @@ extern "C" int amav_selfattn_forward_bounded(int B, int S, int H, int D, const f
                                            nullptr, 0, workspace, workspace_bytes, stream_);
 }
 
+static int selfattn_forward_impl(int B, int S, int H, int D, const float *q, const float *k, const float *v,
+                                 int64_t row_stride, float *out, int64_t out_row_stride, float scale, float q_bound,
+                                 float k_bound, float v_bound, void *out_split, int split_scale_exp, float *lse,
+                                 void *workspace, size_t workspace_bytes, void *stream_);
+
 extern "C" int amav_selfattn_forward_split_out(int B, int S, int H, int D, const float *q, const float *k, const float *v,
                                                int64_t row_stride, float *out, int64_t out_row_stride, float scale,
                                                float q_bound, float k_bound, float v_bound, void *out_split,
                                                int split_scale_exp, void *workspace, size_t workspace_bytes, void *stream_) {
+    return selfattn_forward_impl(B, S, H, D, q, k, v, row_stride, out, out_row_stride, scale, q_bound, k_bound, v_bound,
+                                 out_split, split_scale_exp, nullptr, workspace, workspace_bytes, stream_);
+}
+
+// The forward of the differentiable path (csrc/attention_backward.hip): measured operand scales, and the row
+// log-sum-exp the backward recomputes the probabilities from.  Only the default fp16 x 2 kernel writes it.
+extern "C" int amav_selfattn_forward_lse(int B, int S, int H, int D, const float *q, const float *k, const float *v,
+                                         int64_t row_stride, float *out, int64_t out_row_stride, float scale, float *lse,
+                                         void *workspace, size_t workspace_bytes, void *stream_) {
+    AMAV_REQUIRE(lse != nullptr, "amav_selfattn_forward_lse: NULL lse");
+    AMAV_REQUIRE(attn_variant() == 2,
+                 "amav_selfattn_forward_lse: the row log-sum-exp is built for the default fp16 x 2 kernel only "
+                 "(attn option / AMAV_ATTN selects %s)", attn_variant() == 0 ? "f32" : "bf16");
+    return selfattn_forward_impl(B, S, H, D, q, k, v, row_stride, out, out_row_stride, scale, 0.f, 0.f, 0.f, nullptr, 0,
+                                 lse, workspace, workspace_bytes, stream_);
+}
+
+static int selfattn_forward_impl(int B, int S, int H, int D, const float *q, const float *k, const float *v,
+                                 int64_t row_stride, float *out, int64_t out_row_stride, float scale, float q_bound,
+                                 float k_bound, float v_bound, void *out_split, int split_scale_exp, float *lse,
+                                 void *workspace, size_t workspace_bytes, void *stream_) {
     AMAV_REQUIRE(out_split == nullptr || ((reinterpret_cast<uintptr_t>(out_split) & 15) == 0 && split_scale_exp >= -126 &&
                                           split_scale_exp <= 126 && out_row_stride == (int64_t)H * D),
                  "amav_selfattn_forward_split_out: out_split must be 16-byte aligned, |scale_exp| <= 126, out rows dense");
@@ -1004,9 +1051,14 @@ extern "C" int amav_selfattn_forward_split_out(int B, int S, int H, int D, const
             attn::split_kv_f16_kernel<<<kv_grid, 256, 0, stream>>>(k, v, S, Spad, row_stride, hdr, given,
                                                                   reinterpret_cast<_Float16 *>(kp),
                                                                   reinterpret_cast<_Float16 *>(vt));
-            attn::selfattn_f16_kernel<<<main_grid, 256, 0, stream>>>(
-                q, reinterpret_cast<const _Float16 *>(kp), reinterpret_cast<const _Float16 *>(vt), out, S, Spad,
-                row_stride, out_row_stride, sl2, ns, static_cast<float *>(workspace), hdr, given, H, B, q_tiles);
+            if (lse)
+                attn::selfattn_f16_kernel<true><<<main_grid, 256, 0, stream>>>(
+                    q, reinterpret_cast<const _Float16 *>(kp), reinterpret_cast<const _Float16 *>(vt), out, S, Spad,
+                    row_stride, out_row_stride, sl2, ns, static_cast<float *>(workspace), hdr, given, H, B, q_tiles, lse);
+            else
+                attn::selfattn_f16_kernel<false><<<main_grid, 256, 0, stream>>>(
+                    q, reinterpret_cast<const _Float16 *>(kp), reinterpret_cast<const _Float16 *>(vt), out, S, Spad,
+                    row_stride, out_row_stride, sl2, ns, static_cast<float *>(workspace), hdr, given, H, B, q_tiles);
         } else {
             attn::split_kv_kernel<<<kv_grid, 256, 0, stream>>>(k, v, S, Spad, row_stride, reinterpret_cast<__bf16 *>(kp),
                                                               reinterpret_cast<__bf16 *>(vt));
@@ -1023,6 +1075,10 @@ extern "C" int amav_selfattn_forward_split_out(int B, int S, int H, int D, const
             attn::combine_kernel<true><<<(unsigned)((threads + 255) / 256), 256, 0, stream>>>(
                 static_cast<const float *>(workspace), out, B, H, S, ns, out_row_stride, static_cast<_Float16 *>(out_split),
                 std::ldexp(1.0f, split_scale_exp));
+        else if (lse)
+            attn::combine_kernel<false, true><<<(unsigned)((threads + 255) / 256), 256, 0, stream>>>(
+                static_cast<const float *>(workspace), out, B, H, S, ns, out_row_stride, nullptr, 1.0f,
+                attn::LseOut<true>{lse});
         else
             attn::combine_kernel<false><<<(unsigned)((threads + 255) / 256), 256, 0, stream>>>(
                 static_cast<const float *>(workspace), out, B, H, S, ns, out_row_stride, nullptr, 1.0f);

@@ -99,6 +99,34 @@ class AudioDrivenAvatar(nn.Module):
         """lightning_model_wrapper.py:599-605,640: returns audio_rendered_images [B,T_out,H,W,3]."""
         return self.audio_triplane(audio_features, triplanes, ref_img_features, cam_params, smplx_tokens)[0]
 
+    # ---- stage-2 training ------------------------------------------------------------------------------------------
+    def training_step(self, triplanes, smplx_tokens, audio_features, cam_params, target_video, target_smpl_params):
+        """lightning_model_wrapper.py:418-572 (`AudioDrivenTriplaneAvatarLightning.training_step`) from its
+        `audio_triplane` call on: the audio net generates the window's tokens, the renderer renders them, and the loss is
+
+            10 * (l1 + 0.1 * (1 - ssim)) + 0.05 * smplx_param_loss(pred_smplx_future, target_smpl_params)[0]
+
+        target_video [B,T_out,3,H,W] (the reference's `pred_batch.video`), target_smpl_params: the dict of
+        `pred_batch.smpl_parms`.  Returns (total, parts) with parts = l1_target, ssim_target (= 1 - ssim), loss_target,
+        smpl_loss_future; call total.backward() for the gradients.  The stage-1 encoder that makes the input tokens and
+        the reference's prediction cache stay with the caller, as for predict_step.
+
+        Gradients reach the audio net (transformer, both temporal reducers) and the renderer's decoder heads; they
+        reach the SMPL-X decoder only with cfg.renderer.differentiable_smplx=True -- without it the renderer refuses a
+        backward through the SMPL-X parameters (only transl is differentiable there).  The step runs in the module's
+        current mode: the reference trains in .train(), which turns on the 0.1 dropout of SMPLXTemporalReducer's
+        attention; .eval() makes the step deterministic."""
+        from .losses import l1_loss, smplx_param_loss, ssim
+
+        images, _, pred_smplx_future, _, _ = self.audio_triplane(audio_features, triplanes, None, cam_params,
+                                                                 smplx_tokens)
+        target = target_video.permute(0, 1, 3, 4, 2)
+        parts = {"l1_target": l1_loss(images, target), "ssim_target": 1 - ssim(images, target)}
+        parts["loss_target"] = parts["l1_target"] + 0.1 * parts["ssim_target"]
+        parts["smpl_loss_future"] = smplx_param_loss(pred_smplx_future, target_smpl_params)[0]
+        total = 10 * parts["loss_target"] + 0.05 * parts["smpl_loss_future"]
+        return total, parts
+
     # ---- chained windows (demo) ------------------------------------------------------------------------------------
     @torch.no_grad()
     def rollout(self, triplanes, smplx_tokens, audio_features, cam_params, num_windows=None):

@@ -1108,6 +1108,95 @@ def selfattn(q, k, v, heads, scale=None, bounds=None, split_out_exp=None):
     return out if split is None else split
 
 
+def _qkv_views(qkv, heads):
+    """[B,S,3*H*D] fused projection output (unit inner stride, dense batch stride) -> (B, S, H*D, D)."""
+    _need(qkv, "qkv")
+    if qkv.dim() != 3 or qkv.stride(2) != 1 or qkv.stride(0) != qkv.shape[1] * qkv.stride(1) or qkv.shape[2] % (3 * heads):
+        raise AmavError(f"qkv: need [B,S,3*H*D] with unit inner stride and dense batch stride, got {tuple(qkv.shape)}")
+    B, S, C = qkv.shape
+    return B, S, C // 3, C // (3 * heads)
+
+
+def selfattn_lse(qkv, heads, scale=None):
+    """amav_selfattn_forward_lse on a fused [B,S,3*H*D] qkv (read in place) -> (out [B,S,H*D], lse [B,H,S]), lse in
+    natural units.  `out` equals selfattn()'s bit for bit; refused unless the default fp16 x 2 kernel is selected."""
+    B, S, HD, D = _qkv_views(qkv, heads)
+    out = torch.empty(B, S, HD, device=qkv.device)
+    lse = torch.empty(B, heads, S, device=qkv.device)
+    nbytes = _lib.lib().amav_selfattn_workspace_bytes(B, S, heads, D)
+    if nbytes == 0:
+        raise AmavError(f"amav_selfattn_workspace_bytes rejected B={B} S={S} H={heads} D={D}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=qkv.device)
+    p = qkv.data_ptr()
+    check(_lib.lib().amav_selfattn_forward_lse(B, S, heads, D, p, p + 4 * HD, p + 8 * HD, qkv.stride(1), out.data_ptr(),
+                                               HD, float(scale if scale is not None else D ** -0.5), lse.data_ptr(),
+                                               ws.data_ptr(), nbytes, _stream()),
+          "amav_selfattn_forward_lse")
+    return out, lse
+
+
+def selfattn_backward(qkv, out, lse, grad_out, heads, scale=None, grad_qkv=None):
+    """amav_selfattn_backward: the gradient [B,S,3*H*D] (dq | dk | dv) of a fused qkv given the forward's out and lse
+    (selfattn_lse) and grad_out = dLoss/d out.  out / grad_out: [B,S,H*D] with unit inner stride and dense batch stride;
+    grad_qkv: optional [B,S,>=3*H*D] destination view (its first 3*H*D columns are written)."""
+    B, S, HD, D = _qkv_views(qkv, heads)
+    for name, t in (("out", out), ("grad_out", grad_out)):
+        _need(t, name)
+        if tuple(t.shape) != (B, S, HD) or t.stride(2) != 1 or t.stride(0) != S * t.stride(1):
+            raise AmavError(f"{name}: need [B,S,H*D] = {(B, S, HD)} with unit inner stride, got {tuple(t.shape)}")
+    lse = _contig(lse, "lse")
+    if tuple(lse.shape) != (B, heads, S):
+        raise AmavError(f"lse: need [B,H,S] = {(B, heads, S)}, got {tuple(lse.shape)}")
+    if grad_qkv is None:
+        grad_qkv = torch.empty(B, S, 3 * HD, device=qkv.device)
+    _need(grad_qkv, "grad_qkv")
+    if (grad_qkv.dim() != 3 or tuple(grad_qkv.shape[:2]) != (B, S) or grad_qkv.shape[2] < 3 * HD
+            or grad_qkv.stride(2) != 1 or grad_qkv.stride(0) != S * grad_qkv.stride(1)):
+        raise AmavError(f"grad_qkv: need [B,S,>=3*H*D] with unit inner stride, got {tuple(grad_qkv.shape)}")
+    nbytes = _lib.lib().amav_selfattn_backward_workspace_bytes(B, S, heads, D)
+    if nbytes == 0:
+        raise AmavError(f"amav_selfattn_backward_workspace_bytes rejected B={B} S={S} H={heads} D={D}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=qkv.device)
+    p = qkv.data_ptr()
+    check(_lib.lib().amav_selfattn_backward(B, S, heads, D, p, p + 4 * HD, p + 8 * HD, qkv.stride(1), out.data_ptr(),
+                                            out.stride(1), lse.data_ptr(), grad_out.data_ptr(), grad_out.stride(1),
+                                            grad_qkv.data_ptr(), grad_qkv.stride(1),
+                                            float(scale if scale is not None else D ** -0.5), ws.data_ptr(), nbytes,
+                                            _stream()),
+          "amav_selfattn_backward")
+    return grad_qkv
+
+
+class _SelfAttn(torch.autograd.Function):
+    """selfattn_lse with amav_selfattn_backward as the backward; qkv, the output and the row log-sum-exp are kept."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads, scale):
+        out, lse = selfattn_lse(qkv, heads, scale)
+        ctx.heads, ctx.scale = heads, scale
+        ctx.save_for_backward(qkv, out, lse)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        qkv, out, lse = ctx.saved_tensors
+        grad_out = grad_out.float()
+        if grad_out.stride(2) != 1 or grad_out.stride(0) != grad_out.shape[1] * grad_out.stride(1) or \
+                grad_out.stride(1) % 4 or grad_out.data_ptr() % 16:
+            grad_out = grad_out.contiguous()
+        return selfattn_backward(qkv, out, lse, grad_out, ctx.heads, ctx.scale), None, None
+
+
+def selfattn_differentiable(qkv, heads, scale=None):
+    """softmax(q k^T * scale) v as a torch.autograd.Function over a fused [B,S,3*H*D] qkv (q | k | v along the last axis,
+    D = 64) -> [B,S,H*D]; the backward returns d qkv in the same fused layout (amav_selfattn_backward), so the gradient
+    of a fused q/k/v weight is one GEMM.  Needs the default fp16 x 2 forward (set_option("attn", ...) = fp16)."""
+    if qkv.stride(2) != 1 or qkv.stride(0) != qkv.shape[1] * qkv.stride(1) or qkv.stride(1) % 4 or qkv.data_ptr() % 16:
+        qkv = qkv.contiguous()
+    return _SelfAttn.apply(qkv, int(heads), scale)
+
+
 _GEMM_WS = {}
 
 

@@ -22,8 +22,10 @@ def matrix_to_axis_angle(m: torch.Tensor) -> torch.Tensor:
     """pytorch3d's default path: matrix -> quaternion (largest-denominator candidate, w >= 0) -> axis-angle."""
     lead = m.shape[:-2]
     m00, m01, m02, m10, m11, m12, m20, m21, m22 = m.reshape(lead + (9,)).unbind(-1)
-    q_abs = torch.sqrt(torch.clamp_min(torch.stack(
-        [1.0 + m00 + m11 + m22, 1.0 + m00 - m11 - m22, 1.0 - m00 + m11 - m22, 1.0 - m00 - m11 + m22], -1), 0.0))
+    q2 = torch.stack([1.0 + m00 + m11 + m22, 1.0 + m00 - m11 - m22, 1.0 - m00 + m11 - m22, 1.0 - m00 - m11 + m22], -1)
+    # pytorch3d's _sqrt_positive_part: sqrt(max(x, 0)) with a zero (not infinite) derivative where x <= 0
+    pos = q2 > 0
+    q_abs = torch.where(pos, torch.sqrt(torch.where(pos, q2, torch.ones_like(q2))), torch.zeros_like(q2))
     cand = torch.stack([
         torch.stack([q_abs[..., 0] ** 2, m21 - m12, m02 - m20, m10 - m01], -1),
         torch.stack([m21 - m12, q_abs[..., 1] ** 2, m10 + m01, m02 + m20], -1),

@@ -169,9 +169,10 @@ class Attention(nn.Module):
         if attention_mask is not None:
             raise NotImplementedError("attention masks are not used on this path (transformers.py:1026-1031)")
         if encoder_hidden_states is None:
-            if torch.is_grad_enabled() and (hidden_states.requires_grad or self.to_q.weight.requires_grad):
-                raise NotImplementedError("the MFMA self-attention kernel is inference-only (no backward): run under "
-                                          "torch.no_grad() / inference_mode (INTEGRATION.md)")
+            if torch.is_grad_enabled() and (hidden_states.requires_grad or any(
+                    w.requires_grad for w in (self.to_q.weight, self.to_k.weight, self.to_v.weight,
+                                              self.to_out[0].weight, self.to_out[0].bias))):
+                return self._forward_differentiable(hidden_states)
             qkv = linear(hidden_states, self._qkv_weight())            # [B,S,3*inner], one GEMM
             return self.attend(qkv)
         if encoder_hidden_states.shape[1] != 1:
@@ -187,6 +188,22 @@ class Attention(nn.Module):
         # one key: softmax == 1, so the output is to_out(to_v(context)) for every query
         ctx = self.to_out[0](self.to_v(encoder_hidden_states))        # [B,1,query_dim]
         return ctx.expand(-1, hidden_states.shape[1], -1)
+
+    def _forward_differentiable(self, hidden_states):
+        """Self-attention under autograd: one fp32 F.linear over the concatenated q/k/v weights (so that gradients reach
+        all three), the MFMA flash kernel with its HIP backward on the GPU (ops.selfattn_differentiable), the library's
+        SDPA on the CPU, then to_out."""
+        w = torch.cat([self.to_q.weight, self.to_k.weight, self.to_v.weight], dim=0)
+        qkv = F.linear(hidden_states, w)                                # [B,S,3*inner]
+        if qkv.is_cuda and qkv.dtype == torch.float32:
+            out = ops.selfattn_differentiable(qkv, self.heads, self.dim_head ** -0.5)
+        elif qkv.is_cuda:
+            raise NotImplementedError(f"self-attention under autograd runs in fp32 on the GPU, got {qkv.dtype}")
+        else:
+            B, S, _ = qkv.shape
+            q, k, v = (t.view(B, S, self.heads, self.dim_head).transpose(1, 2) for t in qkv.split(self.inner_dim, -1))
+            out = F.scaled_dot_product_attention(q, k, v).transpose(1, 2).reshape(B, S, self.inner_dim)
+        return F.linear(out, self.to_out[0].weight, self.to_out[0].bias)
 
 
 class GEGLU(nn.Module):

@@ -470,6 +470,24 @@ int amav_selfattn_forward_split_out(int batch, int seq_len, int heads, int head_
                                     const float *v_dev, int64_t row_stride, float *out_dev, int64_t out_row_stride,
                                     float scale, float q_bound, float k_bound, float v_bound, void *out_split_dev,
                                     int split_scale_exp, void *workspace, size_t workspace_bytes, void *stream);
+/* The forward of the differentiable path: as amav_selfattn_forward (measured operand scales, same workspace size), and
+ * the row log-sum-exp lse_dev [B, H, S] fp32 in natural units, lse[b,h,i] = ln sum_j exp(scale q_i . k_j), which
+ * amav_selfattn_backward recomputes the probabilities from.  out_dev equals amav_selfattn_forward's bit for bit.  Built
+ * for the default fp16 x 2 kernel only: refused (AMAV_ERR_INVALID_ARG) when attn = bf16 | f32 is selected. */
+int amav_selfattn_forward_lse(int batch, int seq_len, int heads, int head_dim, const float *q_dev, const float *k_dev,
+                              const float *v_dev, int64_t row_stride, float *out_dev, int64_t out_row_stride, float scale,
+                              float *lse_dev, void *workspace, size_t workspace_bytes, void *stream);
+/* Self-attention backward (flash-attention-2 form): from the forward's q, k, v (row stride
+ * row_stride, as the forward reads them), its output out_dev, its lse_dev and dout_dev = dLoss/d out ([B, S, H*D], row
+ * stride dout_row_stride), writes dq | dk | dv into dqkv_dev [B, S, 3*H*D] (row stride dqkv_row_stride >= 3*H*D; columns
+ * past 3*H*D untouched): the gradient of a fused q/k/v projection's output.  Deterministic bit for bit (fixed-order sums,
+ * no atomics); exact fp32 products on v_mfma_f32_32x32x2_f32.  D must be 64; q/k/v/out/dout/dqkv 16-byte aligned, row
+ * strides multiples of 4 floats.  workspace: amav_selfattn_backward_workspace_bytes(B, S, H, D) bytes (0 = bad sizes). */
+size_t amav_selfattn_backward_workspace_bytes(int batch, int seq_len, int heads, int head_dim);
+int amav_selfattn_backward(int batch, int seq_len, int heads, int head_dim, const float *q_dev, const float *k_dev,
+                           const float *v_dev, int64_t row_stride, const float *out_dev, int64_t out_row_stride,
+                           const float *lse_dev, const float *dout_dev, int64_t dout_row_stride, float *dqkv_dev,
+                           int64_t dqkv_row_stride, float scale, void *workspace, size_t workspace_bytes, void *stream);
 
 /* Operand of an fp32-equivalent nn.Linear (src/models/transformers.py:70-84, 448, 505: the to_q/k/v, to_out and
  * feed-forward projections) computed as ONE low-precision GEMM with fp32 accumulation over operands split into parts

@@ -1,0 +1,103 @@
+#!/usr/bin/env python3
+"""Diagnostic: the self-attention backward at the reference shape (B = 1, S = 6304, H = 8, D = 64) -- forward with the
+row log-sum-exp, backward, and the backward's three kernels (delta pre-pass, key-major dK/dV, query-major dQ) -- and one
+full stage-2 training step (AudioDrivenAvatar.training_step forward + backward, 6 output frames, 8 layers, 512^2
+frames, B = 1) with its peak allocated memory.  Times are medians over repeats between HIP events; the per-kernel split
+is the profiler's device time of each kernel, median over the same repeats.  Prints one JSON line."""
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from audio_motion_avatar_amd import ops  # noqa: E402
+
+
+def timed(fn, repeats, warmup=2):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(repeats):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        out.append(a.elapsed_time(b))
+    return statistics.median(out)
+
+
+def kernel_split(fn, repeats):
+    """median device ms per call of each kernel whose name mentions attn_bwd (torch.profiler)."""
+    from torch.profiler import ProfilerActivity, profile
+
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        for _ in range(repeats):
+            fn()
+        torch.cuda.synchronize()
+    times = {}
+    for e in prof.events():
+        if e.device_type.name == "CUDA" and "attn_bwd" in e.name:
+            key = e.name.split("(")[0].split("::")[-1]
+            times.setdefault(key, []).append(e.device_time / 1e3 if hasattr(e, "device_time") else e.cuda_time / 1e3)
+    return {k: round(statistics.median(v), 4) for k, v in times.items()}
+
+
+def attention_numbers(repeats):
+    B, S, H = 1, 6304, 8
+    g = torch.Generator().manual_seed(0)
+    qkv = torch.randn(B, S, 3 * H * 64, generator=g).cuda()
+    dout = torch.randn(B, S, H * 64, generator=g).cuda()
+    out, lse = ops.selfattn_lse(qkv, H)
+    grad = torch.empty(B, S, 3 * H * 64, device="cuda")
+    fwd = timed(lambda: ops.selfattn_lse(qkv, H), repeats)
+    bwd = timed(lambda: ops.selfattn_backward(qkv, out, lse, dout, H, grad_qkv=grad), repeats)
+    split = kernel_split(lambda: ops.selfattn_backward(qkv, out, lse, dout, H, grad_qkv=grad), repeats)
+    flop = 10.0 * B * H * S * S * 64
+    return {"forward_lse_ms": round(fwd, 4), "backward_ms": round(bwd, 4), "backward_kernels_ms": split,
+            "backward_tflops_fp32": round(flop / (bwd * 1e-3) / 1e12, 1)}
+
+
+def training_step_numbers(repeats):
+    from audio_motion_avatar_amd.config import ModelConfig
+    from audio_motion_avatar_amd.harness import AudioDrivenAvatar
+    from audio_motion_avatar_amd.synthetic import init_random_heads, make_render_inputs
+
+    cfg = ModelConfig()
+    cfg.renderer.differentiable_smplx = True
+    model = AudioDrivenAvatar(cfg)
+    init_random_heads(model.renderer)
+    model = model.cuda().eval()
+    a, r = cfg.triplane_audio_net, cfg.renderer
+    T = a.triplane_output_frames
+    _, smpl, cam = make_render_inputs(T, r, seed=1)
+    g = torch.Generator().manual_seed(2)
+    tri = torch.randn(1, a.triplane_input_frames, a.triplane_feature_dim, 3 * a.triplane_resolution ** 2, generator=g)
+    st = torch.randn(1, a.triplane_input_frames, a.smpl_token_dim, a.smpl_token_len, generator=g) * 0.2
+    audio = torch.randn(1, T, a.audio_feature_dim, generator=g)
+    Hh, Ww = r.image_size
+    target = torch.rand(1, T, 3, Hh, Ww, generator=g)
+    tri, st, audio, target = (t.cuda() for t in (tri, st, audio, target))
+
+    def step():
+        model.zero_grad(set_to_none=True)
+        loss, _ = model.training_step(tri, st, audio, cam, target, smpl)
+        loss.backward()
+
+    step()
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    ms = timed(step, repeats, warmup=1)
+    return {"training_step_ms": round(ms, 2), "training_step_peak_gib": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2),
+            "frames": T, "layers": a.transformer_layers, "image": list(r.image_size)}
+
+
+if __name__ == "__main__":
+    repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 10
+    res = {"attention": attention_numbers(repeats)}
+    if "--no-step" not in sys.argv:
+        res["training_step"] = training_step_numbers(max(3, repeats // 3))
+    print(json.dumps(res))
