@@ -1475,7 +1475,9 @@ def unpool_merge(x, scale, shift, up, cluster):
 
 def rows_norm(x, base, norm_b, norm_a=None):
     """-> (s = base + (LayerNorm_a(x) if norm_a else x), LayerNorm_b(s)) for [n, C] rows, C in {32,...,512};
-    norm_a / norm_b are nn.LayerNorm modules (weight, bias, eps)."""
+    norm_a / norm_b are nn.LayerNorm modules (weight, bias, eps); the kernel takes one eps, so both must have the same."""
+    if norm_a is not None and float(norm_a.eps) != float(norm_b.eps):
+        raise AmavError(f"rows_norm: norm_a.eps {norm_a.eps} != norm_b.eps {norm_b.eps} (amav_rows_norm takes one eps)")
     x, base = _contig(x, "x"), _contig(base, "base")
     n, C = x.shape
     if base.shape != x.shape:

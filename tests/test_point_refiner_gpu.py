@@ -216,6 +216,77 @@ def test_batched_clouds_equal_single_clouds():
     assert (both - want).abs().max() <= 1e-4 * max(1.0, float(want.abs().max()))
 
 
+def test_default_width_network_matches_fp64_oracle(monkeypatch):
+    """PointTransformerV3 as RendererConfig configures it (the reference's ptv3_encoder.yaml: encoder 32..512 channels,
+    decoder 256/128/256/512, patch 512, a 768-channel stem input) on two 5000-point clouds, against
+    oracle.ptv3.ptv3_cloud in fp64.  Bound: 4x the error of the same oracle run in fp32, or 2e-5 of the largest
+    output, never looser than the 1e-4 of the narrow network tests.  Also checks that the run reached the wide kernel
+    variants it is meant to pin (rows_norm at 256 / 512, cluster_max into 512, attention at head dims 16 / 32 / 64 on
+    full 512-point patches)."""
+    from audio_motion_avatar_amd.config import RendererConfig
+    from oracle import ptv3 as o_pt
+
+    ops, pt = _mods()
+    rc = RendererConfig()
+    pcfg = {k: tuple(getattr(rc, k)) for k in ("stride", "enc_depths", "enc_channels", "enc_num_head", "enc_patch_size",
+                                                "dec_depths", "dec_channels", "dec_num_head", "dec_patch_size")}
+    in_channels = 3 * rc.triplane_feature_dim
+    assert in_channels == 768
+    net = pt.PointTransformerV3(in_channels=in_channels, **pcfg).eval()
+    with torch.no_grad():
+        for m in net.modules():
+            if isinstance(m, torch.nn.BatchNorm1d):
+                m.running_mean.normal_(0, 0.2)
+                m.running_var.uniform_(0.5, 1.5)
+    F_, N = 2, 5000
+    assert N > 512 and N % 512
+    pts = _clouds(41, F_, N)
+    feat = torch.randn(F_, N, in_channels, generator=torch.Generator().manual_seed(42))
+
+    seen, child_counts = set(), []
+    rows_norm, cluster_max, patch_attention, pool = ops.rows_norm, ops.cluster_max, ops.patch_attention, pt.Level.pool
+
+    def rec_rows_norm(x, base, norm_b, norm_a=None):
+        seen.add(("rows_norm", x.shape[1]))
+        return rows_norm(x, base, norm_b, norm_a=norm_a)
+
+    def rec_cluster_max(x, members, seg, scale, shift):
+        seen.add(("cluster_max", x.shape[1]))
+        return cluster_max(x, members, seg, scale, shift)
+
+    def rec_patch_attention(qkv, order, patch_desc, heads, max_patch, scale=None):
+        seen.add(("patch_attention", qkv.shape[1] // 3 // heads, max_patch))
+        return patch_attention(qkv, order, patch_desc, heads, max_patch, scale=scale)
+
+    def rec_pool(level):
+        child, cluster, seg = pool(level)
+        child_counts.append([int(c) for c in child.counts])
+        return child, cluster, seg
+
+    monkeypatch.setattr(ops, "rows_norm", rec_rows_norm)
+    monkeypatch.setattr(ops, "cluster_max", rec_cluster_max)
+    monkeypatch.setattr(ops, "patch_attention", rec_patch_attention)
+    monkeypatch.setattr(pt.Level, "pool", rec_pool)
+    got = net.cuda()(pts.cuda(), feat.cuda()).cpu()
+    print("recorded:", sorted(seen), "clouds per level:", child_counts)
+    assert {("rows_norm", 256), ("rows_norm", 512), ("cluster_max", 512), ("patch_attention", 16, 512),
+            ("patch_attention", 32, 512), ("patch_attention", 64, 512)} <= seen
+    assert len(child_counts) == len(pcfg["stride"]) and all(c > 1 for c in child_counts[-1]), child_counts
+
+    cfg = {k: list(pcfg[k]) for k in ("enc_depths", "enc_num_head", "enc_patch_size", "dec_depths", "dec_num_head",
+                                      "dec_patch_size")}
+    state = {k: v.detach().cpu() for k, v in net.state_dict().items() if v.is_floating_point()}
+    p64 = {k: v.double() for k, v in state.items()}
+    for f in range(F_):
+        grid = o_pt.frame_grid(pts[f])
+        ref = o_pt.ptv3_cloud(p64, "", grid, feat[f].double(), cfg)
+        err32 = float((o_pt.ptv3_cloud(state, "", grid, feat[f], cfg).double() - ref).abs().max())
+        err = float((got[f * N:(f + 1) * N].double() - ref).abs().max())
+        big = float(ref.abs().max())
+        print(f"cloud {f}: HIP {err:.3e}, fp32 oracle {err32:.3e}, largest |out| {big:.3f}")
+        assert err <= min(max(4 * err32, 2e-5 * big), 1e-4 * max(1.0, big)), (f, err, err32)
+
+
 def test_renderer_with_point_refiner_matches_oracle():
     """cfg.no_point_refiner=False: LBS -> sample -> PTv3 -> MLP -> refined points -> fused decode (renderer.py:127-181)
     against the CPU chain, with a non-zero last refiner layer (the reference zero-initialises it)."""
