@@ -163,6 +163,15 @@ SIGNATURES = {
     "amav_points_project": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                            c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_float, c_float_p,
                                            ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "amav_cell_max_backward_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "amav_cell_max_backward": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_float_p,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_float_p, c_float_p,
+                                              ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "amav_cell_mean_backward": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                               ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_void_p]),
+    "amav_points_project_backward": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                    c_float_p, ctypes.c_void_p, ctypes.c_size_t, c_float_p,
+                                                    ctypes.c_void_p]),
     "amav_cloud_voxelize": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, c_float_p, ctypes.c_void_p, ctypes.c_float,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "amav_cloud_codes": (ctypes.c_int, [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,

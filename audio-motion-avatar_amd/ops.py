@@ -1054,6 +1054,11 @@ def cell_splat_mean(feat, cell_of, cells, segments=None):
 def points_project(points, w2c, intrinsics, features, radius_px):
     """points_projection (graphic_utils.py:275-331): points [B,N,3], w2c [B,4,4], intrinsics [B,3,3], features
     [B,C,H,W] -> [B,N,C] (include/amav.h, amav_points_project)."""
+    return _points_project(points, w2c, intrinsics, features, radius_px)[0]
+
+
+def _points_project(points, w2c, intrinsics, features, radius_px):
+    """points_project -> (out, workspace): the workspace holds the z-buffer amav_points_project_backward reads."""
     points, w2c = _contig(points, "points"), _contig(w2c, "w2c")
     intrinsics, features = _contig(intrinsics, "intrinsics"), _contig(features, "features")
     B, N, _ = points.shape
@@ -1066,7 +1071,126 @@ def points_project(points, w2c, intrinsics, features, radius_px):
     check(_lib.lib().amav_points_project(B, N, C, H, W, points.data_ptr(), w2c.data_ptr(), intrinsics.data_ptr(),
                                          features.data_ptr(), float(radius_px), out.data_ptr(), ws.data_ptr(), nbytes,
                                          _stream()), "amav_points_project")
-    return out
+    return out, ws
+
+
+def cell_pool_max_backward(feat, cell_of, cells, segments, grad_out):
+    """Gradient of cell_pool_max(feat, cell_of, cells, segments) w.r.t. feat, given grad_out [B,N,C]
+    (amav_cell_max_backward): per plane, the cell's summed gradient goes to the one point that holds the maximum, the
+    lowest point id among ties."""
+    feat, grad_out = _contig(feat, "feat"), _contig(grad_out, "grad_out")
+    B, N, C = feat.shape
+    if tuple(grad_out.shape) != (B, N, C):
+        raise AmavError(f"cell_pool_max_backward: grad_out {tuple(grad_out.shape)} != {(B, N, C)}")
+    cell_of = _contig(cell_of, "cell_of", torch.int32)
+    if tuple(cell_of.shape) != (B, 3, N):
+        raise AmavError(f"cell_of must be int32 [B,3,N] = {(B, 3, N)}, got {tuple(cell_of.shape)}")
+    order, seg = _contig(segments[0], "order", torch.int32), _contig(segments[1], "seg", torch.int32)
+    nbytes = _lib.lib().amav_cell_max_backward_workspace_bytes(B, C, int(cells))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=feat.device)
+    grad_feat = torch.empty_like(feat)
+    check(_lib.lib().amav_cell_max_backward(B, N, C, int(cells), feat.data_ptr(), order.data_ptr(), seg.data_ptr(),
+                                            cell_of.data_ptr(), grad_out.data_ptr(), grad_feat.data_ptr(),
+                                            ws.data_ptr(), nbytes, _stream()), "amav_cell_max_backward")
+    return grad_feat
+
+
+def cell_splat_mean_backward(grad_planes, cells, segments, num_points):
+    """Gradient of cell_splat_mean(feat, cell_of, cells, segments) w.r.t. feat [B,N,C], given grad_planes [B,C,cells]
+    (amav_cell_mean_backward): every point takes its cell's gradient divided by the cell's point count."""
+    grad_planes = _contig(grad_planes, "grad_planes")
+    B, C, _ = grad_planes.shape
+    if grad_planes.shape[2] != cells:
+        raise AmavError(f"cell_splat_mean_backward: grad_planes {tuple(grad_planes.shape)} has not {cells} cells")
+    order, seg = _contig(segments[0], "order", torch.int32), _contig(segments[1], "seg", torch.int32)
+    if tuple(order.shape) != (B, num_points) or tuple(seg.shape) != (B, cells + 1):
+        raise AmavError("cell_splat_mean_backward: segments do not match the batch / point / cell counts")
+    grad_feat = torch.empty(B, num_points, C, device=grad_planes.device)
+    check(_lib.lib().amav_cell_mean_backward(B, num_points, C, int(cells), order.data_ptr(), seg.data_ptr(),
+                                             grad_planes.data_ptr(), grad_feat.data_ptr(), _stream()),
+          "amav_cell_mean_backward")
+    return grad_feat
+
+
+def points_project_backward(grad_out, workspace, height, width):
+    """Gradient of points_project w.r.t. its features [B,C,H,W], given grad_out [B,N,C] and the forward's workspace
+    (_points_project; amav_points_project_backward): every pixel a point wins takes that point's gradient row."""
+    grad_out = _contig(grad_out, "grad_out")
+    B, N, C = grad_out.shape
+    grad = torch.empty(B, C, height, width, device=grad_out.device)
+    check(_lib.lib().amav_points_project_backward(B, N, C, int(height), int(width), grad_out.data_ptr(),
+                                                  workspace.data_ptr(), workspace.numel(), grad.data_ptr(), _stream()),
+          "amav_points_project_backward")
+    return grad
+
+
+class _CellPoolMax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat, cell_of, order, seg, cells):
+        feat = _contig(feat, "feat")
+        ctx.cells = cells
+        ctx.save_for_backward(feat, cell_of, order, seg)
+        return cell_pool_max(feat, cell_of, cells, (order, seg))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        feat, cell_of, order, seg = ctx.saved_tensors
+        return cell_pool_max_backward(feat, cell_of, ctx.cells, (order, seg), grad_out.float()), None, None, None, None
+
+
+class _CellSplatMean(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat, cell_of, order, seg, cells):
+        ctx.cells, ctx.num_points = cells, int(feat.shape[1])
+        ctx.save_for_backward(order, seg)
+        return cell_splat_mean(feat, cell_of, cells, (order, seg))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_planes):
+        order, seg = ctx.saved_tensors
+        return cell_splat_mean_backward(grad_planes.float(), ctx.cells, (order, seg), ctx.num_points), None, None, None, None
+
+
+class _PointsProject(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points, w2c, intrinsics, features, radius_px):
+        out, ws = _points_project(points, w2c, intrinsics, features, radius_px)
+        ctx.size, ctx.ws = tuple(features.shape[2:]), ws  # the z-buffer the backward reads
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        grad = points_project_backward(grad_out.float(), ctx.ws, *ctx.size) if ctx.needs_input_grad[3] else None
+        return None, None, None, grad, None
+
+
+def _segments(cell_of, cells, segments):
+    order, seg = segments if segments is not None else cell_segments(cell_of, cells)
+    return _contig(order, "order", torch.int32), _contig(seg, "seg", torch.int32)
+
+
+def cell_pool_max_differentiable(feat, cell_of, cells, segments=None):
+    """cell_pool_max as a torch.autograd.Function: the same values bit for bit, differentiable in feat
+    (amav_cell_max_backward: the whole gradient of a cell's maximum to the lowest point id that holds it)."""
+    order, seg = _segments(cell_of, cells, segments)
+    return _CellPoolMax.apply(feat, _contig(cell_of, "cell_of", torch.int32), order, seg, int(cells))
+
+
+def cell_splat_mean_differentiable(feat, cell_of, cells, segments=None):
+    """cell_splat_mean as a torch.autograd.Function: the same values bit for bit, differentiable in feat
+    (amav_cell_mean_backward)."""
+    order, seg = _segments(cell_of, cells, segments)
+    return _CellSplatMean.apply(feat, _contig(cell_of, "cell_of", torch.int32), order, seg, int(cells))
+
+
+def points_project_differentiable(points, w2c, intrinsics, features, radius_px):
+    """points_project as a torch.autograd.Function: the same values bit for bit, differentiable in features
+    (amav_points_project_backward: index_put's backward, every pixel a point wins takes that point's gradient row).
+    points, w2c and intrinsics get no gradient: the selection is piecewise constant."""
+    return _PointsProject.apply(points, w2c, intrinsics, features, float(radius_px))
 
 
 # ------------------------------------------------------------------------------------------------------ attention

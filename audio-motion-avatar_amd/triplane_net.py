@@ -11,7 +11,7 @@ correctness and determinism, on library kernels except where the reference's own
     this module: `forward` takes its output (`image_tokens [B,T,4096,1536]`) as an extra argument and raises when it is
     missing;
   * `torch_scatter.scatter_max / scatter_mean` (atomics: sum order undefined) -> deterministic segment reductions over
-    points stably sorted by cell (csrc/splat.hip);
+    points stably sorted by cell (csrc/splat.hip), with HIP backwards for stage-1 training (csrc/splat_backward.hip);
   * `points_projection` (pytorch3d point rasterizer + an index_put with duplicate indices: which pixel a point
     receives is undefined) -> z-buffer kernel with a fixed rule: the last pixel in (y, x) order that the point wins
     (what a sequential index_put does);
@@ -160,7 +160,19 @@ class SMPLXTriplaneEncoder(nn.Module):
             cells.append(torch.clamp(x[..., 0] + R * x[..., 1], 0, R * R - 1))
         return torch.stack(cells, dim=1).to(torch.int32)
 
+    def _wants_grad(self, *tensors, smpl_params=None):
+        """Autograd would record this call: grad mode is on and a parameter or one of the inputs requires grad."""
+        if not torch.is_grad_enabled():
+            return False
+        tensors = tensors + tuple(v for v in (smpl_params or {}).values() if isinstance(v, torch.Tensor))
+        return any(t is not None and t.requires_grad for t in tensors) or any(p.requires_grad for p in self.parameters())
+
     def forward(self, cam_params, img_tokens, smpl_params_gt=None, img=None):
+        """Under autograd (grad mode on and a parameter or input requires grad) the three HIP reductions run as
+        autograd Functions (ops.*_differentiable: the same values bit for bit, csrc/splat_backward.hip), so the point
+        network, vertex_emb and the image features (with sample_feature) receive gradients; with predicted SMPL-X
+        parameters the vertices carry them on to the predictor through BodyModel's LBS backward.  Neither the cell
+        indices nor the projection's pixel selection carry a gradient."""
         B, T, S, C = img_tokens.shape
         pred_smpl_params = smpl_tokens = None
         if self.cfg.predict_smplx_params:
@@ -168,15 +180,18 @@ class SMPLXTriplaneEncoder(nn.Module):
         smpl_params = smpl_params_gt if smpl_params_gt is not None else pred_smpl_params
         if smpl_params is None:
             raise AmavError("SMPLXTriplaneEncoder: no SMPL-X parameters (predict_smplx_params off, no smpl_params_gt)")
+        grad = self._wants_grad(img_tokens, img, smpl_params=smpl_params)
+        project = ops.points_project_differentiable if grad else ops.points_project
+        pool = ops.cell_pool_max_differentiable if grad else ops.cell_pool_max
+        splat = ops.cell_splat_mean_differentiable if grad else ops.cell_splat_mean
         verts = self.get_smplx_verts(smpl_params)                                    # [BT, N, 3]
         verts_emb = self.vertex_emb.weight.unsqueeze(0).expand(verts.shape[0], -1, -1)
         if self.cfg.sample_feature:                                                  # :139-157
             Himg, Wimg = img.shape[-2:]
             pts = verts + smpl_params["transl"].reshape(B * T, 1, 3)
-            sampled = ops.points_project(pts.contiguous(), cam_params["extrinsic"].reshape(B * T, 4, 4).float(),
-                                         cam_params["intrinsic"].reshape(B * T, 3, 3).float(),
-                                         img.reshape(B * T, *img.shape[2:]).float(),
-                                         POINT_RADIUS_NDC * min(Himg, Wimg) / 2.0)
+            sampled = project(pts.contiguous(), cam_params["extrinsic"].reshape(B * T, 4, 4).float(),
+                              cam_params["intrinsic"].reshape(B * T, 3, 3).float(),
+                              img.reshape(B * T, *img.shape[2:]).float(), POINT_RADIUS_NDC * min(Himg, Wimg) / 2.0)
             verts_feat = torch.cat([verts_emb, sampled], dim=-1)
         else:
             verts_feat = verts_emb
@@ -185,11 +200,11 @@ class SMPLXTriplaneEncoder(nn.Module):
         cells = self.triplane_resolution ** 2
         segments = ops.cell_segments(cell_of, cells)
         for block in self.blocks[1:]:                                                # :185-188
-            pooled = ops.cell_pool_max(net, cell_of, cells, segments)
+            pooled = pool(net, cell_of, cells, segments)
             net = block(torch.cat([net, pooled], dim=2))
         c = self.fc_c(net)
-        planes = [ops.cell_splat_mean(c, cell_of[:, p].contiguous(), cells,
-                                      (segments[0][:, p].contiguous(), segments[1][:, p].contiguous()))
+        planes = [splat(c, cell_of[:, p].contiguous(), cells,
+                        (segments[0][:, p].contiguous(), segments[1][:, p].contiguous()))
                   for p in range(3)]
         R = self.triplane_resolution
         smplx_triplanes = torch.stack(planes, dim=1).view(B, T, 3, -1, R, R)
@@ -254,3 +269,42 @@ class TriplaneGaussianAvatar(nn.Module):
         fused_tokens, smpl_tokens = self.fusion_network(smplx_triplane, image_tokens, smpl_tokens)
         rendered_images, gaussians, pred_smpl_2 = self.renderer(fused_tokens, cam_params, smpl_tokens, smpl_params_gt)
         return rendered_images, gaussians, fused_tokens, image_tokens, pred_smpl_1, pred_smpl_2, smpl_tokens
+
+    def training_step(self, ref_images, smpl_params, cam_params, image_tokens, test_images=None, test_cam_params=None):
+        """lightning_model_wrapper.py:82-170 (`TriplaneGaussianAvatarLightning.training_step`): renders the reference
+        views, and the test views from the same Gaussians (render_multi_view), and returns (total, parts) with
+
+            total = l1_train + 0.1 * ssim_train + (l1_test + 0.1 * ssim_test)
+                    + 0.01 * (smplx_param_loss(pred_smpl_1, smpl_params)[0] + smplx_param_loss(pred_smpl_2, smpl_params)[0])
+
+        ref_images / test_images [B,T,3,H,W] in [0,1], smpl_params the ground-truth dict of [B,T,...], cam_params /
+        test_cam_params the camera dicts, image_tokens [B,T,4096,image_feature_dim] (the Sapiens output, from the
+        caller as for forward).  parts: l1_train, ssim_train (= 1 - ssim), l1_test, ssim_test (0 without test images),
+        loss_smplx.  Call total.backward() for the gradients.
+
+        Every stage-1 parameter receives a gradient: ImageFeature.feature_reducer, the point network (fc_pos, blocks,
+        fc_c) and vertex_emb through the HIP backwards of the encoder's reductions, the SMPL-X predictor (smpl_tokens,
+        cross_attn) and the shared SMPL-X decoder through the parameter loss and the SMPL-X tokens, the fusion network,
+        and the renderer's decoder heads.  The reference renders with the ground-truth parameters, so LBS sits outside
+        the graph here.  The step runs in the module's current mode; .eval() and .train() differ only in the
+        transformers' dropout, which is 0 at the reference's settings."""
+        from .losses import l1_loss, smplx_param_loss, ssim
+        from .renderer import render_multi_view
+
+        rendered, gaussians, _, _, pred_smpl_1, pred_smpl_2, _ = self(ref_images, smpl_params, cam_params, image_tokens)
+        parts = {"l1_train": l1_loss(rendered, ref_images.permute(0, 1, 3, 4, 2)),
+                 "ssim_train": 1 - ssim(rendered, ref_images.permute(0, 1, 3, 4, 2))}
+        if test_images is not None:
+            B, T = test_images.shape[:2]
+            args = type("Args", (), {"image_size": self.cfg.image_size, "rgb": True, "sh_degree": 3})()
+            target = render_multi_view(gaussians, test_cam_params["intrinsic"].reshape(B, T, 3, 3),
+                                       test_cam_params["extrinsic"].reshape(B, T, 4, 4), args)
+            parts["l1_test"] = l1_loss(target, test_images.permute(0, 1, 3, 4, 2))
+            parts["ssim_test"] = 1 - ssim(target, test_images.permute(0, 1, 3, 4, 2))
+        else:
+            parts["l1_test"] = torch.zeros((), device=rendered.device)
+            parts["ssim_test"] = torch.zeros((), device=rendered.device)
+        parts["loss_smplx"] = smplx_param_loss(pred_smpl_1, smpl_params)[0] + smplx_param_loss(pred_smpl_2, smpl_params)[0]
+        total = (parts["l1_train"] + 0.1 * parts["ssim_train"] + (parts["l1_test"] + 0.1 * parts["ssim_test"])
+                 + 0.01 * parts["loss_smplx"])
+        return total, parts

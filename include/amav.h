@@ -438,6 +438,34 @@ int amav_points_project(int batch, int num_points, int channels, int height, int
                         const float *w2c_dev, const float *intrinsics_dev, const float *features_dev, float radius_px,
                         float *out_dev, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Backwards of the three stage-1 ops (training stage 1, lightning_model_wrapper.py:82-170).  No
+ * float atomics, every sum in a fixed order: bitwise reproducible and independent of how frames are batched.
+ * amav_cell_max_backward: grad_feat [B,N,C] (overwritten) of amav_cell_max + amav_cell_gather, given grad_out [B,N,C]
+ *   and the forward's feat, order, seg and cell_of.  For every plane p, the whole gradient of a cell's maximum, S_p =
+ *   sum of grad_out over the cell's points in ascending point id, goes to the ONE point that holds the maximum (the
+ *   lowest point id among ties: a sequential scan with a strict >), as torch_scatter's scatter_max backward routes it;
+ *   grad_feat = (v_0 + v_1) + v_2.  workspace: amav_cell_max_backward_workspace_bytes(B, C, cells) bytes (0 = bad
+ *   sizes): the arg and S tables [B,3,cells,C].
+ * amav_cell_mean_backward: grad_feat [B,N,C] of amav_cell_mean, given grad_planes [B,C,cells] and the forward's order
+ *   and seg: grad_feat[n][c] = grad_planes[c][cell(n)] / count(cell(n)), one fp32 division.  Every row is written once
+ *   provided order is a permutation of the point ids with seg[cells] = N (as the forward's segments are).
+ * amav_points_project_backward: grad_features [B,C,H,W] (overwritten) of amav_points_project w.r.t. its features, given
+ *   grad_out [B,N,C] and the forward's WORKSPACE, unchanged since that call: the backward reads its z-buffer (the first
+ *   B*H*W uint64 keys, (depth bits << 32) | point id, all ones where no point covers the pixel).  index_put's backward:
+ *   every pixel a point wins takes that point's gradient row (also the won pixels whose features the forward
+ *   discarded), 0 where no point won.  Points, w2c and intrinsics get no gradient (the selection is piecewise
+ *   constant). */
+size_t amav_cell_max_backward_workspace_bytes(int batch, int channels, int cells);
+int amav_cell_max_backward(int batch, int num_points, int channels, int cells, const float *feat_dev,
+                           const int32_t *order_dev, const int32_t *seg_dev, const int32_t *cell_of_dev,
+                           const float *grad_out_dev, float *grad_feat_dev, void *workspace, size_t workspace_bytes,
+                           void *stream);
+int amav_cell_mean_backward(int batch, int num_points, int channels, int cells, const int32_t *order_dev,
+                            const int32_t *seg_dev, const float *grad_planes_dev, float *grad_feat_dev, void *stream);
+int amav_points_project_backward(int batch, int num_points, int channels, int height, int width,
+                                 const float *grad_out_dev, const void *forward_workspace, size_t workspace_bytes,
+                                 float *grad_features_dev, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Self-attention of the audio transformer (diffusers Attention -> F.scaled_dot_product_attention as reached from
  * src/models/transformers.py:329-336): softmax(Q K^T * scale) V, fp32 in/out, no mask.  q,k,v,out: [B, S, H*D] with
