@@ -5,6 +5,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import attention_cases as ac
+
 pytestmark = pytest.mark.gpu
 
 BOUND = 1e-5
@@ -77,6 +79,9 @@ def test_gradients_match_fp64(B, S, H):
     print(f"B={B} S={S} H={H}: dq/dk/dv error / max {['%.2e' % e for e in err]} (torch fp32 SDPA "
           f"{['%.2e' % e for e in err32]}); lse {lse_err:.2e}")
     assert lse_err <= 1e-6
+    # the forward's output against the same fp64 reference: <= 4 x (CPU fp32 SDPA's error) + 2^-22 max |v|
+    yard = ac.reference(ac.Case("qkv", *(t.cpu().contiguous() for t in qkv.split(HD, -1)), H))
+    ac.check(out.cpu(), ac.Reference(o64.cpu(), yard.err32, yard.vmax), f"B={B} S={S} H={H}: out")
     assert torch.equal(out, ops.selfattn(qkv[..., :HD], qkv[..., HD:2 * HD], qkv[..., 2 * HD:], H))
     for e, e32 in zip(err, err32):
         assert e <= BOUND, (err, err32)

@@ -361,6 +361,10 @@ def test_measured_bounds_attention_is_hip_graph_capturable():
         graph.replay()
         torch.cuda.synchronize()
         assert torch.equal(out, eager)
+        sdpa64 = lambda: torch.nn.functional.scaled_dot_product_attention(
+            *(t.view(B, S, H, D).transpose(1, 2).double() for t in (qkv[..., :i], qkv[..., i:2 * i], qkv[..., 2 * i:])))
+        # unit-scale inputs (outputs of O(1)): the replayed result meets the kernel's 2e-5 bar as an absolute error
+        assert float((out.view(B, S, H, D).transpose(1, 2).double() - sdpa64()).abs().max()) <= 2e-5
         qkv.mul_(3.0)                      # new magnitudes: the replayed absmax pass must see them
         want = call().clone()              # eager call of the same entry point between two replays
         graph.replay()
@@ -371,9 +375,9 @@ def test_measured_bounds_attention_is_hip_graph_capturable():
             graph.replay()
         torch.cuda.synchronize()
         assert torch.equal(out, want)
-    ref = torch.nn.functional.scaled_dot_product_attention(
-        *(t.view(B, S, H, D).transpose(1, 2).double() for t in (qkv[..., :i], qkv[..., i:2 * i], qkv[..., 2 * i:])))
-    # inputs were scaled by 3 (|v| up to 13): the kernel's 2e-5 bar is relative to the output's magnitude
+    ref = sdpa64()
+    # relative here: the inputs were scaled by 3, so the scores are 9 x sharper and |v| reaches 13 -- every output is a
+    # convex combination of value rows, and an error of 2^-22-ish of them scales with their magnitude, not with 1
     assert float((out.view(B, S, H, D).transpose(1, 2).double() - ref).abs().max()) <= 2e-5 * max(1.0, float(ref.abs().max()))
 
 
