@@ -202,6 +202,26 @@ SIGNATURES = {
                                       c_float_p, ctypes.c_float, c_float_p, c_float_p, ctypes.c_void_p]),
     "amav_unpool_merge": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, c_float_p, c_float_p, c_float_p, c_float_p,
                                          ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_void_p]),
+    "amav_patch_attention_lse": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_float_p,
+                                                ctypes.c_void_p, ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_float,
+                                                ctypes.c_void_p]),
+    "amav_patch_attention_backward_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
+    "amav_patch_attention_backward": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                     c_float_p, ctypes.c_void_p, ctypes.c_void_p, c_float_p, c_float_p,
+                                                     c_float_p, c_float_p, ctypes.c_float, ctypes.c_void_p,
+                                                     ctypes.c_size_t, ctypes.c_void_p]),
+    "amav_subm_pair_sum_csr": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, c_float_p, ctypes.c_int64, ctypes.c_int64,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, c_float_p, ctypes.c_void_p]),
+    "amav_subm_pair_wgrad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "amav_subm_pair_wgrad": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, c_float_p, c_float_p, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p, c_float_p, ctypes.c_void_p, ctypes.c_size_t,
+                                            ctypes.c_void_p]),
+    "amav_cluster_max_backward": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, c_float_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                 c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p,
+                                                 ctypes.c_void_p]),
+    "amav_cluster_sum": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, c_float_p, ctypes.c_void_p, ctypes.c_void_p,
+                                        c_float_p, ctypes.c_void_p]),
     "amav_lbs_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.POINTER(BodyTables)]),
     "amav_lbs_blend_split_bytes": (ctypes.c_size_t, [ctypes.POINTER(BodyTables)]),
     "amav_lbs_prepare_blend_split": (ctypes.c_int, [ctypes.POINTER(BodyTables), ctypes.c_void_p, ctypes.c_size_t,

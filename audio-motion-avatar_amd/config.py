@@ -54,6 +54,8 @@ class RendererConfig:
     #                                   clouds, so larger passes cost less per frame (10 k points: 8 -> 2.26, 16 -> 1.85,
     #                                   32 -> 1.62 ms per frame); frames are independent, the split changes nothing
     refiner_points_per_pass: int = 320_000  # ... but a pass holds at most this many points (working set ~0.4 MB per 1 k points)
+    differentiable_refiner: bool = False  # PTv3Encoder records an autograd graph (HIP backwards) when
+    #                                       called under grad mode on its own; Renderer still refuses autograd with a refiner
     use_gaussian_splatting: bool = True
     gaussian_feature_dim: int = 256
     rgb: bool = True

@@ -469,11 +469,13 @@ __global__ __launch_bounds__(256) void pair_sum_kernel(long long n, int taps, in
 // borrowed slots take part as keys and their query results are dropped (the `unpad` gather at :462,493).
 // One workgroup = 128 queries of one (patch, head); S^T = K Q^T and O^T = V^T P^T on v_mfma_f32_32x32x2_f32 with the
 // probabilities kept in registers (layout notes: attention.hip).
-template <int D>
+// LSE: also write the row log-sum-exp of the scaled scores (natural units) to lse [n, heads], what
+// amav_patch_attention_backward recomputes the probabilities from; `out` is the same bit for bit.
+template <int D, bool LSE = false>
 __global__ __launch_bounds__(256, 3) void patch_attention_kernel(const float *__restrict__ qkv,
                                                               const long long *__restrict__ order,
                                                               const int4 *__restrict__ desc, float *__restrict__ out,
-                                                              int C, float scale_log2e) {
+                                                              int C, float scale_log2e, float *__restrict__ lse = nullptr) {
     constexpr int DV = D < 32 ? 32 : D;  // width of the V tile (zero padded: the MFMA produces 32 rows of O^T)
     constexpr int NO = DV / 32;
     constexpr int kLdk = 65;
@@ -611,7 +613,10 @@ __global__ __launch_bounds__(256, 3) void patch_attention_kernel(const float *__
         __syncthreads();
     }
 
-    const float inv = 1.0f / (l_run + __shfl_xor(l_run, 32, 64));
+    const float l_all = l_run + __shfl_xor(l_run, 32, 64);
+    const float inv = 1.0f / l_all;
+    if (LSE && hh == 0 && q0 + c < own)
+        lse[qrow * gridDim.y + head] = (m_run + log2f(l_all)) * 0.69314718055994530942f;
     if (q0 + c < own) {  // own <= K; the slots behind it are another patch's points
         float *orow = out + qrow * C + head * D;
 #pragma unroll
@@ -890,6 +895,31 @@ extern "C" int amav_patch_attention(int patches, int max_patch, int heads, int h
     else
         cloud::patch_attention_kernel<64><<<grid, 256, 0, stream>>>(qkv, ord, pd, out, C, sl);
     return check_launch("amav_patch_attention");
+}
+
+extern "C" int amav_patch_attention_lse(int patches, int max_patch, int heads, int head_dim, const float *qkv,
+                                        const int64_t *order, const int32_t *patch_desc, float *out, float *lse, float scale,
+                                        void *stream_) {
+    AMAV_REQUIRE(patches > 0 && patches <= 65535 && heads > 0 && heads <= 65535 && max_patch > 0,
+                 "amav_patch_attention_lse: bad sizes patches=%d heads=%d max_patch=%d", patches, heads, max_patch);
+    AMAV_REQUIRE(head_dim == 16 || head_dim == 32 || head_dim == 64, "amav_patch_attention_lse: head_dim %d (16, 32, 64 are built)",
+                 head_dim);
+    AMAV_REQUIRE(qkv && order && patch_desc && out && lse, "amav_patch_attention_lse: NULL pointer");
+    AMAV_REQUIRE(aligned16(qkv) && aligned16(out) && aligned16(patch_desc) && (reinterpret_cast<uintptr_t>(lse) & 3) == 0,
+                 "amav_patch_attention_lse: buffers must be 16-byte aligned (lse: 4)");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const dim3 grid((unsigned)((max_patch + 127) / 128), (unsigned)heads, (unsigned)patches);
+    const int C = heads * head_dim;
+    const float sl = scale * 1.4426950408889634f;
+    const long long *ord = reinterpret_cast<const long long *>(order);
+    const int4 *pd = reinterpret_cast<const int4 *>(patch_desc);
+    if (head_dim == 16)
+        cloud::patch_attention_kernel<16, true><<<grid, 256, 0, stream>>>(qkv, ord, pd, out, C, sl, lse);
+    else if (head_dim == 32)
+        cloud::patch_attention_kernel<32, true><<<grid, 256, 0, stream>>>(qkv, ord, pd, out, C, sl, lse);
+    else
+        cloud::patch_attention_kernel<64, true><<<grid, 256, 0, stream>>>(qkv, ord, pd, out, C, sl, lse);
+    return check_launch("amav_patch_attention_lse");
 }
 
 extern "C" int amav_cluster_max(int64_t clusters, int channels, const float *x, const int64_t *members, const int64_t *seg,

@@ -1613,3 +1613,270 @@ def rows_norm(x, base, norm_b, norm_a=None):
                                     ptr(norm_b.weight), ptr(norm_b.bias), float(norm_b.eps), out_sum.data_ptr(),
                                     out_norm.data_ptr(), _stream()), "amav_rows_norm")
     return out_sum, out_norm
+
+
+# ------------------------------------------------------------------------------------- point refiner: backward
+SUBM_WGRAD_CHUNK = 128            # granularity (pairs) of a split-K slice of amav_subm_pair_wgrad
+SUBM_WGRAD_WORKSPACE = 64 << 20   # the slices grow in multiples of the granularity to keep the partial matrices under this
+SUBM_DGRAD_BUFFER = 256 << 20     # largest per-pair product buffer of the feature gradient; larger ones are swept by taps
+
+
+def patch_attention_lse(qkv, order, patch_desc, heads, max_patch, scale=None):
+    """patch_attention that also returns the row log-sum-exp [n, heads] (natural units); `out` is the same bit for bit."""
+    qkv, order = _contig(qkv, "qkv"), _contig(order, "order", torch.int64)
+    patch_desc = _contig(patch_desc, "patch_desc", torch.int32)
+    n, C3 = qkv.shape
+    C = C3 // 3
+    D = C // heads
+    if C3 != 3 * heads * D or order.shape != (n,) or patch_desc.dim() != 2 or patch_desc.shape[1] != 4:
+        raise AmavError("patch_attention_lse: shapes do not match")
+    out = torch.empty(n, C, device=qkv.device)
+    lse = torch.empty(n, heads, device=qkv.device)
+    check(_lib.lib().amav_patch_attention_lse(patch_desc.shape[0], int(max_patch), int(heads), D, qkv.data_ptr(),
+                                              order.data_ptr(), patch_desc.data_ptr(), out.data_ptr(), lse.data_ptr(),
+                                              float(scale if scale is not None else D ** -0.5), _stream()),
+          "amav_patch_attention_lse")
+    return out, lse
+
+
+def patch_attention_backward(qkv, order, patch_desc, out, lse, grad_out, heads, max_patch, scale=None):
+    """amav_patch_attention_backward: d qkv [n, 3*C] (dq | dk | dv, point order) from the forward's out and lse
+    (patch_attention_lse) and grad_out [n, C]."""
+    qkv, order = _contig(qkv, "qkv"), _contig(order, "order", torch.int64)
+    patch_desc = _contig(patch_desc, "patch_desc", torch.int32)
+    n, C3 = qkv.shape
+    C = C3 // 3
+    D = C // heads
+    if C3 != 3 * heads * D or order.shape != (n,) or patch_desc.dim() != 2 or patch_desc.shape[1] != 4:
+        raise AmavError("patch_attention_backward: shapes do not match")
+    out, grad_out, lse = _shaped(out, "out", (n, C)), _shaped(grad_out, "grad_out", (n, C)), _shaped(lse, "lse", (n, heads))
+    nbytes = _lib.lib().amav_patch_attention_backward_workspace_bytes(n, int(heads), D)
+    if nbytes == 0:
+        raise AmavError(f"amav_patch_attention_backward_workspace_bytes rejected n={n} heads={heads} D={D}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=qkv.device)
+    grad_qkv = torch.empty_like(qkv)
+    check(_lib.lib().amav_patch_attention_backward(n, patch_desc.shape[0], int(max_patch), int(heads), D, qkv.data_ptr(),
+                                                   order.data_ptr(), patch_desc.data_ptr(), out.data_ptr(), lse.data_ptr(),
+                                                   grad_out.data_ptr(), grad_qkv.data_ptr(),
+                                                   float(scale if scale is not None else D ** -0.5), ws.data_ptr(), nbytes,
+                                                   _stream()), "amav_patch_attention_backward")
+    return grad_qkv
+
+
+class _PatchAttention(torch.autograd.Function):
+    """patch_attention_lse with amav_patch_attention_backward as the backward; qkv, the output and the lse are kept."""
+
+    @staticmethod
+    def forward(ctx, qkv, order, patch_desc, heads, max_patch, scale):
+        qkv = _contig(qkv, "qkv")
+        out, lse = patch_attention_lse(qkv, order, patch_desc, heads, max_patch, scale)
+        ctx.settings = (heads, max_patch, scale)
+        ctx.save_for_backward(qkv, order, patch_desc, out, lse)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        qkv, order, patch_desc, out, lse = ctx.saved_tensors
+        heads, max_patch, scale = ctx.settings
+        grad = patch_attention_backward(qkv, order, patch_desc, out, lse, grad_out.float().contiguous(), heads, max_patch,
+                                        scale)
+        return grad, None, None, None, None, None
+
+
+def patch_attention_differentiable(qkv, order, patch_desc, heads, max_patch, scale=None):
+    """patch_attention as a torch.autograd.Function: the same values bit for bit, differentiable in qkv."""
+    return _PatchAttention.apply(qkv, order, patch_desc, int(heads), int(max_patch), scale)
+
+
+def subm_pair_sum_csr(products, src_start, src_pairs, pair_lo=0, out=None):
+    """out [n, C] (+)= per source row, the sum of products[p - pair_lo] over the row's pairs p (ascending) that lie in
+    [pair_lo, pair_lo + len(products)); src_start int32 [n+1], src_pairs int32 [P].  out given: added to it."""
+    products = _contig(products, "products")
+    src_start, src_pairs = _contig(src_start, "src_start", torch.int32), _contig(src_pairs, "src_pairs", torch.int32)
+    n, C = src_start.shape[0] - 1, products.shape[1]
+    accumulate = out is not None
+    if out is None:
+        out = torch.empty(n, C, device=products.device)
+    _shaped(out, "out", (n, C))
+    check(_lib.lib().amav_subm_pair_sum_csr(n, C, products.data_ptr(), int(pair_lo), products.shape[0], src_start.data_ptr(),
+                                            src_pairs.data_ptr(), int(accumulate), out.data_ptr(), _stream()),
+          "amav_subm_pair_sum_csr")
+    return out
+
+
+def subm_wgrad_slices(tap_counts, cin, cout):
+    """Host-side slice table of subm_pair_wgrad for the taps' pair counts (numpy int64 [taps]) -> (chunk, slice_start
+    numpy int32 [taps+1]): slices of SUBM_WGRAD_CHUNK pairs, doubled until the partial matrices fit the workspace bound."""
+    import numpy as np
+
+    chunk = SUBM_WGRAD_CHUNK
+    while True:
+        per_tap = (tap_counts + chunk - 1) // chunk
+        if int(per_tap.sum()) * cin * cout * 4 <= SUBM_WGRAD_WORKSPACE or int(per_tap.max()) <= 1:
+            break
+        chunk *= 2
+    return chunk, np.concatenate([[0], np.cumsum(per_tap)]).astype(np.int32)
+
+
+def subm_pair_wgrad(feat, grad_out, pair_src, pair_dst, tap_start, slice_start, slices, chunk):
+    """-> [taps, C_in, C_out]: per tap, the sum over its pairs of feat[pair_src[p]]^T (x) grad_out[pair_dst[p]]
+    (include/amav.h); slice_start int32 [taps+1] / slices / chunk from subm_wgrad_slices."""
+    feat, grad_out = _contig(feat, "feat"), _contig(grad_out, "grad_out")
+    pair_src, pair_dst = _contig(pair_src, "pair_src", torch.int32), _contig(pair_dst, "pair_dst", torch.int32)
+    tap_start, slice_start = _contig(tap_start, "tap_start", torch.int32), _contig(slice_start, "slice_start", torch.int32)
+    taps, cin, cout = tap_start.shape[0] - 1, feat.shape[1], grad_out.shape[1]
+    if pair_dst.shape != pair_src.shape or slice_start.shape != tap_start.shape:
+        raise AmavError("subm_pair_wgrad: shapes do not match")
+    nbytes = _lib.lib().amav_subm_pair_wgrad_workspace_bytes(int(slices), cin, cout)
+    if nbytes == 0:
+        raise AmavError(f"amav_subm_pair_wgrad_workspace_bytes rejected slices={slices} C_in={cin} C_out={cout}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=feat.device)
+    out = torch.empty(taps, cin, cout, device=feat.device)
+    check(_lib.lib().amav_subm_pair_wgrad(pair_src.shape[0], int(slices), int(chunk), taps, cin, cout, feat.data_ptr(),
+                                          grad_out.data_ptr(), pair_src.data_ptr(), pair_dst.data_ptr(),
+                                          tap_start.data_ptr(), slice_start.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes,
+                                          _stream()), "amav_subm_pair_wgrad")
+    return out
+
+
+def subm_feat_grad(grad_out, weights_t, pairs, max_buffer_bytes=None):
+    """d feat [n, C_in] of a submanifold convolution: the fp32 gather-GEMM with pair_dst as the gather index and the
+    transposed weights [taps, C_out, C_in] (C_in a multiple of 32), then the ordered sum by source row.  The per-pair
+    buffer is bounded by max_buffer_bytes (default SUBM_DGRAD_BUFFER): larger ones are swept over runs of taps, which
+    adds every row's pairs in the same (ascending) order."""
+    grad_out, weights_t = _contig(grad_out, "grad_out"), _contig(weights_t, "weights_t")
+    taps, cout, cin = weights_t.shape
+    limit = SUBM_DGRAD_BUFFER if max_buffer_bytes is None else int(max_buffer_bytes)
+    tap_start = pairs.tap_start_host.astype("int64")
+    if pairs.count * cin * 4 <= limit:
+        products = subm_pair_gemm(grad_out, pairs.pair_dst, pairs.tap_start, pairs.tile_start, pairs.tiles, weights_t)
+        return subm_pair_sum_csr(products, pairs.src_start, pairs.src_pairs)
+    out = torch.zeros(grad_out.shape[0], cin, device=grad_out.device)
+    tile_start = pairs.tile_start_host
+    t0 = 0
+    while t0 < taps:
+        t1 = t0 + 1
+        while t1 < taps and (tap_start[t1 + 1] - tap_start[t0]) * cin * 4 <= limit:
+            t1 += 1
+        lo, count = int(tap_start[t0]), int(tap_start[t1] - tap_start[t0])
+        if count:
+            products = torch.empty(count, cin, device=grad_out.device)
+            rebased = (pairs.tile_start[t0:t1 + 1] - int(tile_start[t0])).contiguous()
+            # the kernel addresses products by the absolute pair index: hand it the address pair `lo` would have
+            check(_lib.lib().amav_subm_pair_gemm(count, int(tile_start[t1] - tile_start[t0]), t1 - t0, cout, cin,
+                                                 grad_out.data_ptr(), pairs.pair_dst.data_ptr(),
+                                                 pairs.tap_start.data_ptr() + 4 * t0, rebased.data_ptr(),
+                                                 weights_t.data_ptr() + 4 * t0 * cout * cin,
+                                                 products.data_ptr() - 4 * lo * cin, _stream()), "amav_subm_pair_gemm")
+            subm_pair_sum_csr(products, pairs.src_start, pairs.src_pairs, pair_lo=lo, out=out)
+        t0 = t1
+    return out
+
+
+class _SubMConv(torch.autograd.Function):
+    """The inference kernels of a SubMConv3d forward (conv.run_kernels) with the HIP backward of DESIGN.md section 4.12."""
+
+    @staticmethod
+    def forward(ctx, feat, weight, bias, conv, pairs):
+        feat = _contig(feat, "feat")
+        ctx.conv, ctx.pairs = conv, pairs
+        ctx.save_for_backward(feat, weight)
+        return conv.run_kernels(feat, pairs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        feat, weight = ctx.saved_tensors
+        conv, pairs = ctx.conv, ctx.pairs
+        g = grad_out.float().contiguous()
+        cout, cin, k = conv.out_channels, conv.in_channels, conv.kernel_size
+        pad = -cin % 32
+        grad_feat = grad_weight = grad_bias = None
+        if ctx.needs_input_grad[0]:
+            wt = weight.detach().reshape(cout, -1, cin).permute(1, 0, 2)  # [taps, C_out, C_in]
+            grad_feat = subm_feat_grad(g, torch.nn.functional.pad(wt, (0, pad)) if pad else wt, pairs)
+            if pad:
+                grad_feat = grad_feat[:, :cin]
+        if ctx.needs_input_grad[1]:
+            chunk, slice_start, slices = pairs.wgrad_slices(cin + pad, cout)
+            gw = subm_pair_wgrad(torch.nn.functional.pad(feat, (0, pad)) if pad else feat, g, pairs.pair_src,
+                                 pairs.pair_dst, pairs.tap_start, slice_start, slices, chunk)
+            grad_weight = gw[:, :cin].permute(2, 0, 1).reshape(cout, k, k, k, cin)
+        if ctx.needs_input_grad[2]:
+            grad_bias = g.sum(0)
+        return grad_feat, grad_weight, grad_bias, None, None
+
+
+def subm_conv_differentiable(feat, conv, pairs):
+    """SubMConv3d (point_transformer.py) on the pairs of a level as a torch.autograd.Function: the values of the inference
+    forward bit for bit (split products, or fp32 under AMAV_SUBM=f32), differentiable in feat, conv.weight and conv.bias.
+    pairs: Level.pairs(k) (its backward tables are built on first use)."""
+    return _SubMConv.apply(feat, conv.weight, conv.bias, conv, pairs)
+
+
+def cluster_max_backward(x, members, seg, scale, shift, grad_out):
+    """amav_cluster_max_backward -> (grad_x [n,C], grad_z [clusters,C], x_max [clusters,C])."""
+    x, members, seg = _contig(x, "x"), _contig(members, "members", torch.int64), _contig(seg, "seg", torch.int64)
+    C = x.shape[1]
+    clusters = seg.shape[0] - 1
+    grad_out = _shaped(grad_out, "grad_out", (clusters, C))
+    grad_x = torch.empty_like(x)
+    grad_z, x_max = torch.empty_like(grad_out), torch.empty_like(grad_out)
+    check(_lib.lib().amav_cluster_max_backward(clusters, C, x.data_ptr(), members.data_ptr(), seg.data_ptr(),
+                                               _shaped(scale, "scale", (C,)).data_ptr(),
+                                               _shaped(shift, "shift", (C,)).data_ptr(), grad_out.data_ptr(),
+                                               grad_x.data_ptr(), grad_z.data_ptr(), x_max.data_ptr(), _stream()),
+          "amav_cluster_max_backward")
+    return grad_x, grad_z, x_max
+
+
+def cluster_sum(x, members, seg):
+    """x [n,C], members int64 [n], seg int64 [clusters+1] -> [clusters,C]: the segment sums, added in segment order."""
+    x, members, seg = _contig(x, "x"), _contig(members, "members", torch.int64), _contig(seg, "seg", torch.int64)
+    C = x.shape[1]
+    clusters = seg.shape[0] - 1
+    out = torch.empty(clusters, C, device=x.device)
+    check(_lib.lib().amav_cluster_sum(clusters, C, x.data_ptr(), members.data_ptr(), seg.data_ptr(), out.data_ptr(),
+                                      _stream()), "amav_cluster_sum")
+    return out
+
+
+class _ClusterMax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, members, seg, scale, shift):
+        x, scale, shift = _contig(x, "x"), _contig(scale, "scale"), _contig(shift, "shift")
+        ctx.save_for_backward(x, members, seg, scale, shift)
+        return cluster_max(x, members, seg, scale, shift)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, members, seg, scale, shift = ctx.saved_tensors
+        grad_x, grad_z, x_max = cluster_max_backward(x, members, seg, scale, shift, grad_out.float().contiguous())
+        return grad_x, None, None, (grad_z * x_max).sum(0), grad_z.sum(0)
+
+
+def cluster_max_differentiable(x, members, seg, scale, shift):
+    """cluster_max as a torch.autograd.Function: the same values bit for bit, differentiable in x, scale and shift (the
+    whole gradient of a maximum to the first member, in segment order, that attains it)."""
+    return _ClusterMax.apply(x, members, seg, scale, shift)
+
+
+class _ClusterGather(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, up, cluster, members, seg):
+        ctx.save_for_backward(members, seg)
+        return up[cluster]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        members, seg = ctx.saved_tensors
+        return cluster_sum(grad_out.float().contiguous(), members, seg), None, None, None
+
+
+def cluster_gather_differentiable(up, cluster, members, seg):
+    """up[cluster] whose backward is cluster_sum over the clusters' member lists (members / seg of Level.pool()) instead
+    of an atomic index_add."""
+    return _ClusterGather.apply(up, cluster, members, seg)

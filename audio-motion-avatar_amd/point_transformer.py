@@ -14,7 +14,17 @@ reproducible output):
 All clouds of a pass run batched: one key sort per order, one neighbour / pair table per level, one gather-GEMM per
 convolution (only the voxel pairs that exist) + an ordered sum, one attention launch per block (patches of all clouds).  The sparse /
 serialised operators are HIP kernels (csrc/cloud.hip); Linear / LayerNorm / sort / prefix sums are torch library calls
-on the same stream.  Inference only.
+on the same stream.
+
+Inference by default.  `PointTransformerV3(..., differentiable=True)` (cfg.differentiable_refiner for PTv3Encoder) makes
+the network trainable: under grad mode, when `feat` or a parameter requires grad, the forward records an autograd graph
+whose sparse / serialised operators have HIP backwards (csrc/cloud_backward.hip) and whose Linear /
+LayerNorm / GELU / BatchNorm arithmetic differentiates through torch.  What is differentiated is the function the
+inference forward computes: the deterministic serialisation, BatchNorm with its RUNNING statistics (constants; weight and
+bias receive gradients), DropPath as the identity.  `.train()` changes nothing: this is fine-tuning with frozen
+statistics, the reference's train-mode batch statistics and stochastic depth are not reproduced.  Gradients go to `feat`
+and to every floating-point parameter; `points` get none (the network sees coordinates through the integer grid only).
+Gradients are bitwise reproducible (no atomics).
 """
 import os
 from types import SimpleNamespace
@@ -60,9 +70,15 @@ class SubMConv3d(nn.Module):
             self._flat = (ver, (F.pad(w, (0, 0, 0, pad)) if pad else w).contiguous())
         return self._flat[1]
 
-    def forward(self, feat, level):
-        """feat [n, C_in] -> [n, C_out]: gather-GEMM over the level's (row, neighbour row) pairs, then the ordered sum."""
+    def forward(self, feat, level, differentiable=False):
+        """feat [n, C_in] -> [n, C_out]: gather-GEMM over the level's (row, neighbour row) pairs, then the ordered sum.
+        differentiable: the same kernels as an autograd node (ops.subm_conv_differentiable)."""
         pairs = level.pairs(self.kernel_size)
+        if differentiable:
+            return ops.subm_conv_differentiable(feat, self, pairs)
+        return self.run_kernels(feat, pairs)
+
+    def run_kernels(self, feat, pairs):
         pad = -self.in_channels % 32
         if pad:
             feat = F.pad(feat, (0, pad))
@@ -86,6 +102,17 @@ def _bn_fold(bn):
         cached = (ver, scale.contiguous(), (bn.bias.detach() - bn.running_mean * scale).contiguous())
         bn._amav_fold = cached
     return cached[1], cached[2]
+
+
+def _bn_live(bn):
+    """_bn_fold from the live parameters, for autograd: weight and bias receive gradients, the statistics are constants."""
+    scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
+    return scale, bn.bias - bn.running_mean * scale
+
+
+def _bn_gelu_live(x, bn):
+    scale, shift = _bn_live(bn)
+    return F.gelu(x * scale + shift)
 
 
 def _bn(channels):
@@ -112,9 +139,10 @@ class SerializedAttention(nn.Module):
         self.qkv = nn.Linear(channels, channels * 3)
         self.proj = nn.Linear(channels, channels)
 
-    def forward(self, feat, level):
+    def forward(self, feat, level, differentiable=False):
         desc, max_patch = level.patches(self.patch_size)
-        out = ops.patch_attention(self.qkv(feat), level.order[self.order_index], desc, self.num_heads, max_patch)
+        attention = ops.patch_attention_differentiable if differentiable else ops.patch_attention
+        out = attention(self.qkv(feat), level.order[self.order_index], desc, self.num_heads, max_patch)
         return self.proj(out)
 
 
@@ -129,16 +157,16 @@ class Block(nn.Module):
         self.norm2 = nn.Sequential(nn.LayerNorm(channels))
         self.mlp = nn.Sequential(MLP(channels, int(channels * mlp_ratio)))
 
-    def forward(self, feat, level, conv_in=None):
-        x = self.cpe[0](feat if conv_in is None else conv_in, level)
+    def forward(self, feat, level, conv_in=None, differentiable=False):
+        x = self.cpe[0](feat if conv_in is None else conv_in, level, differentiable)
         # feat += LayerNorm(cpe linear); norm1 -- and feat += attention; norm2 -- as one pass over the rows each (the
-        # fused pass normalises with one eps)
-        if feat.shape[1] in (32, 64, 128, 256, 512) and self.cpe[2].eps == self.norm1[0].eps:
+        # fused pass normalises with one eps; it has no backward, so the differentiable path takes the library branch)
+        if not differentiable and feat.shape[1] in (32, 64, 128, 256, 512) and self.cpe[2].eps == self.norm1[0].eps:
             feat, n1 = ops.rows_norm(self.cpe[1](x), feat, self.norm1[0], norm_a=self.cpe[2])
             feat, n2 = ops.rows_norm(self.attn(n1, level), feat, self.norm2[0])
             return feat + self.mlp(n2)
         feat = feat + self.cpe[2](self.cpe[1](x))  # other widths or two eps: library LayerNorm
-        feat = feat + self.attn(self.norm1(feat), level)
+        feat = feat + self.attn(self.norm1(feat), level, differentiable)
         return feat + self.mlp(self.norm2(feat))
 
 
@@ -152,10 +180,14 @@ class SerializedPooling(nn.Module):
         self.proj = nn.Linear(in_channels, out_channels)
         self.norm = nn.Sequential(_bn(out_channels))
 
-    def forward(self, feat, level):
+    def forward(self, feat, level, differentiable=False):
+        """-> (pooled features, child level, cluster, (members, seg): the clusters' member lists)."""
         child, cluster, seg = level.pool()
-        scale, shift = _bn_fold(self.norm[0])
-        return ops.cluster_max(self.proj(feat), level.order[0], seg, scale, shift), child, cluster
+        if differentiable:
+            pooled = ops.cluster_max_differentiable(self.proj(feat), level.order[0], seg, *_bn_live(self.norm[0]))
+        else:
+            pooled = ops.cluster_max(self.proj(feat), level.order[0], seg, *_bn_fold(self.norm[0]))
+        return pooled, child, cluster, (level.order[0], seg)
 
 
 class SerializedUnpooling(nn.Module):
@@ -166,11 +198,59 @@ class SerializedUnpooling(nn.Module):
         self.proj = nn.Sequential(nn.Linear(in_channels, out_channels), _bn(out_channels))
         self.proj_skip = nn.Sequential(nn.Linear(skip_channels, out_channels), _bn(out_channels))
 
-    def forward(self, child_feat, parent_feat, cluster):
+    def forward(self, child_feat, parent_feat, cluster, members=None):
+        """members: (members, seg) of the pooling that made the child level -> the differentiable path."""
+        if members is not None:
+            up = _bn_gelu_live(self.proj[0](child_feat), self.proj[1])
+            skip = _bn_gelu_live(self.proj_skip[0](parent_feat), self.proj_skip[1])
+            return skip, skip + ops.cluster_gather_differentiable(up, cluster, *members)
         up = ops.bn_gelu(self.proj[0](child_feat), *_bn_fold(self.proj[1]))
         # -> (skip branch, sum): the next block's convolution reads the skip branch alone (the reference refreshes the
         # parent's sparse tensor in proj_skip, :250-255, but not after the sum at :755), its shortcut is the sum
         return ops.unpool_merge(self.proj_skip[0](parent_feat), *_bn_fold(self.proj_skip[1]), up, cluster)
+
+
+class Pairs(SimpleNamespace):
+    """The pair tables of one (level, kernel size), Level.pairs(); the backward's tables are built on first use, on the
+    device, without a host synchronisation."""
+
+    @property
+    def pair_dst(self):
+        """int32 [P]: the row that owns each pair (pair_of inverted)."""
+        if "_pair_dst" not in self.__dict__:
+            n, taps = self.pair_of.shape
+            dev = self.pair_of.device
+            slot = torch.where(self.pair_of >= 0, self.pair_of, self.count).long().reshape(-1)  # misses -> a spare slot
+            buf = torch.empty(self.count + 1, dtype=torch.int32, device=dev)
+            buf[slot] = torch.arange(n, dtype=torch.int32, device=dev).repeat_interleave(taps)
+            self._pair_dst = buf[:self.count].contiguous()
+        return self._pair_dst
+
+    def _csr(self):
+        if "_src_pairs" not in self.__dict__:
+            sorted_src, perm = torch.sort(self.pair_src, stable=True)
+            rows = torch.arange(self.pair_of.shape[0] + 1, dtype=torch.int32, device=perm.device)
+            self._src_pairs = perm.to(torch.int32)
+            self._src_start = torch.searchsorted(sorted_src, rows).to(torch.int32)
+        return self._src_start, self._src_pairs
+
+    @property
+    def src_start(self):
+        """int32 [n+1]: CSR by source row over src_pairs."""
+        return self._csr()[0]
+
+    @property
+    def src_pairs(self):
+        """int32 [P]: the stable sort of pair_src, so a row's pairs ascend."""
+        return self._csr()[1]
+
+    def wgrad_slices(self, cin, cout):
+        """-> (chunk, slice_start int32 [taps+1] on the device, slices) of ops.subm_pair_wgrad for these widths."""
+        key = ("_slices", cin, cout)
+        if key not in self.__dict__:
+            chunk, table = ops.subm_wgrad_slices(np.diff(self.tap_start_host.astype(np.int64)), cin, cout)
+            self.__dict__[key] = (chunk, torch.from_numpy(table).to(self.pair_of.device), int(table[-1]))
+        return self.__dict__[key]
 
 
 class Level:
@@ -195,7 +275,8 @@ class Level:
     def pairs(self, ksize):
         """The (neighbour row -> row) pairs of a ksize^3 submanifold convolution, grouped by tap (rows ascending inside
         a tap): pair_src int32 [P], pair_of int32 [n, taps] (-1: empty voxel), tap_start / tile_start int32 [taps+1]
-        (tiles of 128 pairs, what amav_subm_pair_gemm launches)."""
+        (tiles of 128 pairs, what amav_subm_pair_gemm launches); pair_dst / src_start / src_pairs (the backward's tables)
+        on first use."""
         if ksize not in self._pairs:
             nbr = self.neighbors(ksize)
             taps, dev = nbr.shape[1], nbr.device
@@ -207,9 +288,10 @@ class Level:
             counts = np.diff(tap_start).astype(np.int64)
             tile_start = np.concatenate([[0], np.cumsum((counts + 127) // 128)]).astype(np.int32)
             pair_of = torch.where(flat, idx, -1).view(taps, self.n).t().contiguous().to(torch.int32)
-            self._pairs[ksize] = SimpleNamespace(
+            self._pairs[ksize] = Pairs(
                 pair_src=nbr.t()[hit].contiguous(), pair_of=pair_of, tap_start=torch.from_numpy(tap_start).to(dev),
-                tile_start=torch.from_numpy(tile_start).to(dev), tiles=int(tile_start[-1]), count=int(tap_start[-1]))
+                tile_start=torch.from_numpy(tile_start).to(dev), tiles=int(tile_start[-1]), count=int(tap_start[-1]),
+                tap_start_host=tap_start, tile_start_host=tile_start)
         return self._pairs[ksize]
 
     def patches(self, patch_size):
@@ -255,14 +337,16 @@ class Level:
 class PointTransformerV3(nn.Module):
     """pointtransformer_v3.py:795-991 (cls_mode=False, no PDNorm, no RPE, no flash): constructor arguments by the
     reference's names; `drop_path`, `shuffle_orders`, `enable_flash` are accepted and have no effect at inference /
-    are replaced by the deterministic semantics above."""
+    are replaced by the deterministic semantics above.  `differentiable`: record an autograd graph when something
+    requires grad (module docstring); off by default, and then `forward` is the inference path whatever the grad mode."""
 
     def __init__(self, in_channels=6, order=ORDERS, stride=(2, 2, 2, 2), enc_depths=(2, 2, 2, 6, 2),
                  enc_channels=(32, 64, 128, 256, 512), enc_num_head=(2, 4, 8, 16, 32),
                  enc_patch_size=(1024, 1024, 1024, 1024, 1024), dec_depths=(2, 2, 2, 2), dec_channels=(64, 64, 128, 256),
                  dec_num_head=(4, 4, 8, 16), dec_patch_size=(1024, 1024, 1024, 1024), mlp_ratio=4, drop_path=0.3,
-                 shuffle_orders=True, enable_flash=False, grid_resolution=100):
+                 shuffle_orders=True, enable_flash=False, grid_resolution=100, differentiable=False):
         super().__init__()
+        self.differentiable = bool(differentiable)
         if tuple(order) != ORDERS:
             raise AmavError(f"PointTransformerV3: orders {tuple(order)} (the kernels build {ORDERS})")
         stages = len(enc_depths)
@@ -295,10 +379,17 @@ class PointTransformerV3(nn.Module):
             setattr(self.dec, f"dec{s}", dec)
         self.out_channels = dec_channels[0]
 
-    @torch.no_grad()
     def forward(self, points, feat):
         """points [F,N,3], feat [F,N,C_in] (fp32, HIP device) -> [F*N, dec_channels[0]] in the input's point order.
-        Inference only (runs under no_grad: the HIP kernels have no backward)."""
+        Runs under no_grad unless the network was built with differentiable=True, grad mode is on and `feat` or a
+        parameter requires grad; then gradients reach `feat` and the parameters (never `points`)."""
+        if (self.differentiable and torch.is_grad_enabled()
+                and (feat.requires_grad or any(p.requires_grad for p in self.parameters()))):
+            return self._run(points.detach(), feat, True)
+        with torch.no_grad():
+            return self._run(points, feat, False)
+
+    def _run(self, points, feat, diff):
         Fc, N, _ = points.shape
         n = Fc * N
         dev = points.device
@@ -306,30 +397,32 @@ class PointTransformerV3(nn.Module):
         grid, depth = ops.cloud_voxelize(points.reshape(n, 3), cloud_of, Fc, self.grid_resolution)
         level = Level(grid, cloud_of, depth, np.full(Fc, N, dtype=np.int64), ops.cloud_codes(grid, cloud_of, depth))
         stem = self.embedding.stem
-        x = ops.bn_gelu(stem.conv(feat.reshape(n, -1).float().contiguous(), level), *_bn_fold(stem.norm))
+        x = stem.conv(feat.reshape(n, -1).float().contiguous(), level, diff)
+        x = _bn_gelu_live(x, stem.norm) if diff else ops.bn_gelu(x, *_bn_fold(stem.norm))
         stack = []
         for s in range(self.num_stages):
             enc = getattr(self.enc, f"enc{s}")
             if s > 0:
-                x_child, child, cluster = enc.down(x, level)
-                stack.append((level, x, cluster))
+                x_child, child, cluster, members = enc.down(x, level, diff)
+                stack.append((level, x, cluster, members))
                 level, x = child, x_child
             for i in range(self.enc_depths[s]):
-                x = getattr(enc, f"block{i}")(x, level)
+                x = getattr(enc, f"block{i}")(x, level, differentiable=diff)
         for s in reversed(range(self.num_stages - 1)):
             dec = getattr(self.dec, f"dec{s}")
-            parent, x_parent, cluster = stack.pop()
-            skip, x = dec.up(x, x_parent, cluster)
+            parent, x_parent, cluster, members = stack.pop()
+            skip, x = dec.up(x, x_parent, cluster, members if diff else None)
             level = parent
             for i in range(self.dec_depths[s]):
-                x = getattr(dec, f"block{i}")(x, level, conv_in=skip if i == 0 else None)
+                x = getattr(dec, f"block{i}")(x, level, conv_in=skip if i == 0 else None, differentiable=diff)
         return x
 
 
 class PTv3Encoder(nn.Module):
     """point_encoder.py:6-40.  cfg: input_dim, stride, enc_channels, enc_depths, dec_channels, dec_depths,
     enc_num_head, dec_num_head, enc_patch_size, dec_patch_size, enable_flash (reference names); optional
-    `refiner_clouds_per_pass` bounds the working set (clouds are independent, so the split changes nothing)."""
+    `refiner_clouds_per_pass` bounds the working set (clouds are independent, so the split changes nothing); optional
+    `differentiable_refiner` (default False) builds the trainable network (module docstring)."""
 
     def __init__(self, cfg=None):
         super().__init__()
@@ -341,7 +434,8 @@ class PTv3Encoder(nn.Module):
             in_channels=in_channels, stride=cfg.stride, enc_channels=cfg.enc_channels, enc_depths=cfg.enc_depths,
             dec_channels=cfg.dec_channels, dec_depths=cfg.dec_depths, enc_num_head=cfg.enc_num_head,
             dec_num_head=cfg.dec_num_head, enc_patch_size=cfg.enc_patch_size, dec_patch_size=cfg.dec_patch_size,
-            enable_flash=getattr(cfg, "enable_flash", False))
+            enable_flash=getattr(cfg, "enable_flash", False),
+            differentiable=getattr(cfg, "differentiable_refiner", False))
         self.grid_resolution = 100
         self.clouds_per_pass = int(getattr(cfg, "refiner_clouds_per_pass", 32))
         self.points_per_pass = int(getattr(cfg, "refiner_points_per_pass", 320_000))

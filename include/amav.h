@@ -627,6 +627,59 @@ int amav_unpool_merge(int64_t rows, int channels, const float *x_dev, const floa
                       const float *up_dev, const int64_t *cluster_dev, float *skip_dev, float *sum_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Backward of the point refiner's operators (csrc/cloud_backward.hip).  Deterministic: no atomics,
+ * every sum in a fixed order; exact fp32 products on the matrix pipe.  No entry point synchronises with the host.
+ *
+ * amav_patch_attention_lse   amav_patch_attention that also writes lse [n, heads]: the log-sum-exp (natural units) of
+ *                       every own query row's scaled scores.  out is amav_patch_attention's bit for bit.
+ * amav_patch_attention_backward  grad_qkv [n, 3*heads*head_dim] (dq | dk | dv, point order, fully overwritten) from qkv,
+ *                       the forward's out and lse and grad_out [n, heads*head_dim].  A row is a query of one patch; as a key
+ *                       it can also sit in a borrowed slot of its cloud's last patch: dk / dv = own patch's part + the
+ *                       borrowing patch's part, added in that order.  workspace:
+ *                       amav_patch_attention_backward_workspace_bytes(n, heads, head_dim) bytes (0 = bad sizes).
+ * amav_subm_pair_sum_csr  out [n, channels] (+)= sum over r in [src_start[i], src_start[i+1]) with
+ *                       pair_lo <= src_pairs[r] < pair_lo + pair_count of products[src_pairs[r] - pair_lo]: the transposed
+ *                       ordered sum of the convolution (products = amav_subm_pair_gemm of grad_out with pair_dst as the
+ *                       gather index and the per-tap transposed weights [taps, cout, cin]).  src_pairs [P] int32 = stable
+ *                       sort of pair_src (a row's pairs ascend), src_start [n+1] int32.  accumulate != 0 adds to out: a
+ *                       sweep over consecutive pair ranges adds in the order of one call over all pairs.
+ * amav_subm_pair_wgrad  grad_weights [taps, cin, cout] = per tap, sum over its pairs of feat[pair_src[p]]^T (x)
+ *                       grad_out[pair_dst[p]]; zeros for a tap without pairs.  Split over slices of `chunk` pairs (a
+ *                       multiple of 128) of one tap: slice_start [taps+1] int32 = prefix sum of ceil(pairs of tap / chunk),
+ *                       slices = its last entry; partial matrices go to the workspace
+ *                       (amav_subm_pair_wgrad_workspace_bytes(slices, cin, cout), 0 = bad sizes) and are added in slice
+ *                       order.  cin, cout multiples of 32.
+ * amav_cluster_max_backward  backward of amav_cluster_max: grad_z [clusters, C] = grad_out * gelu'(x_max * scale + shift),
+ *                       x_max [clusters, C] the raw maxima (the scale / shift gradients are column sums of grad_z * x_max
+ *                       and grad_z); grad_x [n, C]: grad_z * scale on the first member, in segment order, that attains the
+ *                       maximum, zero on every other row of the segment (every row is written once).
+ * amav_cluster_sum      out [clusters, C] = sum of x[members[r]] over r in [seg[j], seg[j+1]) in that order: the backward
+ *                       of the up[cluster] gather of amav_unpool_merge.
+ */
+int amav_patch_attention_lse(int patches, int max_patch, int heads, int head_dim, const float *qkv_dev,
+                             const int64_t *order_dev, const int32_t *patch_desc_dev, float *out_dev, float *lse_dev,
+                             float scale, void *stream);
+size_t amav_patch_attention_backward_workspace_bytes(int64_t n, int heads, int head_dim);
+int amav_patch_attention_backward(int64_t n, int patches, int max_patch, int heads, int head_dim, const float *qkv_dev,
+                                  const int64_t *order_dev, const int32_t *patch_desc_dev, const float *out_dev,
+                                  const float *lse_dev, const float *grad_out_dev, float *grad_qkv_dev, float scale,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+int amav_subm_pair_sum_csr(int64_t n, int channels, const float *products_dev, int64_t pair_lo, int64_t pair_count,
+                           const int32_t *src_start_dev, const int32_t *src_pairs_dev, int accumulate, float *out_dev,
+                           void *stream);
+size_t amav_subm_pair_wgrad_workspace_bytes(int slices, int cin, int cout);
+int amav_subm_pair_wgrad(int64_t pairs, int slices, int chunk, int taps, int cin, int cout, const float *feat_dev,
+                         const float *grad_out_dev, const int32_t *pair_src_dev, const int32_t *pair_dst_dev,
+                         const int32_t *tap_start_dev, const int32_t *slice_start_dev, float *grad_weights_dev,
+                         void *workspace, size_t workspace_bytes, void *stream);
+int amav_cluster_max_backward(int64_t clusters, int channels, const float *x_dev, const int64_t *members_dev,
+                              const int64_t *seg_dev, const float *scale_dev, const float *shift_dev,
+                              const float *grad_out_dev, float *grad_x_dev, float *grad_z_dev, float *x_max_dev,
+                              void *stream);
+int amav_cluster_sum(int64_t clusters, int channels, const float *x_dev, const int64_t *members_dev, const int64_t *seg_dev,
+                     float *out_dev, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Library GEMM of the fp16 x 2 split projections: out[rows, n] fp32 = alpha * a[rows, k3] x
  * w[n, k3]^T with fp16 operands and fp32 accumulation -- the three partial products of an fp32-equivalent nn.Linear
  * (src/models/transformers.py:70-84, 448, 505) concatenated along K.  hipBLASLt does the arithmetic; `algo_index` names

@@ -1,0 +1,439 @@
+"""Backward of the point refiner (csrc/cloud_backward.hip) against fp64 torch autograd of the
+oracle/ptv3.py restatements on the CPU.
+
+Bound per gradient tensor, the form and the constants of test_default_width_network_matches_fp64_oracle:
+    max|g - g64| <= max(4 * err32, 2e-5 * max|g64|),   err32 = max|g32 - g64| of the same restatement run in fp32.
+Every comparison prints err, err32 and max|g64| before it asserts."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+
+def _mods():
+    from audio_motion_avatar_amd import ops, point_transformer
+
+    return ops, point_transformer
+
+
+def _clouds(seed, F, N, extent=(0.3, 0.5, 0.2)):
+    g = torch.Generator().manual_seed(seed)
+    d = torch.nn.functional.normalize(torch.randn(F, N, 3, generator=g), dim=-1)
+    pts = d * torch.tensor(extent) * (1.0 + 0.05 * torch.randn(F, N, 1, generator=g))
+    pts[:, N - N // 8:] = pts[:, : N // 8] + 0.002 * torch.randn(F, N // 8, 3, generator=g)  # shared voxels
+    return pts + torch.randn(F, 1, 3, generator=g) * 0.3
+
+
+def _check(name, got, g64, g32):
+    """The module's bound; returns err / bound."""
+    g64 = g64.double()
+    err = float((got.detach().cpu().double() - g64).abs().max())
+    err32 = float((g32.double() - g64).abs().max())
+    big = float(g64.abs().max())
+    bound = max(4 * err32, 2e-5 * big)
+    print(f"{name}: err {err:.3e}  err32 {err32:.3e}  max|g64| {big:.3e}  err/bound {err / max(bound, 1e-300):.3f}")
+    assert err <= bound, (name, err, err32, big)
+    return err / max(bound, 1e-300)
+
+
+def _level(pts):
+    ops, pt = _mods()
+    F, N = pts.shape[:2]
+    n = F * N
+    cloud_of = torch.arange(F, dtype=torch.int32).repeat_interleave(N).cuda()
+    grid, depth = ops.cloud_voxelize(pts.reshape(n, 3).cuda(), cloud_of, F)
+    return pt.Level(grid, cloud_of, depth, np.full(F, N), ops.cloud_codes(grid, cloud_of, depth))
+
+
+# ------------------------------------------------------------------------------------------------- 1. convolution
+def _conv_reference(conv, pts, feat, dout, ksize, dtype):
+    from oracle import ptv3 as o_pt
+
+    F, N = pts.shape[:2]
+    x = feat.detach().clone().to(dtype).requires_grad_()
+    w = conv.weight.detach().cpu().to(dtype).requires_grad_()
+    b = conv.bias.detach().cpu().to(dtype).requires_grad_()
+    outs = []
+    for f in range(F):
+        nbr = o_pt.neighbor_table(o_pt.frame_grid(pts[f]), torch.zeros(N, dtype=torch.long), ksize)
+        outs.append(o_pt.subm_conv3d(x[f * N:(f + 1) * N], nbr, w, b))
+    torch.cat(outs).backward(dout.to(dtype))
+    return dict(feat=x.grad, weight=w.grad, bias=b.grad)
+
+
+@pytest.mark.parametrize("cin,cout,ksize,F,N", [(12, 32, 5, 1, 400), (64, 64, 3, 2, 700), (768, 32, 5, 1, 900),
+                                                 (256, 256, 3, 2, 500), (96, 160, 3, 1, 300)])
+def test_subm_conv_backward_matches_fp64_autograd(cin, cout, ksize, F, N):
+    """dfeat (the transposed ordered sum over a CSR by source row), dweight in the parameter's layout (split-K over pair
+    chunks) and dbias; the inputs do exercise a source row with two pairs of one tap (shared voxels: the pair relation is
+    not symmetric) and a tap whose pair count is not a multiple of the split-K chunk.  Also: the differentiable forward
+    is the inference forward bit for bit, the weight gradient does not depend on whether feat requires grad, a second
+    backward is bitwise the same, and the tap-swept feature gradient is the one-buffer feature gradient bit for bit."""
+    ops, pt = _mods()
+    pts = _clouds(7, F, N)
+    n = F * N
+    level = _level(pts)
+    gen = torch.Generator().manual_seed(8)
+    feat = torch.randn(n, cin, generator=gen)
+    conv = pt.SubMConv3d(cin, cout, ksize, bias=True)
+    with torch.no_grad():
+        conv.bias.copy_(torch.randn(cout, generator=gen) * 0.1)
+    dout = torch.randn(n, cout, generator=gen)
+    conv = conv.cuda()
+
+    pairs = level.pairs(ksize)
+    tap_of = torch.searchsorted(pairs.tap_start.long(), torch.arange(pairs.count, device="cuda"), right=True) - 1
+    key = tap_of * n + pairs.pair_src.long()
+    assert int(torch.unique(key).numel()) < pairs.count, "no source row owns two pairs of one tap"
+    assert torch.equal(pairs.pair_of[pairs.pair_dst.long(), tap_of], torch.arange(pairs.count, device="cuda", dtype=torch.int32))
+    chunk, _, slices = pairs.wgrad_slices(cin + (-cin % 32), cout)
+    counts = np.diff(pairs.tap_start_host.astype(np.int64))
+    assert chunk % ops.SUBM_WGRAD_CHUNK == 0 and (counts % chunk != 0).any(), (chunk, counts)
+    if (cin, N) == (12, 400):
+        assert (counts == 0).any() and (counts > 0).any()  # the sparse 5^3 case has empty taps: they write zeros
+
+    def run(feat_grad):
+        x = feat.cuda().requires_grad_(feat_grad)
+        conv.zero_grad(set_to_none=True)
+        out = conv(x, level, differentiable=True)
+        out.backward(dout.cuda())
+        return out.detach(), dict(feat=x.grad, weight=conv.weight.grad.clone(), bias=conv.bias.grad.clone())
+
+    out, got = run(True)
+    with torch.no_grad():
+        assert torch.equal(out, conv(feat.cuda(), level))
+    _, again = run(True)
+    for k in got:
+        assert torch.equal(got[k], again[k]), k
+    _, frozen = run(False)
+    assert frozen["feat"] is None and torch.equal(frozen["weight"], got["weight"]) and torch.equal(frozen["bias"], got["bias"])
+
+    g64 = _conv_reference(conv, pts, feat, dout, ksize, torch.float64)
+    g32 = _conv_reference(conv, pts, feat, dout, ksize, torch.float32)
+    for k in ("feat", "weight", "bias"):
+        assert got[k].shape == g64[k].shape
+        _check(f"conv {cin}->{cout} k{ksize} d{k}", got[k], g64[k], g32[k])
+
+    pad = -cin % 32
+    wt = conv.weight.detach().reshape(cout, -1, cin).permute(1, 0, 2)
+    wt = torch.nn.functional.pad(wt, (0, pad)).contiguous()
+    whole = ops.subm_feat_grad(dout.cuda(), wt, pairs)
+    swept = ops.subm_feat_grad(dout.cuda(), wt, pairs, max_buffer_bytes=pairs.count * (cin + pad) * 4 // 5)
+    assert torch.equal(whole[:, :cin], got["feat"]) and torch.equal(whole, swept)
+
+
+# --------------------------------------------------------------------------------------------------- 2. attention
+def _attention_reference(qkv, order, counts, heads, dim, patch, dout, dtype):
+    """fp autograd of the padded-patch restatement (patch_layout + softmax, as oracle.ptv3.serialized_attention) ->
+    (out, lse [n, heads], d qkv)."""
+    from oracle import ptv3 as o_pt
+
+    C = heads * dim
+    x_all = qkv.detach().clone().to(dtype).requires_grad_()
+    outs, lses = [], []
+    start = 0
+    for c in counts:
+        o = order[start:start + c] - start
+        inv = torch.empty_like(o)
+        inv[o] = torch.arange(c)
+        K, pad, unpad = o_pt.patch_layout(c, patch)
+        x = x_all[start:start + c][o[pad]]
+        q, k, v = x.reshape(-1, K, 3, heads, dim).permute(2, 0, 3, 1, 4).unbind(0)
+        s = (q * dim ** -0.5) @ k.transpose(-2, -1)
+        outs.append((torch.softmax(s, -1) @ v).transpose(1, 2).reshape(-1, C)[unpad[inv]])
+        lses.append(torch.logsumexp(s, -1).transpose(1, 2).reshape(-1, heads)[unpad[inv]])
+        start += c
+    out = torch.cat(outs)
+    out.backward(dout.to(dtype))
+    return out.detach(), torch.cat(lses).detach(), x_all.grad
+
+
+def _attention_case(heads, dim, counts, patch):
+    _, pt = _mods()
+    C = heads * dim
+    n = sum(counts)
+    gen = torch.Generator().manual_seed(11)
+    qkv = torch.randn(n, 3 * C, generator=gen)
+    order = torch.cat([torch.randperm(c, generator=gen) + s for c, s in zip(counts, np.cumsum([0] + counts[:-1]))])
+    dout = torch.randn(n, C, generator=gen)
+    level = pt.Level.__new__(pt.Level)
+    level.counts, level.starts_host = counts, np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    level.grid, level._patches = qkv.cuda(), {}
+    desc, max_patch = level.patches(patch)
+    return qkv, order, dout, desc, max_patch
+
+
+@pytest.mark.parametrize("heads,dim,counts,patch", [(4, 64, [1300, 512, 70], 512), (2, 32, [300, 130], 128),
+                                                    (2, 16, [257, 33, 64], 128), (1, 64, [5], 512)])
+def test_patch_attention_backward_matches_fp64_autograd(heads, dim, counts, patch):
+    """The LSE entry's out is patch_attention's bit for bit, its lse the fp64 one to 1e-5; d qkv within the module's
+    bound; a second backward is bitwise the same."""
+    ops, _ = _mods()
+    qkv, order, dout, desc, max_patch = _attention_case(heads, dim, counts, patch)
+    out, lse = ops.patch_attention_lse(qkv.cuda(), order.cuda(), desc, heads, max_patch)
+    assert torch.equal(out, ops.patch_attention(qkv.cuda(), order.cuda(), desc, heads, max_patch))
+    o64, l64, g64 = _attention_reference(qkv, order, counts, heads, dim, patch, dout, torch.float64)
+    _, _, g32 = _attention_reference(qkv, order, counts, heads, dim, patch, dout, torch.float32)
+    lse_err = float((lse.cpu().double() - l64).abs().max())
+    print(f"lse err {lse_err:.3e}")
+    assert lse_err <= 1e-5
+
+    def run():
+        x = qkv.cuda().requires_grad_()
+        y = ops.patch_attention_differentiable(x, order.cuda(), desc, heads, max_patch)
+        y.backward(dout.cuda())
+        return y.detach(), x.grad
+
+    y, got = run()
+    assert torch.equal(y, out)
+    assert torch.equal(run()[1], got)
+    C = heads * dim
+    for i, part in enumerate(("dq", "dk", "dv")):
+        sl = slice(i * C, (i + 1) * C)
+        _check(f"attention h{heads} d{dim} {counts} {part}", got[:, sl], g64[:, sl], g32[:, sl])
+
+
+def test_patch_attention_backward_borrowed_keys_carry_both_contributions():
+    """counts [257, ...], patch 128: the first cloud's last patch has one own query (sorted position 256) and 127
+    borrowed keys, sorted positions 129..255 (the 130th..256th).  Their dK is the own patch's part plus the borrowing
+    patch's: zeroing d out of that one query changes the dK of every one of them, and of no other row."""
+    ops, _ = _mods()
+    heads, dim, counts, patch = 2, 16, [257, 33, 64], 128
+    qkv, order, dout, desc, max_patch = _attention_case(heads, dim, counts, patch)
+    C = heads * dim
+    out, lse = ops.patch_attention_lse(qkv.cuda(), order.cuda(), desc, heads, max_patch)
+    full = ops.patch_attention_backward(qkv.cuda(), order.cuda(), desc, out, lse, dout.cuda(), heads, max_patch).cpu()
+    cut = dout.clone()
+    cut[order[256]] = 0
+    part = ops.patch_attention_backward(qkv.cuda(), order.cuda(), desc, out, lse, cut.cuda(), heads, max_patch).cpu()
+    changed = ((full[:, C:2 * C] - part[:, C:2 * C]).abs().amax(1) > 0)
+    want = torch.zeros(sum(counts), dtype=torch.bool)
+    want[order[129:256]] = True
+    want[order[256]] = True  # the last patch's own point is a key of its own patch too
+    assert torch.equal(changed, want), (int(changed.sum()), int(want.sum()))
+
+
+# --------------------------------------------------------------------------------------------- 3. segment kernels
+def _segments(gen, C):
+    sizes = [1, 2, 3, 4, 5, 6, 7, 8, 1, 8, 2, 5]
+    n = sum(sizes)
+    members = torch.randperm(n, generator=gen)
+    seg = torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int64)
+    return sizes, n, members, seg
+
+
+@pytest.mark.parametrize("C", [32, 260, 512])
+def test_cluster_max_backward_matches_fp64(C):
+    """dx, and the scale / shift gradients of the autograd node, against fp64 on the CPU with the tie convention (the
+    first maximal member in segment order takes the whole gradient), incl. a deliberate tie: two equal rows in one
+    cluster.  Bound 4e-6 of the tensor's largest reference value: gelu'(z) in fp32 is an erf, an exp and five
+    multiply-adds (each a few ulp of 6e-8 on values <= ~1), z = max * scale + shift carries one rounding of |z| <= ~10
+    through |gelu''| <= 0.8, and the two column sums add <= 12 such terms."""
+    ops, _ = _mods()
+    gen = torch.Generator().manual_seed(51 + C)
+    sizes, n, members, seg = _segments(gen, C)
+    x = torch.randn(n, C, generator=gen)
+    tie_first, tie_second = int(members[seg[9]]), int(members[seg[9] + 3])  # the cluster of 8
+    x[tie_first] = x[tie_second] = 6.0  # both rows are the maximum of every channel
+    scale, shift = torch.rand(C, generator=gen) + 0.5, torch.randn(C, generator=gen) * 0.3
+    dout = torch.randn(len(sizes), C, generator=gen)
+
+    xg, sg, bg = x.cuda().requires_grad_(), scale.cuda().requires_grad_(), shift.cuda().requires_grad_()
+    out = ops.cluster_max_differentiable(xg, members.cuda(), seg.cuda(), sg, bg)
+    assert torch.equal(out, ops.cluster_max(x.cuda(), members.cuda(), seg.cuda(), scale.cuda(), shift.cuda()))
+    out.backward(dout.cuda())
+
+    x64 = x.double().requires_grad_()
+    s64, b64 = scale.double().requires_grad_(), shift.double().requires_grad_()
+    rows = []
+    for j in range(len(sizes)):
+        m = x64[members[seg[j]:seg[j + 1]]]
+        first = torch.from_numpy(np.argmax(m.detach().numpy(), axis=0))  # numpy: the first occurrence
+        rows.append(m.gather(0, first[None])[0])
+    torch.nn.functional.gelu(torch.stack(rows) * s64 + b64).backward(dout.double())
+    for name, got, ref in (("dx", xg.grad, x64.grad), ("dscale", sg.grad, s64.grad), ("dshift", bg.grad, b64.grad)):
+        err, big = float((got.cpu().double() - ref).abs().max()), float(ref.abs().max())
+        print(f"cluster_max_backward C={C} {name}: err {err:.3e} max|ref| {big:.3e}")
+        assert err <= 4e-6 * big, (name, err, big)
+    assert float(xg.grad[tie_first].abs().min()) > 0 and float(xg.grad[tie_second].abs().max()) == 0.0
+    assert int((xg.grad != 0).sum()) <= len(sizes) * C  # one row per (cluster, channel)
+
+
+@pytest.mark.parametrize("C", [32, 260, 512])
+def test_cluster_sum_is_the_sequential_fp32_sum(C):
+    ops, _ = _mods()
+    gen = torch.Generator().manual_seed(61 + C)
+    sizes, n, members, seg = _segments(gen, C)
+    x = torch.randn(n, C, generator=gen)
+    got = ops.cluster_sum(x.cuda(), members.cuda(), seg.cuda()).cpu()
+    want = torch.empty(len(sizes), C)
+    for j in range(len(sizes)):
+        acc = x[members[seg[j]]].clone()
+        for r in range(int(seg[j]) + 1, int(seg[j + 1])):
+            acc = acc + x[members[r]]
+        want[j] = acc
+    assert torch.equal(got, want)
+    # as the backward of the gather
+    up = torch.randn(len(sizes), C, generator=gen).cuda().requires_grad_()
+    cluster = torch.empty(n, dtype=torch.int64)
+    for j in range(len(sizes)):
+        cluster[members[seg[j]:seg[j + 1]]] = j
+    y = ops.cluster_gather_differentiable(up, cluster.cuda(), members.cuda(), seg.cuda())
+    assert torch.equal(y, up.detach()[cluster.cuda()])
+    y.backward(x.cuda())
+    assert torch.equal(up.grad.cpu(), want)
+
+
+# ------------------------------------------------------------------------------------------------------ 4. network
+PCFG = dict(stride=(2, 2), enc_depths=(1, 1, 1), enc_channels=(32, 64, 128), enc_num_head=(2, 4, 4),
+            enc_patch_size=(256, 256, 256), dec_depths=(1, 1), dec_channels=(64, 64), dec_num_head=(1, 2),
+            dec_patch_size=(256, 256))
+IN_CHANNELS = 48
+
+
+def _network(differentiable=True):
+    _, pt = _mods()
+    torch.manual_seed(0)
+    net = pt.PointTransformerV3(in_channels=IN_CHANNELS, differentiable=differentiable, **PCFG).eval()
+    with torch.no_grad():
+        for m in net.modules():
+            if isinstance(m, torch.nn.BatchNorm1d):
+                m.running_mean.normal_(0, 0.2)
+                m.running_var.uniform_(0.5, 1.5)
+    return net
+
+
+def _inputs(F, N):
+    pts = _clouds(41, F, N)
+    feat = torch.randn(F, N, IN_CHANNELS, generator=torch.Generator().manual_seed(42))
+    dout = torch.randn(F * N, PCFG["dec_channels"][0], generator=torch.Generator().manual_seed(43))
+    return pts, feat, dout
+
+
+def _oracle_grads(net, pts, feat, dout, dtype):
+    """oracle.ptv3.ptv3_cloud on one cloud under torch autograd -> (out, {name: grad}, d feat)."""
+    from oracle import ptv3 as o_pt
+
+    cfg = {k: list(PCFG[k]) for k in ("enc_depths", "enc_num_head", "enc_patch_size", "dec_depths", "dec_num_head",
+                                      "dec_patch_size")}
+    names = {k for k, _ in net.named_parameters()}
+    p = {k: v.detach().cpu().to(dtype).requires_grad_(k in names) for k, v in net.state_dict().items()
+         if v.is_floating_point()}
+    x = feat.detach().clone().to(dtype).requires_grad_()
+    out = o_pt.ptv3_cloud(p, "", o_pt.frame_grid(pts), x, cfg)
+    out.backward(dout.to(dtype))
+    return out.detach(), {k: p[k].grad for k in names}, x.grad
+
+
+@functools.lru_cache(maxsize=None)
+def _reference():
+    """The fp64 reference and the fp32 yardstick of the 700-point case, computed once for the module."""
+    net = _network()
+    pts, feat, dout = _inputs(1, 700)
+    return _oracle_grads(net, pts[0], feat[0], dout, torch.float64), _oracle_grads(net, pts[0], feat[0], dout, torch.float32)
+
+
+def _hip_grads(net, pts, feat, dout):
+    net.zero_grad(set_to_none=True)
+    x = feat.cuda().requires_grad_()
+    out = net(pts.cuda(), x)
+    out.backward(dout.cuda())
+    return out.detach(), {k: v.grad.clone() for k, v in net.named_parameters()}, x.grad
+
+
+def test_network_gradients_match_fp64_oracle():
+    """The small configuration of test_renderer_with_point_refiner_matches_oracle (48 input channels, randomised
+    BatchNorm statistics) on one cloud of 700 = 2 * 256 + 188 points (a borrowed tail at level 0): every parameter
+    gradient and d feat against oracle.ptv3.ptv3_cloud, and the differentiable forward with the forward test's bound."""
+    (o64, p64, f64), (o32, p32, f32) = _reference()
+    net = _network().cuda()
+    assert len(p64) == len(list(net.named_parameters())) > 100  # every parameter tensor, and feat, gets a gradient
+    assert all(g is not None for g in p64.values()) and f64 is not None
+    pts, feat, dout = _inputs(1, 700)
+    out, grads, dfeat = _hip_grads(net, pts, feat, dout)
+    assert out.requires_grad is False and all(g is not None for g in grads.values())
+    err, err32, big = (float((out.cpu().double() - o64).abs().max()), float((o32.double() - o64).abs().max()),
+                       float(o64.abs().max()))
+    print(f"forward: err {err:.3e} err32 {err32:.3e} largest |out| {big:.3f}")
+    assert err <= min(max(4 * err32, 2e-5 * big), 1e-4 * max(1.0, big))
+    worst = max(_check(k, grads[k], p64[k], p32[k]) for k in sorted(p64))
+    worst = max(worst, _check("d feat", dfeat[0], f64, f32))
+    print(f"worst err / bound: {worst:.3f}")
+
+
+def test_network_batched_clouds_equal_single_clouds():
+    """Two clouds of 420 points in one batch: d feat of each cloud within 2e-5 (relative) of the cloud run alone -- the
+    forward test's allowance for library GEMMs that split a [2N, C] and an [N, C] product differently."""
+    net = _network().cuda()
+    pts, feat, dout = _inputs(2, 420)
+    _, _, both = _hip_grads(net, pts, feat, dout)
+    for f in range(2):
+        _, _, alone = _hip_grads(net, pts[f:f + 1], feat[f:f + 1], dout[f * 420:(f + 1) * 420])
+        err, big = float((both[f] - alone[0]).abs().max()), float(alone.abs().max())
+        print(f"cloud {f}: |batched - alone| {err:.3e}, largest |d feat| {big:.3e}")
+        assert err <= 2e-5 * big, (f, err, big)
+
+
+# -------------------------------------------------------------------------------------------------- 5. determinism
+def test_network_gradients_are_bitwise_reproducible():
+    net = _network().cuda()
+    pts, feat, dout = _inputs(1, 700)
+    out_a, grads_a, dfeat_a = _hip_grads(net, pts, feat, dout)
+    out_b, grads_b, dfeat_b = _hip_grads(net, pts, feat, dout)
+    assert torch.equal(out_a, out_b) and torch.equal(dfeat_a, dfeat_b)
+    for k in grads_a:
+        assert torch.equal(grads_a[k], grads_b[k]), k
+
+
+# ----------------------------------------------------------------------------------------------------- 6. switches
+def test_switches_keep_the_inference_path():
+    pts, feat, _ = _inputs(1, 700)
+    off = _network(differentiable=False).cuda()
+    assert all(p.requires_grad for p in off.parameters())
+    with torch.no_grad():
+        want = off(pts.cuda(), feat.cuda())
+    got = off(pts.cuda(), feat.cuda().requires_grad_())   # the default, under grad mode
+    assert got.requires_grad is False and torch.equal(got, want)
+    on = _network(differentiable=True).cuda()
+    with torch.no_grad():
+        got = on(pts.cuda(), feat.cuda().requires_grad_())  # the flag on, grad mode off
+    assert got.requires_grad is False and torch.equal(got, want)
+    assert on(pts.cuda(), feat.cuda().requires_grad_()).requires_grad is True
+
+
+def test_renderer_still_refuses_autograd_with_a_differentiable_refiner():
+    from audio_motion_avatar_amd.config import RendererConfig
+    from audio_motion_avatar_amd.renderer import Renderer
+    from audio_motion_avatar_amd.synthetic import init_random_heads, make_render_inputs
+
+    cfg = RendererConfig(image_size=(64, 64), subdivide_steps=0, triplane_feature_dim=16, triplane_resolution=8,
+                         predict_smplx_params=False, no_point_refiner=False, num_gaussians=1500,
+                         differentiable_refiner=True, **PCFG)
+    assert RendererConfig().differentiable_refiner is False
+    r = init_random_heads(Renderer(cfg).eval(), std=0.05)
+    assert r.point_encoder.point_transformer.differentiable is True
+    tokens, smpl, cam = make_render_inputs(2, cfg, seed=4)
+    with pytest.raises(NotImplementedError, match="point refiner"):
+        r(tokens.requires_grad_(), cam, torch.zeros(1, 2, 1, 1, device="cuda"), smpl)
+
+
+# ----------------------------------------------------------------------------------------------------- 7. it trains
+def test_network_trains():
+    """16 Adam steps (lr 1e-3) on the MSE to a fixed random target at N = 300: the loss at least halves (the CPU oracle
+    on this set-up goes 2.58 -> 0.87)."""
+    net = _network().cuda()
+    pts, feat, target = _inputs(1, 300)
+    pts, feat, target = pts.cuda(), feat.cuda(), target.cuda()
+    opt = torch.optim.Adam(net.parameters(), lr=1e-3)
+    losses = []
+    for _ in range(16):
+        opt.zero_grad(set_to_none=True)
+        loss = torch.nn.functional.mse_loss(net(pts, feat), target)
+        loss.backward()
+        opt.step()
+        losses.append(float(loss))
+    print("losses:", " ".join(f"{v:.4f}" for v in losses))
+    assert losses[-1] < 0.5 * losses[0], losses
