@@ -65,6 +65,20 @@ class TriplaneDecodeBackwardArgs(ctypes.Structure):
     ]
 
 
+class TriplaneSampleBackwardArgs(ctypes.Structure):
+    _fields_ = [
+        ("num_frames", ctypes.c_int32), ("num_points", ctypes.c_int32), ("channels", ctypes.c_int32),
+        ("resolution", ctypes.c_int32), ("radius", ctypes.c_float),
+        ("planes", ctypes.c_void_p), ("planes_frame_stride", ctypes.c_int64), ("planes_plane_stride", ctypes.c_int64),
+        ("planes_chan_stride", ctypes.c_int64),
+        ("points", ctypes.c_void_p), ("grad_out", ctypes.c_void_p),
+        ("grad_planes", ctypes.c_void_p), ("grad_frame_stride", ctypes.c_int64), ("grad_plane_stride", ctypes.c_int64),
+        ("grad_chan_stride", ctypes.c_int64),
+        ("grad_points", ctypes.c_void_p),
+        ("scratch", ctypes.c_void_p), ("scratch_bytes", ctypes.c_size_t),
+    ]
+
+
 class DecodeSource(ctypes.Structure):
     _fields_ = [
         ("resolution", ctypes.c_int32), ("num_verts", ctypes.c_int32),
@@ -252,6 +266,10 @@ SIGNATURES = {
     "amav_triplane_sample_features": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                      c_float_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                                      c_float_p, ctypes.c_float, c_float_p, ctypes.c_void_p]),
+    "amav_triplane_sample_features_backward_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                                       ctypes.c_int]),
+    "amav_triplane_sample_features_backward": (ctypes.c_int, [ctypes.POINTER(TriplaneSampleBackwardArgs),
+                                                              ctypes.c_void_p]),
     "amav_selfattn_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "amav_selfattn_forward": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_float_p,
                                              c_float_p, c_float_p, ctypes.c_int64, c_float_p, ctypes.c_int64,

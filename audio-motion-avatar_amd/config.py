@@ -56,6 +56,9 @@ class RendererConfig:
     refiner_points_per_pass: int = 320_000  # ... but a pass holds at most this many points (working set ~0.4 MB per 1 k points)
     differentiable_refiner: bool = False  # PTv3Encoder records an autograd graph (HIP backwards) when
     #                                       called under grad mode on its own; Renderer still refuses autograd with a refiner
+    differentiable_refine_points: bool = False  # ... unless this is on too (needs differentiable_refiner): refine_points
+    #                                       becomes an autograd graph (HIP backward of the feature sampling, DESIGN.md section
+    #                                       4.13), so an image loss reaches the refiner, its MLP and the tokens through it
     use_gaussian_splatting: bool = True
     gaussian_feature_dim: int = 256
     rgb: bool = True

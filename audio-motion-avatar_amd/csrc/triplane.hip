@@ -21,6 +21,7 @@
 
 #include "amav_common.h"
 #include "decode_quad.h"
+#include "sample_taps.h"
 #include "triplane_region.h"
 
 namespace amav {
@@ -141,23 +142,6 @@ __global__ __launch_bounds__(256) void project_kernel_scalar(int C, int RR, cons
     float *dst = out + (((size_t)f * 3 + plane) * RR + s) * 16;
 #pragma unroll
     for (int o = 0; o < 16; ++o) dst[o] = acc[o];
-}
-
-// torch grid_sampler, bilinear, align_corners=False, padding zeros: pixel = ((g + 1) * size - 1) / 2
-struct Taps {
-    int ix0, iy0;
-    float wx0, wx1, wy0, wy1;
-};
-
-__device__ __forceinline__ Taps make_taps(float gx, float gy, int R) {
-    const float ix = ((gx + 1.0f) * (float)R - 1.0f) * 0.5f;
-    const float iy = ((gy + 1.0f) * (float)R - 1.0f) * 0.5f;
-    const float fx = floorf(ix), fy = floorf(iy);
-    Taps t;
-    t.ix0 = (int)fx, t.iy0 = (int)fy;
-    t.wx1 = ix - fx, t.wx0 = (fx + 1.0f) - ix;
-    t.wy1 = iy - fy, t.wy0 = (fy + 1.0f) - iy;
-    return t;
 }
 
 // Lane group of 4 per point; lane q owns projected channels 4q..4q+3 (decode_quad.h):

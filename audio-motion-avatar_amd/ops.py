@@ -9,7 +9,7 @@ import torch
 
 from . import _lib
 from ._lib import (AmavError, Attr, BodyTables, DecodeSource, LbsBackwardArgs, PoseParts, RasterArgs,
-                   RasterBackwardArgs, TriplaneDecodeBackwardArgs, check)
+                   RasterBackwardArgs, TriplaneDecodeBackwardArgs, TriplaneSampleBackwardArgs, check)
 
 SCALE_BIAS = 3.9    # src/models/renderer.py:428
 OPACITY_BIAS = 0.0  # src/models/renderer.py:429
@@ -1000,6 +1000,74 @@ def triplane_sample_features(planes, points, radius):
                                                    out.data_ptr(), _stream()), "amav_triplane_sample_features")
     return out
 
+
+
+def triplane_sample_features_backward(planes, points, grad_out, radius, want_planes=True, want_points=True):
+    """Gradients of triplane_sample_features(planes, points, radius) given grad_out [F,N,3C]
+    (amav_triplane_sample_features_backward).  Returns (grad_planes or None, grad_points or None).  grad_planes has the
+    shape of `planes` and, for a dense `planes` (the renderer's permuted view of the token slab included), its strides:
+    autograd's way back to the tokens is then a view.  Every element is written.  Deterministic; no host sync."""
+    _need(planes, "planes")
+    points = _contig(points, "points")
+    grad_out = _contig(grad_out, "grad_out")
+    F, P, C, R, R2 = planes.shape
+    if P != 3 or R != R2:
+        raise AmavError(f"planes must be [F,3,C,R,R], got {tuple(planes.shape)}")
+    if planes.stride(4) != 1 or planes.stride(3) != R:
+        planes = planes.contiguous()
+    N = points.shape[1]
+    if tuple(points.shape) != (F, N, 3) or tuple(grad_out.shape) != (F, N, 3 * C):
+        raise AmavError(f"points {tuple(points.shape)} / grad_out {tuple(grad_out.shape)} do not match planes "
+                        f"{tuple(planes.shape)}")
+    dev = planes.device
+    g_planes = g_points = scratch = None
+    a = TriplaneSampleBackwardArgs()
+    a.num_frames, a.num_points, a.channels, a.resolution, a.radius = F, N, C, R, float(radius)
+    a.planes = planes.data_ptr()
+    a.planes_frame_stride, a.planes_plane_stride, a.planes_chan_stride = planes.stride(0), planes.stride(1), planes.stride(2)
+    a.points, a.grad_out = points.data_ptr(), grad_out.data_ptr()
+    if want_planes:
+        g_planes = torch.empty_like(planes)  # keeps a dense input's strides
+        if g_planes.stride(4) != 1 or g_planes.stride(3) != R or min(g_planes.stride()[:3]) < R * R:
+            g_planes = torch.empty(F, 3, C, R, R, device=dev)
+        nbytes = _lib.lib().amav_triplane_sample_features_backward_bytes(F, N, C, R)
+        if nbytes == 0:
+            raise AmavError(f"amav_triplane_sample_features_backward_bytes rejected F={F} N={N} C={C} R={R}")
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        a.grad_planes = g_planes.data_ptr()
+        a.grad_frame_stride, a.grad_plane_stride, a.grad_chan_stride = g_planes.stride(0), g_planes.stride(1), g_planes.stride(2)
+        a.scratch, a.scratch_bytes = scratch.data_ptr(), nbytes
+    if want_points:
+        g_points = torch.empty(F, N, 3, device=dev)
+        a.grad_points = g_points.data_ptr()
+    if want_planes or want_points:
+        check(_lib.lib().amav_triplane_sample_features_backward(ctypes.byref(a), _stream()),
+              "amav_triplane_sample_features_backward")
+    return g_planes, g_points
+
+
+class _TriplaneSampleFeatures(torch.autograd.Function):
+    """triplane_sample_features (the unchanged forward kernels) with amav_triplane_sample_features_backward."""
+
+    @staticmethod
+    def forward(ctx, planes, points, radius):
+        ctx.radius = radius
+        ctx.save_for_backward(planes, points)
+        return triplane_sample_features(planes, points, radius)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        planes, points = ctx.saved_tensors
+        g_planes, g_points = triplane_sample_features_backward(planes, points, grad_out.float(), ctx.radius,
+                                                               want_planes=ctx.needs_input_grad[0],
+                                                               want_points=ctx.needs_input_grad[1])
+        return g_planes, g_points, None
+
+
+def triplane_sample_features_differentiable(planes, points, radius):
+    """triplane_sample_features as a torch.autograd.Function: the same output bit for bit; gradients reach `planes`
+    (through any view it is, e.g. the token slab) and `points`, each only when it requires grad."""
+    return _TriplaneSampleFeatures.apply(planes, points, float(radius))
 
 # ---------------------------------------------------------------------------------------------- stage-1 reductions
 def cell_segments(cell_of, cells):

@@ -61,6 +61,10 @@ class Renderer(nn.Module):
     def __init__(self, cfg=None, smpl_decoder=None):
         super().__init__()
         self.cfg = cfg
+        if getattr(cfg, "differentiable_refine_points", False) and (
+                getattr(cfg, "no_point_refiner", True) or not getattr(cfg, "differentiable_refiner", False)):
+            raise ValueError("RendererConfig.differentiable_refine_points=True needs a trainable point refiner: set "
+                             "no_point_refiner=False and differentiable_refiner=True")
         self.smplx_model = self.init_smplx_model()
         # the reference's table (renderer.py:14-18,25); `num_gaussians` overrides it (BASELINE's 50 000-Gaussian stress
         # config has no entry there)
@@ -150,25 +154,34 @@ class Renderer(nn.Module):
         batched = points.ndim == 3
         if not batched:
             triplane_features, points = triplane_features[None], points[None]
-        out = ops.triplane_sample_features(triplane_features.float(), points.float(), self.cfg.radius)
+        planes, points = triplane_features.float(), points.float()
+        if torch.is_grad_enabled() and (planes.requires_grad or points.requires_grad):
+            out = ops.triplane_sample_features_differentiable(planes, points, self.cfg.radius)
+        else:
+            out = ops.triplane_sample_features(planes, points, self.cfg.radius)
         return out if batched else out.squeeze(0)
 
-    def refine_points(self, triplane_tokens, points):
+    def refine_points(self, triplane_tokens, points, differentiable=False):
         """renderer.py:136-151: features at the initial points -> PTv3 -> 3-layer MLP -> points + offsets.
         tokens [F,C,3R^2], points [F,N,3] -> refined points [F,N,3].  Frames are refined in groups of
-        cfg.refiner_clouds_per_pass (they do not interact; the group only bounds the working set)."""
+        cfg.refiner_clouds_per_pass (they do not interact; the group only bounds the working set).
+        differentiable (cfg.differentiable_refine_points, under grad mode): the same kernels in the same frame groups as
+        an autograd graph -- the sampling's HIP backward (ops.triplane_sample_features_differentiable) carries gradients
+        to the tokens and the points, the trainable PTv3 (point_transformer.py) to its parameters and the features, torch
+        to the MLP.  PTv3 gives its `points` argument no gradient: the points' comes from the residual and the sampling."""
         F, N, _ = points.shape
         R = self._plane_resolution(triplane_tokens)
         planes = triplane_tokens.view(F, triplane_tokens.shape[1], 3, R, R).permute(0, 2, 1, 3, 4)
         step = max(1, min(int(getattr(self.cfg, "refiner_clouds_per_pass", 32)),
                           int(getattr(self.cfg, "refiner_points_per_pass", 320_000)) // max(N, 1)))
-        refined = torch.empty_like(points)
+        sample = ops.triplane_sample_features_differentiable if differentiable else ops.triplane_sample_features
+        refined = []
         for s in range(0, F, step):
             pts = points[s:s + step].contiguous()
-            feats = ops.triplane_sample_features(planes[s:s + step], pts, self.cfg.radius)
+            feats = sample(planes[s:s + step], pts, self.cfg.radius)
             offsets = self.point_refiner(self.point_encoder.point_transformer(pts, feats))
-            refined[s:s + step] = pts + offsets.view(pts.shape)
-        return refined
+            refined.append(pts + offsets.view(pts.shape))
+        return refined[0] if len(refined) == 1 else torch.cat(refined)
 
     def _head_layers(self):
         gd = self.gaussian_decoder
@@ -190,22 +203,29 @@ class Renderer(nn.Module):
     def _differentiable_smplx(self):
         return bool(getattr(self.cfg, "differentiable_smplx", False))
 
+    def _differentiable_refine_points(self):
+        return bool(getattr(self.cfg, "differentiable_refine_points", False)) and hasattr(self, "point_encoder")
+
     def _wants_grad(self, *tensors, smpl_params=None):
         """Gradients are recorded through the decode when grad mode is on and the tokens, a head parameter or transl
-        (among `tensors`) requires grad -- with cfg.differentiable_smplx, also any tensor of `smpl_params`; otherwise
-        every call runs the inference path exactly as before."""
+        (among `tensors`) requires grad -- with cfg.differentiable_smplx, also any tensor of `smpl_params`, with
+        cfg.differentiable_refine_points, also any point_encoder / point_refiner parameter; otherwise every call runs
+        the inference path exactly as before."""
         if not torch.is_grad_enabled():
             return False
         if smpl_params is not None and self._differentiable_smplx():
             tensors = tensors + tuple(v for v in smpl_params.values() if isinstance(v, torch.Tensor))
+        if self._differentiable_refine_points():
+            tensors = tensors + tuple(self.point_encoder.parameters()) + tuple(self.point_refiner.parameters())
         return any(t is not None and t.requires_grad for t in tensors) or any(
             p.requires_grad for p in self.gaussian_decoder.parameters())
 
     def _refuse_under_grad(self, smpl_params):
         """Configurations with no backward are refused rather than silently dropping gradient."""
-        if hasattr(self, "point_encoder"):
+        if hasattr(self, "point_encoder") and not self._differentiable_refine_points():
             raise NotImplementedError("Renderer: the point refiner has no backward; disable gradients "
-                                      "(torch.no_grad()) or use no_point_refiner=True")
+                                      "(torch.no_grad()) or use no_point_refiner=True (to train through it, set "
+                                      "differentiable_refiner=True and differentiable_refine_points=True)")
         if self._differentiable_smplx():
             return
         bad = sorted(k for k, v in smpl_params.items() if k != "transl" and isinstance(v, torch.Tensor) and v.requires_grad)
@@ -250,8 +270,10 @@ class Renderer(nn.Module):
         Other configurations decode here and return None in that place.
         Differentiable (ops.triplane_decode_differentiable; the same records) when grad mode is on and the tokens, a
         head parameter or transl requires grad (with cfg.differentiable_smplx: any SMPL-X parameter, whose gradient then
-        comes from the gather and LBS backwards); `out`, `window_plan`, `defer_decode`, the point refiner and -- without
-        that flag -- SMPL-X parameters other than transl that require grad are refused then (NotImplementedError).
+        comes from the gather and LBS backwards; with cfg.differentiable_refine_points: any point refiner parameter,
+        and the points are refined by refine_points(differentiable=True)); `out`, `window_plan`, `defer_decode`, the point
+        refiner without that flag and -- without differentiable_smplx -- SMPL-X parameters other than transl that require
+        grad are refused then (NotImplementedError).
         """
         F = triplane_tokens.shape[0]
         if self._wants_grad(triplane_tokens, smpl_params["transl"], smpl_params=smpl_params):
@@ -265,6 +287,8 @@ class Renderer(nn.Module):
             # the SMPL-X parameters that require grad (BodyModel + points_gather_differentiable)
             with torch.set_grad_enabled(self._differentiable_smplx()):
                 points = self.get_smpl_vertices(smpl_params)
+            if hasattr(self, "point_encoder"):  # cfg.differentiable_refine_points (anything else was refused above)
+                points = self.refine_points(triplane_tokens, points, differentiable=True)
             packed = self._differentiable_decode(triplane_tokens, points, smpl_params["transl"].reshape(F, 3).float(),
                                                  region=self.project_sampled_region)
             return packed if side_work is None else (packed, side_result)

@@ -410,6 +410,39 @@ int amav_triplane_sample_features(int num_frames, int num_points, int channels, 
                                   const float *planes_dev, int64_t frame_stride, int64_t plane_stride,
                                   int64_t chan_stride, const float *points_dev, float radius,
                                   float *out_features_dev, void *stream);
+/* amav_triplane_sample_features, backward (training through the point refiner, whose input features are these samples):
+ * given grad_out = dL/d features [F,N,3C],
+ *   grad_planes (f, plane, c, y, x), written at grad_planes[f*grad_frame_stride + plane*grad_plane_stride +
+ *     c*grad_chan_stride + y*R + x] = sum over the frame's taps on that texel of w * grad_out[f,n,plane*C+c].  EVERY element
+ *     is written (exact zeros where no tap lands); out-of-plane taps are skipped, as the forward's zero padding does.
+ *   grad_points [F,N,3]: the bilinear weights' derivative as torch's grid_sampler backward takes it (out-of-plane taps
+ *     count with value 0), * R / 2, through clamp(p / radius, -1, 1) (gradient where -1 <= p / radius <= 1, zero beyond),
+ *     / radius; each coordinate collects from the two planes that sample it.  Needs the forward's planes and strides.
+ * Either output may be NULL (not wanted); the other one's bits do not change.  One kernel pair serves every C.
+ * Deterministic: no float atomics.  A texel sums its taps in a fixed order (the four base cells that reach it, rows then
+ * columns; points ascending inside a cell; the order comes from a stable counting sort of the frame's points), a point
+ * its channels ascending in four interleaved runs: bitwise the same from run to run, and a frame's gradients do not
+ * depend on the other frames of the call.
+ * scratch: amav_triplane_sample_features_backward_bytes(F, N, C, R) bytes, 16-B aligned (0 = bad sizes); only
+ * grad_planes uses it.  Refused with an error code before any launch: NULL args / points / grad_out / both outputs /
+ * planes with grad_points / scratch with grad_planes, sizes <= 0, F > 65535, R > 4096, C > 64 * 21845, radius <= 0,
+ * grad_planes strides that make elements overlap (plane and channel stride below R^2, frame stride below 3 C R^2),
+ * negative planes strides, a misaligned or too small scratch.  No allocation and no host synchronisation. */
+typedef struct amav_triplane_sample_backward_args {
+    int32_t num_frames, num_points, channels, resolution;
+    float radius;
+    const float *planes;            /* as given to amav_triplane_sample_features; NULL allowed without grad_points */
+    int64_t planes_frame_stride, planes_plane_stride, planes_chan_stride; /* floats */
+    const float *points;            /* [F,N,3] */
+    const float *grad_out;          /* [F,N,3C] */
+    float *grad_planes;             /* strided as below, or NULL */
+    int64_t grad_frame_stride, grad_plane_stride, grad_chan_stride;       /* floats */
+    float *grad_points;             /* [F,N,3] or NULL */
+    void *scratch;
+    size_t scratch_bytes;
+} amav_triplane_sample_backward_args;
+size_t amav_triplane_sample_features_backward_bytes(int num_frames, int num_points, int channels, int resolution);
+int amav_triplane_sample_features_backward(const amav_triplane_sample_backward_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Stage-1 identity encoder: the point <-> triplane-cell reductions of
