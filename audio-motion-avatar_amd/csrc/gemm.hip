@@ -239,9 +239,9 @@ static int check_gemm_args(const char *who, int64_t rows, int n, int k3, const v
     return AMAV_OK;
 }
 
-extern "C" int amav_gemm_split_fp16(int64_t rows, int n, int k3, const void *a, const void *w, float alpha, float *out,
+extern "C" int amav_gemm_split_fp16(int64_t rows, int n, int k3, const void *a, const void *w, float alpha, float *out_dev,
                                     int algo_index, void *workspace, size_t workspace_bytes, void *stream) {
-    if (int rc = check_gemm_args("amav_gemm_split_fp16", rows, n, k3, a, w, out)) return rc;
+    if (int rc = check_gemm_args("amav_gemm_split_fp16", rows, n, k3, a, w, out_dev)) return rc;
     if (algo_index == -2) {  // the hand-written kernel
         AMAV_REQUIRE(gemm::split_gemm_supported(rows, n, k3), "amav_gemm_split_fp16: the hand-written kernel needs n %% 128 == 0 and "
                      "k3 = 3 K with K %% 32 == 0 (rows=%lld n=%d k3=%d)", (long long)rows, n, k3);
@@ -250,7 +250,7 @@ extern "C" int amav_gemm_split_fp16(int64_t rows, int n, int k3, const void *a, 
         if (attr != hipSuccess) return fail(AMAV_ERR_LAUNCH, "amav_gemm_split_fp16: cannot raise the dynamic LDS limit");
         const unsigned blocks = (unsigned)((rows + gemm::kBM - 1) / gemm::kBM * (n / gemm::kBN));
         gemm::split_gemm_kernel<<<blocks, 256, 2 * gemm::kStageBytes, static_cast<hipStream_t>(stream)>>>(
-            rows, n, k3 / 3, static_cast<const _Float16 *>(a), static_cast<const _Float16 *>(w), alpha, out);
+            rows, n, k3 / 3, static_cast<const _Float16 *>(a), static_cast<const _Float16 *>(w), alpha, out_dev);
         return check_launch("amav_gemm_split_fp16");
     }
     const gemm::Plan *p = gemm::plan_for(rows, n, k3, algo_index, workspace ? workspace_bytes : 0);
@@ -258,23 +258,23 @@ extern "C" int amav_gemm_split_fp16(int64_t rows, int n, int k3, const void *a, 
                         (long long)rows, n, k3, workspace_bytes);
     const float beta = 0.f;
     hipblasLtMatmulAlgo_t algo = p->algo;
-    const hipblasStatus_t st = hipblasLtMatmul(gemm::handle(), p->desc, &alpha, w, p->la, a, p->lb, &beta, out, p->ld, out, p->ld, &algo,
+    const hipblasStatus_t st = hipblasLtMatmul(gemm::handle(), p->desc, &alpha, w, p->la, a, p->lb, &beta, out_dev, p->ld, out_dev, p->ld, &algo,
                                                workspace, workspace_bytes, static_cast<hipStream_t>(stream));
     if (st != HIPBLAS_STATUS_SUCCESS) return fail(AMAV_ERR_LAUNCH, "amav_gemm_split_fp16: hipblasLtMatmul failed (%d)", (int)st);
     return AMAV_OK;
 }
 
-extern "C" int amav_gemm_split_fp16_tune(int64_t rows, int n, int k3, const void *a, const void *w, float *out, void *workspace,
+extern "C" int amav_gemm_split_fp16_tune(int64_t rows, int n, int k3, const void *a, const void *w, float *out_dev, void *workspace,
                                          size_t workspace_bytes, int repeats, int copies, int32_t *best_index, float *best_ms,
                                          float *heuristic_ms, void *stream_) {
-    if (int rc = check_gemm_args("amav_gemm_split_fp16_tune", rows, n, k3, a, w, out)) return rc;
+    if (int rc = check_gemm_args("amav_gemm_split_fp16_tune", rows, n, k3, a, w, out_dev)) return rc;
     AMAV_REQUIRE(best_index && best_ms && heuristic_ms && repeats > 0 && copies > 0, "amav_gemm_split_fp16_tune: NULL result pointer");
-    // `copies` > 1: a, w and out are `copies` consecutive operand sets and run i uses set i % copies, so that a kernel is
+    // `copies` > 1: a, w and out_dev are `copies` consecutive operand sets and run i uses set i % copies, so that a kernel is
     // timed as it runs inside the transformer step (weights and activations come from MALL / HBM, not from a hot L2)
     const size_t a_step = (size_t)rows * k3 * 2, w_step = (size_t)n * k3 * 2, o_step = (size_t)rows * n * 4;
     auto A = [&](int i) { return static_cast<const char *>(a) + (size_t)(i % copies) * a_step; };
     auto W = [&](int i) { return static_cast<const char *>(w) + (size_t)(i % copies) * w_step; };
-    auto O = [&](int i) { return reinterpret_cast<float *>(reinterpret_cast<char *>(out) + (size_t)(i % copies) * o_step); };
+    auto O = [&](int i) { return reinterpret_cast<float *>(reinterpret_cast<char *>(out_dev) + (size_t)(i % copies) * o_step); };
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     gemm::Plan p;
     AMAV_REQUIRE(gemm::handle() && gemm::make_layouts(p, rows, n, k3), "amav_gemm_split_fp16_tune: hipBLASLt set-up failed");

@@ -134,7 +134,7 @@ class FrameAllGather:
         t = torch.tensor([count], dtype=torch.int64, device=self.device)
         if self.world > 1:
             dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
-        tiles = F * ((H + 15) // 16) * ((W + 15) // 16)
+        tiles = F * ops.tile_count(H, W)
         self.capacity = min(tiles, int(int(t.item()) * headroom) + 64)
         nbytes = ops.frames_wire_bytes(F, H, W, self.capacity)
         self.local = [torch.empty(nbytes, dtype=torch.uint8, device=self.device) for _ in range(2)]

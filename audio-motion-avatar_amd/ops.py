@@ -14,7 +14,9 @@ from ._lib import (AmavError, Attr, BodyTables, DecodeSource, LbsBackwardArgs, P
 SCALE_BIAS = 3.9    # src/models/renderer.py:428
 OPACITY_BIAS = 0.0  # src/models/renderer.py:429
 SCALE_MAX = 0.1     # src/models/renderer.py:532
-GAUSS_STRIDE = 16   # floats per packed Gaussian record (AMAV_GAUSS_STRIDE)
+TILE = _lib.DEFINES["AMAV_TILE"]                   # rasterizer tile edge, pixels
+GAUSS_STRIDE = _lib.DEFINES["AMAV_GAUSS_STRIDE"]   # floats per packed Gaussian record
+SPLIT_BF16X3, SPLIT_FP16X2 = _lib.DEFINES["AMAV_SPLIT_BF16X3"], _lib.DEFINES["AMAV_SPLIT_FP16X2"]
 # channel offsets inside a packed record
 REC_XYZ, REC_OPACITY, REC_ROT, REC_SCALE, REC_COLOR = 0, 3, 4, 8, 12
 
@@ -34,6 +36,26 @@ def set_option(name: str, value: str):
 
 def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _call(name, *args):
+    """Entry point `name` with `args` and the current stream as its last argument; a non-zero return code raises."""
+    check(getattr(_lib.lib(), name)(*args, _stream()), name)
+
+
+def _scratch(query, device, *sizes, rejected=None):
+    """uint8 device buffer of the size the *_bytes entry point `query` reports for `sizes`.  0 bytes = the library
+    refused them: the error names the entry point and `rejected` (the sizes as text; None: "the tables" and the
+    library's own message)."""
+    nbytes = getattr(_lib.lib(), query)(*sizes)
+    if nbytes == 0:
+        raise AmavError(f"{query} rejected " + (rejected or "the tables: " + _lib.lib().amav_last_error().decode()))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def tile_count(height, width) -> int:
+    """Tiles of one frame: the rasterizer's and the frame exchange's grid of AMAV_TILE x AMAV_TILE pixels."""
+    return ((int(height) + TILE - 1) // TILE) * ((int(width) + TILE - 1) // TILE)
 
 
 def _need(t: torch.Tensor, name: str, dtype=torch.float32):
@@ -70,7 +92,7 @@ class Event:
         self.handle = h
 
     def record(self):
-        check(_lib.lib().amav_event_record(self.handle, _stream()), "amav_event_record")
+        _call("amav_event_record", self.handle)
 
     def elapsed_ms(self, stop) -> float:
         ms = ctypes.c_float(0)
@@ -100,9 +122,8 @@ def camera_from_intrinsics(K, E, height, width, znear=0.01, zfar=100.0):
     proj = torch.empty(F, 16, device=dev)
     tanfov = torch.empty(F, 2, device=dev)
     campos = torch.empty(F, 3, device=dev)
-    check(_lib.lib().amav_camera_from_intrinsics(F, K.data_ptr(), E.data_ptr(), int(height), int(width), znear, zfar,
-                                                 view.data_ptr(), proj.data_ptr(), tanfov.data_ptr(),
-                                                 campos.data_ptr(), _stream()), "amav_camera_from_intrinsics")
+    _call("amav_camera_from_intrinsics", F, K.data_ptr(), E.data_ptr(), int(height), int(width), znear, zfar,
+          view.data_ptr(), proj.data_ptr(), tanfov.data_ptr(), campos.data_ptr())
     return view, proj, tanfov, campos
 
 
@@ -113,19 +134,16 @@ class RasterWorkspace:
     def __init__(self, num_frames, num_gaussians, height, width, instance_capacity, device):
         self.key = (num_frames, num_gaussians, height, width)
         self.capacity = int(instance_capacity)
-        nbytes = _lib.lib().amav_rasterize_workspace_bytes(num_frames, num_gaussians, height, width, self.capacity)
-        if nbytes == 0:
-            raise AmavError(f"amav_rasterize_workspace_bytes rejected {self.key} capacity={self.capacity}")
-        self.buffer = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        self.buffer = _scratch("amav_rasterize_workspace_bytes", device, *self.key, self.capacity,
+                               rejected=f"{self.key} capacity={self.capacity}")
 
     def tile_counts(self, out=None):
         """Per-tile Gaussian list lengths of the last forward, int32 [F * tiles] (no host sync)."""
         F, N, H, W = self.key
-        n = F * ((H + 15) // 16) * ((W + 15) // 16)
+        n = F * tile_count(H, W)
         if out is None:
             out = torch.empty(n, dtype=torch.int32, device=self.buffer.device)
-        check(_lib.lib().amav_rasterize_tile_counts(self.buffer.data_ptr(), F, N, H, W, self.capacity, out.data_ptr(),
-                                                    _stream()), "amav_rasterize_tile_counts")
+        _call("amav_rasterize_tile_counts", self.buffer.data_ptr(), F, N, H, W, self.capacity, out.data_ptr())
         return out
 
     def status(self):
@@ -136,8 +154,8 @@ class RasterWorkspace:
     def status_full(self):
         """(total_instances, max_instances_of_a_frame, overflowed).  Synchronises the current stream."""
         total, mx, over = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int32(0)
-        check(_lib.lib().amav_rasterize_status(self.buffer.data_ptr(), ctypes.byref(total), ctypes.byref(mx),
-                                               ctypes.byref(over), _stream()), "amav_rasterize_status")
+        _call("amav_rasterize_status", self.buffer.data_ptr(), ctypes.byref(total), ctypes.byref(mx),
+              ctypes.byref(over))
         return total.value, mx.value, bool(over.value)
 
 
@@ -157,6 +175,43 @@ def decode_bin_enabled():
     return os.environ.get("AMAV_DECODE_BIN", "1") != "0"
 
 
+_GAUSSIAN_WIDTHS = (("means3d", 3), ("rotations", 4), ("scales", 3), ("opacities", 1), ("colors", 3))
+
+
+def _use_workspace(args, ws):
+    args.workspace, args.workspace_bytes, args.instance_capacity = ws.buffer.data_ptr(), ws.buffer.numel(), ws.capacity
+
+
+def _raster_args(gaussians, camera, height, width, bg, scale_modifier, apply_activations, workspace):
+    """The part of amav_raster_args that rasterize() and rasterize_backward() fill alike: sizes, the five attributes,
+    camera, background, activations and workspace (None: a new one of the default capacity).
+    -> (args, the tensors it points into: attributes, then camera; the workspace)."""
+    args, keep = RasterArgs(), []
+    for (name, w), t in zip(_GAUSSIAN_WIDTHS, gaussians):
+        attr, t = _attr(t, name, w)
+        setattr(args, name, attr)
+        keep.append(t)
+    F, N = keep[0].shape[0], keep[0].shape[1]
+    for (name, _), t in zip(_GAUSSIAN_WIDTHS[1:], keep[1:]):
+        if t.shape[0] != F or t.shape[1] != N:
+            raise AmavError(f"{name}: shape {tuple(t.shape)} does not match means3d [F={F},N={N},3]")
+    H, W = int(height), int(width)
+    if workspace is None:
+        workspace = RasterWorkspace(F, N, H, W, default_instance_capacity(F, N), keep[0].device)
+    elif workspace.key != (F, N, H, W):
+        raise AmavError(f"workspace was sized for {workspace.key}, call is {(F, N, H, W)}")
+    for name, t, cols in zip(("viewmatrix", "projmatrix", "tanfov"), camera, (16, 16, 2)):
+        keep.append(_contig(t.reshape(F, cols), name))
+        setattr(args, name, keep[-1].data_ptr())
+    args.num_frames, args.num_gaussians, args.height, args.width = F, N, H, W
+    args.bg = (ctypes.c_float * 3)(*[float(b) for b in bg])
+    args.scale_modifier = float(scale_modifier)
+    args.apply_activations = int(bool(apply_activations))
+    args.scale_bias, args.scale_max, args.opacity_bias = SCALE_BIAS, SCALE_MAX, OPACITY_BIAS
+    _use_workspace(args, workspace)
+    return args, keep, workspace
+
+
 def rasterize(means3d, rotations, scales, opacities, colors, viewmatrix, projmatrix, tanfov, height, width,
               bg=(1.0, 1.0, 1.0), apply_activations=False, scale_modifier=1.0, antialiasing=False, clamp_output=False,
               want_inv_depth=False, want_radii=False, workspace=None, check_overflow=True, out_rgba=None,
@@ -173,20 +228,11 @@ def rasterize(means3d, rotations, scales, opacities, colors, viewmatrix, projmat
     first: with fuse_decode (None = decode_bin_enabled()) by the rasterizer's own launch (amav_rasterize_decode_forward,
     again on an overflow retry), else by triplane_sample_decode_indexed ahead of it.  Same records and frames either way.
     """
-    a_m, means3d = _attr(means3d, "means3d", 3)
-    a_r, rotations = _attr(rotations, "rotations", 4)
-    a_s, scales = _attr(scales, "scales", 3)
-    a_o, opacities = _attr(opacities, "opacities", 1)
-    a_c, colors = _attr(colors, "colors", 3)
-    F, N = means3d.shape[0], means3d.shape[1]
-    for name, t in (("rotations", rotations), ("scales", scales), ("opacities", opacities), ("colors", colors)):
-        if t.shape[0] != F or t.shape[1] != N:
-            raise AmavError(f"{name}: shape {tuple(t.shape)} does not match means3d [F={F},N={N},3]")
-    viewmatrix = _contig(viewmatrix.reshape(F, 16), "viewmatrix")
-    projmatrix = _contig(projmatrix.reshape(F, 16), "projmatrix")
-    tanfov = _contig(tanfov.reshape(F, 2), "tanfov")
-    dev = means3d.device
-    H, W = int(height), int(width)
+    args, keep, workspace = _raster_args((means3d, rotations, scales, opacities, colors),
+                                         (viewmatrix, projmatrix, tanfov), height, width, bg, scale_modifier,
+                                         apply_activations, workspace)
+    means3d, dev = keep[0], keep[0].device
+    F, N, H, W = workspace.key
     if out_rgba is None:
         out_rgba = torch.empty(F, H, W, 4, device=dev)
     else:
@@ -195,10 +241,17 @@ def rasterize(means3d, rotations, scales, opacities, colors, viewmatrix, projmat
             raise AmavError(f"out_rgba must be contiguous [F,H,W,4] = {(F, H, W, 4)}")
     inv_depth = torch.empty(F, H, W, device=dev) if want_inv_depth else None
     radii = torch.empty(F, N, dtype=torch.int32, device=dev) if want_radii else None
-    if workspace is None:
-        workspace = RasterWorkspace(F, N, H, W, default_instance_capacity(F, N), dev)
-    elif workspace.key != (F, N, H, W):
-        raise AmavError(f"workspace was sized for {workspace.key}, call is {(F, N, H, W)}")
+    args.antialiasing, args.clamp_output = int(bool(antialiasing)), int(bool(clamp_output))
+    args.out_rgba = out_rgba.data_ptr()
+    args.out_inv_depth = inv_depth.data_ptr() if inv_depth is not None else None
+    args.out_radii = radii.data_ptr() if radii is not None else None
+    if DEBUG_STAMPS is not None:
+        args.debug_stamps = DEBUG_STAMPS.data_ptr()
+    if wire is not None:
+        buf, cap = wire
+        if buf.dtype != torch.uint8 or not buf.is_cuda or not buf.is_contiguous():
+            raise AmavError("rasterize: wire must be a contiguous uint8 device buffer")
+        args.wire, args.wire_bytes, args.wire_capacity_tiles = buf.data_ptr(), buf.numel(), int(cap)
 
     fused = False
     if decode is not None:
@@ -211,38 +264,16 @@ def rasterize(means3d, rotations, scales, opacities, colors, viewmatrix, projmat
                                            d["head_w_point"], out=d["out"])
 
     def launch(ws):
-        args = RasterArgs()
-        args.num_frames, args.num_gaussians, args.height, args.width = F, N, H, W
-        args.means3d, args.rotations, args.scales, args.opacities, args.colors = a_m, a_r, a_s, a_o, a_c
-        args.viewmatrix, args.projmatrix, args.tanfov = viewmatrix.data_ptr(), projmatrix.data_ptr(), tanfov.data_ptr()
-        args.bg = (ctypes.c_float * 3)(*[float(b) for b in bg])
-        args.scale_modifier = float(scale_modifier)
-        args.apply_activations = int(bool(apply_activations))
-        args.scale_bias, args.scale_max, args.opacity_bias = SCALE_BIAS, SCALE_MAX, OPACITY_BIAS
-        args.antialiasing = int(bool(antialiasing))
-        args.clamp_output = int(bool(clamp_output))
-        args.out_rgba = out_rgba.data_ptr()
-        args.out_inv_depth = inv_depth.data_ptr() if inv_depth is not None else None
-        args.out_radii = radii.data_ptr() if radii is not None else None
-        args.workspace, args.workspace_bytes = ws.buffer.data_ptr(), ws.buffer.numel()
-        args.instance_capacity = ws.capacity
-        if DEBUG_STAMPS is not None:
-            args.debug_stamps = DEBUG_STAMPS.data_ptr()
-        if wire is not None:
-            buf, cap = wire
-            if buf.dtype != torch.uint8 or not buf.is_cuda or not buf.is_contiguous():
-                raise AmavError("rasterize: wire must be a contiguous uint8 device buffer")
-            args.wire, args.wire_bytes, args.wire_capacity_tiles = buf.data_ptr(), buf.numel(), int(cap)
+        _use_workspace(args, ws)
         ev = profile_events
         if ev is None and PROFILE_EVENTS:
             ev = PROFILE_EVENTS.pop(0)
-        if ev is not None:
-            args.profile_start_event, args.profile_stop_event = ev[0].handle, ev[1].handle
+        start, stop = (ev[0].handle, ev[1].handle) if ev is not None else (None, None)
+        args.profile_start_event, args.profile_stop_event = start, stop
         if fused:
-            check(_lib.lib().amav_rasterize_decode_forward(ctypes.byref(args), ctypes.byref(decode["struct"]), _stream()),
-                  "amav_rasterize_decode_forward")
+            _call("amav_rasterize_decode_forward", ctypes.byref(args), ctypes.byref(decode["struct"]))
         else:
-            check(_lib.lib().amav_rasterize_forward(ctypes.byref(args), _stream()), "amav_rasterize_forward")
+            _call("amav_rasterize_forward", ctypes.byref(args))
 
     launch(workspace)
     if check_overflow:
@@ -268,49 +299,26 @@ def rasterize_backward(means3d, rotations, scales, opacities, colors, viewmatrix
     gradients (a frame-stride-0 input gets one row per frame), and with want_alpha the replay's 1 - T_final [F,H,W]
     ("alpha"; bit-identical to the forward's alpha channel).  No host sync.
     """
-    a_m, means3d = _attr(means3d, "means3d", 3)
-    a_r, rotations = _attr(rotations, "rotations", 4)
-    a_s, scales = _attr(scales, "scales", 3)
-    a_o, opacities = _attr(opacities, "opacities", 1)
-    a_c, colors = _attr(colors, "colors", 3)
-    F, N = means3d.shape[0], means3d.shape[1]
-    H, W = int(height), int(width)
-    if workspace.key != (F, N, H, W):
-        raise AmavError(f"workspace was sized for {workspace.key}, call is {(F, N, H, W)}")
-    viewmatrix = _contig(viewmatrix.reshape(F, 16), "viewmatrix")
-    projmatrix = _contig(projmatrix.reshape(F, 16), "projmatrix")
-    tanfov = _contig(tanfov.reshape(F, 2), "tanfov")
+    args, keep, _ = _raster_args((means3d, rotations, scales, opacities, colors), (viewmatrix, projmatrix, tanfov),
+                                 height, width, bg, scale_modifier, apply_activations, workspace)
+    F, N, H, W = workspace.key
     grad_rgba = _contig(grad_rgba, "grad_rgba")
     if tuple(grad_rgba.shape) != (F, H, W, 4):
         raise AmavError(f"grad_rgba must be [F,H,W,4] = {(F, H, W, 4)}, got {tuple(grad_rgba.shape)}")
-    dev = means3d.device
-    grads = {k: torch.empty(F, N, w, device=dev) for k, w in
-             (("means3d", 3), ("rotations", 4), ("scales", 3), ("opacities", 1), ("colors", 3))}
+    dev = keep[0].device
+    grads = {k: torch.empty(F, N, w, device=dev) for k, w in _GAUSSIAN_WIDTHS}
     alpha = torch.empty(F, H, W, device=dev) if want_alpha else None
-    nbytes = _lib.lib().amav_rasterize_backward_bytes(F, N, int(max_frame))
-    if nbytes == 0:
-        raise AmavError(f"amav_rasterize_backward_bytes rejected F={F} N={N} max_frame={max_frame}")
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-
-    args = RasterArgs()
-    args.num_frames, args.num_gaussians, args.height, args.width = F, N, H, W
-    args.means3d, args.rotations, args.scales, args.opacities, args.colors = a_m, a_r, a_s, a_o, a_c
-    args.viewmatrix, args.projmatrix, args.tanfov = viewmatrix.data_ptr(), projmatrix.data_ptr(), tanfov.data_ptr()
-    args.bg = (ctypes.c_float * 3)(*[float(b) for b in bg])
-    args.scale_modifier = float(scale_modifier)
-    args.apply_activations = int(bool(apply_activations))
-    args.scale_bias, args.scale_max, args.opacity_bias = SCALE_BIAS, SCALE_MAX, OPACITY_BIAS
-    args.workspace, args.workspace_bytes = workspace.buffer.data_ptr(), workspace.buffer.numel()
-    args.instance_capacity = workspace.capacity
+    scratch = _scratch("amav_rasterize_backward_bytes", dev, F, N, int(max_frame),
+                       rejected=f"F={F} N={N} max_frame={max_frame}")
     b = RasterBackwardArgs()
     b.grad_rgba = grad_rgba.data_ptr()
     b.grad_means3d, b.grad_rotations = grads["means3d"].data_ptr(), grads["rotations"].data_ptr()
     b.grad_scales, b.grad_opacities = grads["scales"].data_ptr(), grads["opacities"].data_ptr()
     b.grad_colors = grads["colors"].data_ptr()
     b.max_frame_instances = int(max_frame)
-    b.scratch, b.scratch_bytes = scratch.data_ptr(), nbytes
+    b.scratch, b.scratch_bytes = scratch.data_ptr(), scratch.numel()
     b.debug_alpha = alpha.data_ptr() if alpha is not None else None
-    check(_lib.lib().amav_rasterize_backward(ctypes.byref(args), ctypes.byref(b), _stream()), "amav_rasterize_backward")
+    _call("amav_rasterize_backward", ctypes.byref(args), ctypes.byref(b))
     if want_alpha:
         grads["alpha"] = alpha
     return grads
@@ -391,8 +399,7 @@ def frames_to_rgb8(rgba, out=None):
         out = torch.empty(shape, dtype=torch.uint8, device=rgba.device)
     elif tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous():
         raise AmavError(f"frames_to_rgb8: out must be contiguous uint8 {shape}")
-    check(_lib.lib().amav_frames_to_rgb8(rgba.numel() // 4, rgba.data_ptr(), out.data_ptr(), _stream()),
-          "amav_frames_to_rgb8")
+    _call("amav_frames_to_rgb8", rgba.numel() // 4, rgba.data_ptr(), out.data_ptr())
     return out
 
 
@@ -420,11 +427,11 @@ def frames_pack_tiles(rgba, capacity_tiles, bg=(1.0, 1.0, 1.0), wire=None, tile_
     hint_ptr = None
     if tile_hint is not None:
         tile_hint = _need(tile_hint, "tile_hint", torch.int32)
-        if not tile_hint.is_contiguous() or tile_hint.numel() != F * ((H + 15) // 16) * ((W + 15) // 16):
+        if not tile_hint.is_contiguous() or tile_hint.numel() != F * tile_count(H, W):
             raise AmavError("frames_pack_tiles: tile_hint must be a contiguous int32 [F * tiles] tensor")
         hint_ptr = tile_hint.data_ptr()
-    check(_lib.lib().amav_frames_pack_tiles(F, H, W, rgba.data_ptr(), bg3, hint_ptr, int(capacity_tiles),
-                                            wire.data_ptr(), wire.numel(), _stream()), "amav_frames_pack_tiles")
+    _call("amav_frames_pack_tiles", F, H, W, rgba.data_ptr(), bg3, hint_ptr, int(capacity_tiles), wire.data_ptr(),
+          wire.numel())
     return wire
 
 
@@ -455,18 +462,15 @@ def frames_unpack_tiles(wire_all, num_buffers, F, H, W, capacity_tiles, out=None
     if status is None:
         status = torch.zeros(1, dtype=torch.int32, device=dev)
     if state is not None:
-        tiles = num_buffers * F * ((H + 15) // 16) * ((W + 15) // 16)
+        tiles = num_buffers * F * tile_count(H, W)
         state = _need(state, "state", torch.int32)
         if state.numel() != tiles or not state.is_contiguous():
             raise AmavError(f"frames_unpack_tiles: state must be a contiguous int32 tensor of {tiles} entries")
-        check(_lib.lib().amav_frames_unpack_tiles_delta(int(num_buffers), int(F), int(H), int(W), int(capacity_tiles),
-                                                        wire_all.data_ptr(), wire_all.shape[1], out.data_ptr(),
-                                                        state.data_ptr(), status.data_ptr(), _stream()),
-              "amav_frames_unpack_tiles_delta")
+        _call("amav_frames_unpack_tiles_delta", int(num_buffers), int(F), int(H), int(W), int(capacity_tiles),
+              wire_all.data_ptr(), wire_all.shape[1], out.data_ptr(), state.data_ptr(), status.data_ptr())
         return out, status
-    check(_lib.lib().amav_frames_unpack_tiles(int(num_buffers), int(F), int(H), int(W), int(capacity_tiles),
-                                              wire_all.data_ptr(), wire_all.shape[1], out.data_ptr(), status.data_ptr(),
-                                              _stream()), "amav_frames_unpack_tiles")
+    _call("amav_frames_unpack_tiles", int(num_buffers), int(F), int(H), int(W), int(capacity_tiles),
+          wire_all.data_ptr(), wire_all.shape[1], out.data_ptr(), status.data_ptr())
     return out, status
 
 
@@ -477,7 +481,7 @@ def frames_delta_unpack_supported(H, W) -> bool:
     """Whether amav_frames_unpack_tiles_delta accepts frames of this size (width a multiple of 16 and a per-frame tile
     table that fits its 64 KiB of LDS: 14 336 tiles -- the reference's 1296 x 2304 frames have 11 664, a 3840 x 2160
     frame 32 400)."""
-    return W % 16 == 0 and ((H + 15) // 16) * ((W + 15) // 16) <= DELTA_UNPACK_MAX_TILES
+    return W % TILE == 0 and tile_count(H, W) <= DELTA_UNPACK_MAX_TILES
 
 
 def frames_tile_state(num_buffers, F, H, W, device):
@@ -485,7 +489,7 @@ def frames_tile_state(num_buffers, F, H, W, device):
     if not frames_delta_unpack_supported(H, W):
         raise AmavError(f"frames_tile_state: {H}x{W} frames are outside the differential unpack's limits "
                         "(use frames_unpack_tiles without `state`)")
-    return torch.full((num_buffers * F * ((H + 15) // 16) * ((W + 15) // 16),), -1, dtype=torch.int32, device=device)
+    return torch.full((num_buffers * F * tile_count(H, W),), -1, dtype=torch.int32, device=device)
 
 
 # ------------------------------------------------------------------------------------------------------------ LBS
@@ -508,12 +512,8 @@ def lbs_prepare_blend_split(tables: dict):
     amav_lbs_prepare_blend_split).  Put it into the tables dict as "blend_split": lbs_forward then runs the blend product
     on the 16-bit matrix pipe."""
     ts = body_tables_struct({k: v for k, v in tables.items() if k != "blend_split"})
-    nbytes = _lib.lib().amav_lbs_blend_split_bytes(ctypes.byref(ts))
-    if nbytes == 0:
-        raise AmavError("amav_lbs_blend_split_bytes rejected the tables: " + _lib.lib().amav_last_error().decode())
-    out = torch.empty(nbytes, dtype=torch.uint8, device=tables["blend"].device)
-    check(_lib.lib().amav_lbs_prepare_blend_split(ctypes.byref(ts), out.data_ptr(), nbytes, _stream()),
-          "amav_lbs_prepare_blend_split")
+    out = _scratch("amav_lbs_blend_split_bytes", tables["blend"].device, ctypes.byref(ts))
+    _call("amav_lbs_prepare_blend_split", ctypes.byref(ts), out.data_ptr(), out.numel())
     return out
 
 
@@ -527,15 +527,11 @@ def lbs_forward(tables: dict, full_pose, coeffs, want_transforms=False):
         raise AmavError(f"lbs: full_pose {tuple(full_pose.shape)} / coeffs {tuple(coeffs.shape)} do not match "
                         f"J={ts.num_joints}, n_coeff={ts.num_coeffs}")
     dev = full_pose.device
-    nbytes = _lib.lib().amav_lbs_workspace_bytes(F, ctypes.byref(ts))
-    if nbytes == 0:
-        raise AmavError("amav_lbs_workspace_bytes rejected the tables: " + _lib.lib().amav_last_error().decode())
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _scratch("amav_lbs_workspace_bytes", dev, F, ctypes.byref(ts))
     verts = torch.empty(F, ts.num_verts, 3, device=dev)
     A = torch.empty(F, ts.num_joints, 12, device=dev) if want_transforms else None
-    check(_lib.lib().amav_lbs_forward(F, ctypes.byref(ts), full_pose.data_ptr(), coeffs.data_ptr(), verts.data_ptr(),
-                                      A.data_ptr() if A is not None else None, ws.data_ptr(), nbytes, _stream()),
-          "amav_lbs_forward")
+    _call("amav_lbs_forward", F, ctypes.byref(ts), full_pose.data_ptr(), coeffs.data_ptr(), verts.data_ptr(),
+          A.data_ptr() if A is not None else None, ws.data_ptr(), ws.numel())
     return (verts, A) if want_transforms else verts
 
 
@@ -587,15 +583,11 @@ def lbs_forward_parts(tables: dict, pose_parts, coeff_parts, pose_mean=None, wan
     ts = body_tables_struct(tables)
     pp, keep, F = _pose_parts(ts, pose_parts, coeff_parts, pose_mean)
     dev = keep[0].device
-    nbytes = _lib.lib().amav_lbs_workspace_bytes(F, ctypes.byref(ts))
-    if nbytes == 0:
-        raise AmavError("amav_lbs_workspace_bytes rejected the tables: " + _lib.lib().amav_last_error().decode())
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _scratch("amav_lbs_workspace_bytes", dev, F, ctypes.byref(ts))
     verts = torch.empty(F, ts.num_verts, 3, device=dev)
     A = torch.empty(F, ts.num_joints, 12, device=dev) if want_transforms else None
-    check(_lib.lib().amav_lbs_forward_parts(F, ctypes.byref(ts), ctypes.byref(pp), verts.data_ptr(),
-                                            A.data_ptr() if A is not None else None, ws.data_ptr(), nbytes, _stream()),
-          "amav_lbs_forward_parts")
+    _call("amav_lbs_forward_parts", F, ctypes.byref(ts), ctypes.byref(pp), verts.data_ptr(),
+          A.data_ptr() if A is not None else None, ws.data_ptr(), ws.numel())
     return (verts, A) if want_transforms else verts
 
 
@@ -614,10 +606,7 @@ def lbs_backward(tables: dict, pose_parts, coeff_parts, grad_vertices, pose_mean
     if any(k not in tables for k in ("skin_t_offsets", "skin_t_verts", "skin_t_weights")):
         raise AmavError("lbs_backward: the tables lack the transposed skin table (BodyModel.device_tables())")
     dev = grad_vertices.device
-    nbytes = _lib.lib().amav_lbs_backward_bytes(F, ctypes.byref(ts))
-    if nbytes == 0:
-        raise AmavError("amav_lbs_backward_bytes rejected the tables: " + _lib.lib().amav_last_error().decode())
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    scratch = _scratch("amav_lbs_backward_bytes", dev, F, ctypes.byref(ts))
     gpose = torch.empty(F, ts.num_joints * 3, device=dev)
     gcoef = torch.empty(F, ts.num_coeffs, device=dev)
     skin = [_contig(tables["skin_t_offsets"], "skin_t_offsets", torch.int32),
@@ -629,8 +618,8 @@ def lbs_backward(tables: dict, pose_parts, coeff_parts, grad_vertices, pose_mean
     a.num_frames, a.tables, a.parts = F, ctypes.pointer(ts), ctypes.pointer(pp)
     a.grad_vertices, a.grad_full_pose, a.grad_coeffs = grad_vertices.data_ptr(), gpose.data_ptr(), gcoef.data_ptr()
     a.skin_offsets, a.skin_verts, a.skin_weights = (x.data_ptr() for x in skin)
-    a.scratch, a.scratch_bytes = scratch.data_ptr(), nbytes
-    check(_lib.lib().amav_lbs_backward(ctypes.byref(a), _stream()), "amav_lbs_backward")
+    a.scratch, a.scratch_bytes = scratch.data_ptr(), scratch.numel()
+    _call("amav_lbs_backward", ctypes.byref(a))
     return gpose, gcoef
 
 
@@ -685,8 +674,7 @@ def points_gather(vertices, idx4):
     F, V, _ = vertices.shape
     N = idx4.shape[0]
     out = torch.empty(F, N, 3, device=vertices.device)
-    check(_lib.lib().amav_points_gather(F, V, N, vertices.data_ptr(), idx4.data_ptr(), out.data_ptr(), _stream()),
-          "amav_points_gather")
+    _call("amav_points_gather", F, V, N, vertices.data_ptr(), idx4.data_ptr(), out.data_ptr())
     return out
 
 
@@ -719,9 +707,8 @@ def points_gather_backward(grad_points, csr, num_verts):
         raise AmavError(f"points_gather_backward: table of {offsets.numel() - 1} vertices / {entries.numel()} entries "
                         f"does not match V={num_verts}, N={N}")
     out = torch.empty(F, num_verts, 3, device=grad_points.device)
-    check(_lib.lib().amav_points_gather_backward(F, num_verts, N, grad_points.data_ptr(), offsets.data_ptr(),
-                                                 entries.data_ptr(), out.data_ptr(), _stream()),
-          "amav_points_gather_backward")
+    _call("amav_points_gather_backward", F, num_verts, N, grad_points.data_ptr(), offsets.data_ptr(),
+          entries.data_ptr(), out.data_ptr())
     return out
 
 
@@ -785,7 +772,7 @@ def points_bbox(points):
         raise AmavError(f"points_bbox: expected [F,N,3], got {tuple(points.shape)}")
     F, N = int(points.shape[0]), int(points.shape[1])
     out = torch.empty(F, 6, device=points.device)
-    check(_lib.lib().amav_points_bbox(F, N, points.data_ptr(), out.data_ptr(), _stream()), "amav_points_bbox")
+    _call("amav_points_bbox", F, N, points.data_ptr(), out.data_ptr())
     return out
 
 
@@ -813,9 +800,8 @@ def triplane_project(tokens, head_w_plane, resolution, region=None, out=None):
         boxes = _contig(boxes, "region boxes")
         if tuple(boxes.shape) != (F, 6) or not float(radius) > 0.0:
             raise AmavError(f"triplane_project: region boxes {tuple(boxes.shape)} != {(F, 6)} or radius {radius} <= 0")
-    check(_lib.lib().amav_triplane_project_region(F, C, R, tokens.data_ptr(), tokens.stride(0), head_w_plane.data_ptr(),
-                                                  out.data_ptr(), boxes.data_ptr() if boxes is not None else None,
-                                                  float(radius), _stream()), "amav_triplane_project_region")
+    _call("amav_triplane_project_region", F, C, R, tokens.data_ptr(), tokens.stride(0), head_w_plane.data_ptr(),
+          out.data_ptr(), boxes.data_ptr() if boxes is not None else None, float(radius))
     return out
 
 
@@ -840,10 +826,8 @@ def triplane_sample_decode(proj, points, transl, radius, head_w_point, out=None)
     if transl is not None:
         transl = _contig(transl.reshape(F, 3), "transl")
     out = _decode_out(out, F, N, proj.device)
-    check(_lib.lib().amav_triplane_sample_decode(F, N, R, proj.data_ptr(), points.data_ptr(),
-                                                 transl.data_ptr() if transl is not None else None, float(radius),
-                                                 head_w_point.data_ptr(), out.data_ptr(), _stream()),
-          "amav_triplane_sample_decode")
+    _call("amav_triplane_sample_decode", F, N, R, proj.data_ptr(), points.data_ptr(),
+          transl.data_ptr() if transl is not None else None, float(radius), head_w_point.data_ptr(), out.data_ptr())
     return out
 
 
@@ -860,11 +844,8 @@ def triplane_sample_decode_indexed(proj, vertices, idx4, transl, radius, head_w_
     if transl is not None:
         transl = _contig(transl.reshape(F, 3), "transl")
     out = _decode_out(out, F, N, proj.device)
-    check(_lib.lib().amav_triplane_sample_decode_indexed(F, N, R, V, proj.data_ptr(), vertices.data_ptr(),
-                                                         idx4.data_ptr(),
-                                                         transl.data_ptr() if transl is not None else None,
-                                                         float(radius), head_w_point.data_ptr(), out.data_ptr(),
-                                                         _stream()), "amav_triplane_sample_decode_indexed")
+    _call("amav_triplane_sample_decode_indexed", F, N, R, V, proj.data_ptr(), vertices.data_ptr(), idx4.data_ptr(),
+          transl.data_ptr() if transl is not None else None, float(radius), head_w_point.data_ptr(), out.data_ptr())
     return out
 
 
@@ -926,10 +907,7 @@ def triplane_decode_backward(tokens, head_w_plane, head_w_point, points, proj, g
                head_w_point=torch.empty(16, 4, device=dev),
                points=torch.empty(F, N, 3, device=dev) if want_points else None,
                transl=torch.empty(F, 3, device=dev) if want_transl else None)
-    nbytes = _lib.lib().amav_triplane_decode_backward_bytes(F, N, C, R)
-    if nbytes == 0:
-        raise AmavError(f"amav_triplane_decode_backward_bytes rejected F={F} N={N} C={C} R={R}")
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    scratch = _scratch("amav_triplane_decode_backward_bytes", dev, F, N, C, R, rejected=f"F={F} N={N} C={C} R={R}")
     a = TriplaneDecodeBackwardArgs()
     a.num_frames, a.num_points, a.channels, a.resolution, a.radius = F, N, C, R, float(radius)
     a.tokens, a.tokens_frame_stride = tokens.data_ptr(), tokens.stride(0)
@@ -941,8 +919,8 @@ def triplane_decode_backward(tokens, head_w_plane, head_w_point, points, proj, g
     a.grad_head_w_point = out["head_w_point"].data_ptr()
     a.grad_points = out["points"].data_ptr() if want_points else None
     a.grad_transl = out["transl"].data_ptr() if want_transl else None
-    a.scratch, a.scratch_bytes = scratch.data_ptr(), nbytes
-    check(_lib.lib().amav_triplane_decode_backward(ctypes.byref(a), _stream()), "amav_triplane_decode_backward")
+    a.scratch, a.scratch_bytes = scratch.data_ptr(), scratch.numel()
+    _call("amav_triplane_decode_backward", ctypes.byref(a))
     return out
 
 
@@ -995,9 +973,8 @@ def triplane_sample_features(planes, points, radius):
         planes = planes.contiguous()
     N = points.shape[1]
     out = torch.empty(F, N, 3 * C, device=planes.device)
-    check(_lib.lib().amav_triplane_sample_features(F, N, C, R, planes.data_ptr(), planes.stride(0), planes.stride(1),
-                                                   planes.stride(2), points.data_ptr(), float(radius),
-                                                   out.data_ptr(), _stream()), "amav_triplane_sample_features")
+    _call("amav_triplane_sample_features", F, N, C, R, planes.data_ptr(), planes.stride(0), planes.stride(1),
+          planes.stride(2), points.data_ptr(), float(radius), out.data_ptr())
     return out
 
 
@@ -1030,19 +1007,16 @@ def triplane_sample_features_backward(planes, points, grad_out, radius, want_pla
         g_planes = torch.empty_like(planes)  # keeps a dense input's strides
         if g_planes.stride(4) != 1 or g_planes.stride(3) != R or min(g_planes.stride()[:3]) < R * R:
             g_planes = torch.empty(F, 3, C, R, R, device=dev)
-        nbytes = _lib.lib().amav_triplane_sample_features_backward_bytes(F, N, C, R)
-        if nbytes == 0:
-            raise AmavError(f"amav_triplane_sample_features_backward_bytes rejected F={F} N={N} C={C} R={R}")
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        scratch = _scratch("amav_triplane_sample_features_backward_bytes", dev, F, N, C, R,
+                           rejected=f"F={F} N={N} C={C} R={R}")
         a.grad_planes = g_planes.data_ptr()
         a.grad_frame_stride, a.grad_plane_stride, a.grad_chan_stride = g_planes.stride(0), g_planes.stride(1), g_planes.stride(2)
-        a.scratch, a.scratch_bytes = scratch.data_ptr(), nbytes
+        a.scratch, a.scratch_bytes = scratch.data_ptr(), scratch.numel()
     if want_points:
         g_points = torch.empty(F, N, 3, device=dev)
         a.grad_points = g_points.data_ptr()
     if want_planes or want_points:
-        check(_lib.lib().amav_triplane_sample_features_backward(ctypes.byref(a), _stream()),
-              "amav_triplane_sample_features_backward")
+        _call("amav_triplane_sample_features_backward", ctypes.byref(a))
     return g_planes, g_points
 
 
@@ -1096,10 +1070,8 @@ def cell_pool_max(feat, cell_of, cells, segments=None):
     order, seg = _contig(order, "order", torch.int32), _contig(seg, "seg", torch.int32)
     cellmax = torch.empty(B, 3, cells, C, device=feat.device)
     out = torch.empty_like(feat)
-    check(_lib.lib().amav_cell_max(B, N, C, int(cells), feat.data_ptr(), order.data_ptr(), seg.data_ptr(),
-                                   cellmax.data_ptr(), _stream()), "amav_cell_max")
-    check(_lib.lib().amav_cell_gather(B, N, C, int(cells), cellmax.data_ptr(), cell_of.data_ptr(), out.data_ptr(),
-                                      _stream()), "amav_cell_gather")
+    _call("amav_cell_max", B, N, C, int(cells), feat.data_ptr(), order.data_ptr(), seg.data_ptr(), cellmax.data_ptr())
+    _call("amav_cell_gather", B, N, C, int(cells), cellmax.data_ptr(), cell_of.data_ptr(), out.data_ptr())
     return out
 
 
@@ -1114,8 +1086,7 @@ def cell_splat_mean(feat, cell_of, cells, segments=None):
     order, seg = segments if segments is not None else cell_segments(cell_of, cells)
     order, seg = _contig(order, "order", torch.int32), _contig(seg, "seg", torch.int32)
     out = torch.empty(B, C, cells, device=feat.device)
-    check(_lib.lib().amav_cell_mean(B, N, C, int(cells), feat.data_ptr(), order.data_ptr(), seg.data_ptr(),
-                                    out.data_ptr(), _stream()), "amav_cell_mean")
+    _call("amav_cell_mean", B, N, C, int(cells), feat.data_ptr(), order.data_ptr(), seg.data_ptr(), out.data_ptr())
     return out
 
 
@@ -1133,12 +1104,10 @@ def _points_project(points, w2c, intrinsics, features, radius_px):
     _, C, H, W = features.shape
     if features.shape[0] != B or tuple(w2c.shape) != (B, 4, 4) or tuple(intrinsics.shape) != (B, 3, 3):
         raise AmavError("points_project: batch sizes / matrix shapes do not match")
-    nbytes = _lib.lib().amav_points_project_workspace_bytes(B, N, H, W)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=points.device)
+    ws = _scratch("amav_points_project_workspace_bytes", points.device, B, N, H, W, rejected=f"B={B} N={N} H={H} W={W}")
     out = torch.empty(B, N, C, device=points.device)
-    check(_lib.lib().amav_points_project(B, N, C, H, W, points.data_ptr(), w2c.data_ptr(), intrinsics.data_ptr(),
-                                         features.data_ptr(), float(radius_px), out.data_ptr(), ws.data_ptr(), nbytes,
-                                         _stream()), "amav_points_project")
+    _call("amav_points_project", B, N, C, H, W, points.data_ptr(), w2c.data_ptr(), intrinsics.data_ptr(),
+          features.data_ptr(), float(radius_px), out.data_ptr(), ws.data_ptr(), ws.numel())
     return out, ws
 
 
@@ -1154,12 +1123,11 @@ def cell_pool_max_backward(feat, cell_of, cells, segments, grad_out):
     if tuple(cell_of.shape) != (B, 3, N):
         raise AmavError(f"cell_of must be int32 [B,3,N] = {(B, 3, N)}, got {tuple(cell_of.shape)}")
     order, seg = _contig(segments[0], "order", torch.int32), _contig(segments[1], "seg", torch.int32)
-    nbytes = _lib.lib().amav_cell_max_backward_workspace_bytes(B, C, int(cells))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=feat.device)
+    ws = _scratch("amav_cell_max_backward_workspace_bytes", feat.device, B, C, int(cells),
+                  rejected=f"B={B} C={C} cells={cells}")
     grad_feat = torch.empty_like(feat)
-    check(_lib.lib().amav_cell_max_backward(B, N, C, int(cells), feat.data_ptr(), order.data_ptr(), seg.data_ptr(),
-                                            cell_of.data_ptr(), grad_out.data_ptr(), grad_feat.data_ptr(),
-                                            ws.data_ptr(), nbytes, _stream()), "amav_cell_max_backward")
+    _call("amav_cell_max_backward", B, N, C, int(cells), feat.data_ptr(), order.data_ptr(), seg.data_ptr(),
+          cell_of.data_ptr(), grad_out.data_ptr(), grad_feat.data_ptr(), ws.data_ptr(), ws.numel())
     return grad_feat
 
 
@@ -1174,9 +1142,8 @@ def cell_splat_mean_backward(grad_planes, cells, segments, num_points):
     if tuple(order.shape) != (B, num_points) or tuple(seg.shape) != (B, cells + 1):
         raise AmavError("cell_splat_mean_backward: segments do not match the batch / point / cell counts")
     grad_feat = torch.empty(B, num_points, C, device=grad_planes.device)
-    check(_lib.lib().amav_cell_mean_backward(B, num_points, C, int(cells), order.data_ptr(), seg.data_ptr(),
-                                             grad_planes.data_ptr(), grad_feat.data_ptr(), _stream()),
-          "amav_cell_mean_backward")
+    _call("amav_cell_mean_backward", B, num_points, C, int(cells), order.data_ptr(), seg.data_ptr(),
+          grad_planes.data_ptr(), grad_feat.data_ptr())
     return grad_feat
 
 
@@ -1186,9 +1153,8 @@ def points_project_backward(grad_out, workspace, height, width):
     grad_out = _contig(grad_out, "grad_out")
     B, N, C = grad_out.shape
     grad = torch.empty(B, C, height, width, device=grad_out.device)
-    check(_lib.lib().amav_points_project_backward(B, N, C, int(height), int(width), grad_out.data_ptr(),
-                                                  workspace.data_ptr(), workspace.numel(), grad.data_ptr(), _stream()),
-          "amav_points_project_backward")
+    _call("amav_points_project_backward", B, N, C, int(height), int(width), grad_out.data_ptr(), workspace.data_ptr(),
+          workspace.numel(), grad.data_ptr())
     return grad
 
 
@@ -1281,20 +1247,15 @@ def selfattn(q, k, v, heads, scale=None, bounds=None, split_out_exp=None):
     if k.shape != q.shape or v.shape != q.shape or not (q.stride(1) == k.stride(1) == v.stride(1)):
         raise AmavError("selfattn: q, k, v must share shape and row stride")
     out = torch.empty(B, S, HD, device=q.device)
-    nbytes = _lib.lib().amav_selfattn_workspace_bytes(B, S, heads, D)
-    if nbytes == 0:
-        raise AmavError(f"amav_selfattn_workspace_bytes rejected B={B} S={S} H={heads} D={D}")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
+    ws = _scratch("amav_selfattn_workspace_bytes", q.device, B, S, heads, D, rejected=f"B={B} S={S} H={heads} D={D}")
     ev = ATTN_PROFILE_EVENTS.pop(0) if ATTN_PROFILE_EVENTS else None
     if ev is not None:
         ev[0].record()
     qb, kb, vb = (float(x) for x in bounds) if bounds is not None else (0.0, 0.0, 0.0)
     split = None if split_out_exp is None else _split_buffer(B * S, HD, SPLIT_FP16X2, q.device)
-    check(_lib.lib().amav_selfattn_forward_split_out(B, S, heads, D, q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(1),
-                                                     out.data_ptr(), HD, float(scale if scale is not None else D ** -0.5),
-                                                     qb, kb, vb, split.data_ptr() if split is not None else None,
-                                                     int(split_out_exp or 0), ws.data_ptr(), nbytes, _stream()),
-          "amav_selfattn_forward_split_out")
+    _call("amav_selfattn_forward_split_out", B, S, heads, D, q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(1),
+          out.data_ptr(), HD, float(scale if scale is not None else D ** -0.5), qb, kb, vb,
+          split.data_ptr() if split is not None else None, int(split_out_exp or 0), ws.data_ptr(), ws.numel())
     if ev is not None:
         ev[1].record()
     return out if split is None else split
@@ -1315,15 +1276,10 @@ def selfattn_lse(qkv, heads, scale=None):
     B, S, HD, D = _qkv_views(qkv, heads)
     out = torch.empty(B, S, HD, device=qkv.device)
     lse = torch.empty(B, heads, S, device=qkv.device)
-    nbytes = _lib.lib().amav_selfattn_workspace_bytes(B, S, heads, D)
-    if nbytes == 0:
-        raise AmavError(f"amav_selfattn_workspace_bytes rejected B={B} S={S} H={heads} D={D}")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=qkv.device)
+    ws = _scratch("amav_selfattn_workspace_bytes", qkv.device, B, S, heads, D, rejected=f"B={B} S={S} H={heads} D={D}")
     p = qkv.data_ptr()
-    check(_lib.lib().amav_selfattn_forward_lse(B, S, heads, D, p, p + 4 * HD, p + 8 * HD, qkv.stride(1), out.data_ptr(),
-                                               HD, float(scale if scale is not None else D ** -0.5), lse.data_ptr(),
-                                               ws.data_ptr(), nbytes, _stream()),
-          "amav_selfattn_forward_lse")
+    _call("amav_selfattn_forward_lse", B, S, heads, D, p, p + 4 * HD, p + 8 * HD, qkv.stride(1), out.data_ptr(), HD,
+          float(scale if scale is not None else D ** -0.5), lse.data_ptr(), ws.data_ptr(), ws.numel())
     return out, lse
 
 
@@ -1345,17 +1301,12 @@ def selfattn_backward(qkv, out, lse, grad_out, heads, scale=None, grad_qkv=None)
     if (grad_qkv.dim() != 3 or tuple(grad_qkv.shape[:2]) != (B, S) or grad_qkv.shape[2] < 3 * HD
             or grad_qkv.stride(2) != 1 or grad_qkv.stride(0) != S * grad_qkv.stride(1)):
         raise AmavError(f"grad_qkv: need [B,S,>=3*H*D] with unit inner stride, got {tuple(grad_qkv.shape)}")
-    nbytes = _lib.lib().amav_selfattn_backward_workspace_bytes(B, S, heads, D)
-    if nbytes == 0:
-        raise AmavError(f"amav_selfattn_backward_workspace_bytes rejected B={B} S={S} H={heads} D={D}")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=qkv.device)
+    ws = _scratch("amav_selfattn_backward_workspace_bytes", qkv.device, B, S, heads, D,
+                  rejected=f"B={B} S={S} H={heads} D={D}")
     p = qkv.data_ptr()
-    check(_lib.lib().amav_selfattn_backward(B, S, heads, D, p, p + 4 * HD, p + 8 * HD, qkv.stride(1), out.data_ptr(),
-                                            out.stride(1), lse.data_ptr(), grad_out.data_ptr(), grad_out.stride(1),
-                                            grad_qkv.data_ptr(), grad_qkv.stride(1),
-                                            float(scale if scale is not None else D ** -0.5), ws.data_ptr(), nbytes,
-                                            _stream()),
-          "amav_selfattn_backward")
+    _call("amav_selfattn_backward", B, S, heads, D, p, p + 4 * HD, p + 8 * HD, qkv.stride(1), out.data_ptr(),
+          out.stride(1), lse.data_ptr(), grad_out.data_ptr(), grad_out.stride(1), grad_qkv.data_ptr(),
+          grad_qkv.stride(1), float(scale if scale is not None else D ** -0.5), ws.data_ptr(), ws.numel())
     return grad_qkv
 
 
@@ -1402,9 +1353,8 @@ def gemm_split_fp16(a, w, alpha=1.0, algo_index=-1):
     ws = _GEMM_WS.get(a.device)
     if ws is None:
         ws = _GEMM_WS[a.device] = torch.empty(32 << 20, dtype=torch.uint8, device=a.device)
-    check(_lib.lib().amav_gemm_split_fp16(a.shape[0], w.shape[0], a.shape[1], a.data_ptr(), w.data_ptr(), float(alpha),
-                                          out.data_ptr(), int(algo_index), ws.data_ptr(), ws.numel(), _stream()),
-          "amav_gemm_split_fp16")
+    _call("amav_gemm_split_fp16", a.shape[0], w.shape[0], a.shape[1], a.data_ptr(), w.data_ptr(), float(alpha),
+          out.data_ptr(), int(algo_index), ws.data_ptr(), ws.numel())
     return out
 
 
@@ -1423,17 +1373,13 @@ def gemm_split_fp16_tune(a, w, repeats=10):
     rows, n = a.shape[0] // copies, w.shape[0] // copies
     ws = torch.empty(64 << 20, dtype=torch.uint8, device=a.device)
     idx, best, heur = ctypes.c_int32(-1), ctypes.c_float(0), ctypes.c_float(0)
-    check(_lib.lib().amav_gemm_split_fp16_tune(rows, n, a.shape[1], a.data_ptr(), w.data_ptr(), out.data_ptr(),
-                                               ws.data_ptr(), ws.numel(), int(repeats), int(copies), ctypes.byref(idx),
-                                               ctypes.byref(best), ctypes.byref(heur), _stream()), "amav_gemm_split_fp16_tune")
+    _call("amav_gemm_split_fp16_tune", rows, n, a.shape[1], a.data_ptr(), w.data_ptr(), out.data_ptr(), ws.data_ptr(),
+          ws.numel(), int(repeats), int(copies), ctypes.byref(idx), ctypes.byref(best), ctypes.byref(heur))
     return int(idx.value), float(best.value), float(heur.value)
 
 
 def gemm_library_version() -> str:
     return _lib.lib().amav_gemm_library_version().decode()
-
-
-SPLIT_BF16X3, SPLIT_FP16X2 = 0, 1  # include/amav.h
 
 
 def _split_buffer(rows, k, fmt, device):
@@ -1458,10 +1404,9 @@ def geglu(proj, bias=None, split_exp=None):
     else:
         out = _split_buffer(rows, inner, SPLIT_FP16X2, proj.device)
     bias_ptr = None if bias is None else _shaped(bias, "bias", (2 * inner,)).data_ptr()
-    check(_lib.lib().amav_geglu(rows, inner, proj.data_ptr(), proj.shape[-1], bias_ptr,
-                                out.data_ptr() if split_exp is None else None,
-                                None if split_exp is None else out.data_ptr(), int(split_exp or 0), _stream()),
-          "amav_geglu")
+    _call("amav_geglu", rows, inner, proj.data_ptr(), proj.shape[-1], bias_ptr,
+          out.data_ptr() if split_exp is None else None, None if split_exp is None else out.data_ptr(),
+          int(split_exp or 0))
     return out
 
 
@@ -1474,8 +1419,8 @@ def split_operand(x, weights=False, fmt=SPLIT_BF16X3, scale_exp=0):
     if x.dim() != 2 or x.stride(1) != 1 or x.shape[1] % 8 or x.stride(0) % 4 or x.data_ptr() % 16:
         raise AmavError("split_operand: need a 16-byte aligned [rows, k] tensor, unit inner stride, k a multiple of 8")
     out = _split_buffer(x.shape[0], x.shape[1], fmt, x.device)
-    check(_lib.lib().amav_split_operand(x.shape[0], x.shape[1], x.data_ptr(), x.stride(0), int(bool(weights)), int(fmt),
-                                        int(scale_exp), out.data_ptr(), _stream()), "amav_split_operand")
+    _call("amav_split_operand", x.shape[0], x.shape[1], x.data_ptr(), x.stride(0), int(bool(weights)), int(fmt),
+          int(scale_exp), out.data_ptr())
     return out
 
 
@@ -1491,13 +1436,11 @@ def add_layernorm(hidden, add, batch_row, weight, bias, eps=1e-5, add_bias=None,
     ptr = lambda t, name, shape: None if t is None else _shaped(t, name, shape).data_ptr()
     h_out = torch.empty_like(hidden)
     out = torch.empty_like(hidden) if split is None else _split_buffer(B * S, dim, split, hidden.device)
-    check(_lib.lib().amav_add_layernorm(B * S, dim, S, ptr(add, "add", (B, S, dim)), ptr(add_bias, "add_bias", (dim,)),
-                                        ptr(batch_row, "batch_row", (B, 1, dim)), hidden.data_ptr(), h_out.data_ptr(),
-                                        _shaped(weight, "weight", (dim,)).data_ptr(),
-                                        _shaped(bias, "bias", (dim,)).data_ptr(), float(eps),
-                                        out.data_ptr() if split is None else None,
-                                        None if split is None else out.data_ptr(), int(split or 0), int(split_exp),
-                                        _stream()), "amav_add_layernorm")
+    _call("amav_add_layernorm", B * S, dim, S, ptr(add, "add", (B, S, dim)), ptr(add_bias, "add_bias", (dim,)),
+          ptr(batch_row, "batch_row", (B, 1, dim)), hidden.data_ptr(), h_out.data_ptr(),
+          _shaped(weight, "weight", (dim,)).data_ptr(), _shaped(bias, "bias", (dim,)).data_ptr(), float(eps),
+          out.data_ptr() if split is None else None, None if split is None else out.data_ptr(), int(split or 0),
+          int(split_exp))
     return h_out, out
 
 
@@ -1519,9 +1462,8 @@ def cloud_voxelize(points, cloud_of, clouds, resolution=100.0):
     grid = torch.empty(n, 3, dtype=torch.int32, device=points.device)
     depth = torch.empty(clouds, dtype=torch.int32, device=points.device)
     bounds = torch.empty(clouds, 6, dtype=torch.int32, device=points.device)
-    check(_lib.lib().amav_cloud_voxelize(n, int(clouds), points.data_ptr(), cloud_of.data_ptr(), float(resolution),
-                                         grid.data_ptr(), depth.data_ptr(), bounds.data_ptr(), _stream()),
-          "amav_cloud_voxelize")
+    _call("amav_cloud_voxelize", n, int(clouds), points.data_ptr(), cloud_of.data_ptr(), float(resolution),
+          grid.data_ptr(), depth.data_ptr(), bounds.data_ptr())
     return grid, depth
 
 
@@ -1531,8 +1473,7 @@ def cloud_codes(grid, cloud_of, cloud_depth):
     cloud_depth = _contig(cloud_depth, "cloud_depth", torch.int32)
     n = grid.shape[0]
     keys = torch.empty(4, n, dtype=torch.int64, device=grid.device)
-    check(_lib.lib().amav_cloud_codes(n, grid.data_ptr(), cloud_of.data_ptr(), cloud_depth.data_ptr(), keys.data_ptr(),
-                                      _stream()), "amav_cloud_codes")
+    _call("amav_cloud_codes", n, grid.data_ptr(), cloud_of.data_ptr(), cloud_depth.data_ptr(), keys.data_ptr())
     return keys
 
 
@@ -1545,9 +1486,8 @@ def cloud_neighbors(grid, cloud_of, cloud_depth, cloud_start, sorted_keys, order
     if sorted_keys.shape != (n,) or order.shape != (n,) or cloud_start.shape[0] != cloud_depth.shape[0] + 1:
         raise AmavError("cloud_neighbors: sorted_keys / order must be [n], cloud_start [clouds + 1]")
     nbr = torch.empty(n, ksize ** 3, dtype=torch.int32, device=grid.device)
-    check(_lib.lib().amav_cloud_neighbors(n, int(ksize), grid.data_ptr(), cloud_of.data_ptr(), cloud_depth.data_ptr(),
-                                          cloud_start.data_ptr(), sorted_keys.data_ptr(), order.data_ptr(),
-                                          nbr.data_ptr(), _stream()), "amav_cloud_neighbors")
+    _call("amav_cloud_neighbors", n, int(ksize), grid.data_ptr(), cloud_of.data_ptr(), cloud_depth.data_ptr(),
+          cloud_start.data_ptr(), sorted_keys.data_ptr(), order.data_ptr(), nbr.data_ptr())
     return nbr
 
 
@@ -1561,9 +1501,8 @@ def subm_pair_gemm(feat, pair_src, tap_start, tile_start, tiles, weights):
     if feat.shape[1] != cin or tap_start.shape != (taps + 1,) or tile_start.shape != (taps + 1,):
         raise AmavError("subm_pair_gemm: shapes do not match")
     products = torch.empty(pair_src.shape[0], cout, device=feat.device)
-    check(_lib.lib().amav_subm_pair_gemm(pair_src.shape[0], int(tiles), taps, cin, cout, feat.data_ptr(),
-                                         pair_src.data_ptr(), tap_start.data_ptr(), tile_start.data_ptr(),
-                                         weights.data_ptr(), products.data_ptr(), _stream()), "amav_subm_pair_gemm")
+    _call("amav_subm_pair_gemm", pair_src.shape[0], int(tiles), taps, cin, cout, feat.data_ptr(), pair_src.data_ptr(),
+          tap_start.data_ptr(), tile_start.data_ptr(), weights.data_ptr(), products.data_ptr())
     return products
 
 
@@ -1576,8 +1515,7 @@ def subm_prepare_weights_split(weights):
     if nbytes == 0:
         raise AmavError(f"subm_prepare_weights_split: channels must be multiples of 32, got {cin} -> {cout}")
     out = torch.empty(nbytes, dtype=torch.uint8, device=weights.device)
-    check(_lib.lib().amav_subm_prepare_weights_split(taps, cin, cout, weights.data_ptr(), out.data_ptr(), nbytes, _stream()),
-          "amav_subm_prepare_weights_split")
+    _call("amav_subm_prepare_weights_split", taps, cin, cout, weights.data_ptr(), out.data_ptr(), nbytes)
     return out
 
 
@@ -1594,10 +1532,9 @@ def subm_pair_gemm_split(feat, pair_src, tap_start, tile_start, tiles, weights_s
         raise AmavError("subm_pair_gemm_split: weights_split was not prepared for these shapes")
     products = torch.empty(pair_src.shape[0], cout, device=feat.device)
     scratch = torch.empty(4, dtype=torch.int32, device=feat.device)
-    check(_lib.lib().amav_subm_pair_gemm_split(pair_src.shape[0], int(tiles), taps, cin, cout, n, feat.data_ptr(),
-                                               pair_src.data_ptr(), tap_start.data_ptr(), tile_start.data_ptr(),
-                                               weights_split.data_ptr(), scratch.data_ptr(), products.data_ptr(),
-                                               _stream()), "amav_subm_pair_gemm_split")
+    _call("amav_subm_pair_gemm_split", pair_src.shape[0], int(tiles), taps, cin, cout, n, feat.data_ptr(),
+          pair_src.data_ptr(), tap_start.data_ptr(), tile_start.data_ptr(), weights_split.data_ptr(),
+          scratch.data_ptr(), products.data_ptr())
     return products
 
 
@@ -1607,9 +1544,8 @@ def subm_pair_sum(products, pair_of, bias=None):
     n, taps = pair_of.shape
     cout = products.shape[1]
     out = torch.empty(n, cout, device=products.device)
-    check(_lib.lib().amav_subm_pair_sum(n, taps, cout, products.data_ptr(), pair_of.data_ptr(),
-                                        None if bias is None else _shaped(bias, "bias", (cout,)).data_ptr(), out.data_ptr(),
-                                        _stream()), "amav_subm_pair_sum")
+    _call("amav_subm_pair_sum", n, taps, cout, products.data_ptr(), pair_of.data_ptr(),
+          None if bias is None else _shaped(bias, "bias", (cout,)).data_ptr(), out.data_ptr())
     return out
 
 
@@ -1623,10 +1559,8 @@ def patch_attention(qkv, order, patch_desc, heads, max_patch, scale=None):
     if C3 != 3 * heads * D or order.shape != (n,) or patch_desc.dim() != 2 or patch_desc.shape[1] != 4:
         raise AmavError("patch_attention: shapes do not match")
     out = torch.empty(n, C, device=qkv.device)
-    check(_lib.lib().amav_patch_attention(patch_desc.shape[0], int(max_patch), int(heads), D, qkv.data_ptr(),
-                                          order.data_ptr(), patch_desc.data_ptr(), out.data_ptr(),
-                                          float(scale if scale is not None else D ** -0.5), _stream()),
-          "amav_patch_attention")
+    _call("amav_patch_attention", patch_desc.shape[0], int(max_patch), int(heads), D, qkv.data_ptr(), order.data_ptr(),
+          patch_desc.data_ptr(), out.data_ptr(), float(scale if scale is not None else D ** -0.5))
     return out
 
 
@@ -1636,9 +1570,8 @@ def cluster_max(x, members, seg, scale, shift):
     C = x.shape[1]
     clusters = seg.shape[0] - 1
     out = torch.empty(clusters, C, device=x.device)
-    check(_lib.lib().amav_cluster_max(clusters, C, x.data_ptr(), members.data_ptr(), seg.data_ptr(),
-                                      _shaped(scale, "scale", (C,)).data_ptr(), _shaped(shift, "shift", (C,)).data_ptr(),
-                                      out.data_ptr(), _stream()), "amav_cluster_max")
+    _call("amav_cluster_max", clusters, C, x.data_ptr(), members.data_ptr(), seg.data_ptr(),
+          _shaped(scale, "scale", (C,)).data_ptr(), _shaped(shift, "shift", (C,)).data_ptr(), out.data_ptr())
     return out
 
 
@@ -1647,8 +1580,8 @@ def bn_gelu(x, scale, shift):
     x = _contig(x, "x")
     rows, C = x.shape
     out = torch.empty_like(x)
-    check(_lib.lib().amav_bn_gelu(rows, C, x.data_ptr(), _shaped(scale, "scale", (C,)).data_ptr(),
-                                  _shaped(shift, "shift", (C,)).data_ptr(), out.data_ptr(), _stream()), "amav_bn_gelu")
+    _call("amav_bn_gelu", rows, C, x.data_ptr(), _shaped(scale, "scale", (C,)).data_ptr(),
+          _shaped(shift, "shift", (C,)).data_ptr(), out.data_ptr())
     return out
 
 
@@ -1659,9 +1592,9 @@ def unpool_merge(x, scale, shift, up, cluster):
     if up.shape[1] != C or cluster.shape != (n,):
         raise AmavError("unpool_merge: shapes do not match")
     skip, total = torch.empty_like(x), torch.empty_like(x)
-    check(_lib.lib().amav_unpool_merge(n, C, x.data_ptr(), _shaped(scale, "scale", (C,)).data_ptr(),
-                                       _shaped(shift, "shift", (C,)).data_ptr(), up.data_ptr(), cluster.data_ptr(),
-                                       skip.data_ptr(), total.data_ptr(), _stream()), "amav_unpool_merge")
+    _call("amav_unpool_merge", n, C, x.data_ptr(), _shaped(scale, "scale", (C,)).data_ptr(),
+          _shaped(shift, "shift", (C,)).data_ptr(), up.data_ptr(), cluster.data_ptr(), skip.data_ptr(),
+          total.data_ptr())
     return skip, total
 
 
@@ -1676,10 +1609,9 @@ def rows_norm(x, base, norm_b, norm_a=None):
         raise AmavError("rows_norm: x and base must have the same shape")
     out_sum, out_norm = torch.empty_like(x), torch.empty_like(x)
     ptr = lambda t: _shaped(t.detach(), "norm parameter", (C,)).data_ptr()
-    check(_lib.lib().amav_rows_norm(n, C, x.data_ptr(), base.data_ptr(),
-                                    None if norm_a is None else ptr(norm_a.weight), None if norm_a is None else ptr(norm_a.bias),
-                                    ptr(norm_b.weight), ptr(norm_b.bias), float(norm_b.eps), out_sum.data_ptr(),
-                                    out_norm.data_ptr(), _stream()), "amav_rows_norm")
+    _call("amav_rows_norm", n, C, x.data_ptr(), base.data_ptr(), None if norm_a is None else ptr(norm_a.weight),
+          None if norm_a is None else ptr(norm_a.bias), ptr(norm_b.weight), ptr(norm_b.bias), float(norm_b.eps),
+          out_sum.data_ptr(), out_norm.data_ptr())
     return out_sum, out_norm
 
 
@@ -1700,10 +1632,9 @@ def patch_attention_lse(qkv, order, patch_desc, heads, max_patch, scale=None):
         raise AmavError("patch_attention_lse: shapes do not match")
     out = torch.empty(n, C, device=qkv.device)
     lse = torch.empty(n, heads, device=qkv.device)
-    check(_lib.lib().amav_patch_attention_lse(patch_desc.shape[0], int(max_patch), int(heads), D, qkv.data_ptr(),
-                                              order.data_ptr(), patch_desc.data_ptr(), out.data_ptr(), lse.data_ptr(),
-                                              float(scale if scale is not None else D ** -0.5), _stream()),
-          "amav_patch_attention_lse")
+    _call("amav_patch_attention_lse", patch_desc.shape[0], int(max_patch), int(heads), D, qkv.data_ptr(),
+          order.data_ptr(), patch_desc.data_ptr(), out.data_ptr(), lse.data_ptr(),
+          float(scale if scale is not None else D ** -0.5))
     return out, lse
 
 
@@ -1718,16 +1649,12 @@ def patch_attention_backward(qkv, order, patch_desc, out, lse, grad_out, heads, 
     if C3 != 3 * heads * D or order.shape != (n,) or patch_desc.dim() != 2 or patch_desc.shape[1] != 4:
         raise AmavError("patch_attention_backward: shapes do not match")
     out, grad_out, lse = _shaped(out, "out", (n, C)), _shaped(grad_out, "grad_out", (n, C)), _shaped(lse, "lse", (n, heads))
-    nbytes = _lib.lib().amav_patch_attention_backward_workspace_bytes(n, int(heads), D)
-    if nbytes == 0:
-        raise AmavError(f"amav_patch_attention_backward_workspace_bytes rejected n={n} heads={heads} D={D}")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=qkv.device)
+    ws = _scratch("amav_patch_attention_backward_workspace_bytes", qkv.device, n, int(heads), D,
+                  rejected=f"n={n} heads={heads} D={D}")
     grad_qkv = torch.empty_like(qkv)
-    check(_lib.lib().amav_patch_attention_backward(n, patch_desc.shape[0], int(max_patch), int(heads), D, qkv.data_ptr(),
-                                                   order.data_ptr(), patch_desc.data_ptr(), out.data_ptr(), lse.data_ptr(),
-                                                   grad_out.data_ptr(), grad_qkv.data_ptr(),
-                                                   float(scale if scale is not None else D ** -0.5), ws.data_ptr(), nbytes,
-                                                   _stream()), "amav_patch_attention_backward")
+    _call("amav_patch_attention_backward", n, patch_desc.shape[0], int(max_patch), int(heads), D, qkv.data_ptr(),
+          order.data_ptr(), patch_desc.data_ptr(), out.data_ptr(), lse.data_ptr(), grad_out.data_ptr(),
+          grad_qkv.data_ptr(), float(scale if scale is not None else D ** -0.5), ws.data_ptr(), ws.numel())
     return grad_qkv
 
 
@@ -1767,9 +1694,8 @@ def subm_pair_sum_csr(products, src_start, src_pairs, pair_lo=0, out=None):
     if out is None:
         out = torch.empty(n, C, device=products.device)
     _shaped(out, "out", (n, C))
-    check(_lib.lib().amav_subm_pair_sum_csr(n, C, products.data_ptr(), int(pair_lo), products.shape[0], src_start.data_ptr(),
-                                            src_pairs.data_ptr(), int(accumulate), out.data_ptr(), _stream()),
-          "amav_subm_pair_sum_csr")
+    _call("amav_subm_pair_sum_csr", n, C, products.data_ptr(), int(pair_lo), products.shape[0], src_start.data_ptr(),
+          src_pairs.data_ptr(), int(accumulate), out.data_ptr())
     return out
 
 
@@ -1796,15 +1722,12 @@ def subm_pair_wgrad(feat, grad_out, pair_src, pair_dst, tap_start, slice_start, 
     taps, cin, cout = tap_start.shape[0] - 1, feat.shape[1], grad_out.shape[1]
     if pair_dst.shape != pair_src.shape or slice_start.shape != tap_start.shape:
         raise AmavError("subm_pair_wgrad: shapes do not match")
-    nbytes = _lib.lib().amav_subm_pair_wgrad_workspace_bytes(int(slices), cin, cout)
-    if nbytes == 0:
-        raise AmavError(f"amav_subm_pair_wgrad_workspace_bytes rejected slices={slices} C_in={cin} C_out={cout}")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=feat.device)
+    ws = _scratch("amav_subm_pair_wgrad_workspace_bytes", feat.device, int(slices), cin, cout,
+                  rejected=f"slices={slices} C_in={cin} C_out={cout}")
     out = torch.empty(taps, cin, cout, device=feat.device)
-    check(_lib.lib().amav_subm_pair_wgrad(pair_src.shape[0], int(slices), int(chunk), taps, cin, cout, feat.data_ptr(),
-                                          grad_out.data_ptr(), pair_src.data_ptr(), pair_dst.data_ptr(),
-                                          tap_start.data_ptr(), slice_start.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes,
-                                          _stream()), "amav_subm_pair_wgrad")
+    _call("amav_subm_pair_wgrad", pair_src.shape[0], int(slices), int(chunk), taps, cin, cout, feat.data_ptr(),
+          grad_out.data_ptr(), pair_src.data_ptr(), pair_dst.data_ptr(), tap_start.data_ptr(), slice_start.data_ptr(),
+          out.data_ptr(), ws.data_ptr(), ws.numel())
     return out
 
 
@@ -1832,11 +1755,9 @@ def subm_feat_grad(grad_out, weights_t, pairs, max_buffer_bytes=None):
             products = torch.empty(count, cin, device=grad_out.device)
             rebased = (pairs.tile_start[t0:t1 + 1] - int(tile_start[t0])).contiguous()
             # the kernel addresses products by the absolute pair index: hand it the address pair `lo` would have
-            check(_lib.lib().amav_subm_pair_gemm(count, int(tile_start[t1] - tile_start[t0]), t1 - t0, cout, cin,
-                                                 grad_out.data_ptr(), pairs.pair_dst.data_ptr(),
-                                                 pairs.tap_start.data_ptr() + 4 * t0, rebased.data_ptr(),
-                                                 weights_t.data_ptr() + 4 * t0 * cout * cin,
-                                                 products.data_ptr() - 4 * lo * cin, _stream()), "amav_subm_pair_gemm")
+            _call("amav_subm_pair_gemm", count, int(tile_start[t1] - tile_start[t0]), t1 - t0, cout, cin,
+                  grad_out.data_ptr(), pairs.pair_dst.data_ptr(), pairs.tap_start.data_ptr() + 4 * t0,
+                  rebased.data_ptr(), weights_t.data_ptr() + 4 * t0 * cout * cin, products.data_ptr() - 4 * lo * cin)
             subm_pair_sum_csr(products, pairs.src_start, pairs.src_pairs, pair_lo=lo, out=out)
         t0 = t1
     return out
@@ -1891,11 +1812,9 @@ def cluster_max_backward(x, members, seg, scale, shift, grad_out):
     grad_out = _shaped(grad_out, "grad_out", (clusters, C))
     grad_x = torch.empty_like(x)
     grad_z, x_max = torch.empty_like(grad_out), torch.empty_like(grad_out)
-    check(_lib.lib().amav_cluster_max_backward(clusters, C, x.data_ptr(), members.data_ptr(), seg.data_ptr(),
-                                               _shaped(scale, "scale", (C,)).data_ptr(),
-                                               _shaped(shift, "shift", (C,)).data_ptr(), grad_out.data_ptr(),
-                                               grad_x.data_ptr(), grad_z.data_ptr(), x_max.data_ptr(), _stream()),
-          "amav_cluster_max_backward")
+    _call("amav_cluster_max_backward", clusters, C, x.data_ptr(), members.data_ptr(), seg.data_ptr(),
+          _shaped(scale, "scale", (C,)).data_ptr(), _shaped(shift, "shift", (C,)).data_ptr(), grad_out.data_ptr(),
+          grad_x.data_ptr(), grad_z.data_ptr(), x_max.data_ptr())
     return grad_x, grad_z, x_max
 
 
@@ -1905,8 +1824,7 @@ def cluster_sum(x, members, seg):
     C = x.shape[1]
     clusters = seg.shape[0] - 1
     out = torch.empty(clusters, C, device=x.device)
-    check(_lib.lib().amav_cluster_sum(clusters, C, x.data_ptr(), members.data_ptr(), seg.data_ptr(), out.data_ptr(),
-                                      _stream()), "amav_cluster_sum")
+    _call("amav_cluster_sum", clusters, C, x.data_ptr(), members.data_ptr(), seg.data_ptr(), out.data_ptr())
     return out
 
 

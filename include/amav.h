@@ -16,6 +16,10 @@
  *   - Return value: 0 = AMAV_OK, negative = error; amav_last_error() returns a thread-local message.
  *   - All floating-point data is IEEE fp32; indices are int32 unless stated.
  *   - Thread-safe for distinct streams/workspaces; no mutable global state.
+ *   - The Python binding (audio-motion-avatar_amd/_lib.py) is generated from this file at import.  Keep to the forms
+ *     used here -- `typedef struct amav_x {...} amav_x;`, plain prototypes, integer #defines -- and to the *_dev suffix:
+ *     a typed pointer parameter is bound as a device address only when its name ends in _dev (any other `float *` /
+ *     `int32_t *` parameter is a host out-parameter); what the parser does not recognise fails the import.
  */
 #ifndef AMAV_H
 #define AMAV_H
@@ -725,9 +729,9 @@ int amav_cluster_sum(int64_t clusters, int channels, const float *x_dev, const i
  * times a kernel as it runs inside the step, not out of a hot L2) and reports the fastest one's index and time next to
  * the heuristic choice's time.
  * amav_gemm_library_version: the library build the indices belong to. */
-int amav_gemm_split_fp16(int64_t rows, int n, int k3, const void *a_fp16, const void *w_fp16, float alpha, float *out,
+int amav_gemm_split_fp16(int64_t rows, int n, int k3, const void *a_fp16, const void *w_fp16, float alpha, float *out_dev,
                          int algo_index, void *workspace, size_t workspace_bytes, void *stream);
-int amav_gemm_split_fp16_tune(int64_t rows, int n, int k3, const void *a_fp16, const void *w_fp16, float *out, void *workspace,
+int amav_gemm_split_fp16_tune(int64_t rows, int n, int k3, const void *a_fp16, const void *w_fp16, float *out_dev, void *workspace,
                               size_t workspace_bytes, int repeats, int copies, int32_t *best_index, float *best_ms,
                               float *heuristic_ms, void *stream);
 const char *amav_gemm_library_version(void);

@@ -3,24 +3,16 @@ error codes (no kernel is launched here: there is no GPU in this container)."""
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as entry
-    from audio_motion_avatar_amd import _lib
-
-    if not os.path.exists(_lib.LIB_PATH):
-        entry.build()
-    return _lib.lib()
+from abi_support import HEADER, lib  # noqa: F401 (lib: fixture)
 
 
 def header_symbols():
-    text = open(os.path.join(ROOT, "include", "amav.h")).read()
+    text = open(HEADER).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     return sorted(set(re.findall(r"\b(amav_[a-z0-9_]+)\s*\(", text)))
 
@@ -35,21 +27,118 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
     assert sorted(_lib.SIGNATURES) == names, "ctypes binding and header disagree"
 
 
-def test_struct_layouts_match_the_header(lib):
-    """Field order of the ctypes mirrors follows the header (sizes are what the compiler lays out for it)."""
+PROBE_KINDS = {ctypes.c_float: "f32", ctypes.c_int32: "i32", ctypes.c_int64: "i64", ctypes.c_size_t: "size", ctypes.c_uint8: "u8"}
+
+
+def compiler_layout(structs, workdir):
+    """{struct: sizeof} and {(struct, field): (offsetof, sizeof, kind)} as the host C compiler lays out include/amav.h:
+    a generated program that includes the header itself prints them.  kind: the scalar type of the field (of its
+    elements, for an array), "other" for pointers and nested structs."""
+    cc = next((c for c in (os.environ.get("CC"), "cc", "gcc", "clang",
+                           os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang"))
+               if c and shutil.which(c)), None)
+    assert cc is not None, "no host C compiler found: the struct layout cannot be checked"
+    lines = ["#include <stdio.h>", '#include "amav.h"',
+             '#define KIND(x) _Generic((x), float: "f32", int32_t: "i32", int64_t: "i64", size_t: "size", uint8_t: "u8", '
+             'default: "other")', "int main(void) {"]
+    for name, S in structs.items():
+        lines.append(f'    printf("{name} - %zu 0 -\\n", sizeof({name}));')
+        for field, ctype in S._fields_:
+            member = f"(({name} *)0)->{field}"
+            element = member + "[0]" if issubclass(ctype, ctypes.Array) else member
+            lines.append(f'    printf("{name} {field} %zu %zu %s\\n", offsetof({name}, {field}), sizeof({member}), '
+                         f"KIND({element}));")
+    lines += ["    return 0;", "}", ""]
+    src, exe = os.path.join(workdir, "layout_probe.c"), os.path.join(workdir, "layout_probe")
+    with open(src, "w") as f:
+        f.write("\n".join(lines))
+    subprocess.run([cc, "-std=c11", "-I", os.path.dirname(HEADER), src, "-o", exe], check=True)
+    sizes, fields = {}, {}
+    for line in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines():
+        name, field, a, b, kind = line.split()
+        if field == "-":
+            sizes[name] = int(a)
+        else:
+            fields[name, field] = (int(a), int(b), kind)
+    return sizes, fields
+
+
+def test_struct_layouts_match_the_header(lib, tmp_path):
+    """ctypes lays every struct of the binding out as the C compiler lays out the header's: size of the struct, offset,
+    size and scalar type of every field."""
     from audio_motion_avatar_amd import _lib
 
-    text = open(os.path.join(ROOT, "include", "amav.h")).read()
-    body = re.search(r"typedef struct amav_raster_args \{(.*?)\} amav_raster_args;", text, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if decl:
-            fields += [re.sub(r"\[.*\]", "", f).strip(" *") for f in decl.split(None, 1)[1].replace("*", " ").split(",")]
-    fields = [f.split()[-1] if " " in f else f for f in fields]
-    assert [f for f, _ in _lib.RasterArgs._fields_] == fields
+    aliases = (_lib.Attr, _lib.RasterArgs, _lib.RasterBackwardArgs, _lib.TriplaneDecodeBackwardArgs,
+               _lib.TriplaneSampleBackwardArgs, _lib.DecodeSource, _lib.BodyTables, _lib.PoseParts, _lib.LbsBackwardArgs)
+    assert len(set(aliases)) == 9 and set(aliases) <= set(_lib.STRUCTS.values())
+    sizes, fields = compiler_layout(_lib.STRUCTS, str(tmp_path))
+    checked = 0
+    for name, S in _lib.STRUCTS.items():
+        assert ctypes.sizeof(S) == sizes[name], name
+        for field, ctype in S._fields_:
+            d = getattr(S, field)
+            element = ctype._type_ if issubclass(ctype, ctypes.Array) else ctype
+            assert (d.offset, d.size, PROBE_KINDS.get(element, "other")) == fields[name, field], (name, field)
+            checked += 1
+    assert checked == len(fields) >= 100
     assert ctypes.sizeof(_lib.Attr) == 24 and ctypes.sizeof(_lib.BodyTables) == 16 + 8 * 8
+
+
+@pytest.mark.parametrize("text", [
+    "int amav_f(unsigned x, void *stream);",                               # a type the rules do not know
+    "typedef struct demo_s { int32_t a; double b; } demo_s;",
+    "int amav_f(int x, void *stream)\nint amav_g(void);",                   # a missing `;`
+    "int amav_f(int x, void *stream)",
+    "typedef struct demo_s { int32_t a; float b } demo_s;",
+    "typedef struct demo_s { int32_t a; } demo_s\nint amav_f(void);",
+    "int amav_f(void (*callback)(int), void *stream);",                    # a function-pointer parameter
+    "typedef struct demo_s { void (*callback)(int); } demo_s;",
+    "float amav_f(void);",                                                 # a return type no entry point has
+    "int amav_f(amav_unknown *args, void *stream);",
+    "typedef struct demo_s { float **rows; } demo_s;",
+    "int amav_f(int);",                                                    # an unnamed parameter: no `_dev` rule to apply
+    "int amav_limit = 3;",
+])
+def test_parser_refuses_what_it_does_not_recognise(text):
+    from audio_motion_avatar_amd import AmavError, _lib
+
+    with pytest.raises(AmavError, match="amav.h"):
+        _lib.parse_header(text)
+
+
+def test_parser_applies_the_binding_rules_to_text():
+    from audio_motion_avatar_amd import _lib
+
+    structs, signatures, defines = _lib.parse_header("""
+        /* a comment with a prototype: int amav_hidden(void); */
+        #define AMAV_N (-3)
+        #ifdef __cplusplus
+        extern "C" {
+        #endif
+        typedef struct demo_s { int32_t a, b[2]; const float *rows[3]; size_t n; } demo_s;  // trailing comment
+        typedef struct demo_t { demo_s s; const demo_s *q; void *scratch; } demo_t;
+        size_t amav_f(const demo_t *t, void **event, const char *name, const float *x_dev, float *ms, int64_t n, void *stream);
+        const char *amav_g(void);
+        #ifdef __cplusplus
+        }
+        #endif
+    """)
+    S, T = structs["demo_s"], structs["demo_t"]
+    assert defines == {"AMAV_N": -3} and list(structs) == ["demo_s", "demo_t"]
+    assert S._fields_ == [("a", ctypes.c_int32), ("b", ctypes.c_int32 * 2), ("rows", ctypes.c_void_p * 3), ("n", ctypes.c_size_t)]
+    assert T._fields_ == [("s", S), ("q", ctypes.POINTER(S)), ("scratch", ctypes.c_void_p)]
+    assert signatures == {
+        "amav_f": (ctypes.c_size_t, [ctypes.POINTER(T), ctypes.POINTER(ctypes.c_void_p), ctypes.c_char_p, ctypes.c_void_p,
+                                     ctypes.POINTER(ctypes.c_float), ctypes.c_int64, ctypes.c_void_p]),
+        "amav_g": (ctypes.c_char_p, [])}
+
+
+def test_a_missing_header_fails_loudly(monkeypatch):
+    from audio_motion_avatar_amd import AmavError, _lib
+
+    monkeypatch.setattr(_lib, "HEADER_PATH", "/nonexistent/include/amav.h")
+    with pytest.raises(AmavError, match="/nonexistent/include/amav.h"):
+        _lib._load_header()
 
 
 def test_version_and_error_reporting(lib):

@@ -1,21 +1,9 @@
 """Host-side argument checks of the self-attention backward's C entry points (amav_selfattn_forward_lse,
 amav_selfattn_backward): every call below is refused before a kernel is launched."""
-import os
 
-import pytest
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as entry
-    from audio_motion_avatar_amd import _lib
-
-    if not os.path.exists(_lib.LIB_PATH):
-        entry.build()
-    return _lib.lib()
+from abi_support import FAKE, lib  # noqa: F401 (lib: fixture)
 
 
-FAKE = 4096  # non-NULL, 16-byte aligned, never dereferenced on these paths
 B, S, H, D = 2, 100, 8, 64
 
 

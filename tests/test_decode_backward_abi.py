@@ -1,24 +1,8 @@
 """Host-side argument checks of the triplane decode backward's C entry points (no kernel is launched: every call below
 is refused before it reaches the device)."""
 import ctypes
-import os
-import re
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FAKE = 4096  # non-NULL, 16-byte aligned, never dereferenced on these paths
-ERR_INVALID, ERR_WORKSPACE = -1, -3
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as entry
-    from audio_motion_avatar_amd import _lib
-
-    if not os.path.exists(_lib.LIB_PATH):
-        entry.build()
-    return _lib.lib()
+from abi_support import ERR_INVALID, ERR_WORKSPACE, FAKE, lib  # noqa: F401 (lib: fixture)
 
 
 def _args(F=2, N=100, C=8, R=8, scratch_bytes=None, lib=None):
@@ -41,21 +25,6 @@ def test_symbols_are_exported_and_bound(lib):
 
     for name in ("amav_triplane_decode_backward", "amav_triplane_decode_backward_bytes"):
         assert hasattr(lib, name) and name in _lib.SIGNATURES
-
-
-def test_struct_field_order_matches_the_header():
-    from audio_motion_avatar_amd import _lib
-
-    text = open(os.path.join(ROOT, "include", "amav.h")).read()
-    body = re.search(r"typedef struct amav_triplane_decode_backward_args \{(.*?)\} amav_triplane_decode_backward_args;",
-                     text, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip().replace("*", " ")
-        if decl:
-            fields += [f.strip().split()[-1] for f in decl.split(None, 1)[1].split(",")]
-    assert [f for f, _ in _lib.TriplaneDecodeBackwardArgs._fields_] == fields
 
 
 def test_scratch_size_query(lib):

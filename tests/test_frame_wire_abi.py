@@ -1,24 +1,10 @@
 """Host-side refusals of the frame exchange's entry points (no kernel is launched: every call here fails its argument
 checks first) and the wire size formula against tests/wire_model.py."""
 import ctypes
-import os
 
-import pytest
+from abi_support import ERR_INVALID, ERR_WORKSPACE, FAKE, lib  # noqa: F401 (lib: fixture)
 
 import wire_model as wm
-
-FAKE = 4096  # a non-NULL, 16-byte aligned address that is never dereferenced on these paths
-ERR_INVALID_ARG, ERR_WORKSPACE = -1, -3
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as entry
-    from audio_motion_avatar_amd import _lib
-
-    if not os.path.exists(_lib.LIB_PATH):
-        entry.build()
-    return _lib.lib()
 
 
 def test_wire_bytes_is_the_models_size_formula(lib):
@@ -41,7 +27,7 @@ def test_pack_refuses_a_wire_buffer_one_byte_short(lib):
         msg = lib.amav_last_error().decode()
         assert str(need - 1) in msg and str(need) in msg, msg
     F, H, W = wm.SMALL
-    assert lib.amav_frames_pack_tiles(F, H, W, rgba, bg, None, F * 9 + 1, FAKE, 1 << 30, None) == ERR_INVALID_ARG
+    assert lib.amav_frames_pack_tiles(F, H, W, rgba, bg, None, F * 9 + 1, FAKE, 1 << 30, None) == ERR_INVALID
     assert b"exceeds the tile count" in lib.amav_last_error()
 
 
@@ -49,22 +35,22 @@ def test_unpack_refuses_a_short_or_unaligned_stride(lib):
     for F, H, W in wm.SIZES.values():
         need = wm.wire_bytes(F, H, W, 5)
         for stride in (need - 16, need + 8):
-            assert lib.amav_frames_unpack_tiles(2, F, H, W, 5, FAKE, stride, FAKE, FAKE, None) == ERR_INVALID_ARG
+            assert lib.amav_frames_unpack_tiles(2, F, H, W, 5, FAKE, stride, FAKE, FAKE, None) == ERR_INVALID
             assert f"wire stride {stride} does not hold a {need}-byte buffer".encode() in lib.amav_last_error()
     F, H, W = wm.WIDE
     need = wm.wire_bytes(F, H, W, 5)
     for stride in (need - 16, need + 8):
-        assert lib.amav_frames_unpack_tiles_delta(2, F, H, W, 5, FAKE, stride, FAKE, FAKE, FAKE, None) == ERR_INVALID_ARG
+        assert lib.amav_frames_unpack_tiles_delta(2, F, H, W, 5, FAKE, stride, FAKE, FAKE, FAKE, None) == ERR_INVALID
         assert b"wire stride" in lib.amav_last_error()
 
 
 def test_delta_unpack_refuses_ragged_widths_and_frames_beyond_its_lds_table(lib):
     for F, H, W in (wm.RAGGED4, wm.RAGGED1, (3, 50, 70)):
         need = wm.wire_bytes(F, H, W, 5)
-        assert lib.amav_frames_unpack_tiles_delta(1, F, H, W, 5, FAKE, need, FAKE, FAKE, FAKE, None) == ERR_INVALID_ARG
+        assert lib.amav_frames_unpack_tiles_delta(1, F, H, W, 5, FAKE, need, FAKE, FAKE, FAKE, None) == ERR_INVALID
         assert b"not a multiple of 16" in lib.amav_last_error()
     need = wm.wire_bytes(1, 2160, 3840, 5)
-    assert lib.amav_frames_unpack_tiles_delta(1, 1, 2160, 3840, 5, FAKE, need, FAKE, FAKE, FAKE, None) == ERR_INVALID_ARG
+    assert lib.amav_frames_unpack_tiles_delta(1, 1, 2160, 3840, 5, FAKE, need, FAKE, FAKE, FAKE, None) == ERR_INVALID
     assert b"LDS table" in lib.amav_last_error()
 
 
@@ -84,7 +70,7 @@ def test_delta_unpack_supported_agrees_with_the_kernels_limit(lib):
         supported = ops.frames_delta_unpack_supported(H, W)
         assert supported == want[(H, W)], (H, W)
         out = FAKE + 4 if supported else FAKE
-        assert lib.amav_frames_unpack_tiles_delta(1, 1, H, W, 1, FAKE, need, out, FAKE, FAKE, None) == ERR_INVALID_ARG
+        assert lib.amav_frames_unpack_tiles_delta(1, 1, H, W, 1, FAKE, need, out, FAKE, FAKE, None) == ERR_INVALID
         msg = lib.amav_last_error()
         if supported:
             assert b"misaligned buffer" in msg and (wm.geometry(H, W)[2] + wm.DELTA_WAVES * 128) * 4 <= 64 * 1024

@@ -1,26 +1,13 @@
 """Host-side argument checks of the LBS and gather backwards' C entry points (no kernel is launched: every call below is
 refused before it reaches the device), and the host-built transposed tables."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FAKE = 4096  # non-NULL, 16-byte aligned, never dereferenced on these paths
-ERR_INVALID, ERR_WORKSPACE = -1, -3
+from abi_support import ERR_INVALID, ERR_WORKSPACE, FAKE, lib  # noqa: F401 (lib: fixture)
+
 V, J, NC, KW = 100, 4, 5, 2
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as entry
-    from audio_motion_avatar_amd import _lib
-
-    if not os.path.exists(_lib.LIB_PATH):
-        entry.build()
-    return _lib.lib()
 
 
 def _tables():
@@ -66,20 +53,6 @@ def test_symbols_are_exported_and_bound(lib):
 
     for name in ("amav_lbs_backward", "amav_lbs_backward_bytes", "amav_points_gather_backward"):
         assert hasattr(lib, name) and name in _lib.SIGNATURES
-
-
-def test_struct_field_order_matches_the_header():
-    from audio_motion_avatar_amd import _lib
-
-    text = open(os.path.join(ROOT, "include", "amav.h")).read()
-    body = re.search(r"typedef struct amav_lbs_backward_args \{(.*?)\} amav_lbs_backward_args;", text, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip().replace("*", " ")
-        if decl:
-            fields += [f.strip().split()[-1] for f in decl.split(None, 1)[1].split(",")]
-    assert [f for f, _ in _lib.LbsBackwardArgs._fields_] == fields
 
 
 def test_scratch_size_query(lib):

@@ -1,22 +1,10 @@
 """Host-side argument checks of the point refiner's C entry points (csrc/cloud.hip): every call below is refused before
 a kernel is launched, so none of the fake pointers is ever dereferenced.  Each case starts from arguments that are
 valid except for the one it names."""
-import os
 
 import pytest
 
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as entry
-    from audio_motion_avatar_amd import _lib
-
-    if not os.path.exists(_lib.LIB_PATH):
-        entry.build()
-    return _lib.lib()
-
-
-FAKE = 4096  # non-NULL, 16-byte aligned, never dereferenced on these paths
+from abi_support import FAKE, lib  # noqa: F401 (lib: fixture)
 
 
 def _refused(lib, rc, *words):

@@ -5,19 +5,7 @@ import os
 
 import pytest
 
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as entry
-    from audio_motion_avatar_amd import _lib
-
-    if not os.path.exists(_lib.LIB_PATH):
-        entry.build()
-    return _lib.lib()
-
-
-FAKE = 4096  # non-NULL, 16-byte aligned, never dereferenced on these paths
-AMAV_ERR_WORKSPACE = -3
+from abi_support import ERR_WORKSPACE, FAKE, lib  # noqa: F401 (lib: fixture)
 
 
 def _refused(lib, rc, *words, code=-1):
@@ -39,7 +27,7 @@ def test_workspace_error_code_is_the_headers():
     import re
 
     m = re.search(r"AMAV_ERR_WORKSPACE\s*\(?(-?\d+)", text)
-    assert m and int(m.group(1)) == AMAV_ERR_WORKSPACE
+    assert m and int(m.group(1)) == ERR_WORKSPACE
 
 
 def test_patch_attention_lse_refusals(lib):
@@ -92,8 +80,8 @@ def test_patch_attention_backward_refusals(lib):
         _refused(lib, call(**{name: FAKE + 4}), b"amav_patch_attention_backward", b"aligned")
     for scale in (float("nan"), float("inf")):
         _refused(lib, call(scale=scale), b"amav_patch_attention_backward", b"scale")
-    _refused(lib, call(ws_bytes=need - 1), b"amav_patch_attention_backward", b"workspace", code=AMAV_ERR_WORKSPACE)
-    _refused(lib, call(ws=None), b"amav_patch_attention_backward", b"workspace", code=AMAV_ERR_WORKSPACE)
+    _refused(lib, call(ws_bytes=need - 1), b"amav_patch_attention_backward", b"workspace", code=ERR_WORKSPACE)
+    _refused(lib, call(ws=None), b"amav_patch_attention_backward", b"workspace", code=ERR_WORKSPACE)
 
 
 def test_subm_pair_sum_csr_refusals(lib):
@@ -146,8 +134,8 @@ def test_subm_pair_wgrad_refusals(lib):
         _refused(lib, call(**{name: None}), b"amav_subm_pair_wgrad", b"NULL")
     for name in ("feat", "g", "dw", "ws"):
         _refused(lib, call(**{name: FAKE + 4}), b"amav_subm_pair_wgrad", b"aligned")
-    _refused(lib, call(ws_bytes=need - 1), b"amav_subm_pair_wgrad", b"workspace", code=AMAV_ERR_WORKSPACE)
-    _refused(lib, call(ws=None), b"amav_subm_pair_wgrad", b"workspace", code=AMAV_ERR_WORKSPACE)
+    _refused(lib, call(ws_bytes=need - 1), b"amav_subm_pair_wgrad", b"workspace", code=ERR_WORKSPACE)
+    _refused(lib, call(ws=None), b"amav_subm_pair_wgrad", b"workspace", code=ERR_WORKSPACE)
 
 
 def test_cluster_max_backward_refusals(lib):

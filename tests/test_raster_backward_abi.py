@@ -1,22 +1,8 @@
 """Host-side argument checks of the rasterizer backward's C entry points (no kernel is launched: every call below is
 refused before it reaches the device)."""
 import ctypes
-import os
 
-import pytest
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as entry
-    from audio_motion_avatar_amd import _lib
-
-    if not os.path.exists(_lib.LIB_PATH):
-        entry.build()
-    return _lib.lib()
-
-
-FAKE = 4096  # non-NULL, 16-byte aligned, never dereferenced on these paths
+from abi_support import FAKE, lib  # noqa: F401 (lib: fixture)
 
 
 def _args(F=2, N=100, H=64, W=64, capacity=3200):

@@ -1,25 +1,11 @@
 """Host-side argument checks of the feature sampling backward's C entry points (no kernel is launched: every call
 below is refused before it reaches the device)."""
 import ctypes
-import os
 import re
 
-import pytest
+from abi_support import ERR_INVALID, ERR_WORKSPACE, FAKE, HEADER, lib  # noqa: F401 (lib: fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FAKE = 4096  # non-NULL, 16-byte aligned, never dereferenced on these paths
-ERR_INVALID, ERR_WORKSPACE = -1, -3
 ENTRY = b"amav_triplane_sample_features_backward"
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as entry
-    from audio_motion_avatar_amd import _lib
-
-    if not os.path.exists(_lib.LIB_PATH):
-        entry.build()
-    return _lib.lib()
 
 
 def _args(lib, F=2, N=100, C=8, R=8, scratch_bytes=None):
@@ -56,23 +42,7 @@ def test_symbols_are_exported_and_bound(lib):
 def test_header_and_bindings_agree():
     from audio_motion_avatar_amd import _lib
 
-    text = open(os.path.join(ROOT, "include", "amav.h")).read()
-    body = re.search(r"typedef struct amav_triplane_sample_backward_args \{(.*?)\} amav_triplane_sample_backward_args;",
-                     text, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields, kinds = [], {}
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        pointer = "*" in decl
-        kind, names = decl.replace("*", " ").replace("const ", "").split(None, 1)
-        for f in names.split(","):
-            fields.append(f.strip())
-            kinds[f.strip()] = ctypes.c_void_p if pointer else {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
-                                                                "float": ctypes.c_float, "size_t": ctypes.c_size_t}[kind]
-    assert [f for f, _ in _lib.TriplaneSampleBackwardArgs._fields_] == fields
-    assert {f: t for f, t in _lib.TriplaneSampleBackwardArgs._fields_} == kinds
+    text = open(HEADER).read()
     assert re.search(r"size_t amav_triplane_sample_features_backward_bytes\(int \w+, int \w+, int \w+, int \w+\);", text)
     assert re.search(r"int amav_triplane_sample_features_backward\(const amav_triplane_sample_backward_args \*\w+, "
                      r"void \*\w+\);", text)

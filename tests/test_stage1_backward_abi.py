@@ -1,21 +1,9 @@
 """Host-side argument checks of the stage-1 backwards' C entry points (amav_cell_max_backward, amav_cell_mean_backward,
 amav_points_project_backward): every call below is refused before a kernel is launched."""
-import os
 
-import pytest
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as entry
-    from audio_motion_avatar_amd import _lib
-
-    if not os.path.exists(_lib.LIB_PATH):
-        entry.build()
-    return _lib.lib()
+from abi_support import FAKE, lib  # noqa: F401 (lib: fixture)
 
 
-FAKE = 4096  # non-NULL, aligned, never dereferenced on these paths
 B, N, C, CELLS, H, W = 2, 300, 48, 64, 40, 56
 
 
