@@ -1220,9 +1220,12 @@ __global__ __launch_bounds__(256) void geglu_kernel(long long quads, int inner4,
         f16x4 p1, p2;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            _Float16 a, b;
-            split2(yv[j] * prescale, a, b);
-            p1[j] = a, p2[j] = b;
+            // split2 with + 0 on the fp32 residual: an exactly-zero residual is +0, as x - x is (one that only underflows
+            // fp16 keeps its sign).  Where y = -0 (a saturated gate) the compiler re-forms `a` for the subtraction as
+            // fma(y, prescale, +0) = +0 and the residual came out as -0 - 0 = -0, unlike split_operand_f16_kernel's.
+            const float ys = yv[j] * prescale;
+            const _Float16 a = (_Float16)ys;
+            p1[j] = a, p2[j] = (_Float16)(__builtin_fmaf((float)a, -1.0f, ys) + 0.0f);
         }
         const long long K = 4LL * inner4;
         _Float16 *dst = out_split + row * 3 * K + 4 * col;

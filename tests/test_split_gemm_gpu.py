@@ -293,3 +293,31 @@ def test_hand_written_split_gemm_kernel_matches_the_library_product(rows, n, k):
     assert float((got - lib).abs().max()) <= 2e-6 * scale
     with pytest.raises(ops.AmavError):
         ops.gemm_split_fp16(a, b[:100].contiguous(), 1.0, -2)   # n not a multiple of 128
+
+
+@pytest.mark.parametrize("alpha", [1.0, 2.0 ** -9])
+@pytest.mark.parametrize("rows,n,k", [(129, 128, 96), (64, 256, 160), (300, 128, 224)])
+def test_hand_written_split_gemm_kernel_odd_step_counts(rows, n, k, alpha):
+    """split_gemm_kernel's two-stage loop at 3, 5 and 7 K-steps of 32: an odd count above 1 leaves through the early
+    `break`, after a compute(0) on the stage the previous iteration's conditional store filled (K = 32, 64, 512, 2048
+    above are 1 and even counts).  One column of tiles under several row tiles, rows < 128, two columns; alpha 1 and a
+    power of two as the pre-scales give.  Same references and bound as the test above."""
+    from audio_motion_avatar_amd import ops
+
+    g = torch.Generator(device="cuda").manual_seed(rows + n + k)
+    h = torch.randn(rows, k, device="cuda", generator=g) * 3.0
+    w = torch.randn(n, k, device="cuda", generator=g) * 2.0
+    h1, w1 = h.half(), w.half()
+    h2, w2 = (h - h1.float()).half(), (w - w1.float()).half()
+    a = torch.cat([h2, h1, h1], dim=1).contiguous()
+    b = torch.cat([w1, w2, w1], dim=1).contiguous()
+    ref = alpha * ((h1.double() + h2.double()) @ (w1.double() + w2.double()).t() - h2.double() @ w2.double().t())
+    scale = float(ref.abs().max())
+    got = ops.gemm_split_fp16(a, b, alpha, -2)
+    lib = ops.gemm_split_fp16(a, b, alpha, -1)
+    assert got.shape == (rows, n)
+    err, err_lib = float((got.double() - ref).abs().max()), float((lib.double() - ref).abs().max())
+    print(f"rows| split_gemm rows={rows} n={n} K={k} alpha={alpha:g}: kernel {err / scale:.3e} of max|ref| "
+          f"(bound 2e-6: {err / scale / 2e-6:.3f}), library {err_lib / scale:.3e}")
+    assert err <= 2e-6 * scale
+    assert float((got - lib).abs().max()) <= 2e-6 * scale
