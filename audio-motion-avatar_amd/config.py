@@ -59,6 +59,10 @@ class RendererConfig:
     differentiable_refine_points: bool = False  # ... unless this is on too (needs differentiable_refiner): refine_points
     #                                       becomes an autograd graph (HIP backward of the feature sampling, DESIGN.md section
     #                                       4.13), so an image loss reaches the refiner, its MLP and the tokens through it
+    differentiable_upsampler: bool = False  # Renderer.forward under grad mode with upsample_triplane: the upsampler becomes
+    #                                       an autograd graph (library convolution backwards, HIP window cuts, DESIGN.md
+    #                                       section 4.14), so an image loss reaches the coarse tokens and every
+    #                                       triplane_upsampler parameter; off = refused under grad as before
     use_gaussian_splatting: bool = True
     gaussian_feature_dim: int = 256
     rgb: bool = True

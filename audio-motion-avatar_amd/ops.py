@@ -1043,6 +1043,94 @@ def triplane_sample_features_differentiable(planes, points, radius):
     (through any view it is, e.g. the token slab) and `points`, each only when it requires grad."""
     return _TriplaneSampleFeatures.apply(planes, points, float(radius))
 
+
+# ------------------------------------------------------------------------------- window cutting (windowed upsampler)
+def windows_lattice(frame, oy, ox, step, off_y, off_x, num_frames, rows, cols):
+    """The lattice the transpose walks: (step, off_y, off_x, table) with table int32 [F, rows, cols] holding the index of
+    the window whose corner is (a * step + off_y, b * step + off_x), or -1.  frame / oy / ox: integer tensors [K] on one
+    device; the corners must lie on the lattice (not checked: no host sync)."""
+    step = int(step)
+    table = torch.full((int(num_frames), int(rows), int(cols)), -1, dtype=torch.int32, device=frame.device)
+    if frame.numel():
+        a = torch.div(oy.long() - int(off_y), step, rounding_mode="floor")
+        b = torch.div(ox.long() - int(off_x), step, rounding_mode="floor")
+        table[frame.long(), a, b] = torch.arange(frame.numel(), dtype=torch.int32, device=frame.device)
+    return step, int(off_y), int(off_x), table
+
+
+def _windows_cut_torch(x, frame, oy, ox, size, lattice):
+    """windows_cut as pad / unfold / advanced index (any dtype and device; host sync: the extent of the corners)."""
+    step, off_y, off_x, _ = lattice
+    F, C, h, w = x.shape
+    K = frame.numel()
+    if K == 0:
+        return x.new_zeros(0, C, size, size)
+    oy, ox = oy.long(), ox.long()
+    top, left = max(0, -int(oy.min())), max(0, -int(ox.min()))
+    bottom, right = max(0, int(oy.max()) + size - h), max(0, int(ox.max()) + size - w)
+    xp = torch.nn.functional.pad(x, (left, right, top, bottom)) if top or left or bottom or right else x
+    ry, rx = (off_y + top) % step, (off_x + left) % step      # first lattice row / column inside the padded source
+    wv = xp[:, :, ry:].unfold(2, size, step).permute(0, 1, 2, 4, 3)
+    wv = wv[..., rx:].unfold(4, size, step)                                     # [F,C,ky,size,kx,size]
+    return wv[frame.long(), :, (oy + top - ry) // step, :, (ox + left - rx) // step, :]
+
+
+def _windows_index(t, name, K):
+    t = _contig(t, name, torch.int32)
+    if t.numel() != K:
+        raise AmavError(f"{name}: {t.numel()} entries for {K} windows")
+    return t
+
+
+def windows_cut(x, frame, oy, ox, size):
+    """x [F,C,h,w], frame / oy / ox int32 [K] -> [K,C,size,size]: window k is x[frame[k], :, oy[k]:oy[k]+size,
+    ox[k]:ox[k]+size], zeros where it lies outside the source (amav_windows_cut)."""
+    x = _contig(x, "x")
+    F, C, h, w = x.shape
+    K = frame.numel()
+    frame, oy, ox = (_windows_index(t, n, K) for t, n in ((frame, "frame"), (oy, "oy"), (ox, "ox")))
+    out = torch.empty(K, C, int(size), int(size), device=x.device)
+    _call("amav_windows_cut", F, C, h, w, x.data_ptr(), K, int(size), frame.data_ptr(), oy.data_ptr(), ox.data_ptr(),
+          out.data_ptr())
+    return out
+
+
+def windows_cut_backward(grad_windows, lattice, shape):
+    """grad_windows [K,C,size,size] -> grad_x of `shape` = (F,C,h,w) (amav_windows_cut_backward): every element is the
+    sum of the windows that cover it, in ascending window index; `lattice` = windows_lattice(...).  Deterministic."""
+    grad_windows = _contig(grad_windows, "grad_windows")
+    step, off_y, off_x, table = lattice
+    table = _contig(table, "lattice table", torch.int32)
+    F, C, h, w = (int(v) for v in shape)
+    K, Cw, size, size2 = grad_windows.shape
+    if Cw != C or size != size2 or table.dim() != 3 or table.shape[0] != F:
+        raise AmavError(f"windows_cut_backward: grad_windows {tuple(grad_windows.shape)} / lattice {tuple(table.shape)} "
+                        f"do not match x {(F, C, h, w)}")
+    out = torch.empty(F, C, h, w, device=grad_windows.device)
+    _call("amav_windows_cut_backward", F, C, h, w, K, size, grad_windows.data_ptr(), int(step), int(off_y), int(off_x),
+          table.shape[1], table.shape[2], table.data_ptr(), out.data_ptr())
+    return out
+
+
+class _WindowsCut(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, frame, oy, ox, size, step, off_y, off_x, table):
+        ctx.lattice, ctx.shape = (step, off_y, off_x, table), tuple(x.shape)
+        return windows_cut(x, frame, oy, ox, size)
+
+    @staticmethod
+    def backward(ctx, grad_windows):
+        return (windows_cut_backward(grad_windows.float(), ctx.lattice, ctx.shape),) + (None,) * 8
+
+
+def windows_cut_differentiable(x, frame, oy, ox, size, lattice):
+    """windows_cut under autograd: the HIP cut and its transpose (a gather over `lattice` = windows_lattice(...): no
+    atomics) for tensors on the device.  CPU tensors -- the upsampler's host tests; the library has no CPU path -- go
+    through the pad / unfold / index formulation and torch's own autograd: the same values exactly (a cut copies)."""
+    if not x.is_cuda:
+        return _windows_cut_torch(x, frame, oy, ox, int(size), lattice)
+    return _WindowsCut.apply(x, frame, oy, ox, int(size), *lattice)
+
 # ---------------------------------------------------------------------------------------------- stage-1 reductions
 def cell_segments(cell_of, cells):
     """cell_of int [..., N] (cell of every point) -> (order int32 [..., N], seg int32 [..., cells + 1]): point ids

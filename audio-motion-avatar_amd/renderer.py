@@ -206,17 +206,23 @@ class Renderer(nn.Module):
     def _differentiable_refine_points(self):
         return bool(getattr(self.cfg, "differentiable_refine_points", False)) and hasattr(self, "point_encoder")
 
+    def _differentiable_upsampler(self):
+        return bool(getattr(self.cfg, "differentiable_upsampler", False)) and hasattr(self, "triplane_upsampler")
+
     def _wants_grad(self, *tensors, smpl_params=None):
         """Gradients are recorded through the decode when grad mode is on and the tokens, a head parameter or transl
         (among `tensors`) requires grad -- with cfg.differentiable_smplx, also any tensor of `smpl_params`, with
-        cfg.differentiable_refine_points, also any point_encoder / point_refiner parameter; otherwise every call runs
-        the inference path exactly as before."""
+        cfg.differentiable_refine_points, also any point_encoder / point_refiner parameter, with
+        cfg.differentiable_upsampler, also any triplane_upsampler parameter; otherwise every call runs the inference
+        path exactly as before."""
         if not torch.is_grad_enabled():
             return False
         if smpl_params is not None and self._differentiable_smplx():
             tensors = tensors + tuple(v for v in smpl_params.values() if isinstance(v, torch.Tensor))
         if self._differentiable_refine_points():
             tensors = tensors + tuple(self.point_encoder.parameters()) + tuple(self.point_refiner.parameters())
+        if self._differentiable_upsampler():
+            tensors = tensors + tuple(self.triplane_upsampler.parameters())
         return any(t is not None and t.requires_grad for t in tensors) or any(
             p.requires_grad for p in self.gaussian_decoder.parameters())
 
@@ -273,12 +279,14 @@ class Renderer(nn.Module):
         comes from the gather and LBS backwards; with cfg.differentiable_refine_points: any point refiner parameter,
         and the points are refined by refine_points(differentiable=True)); `out`, `window_plan`, `defer_decode`, the point
         refiner without that flag and -- without differentiable_smplx -- SMPL-X parameters other than transl that require
-        grad are refused then (NotImplementedError).
+        grad are refused then (NotImplementedError).  With cfg.differentiable_upsampler a `window_plan` is taken under grad
+        too (the refined points are checked against it as on the inference path: _WindowTooSmall).
         """
         F = triplane_tokens.shape[0]
         if self._wants_grad(triplane_tokens, smpl_params["transl"], smpl_params=smpl_params):
             self._refuse_under_grad(smpl_params)
-            refused = [n for n, v in (("out", out), ("window_plan", window_plan)) if v is not None] + (
+            plan_ok = self._differentiable_upsampler()  # Renderer.forward's plan of the differentiable windowed upsampler
+            refused = [n for n, v in (("out", out), ("window_plan", None if plan_ok else window_plan)) if v is not None] + (
                 ["defer_decode"] if defer_decode else [])
             if refused:
                 raise NotImplementedError(f"gaussians_from_tokens: {', '.join(refused)} cannot be combined with gradients")
@@ -289,6 +297,9 @@ class Renderer(nn.Module):
                 points = self.get_smpl_vertices(smpl_params)
             if hasattr(self, "point_encoder"):  # cfg.differentiable_refine_points (anything else was refused above)
                 points = self.refine_points(triplane_tokens, points, differentiable=True)
+                if window_plan is not None and not self.triplane_upsampler.windows_contain(
+                        window_plan, points.detach(), self.cfg.triplane_resolution, self.cfg.radius):
+                    raise _WindowTooSmall()
             packed = self._differentiable_decode(triplane_tokens, points, smpl_params["transl"].reshape(F, 3).float(),
                                                  region=self.project_sampled_region)
             return packed if side_work is None else (packed, side_result)
@@ -351,14 +362,16 @@ class Renderer(nn.Module):
         chunks = max(1, min(int(chunks), F))
         if self._wants_grad(triplane_tokens, smpl_params["transl"], smpl_params=smpl_params):
             # differentiable: separate decode launch, one frame group, then render_batch's differentiable rasterizer
-            refused = [n for n, v in (("workspaces", workspaces), ("wire", wire), ("window_plan", window_plan))
+            plan_ok = self._differentiable_upsampler()  # see gaussians_from_tokens
+            refused = [n for n, v in (("workspaces", workspaces), ("wire", wire),
+                                      ("window_plan", None if plan_ok else window_plan))
                        if v is not None] + (["chunks > 1"] if chunks > 1 else []) + (["fuse_decode"] if fuse_decode else [])
             if refused:
                 raise NotImplementedError(f"render_tokens: {', '.join(refused)} cannot be combined with gradients")
             Kc, Ec = K.float(), E.float()
             packed, camera = self.gaussians_from_tokens(
                 triplane_tokens, {k: v.unsqueeze(0) for k, v in flat.items()},
-                side_work=lambda: ops.camera_from_intrinsics(Kc, Ec, H, W))
+                side_work=lambda: ops.camera_from_intrinsics(Kc, Ec, H, W), window_plan=window_plan)
             rgba = render_batch(self.unpack_gaussians(packed), K.unsqueeze(0), E.unsqueeze(0), self.cfg, bg_color,
                                 return_rgba=True, camera=camera[:3])
             return rgba.reshape(F, H, W, 4), packed
@@ -471,23 +484,26 @@ class Renderer(nn.Module):
                 # point refiner folds its BatchNorms as eval too.  This package is inference-only.
                 raise AmavError("Renderer.forward: the triplane upsampler is in training mode; its BatchNorm layers are "
                                 "evaluated with running statistics only -- call .eval() on the module first")
-            if grad:
+            if grad and not self._differentiable_upsampler():
                 raise NotImplementedError("Renderer.forward: the triplane upsampler has no backward; disable gradients "
-                                          "(torch.no_grad()) or upsample_triplane=False")
+                                          "(torch.no_grad()) or upsample_triplane=False (to train through it, set "
+                                          "differentiable_upsampler=True)")
             coarse = tokens
             if getattr(self.cfg, "upsample_windows", True):
                 # only the texels the body's points can sample are upsampled (TriplaneUpsampler, "windowed evaluation")
                 refiner = hasattr(self, "point_encoder")
                 margin = float(getattr(self.cfg, "upsample_window_margin", 0.05)) if refiner else 0.0
-                plan = up.plan_windows(self.get_smpl_vertices(smpl_params), R, self.cfg.radius, margin)
-                tokens = up.forward_tokens_windowed(coarse, R, plan)
+                with torch.no_grad():  # the plan is discrete: under grad it must not record an LBS graph of its own
+                    plan = up.plan_windows(self.get_smpl_vertices(smpl_params), R, self.cfg.radius, margin)
+                # under grad (cfg.differentiable_upsampler): an autograd graph on a slab of its own
+                tokens = up.forward_tokens_windowed(coarse, R, plan, differentiable=grad)
                 window_plan = plan if refiner else None  # refined points are checked against it
                 self.last_window_plan = plan  # diagnostic only (tests / tools read it); never consumed by the path
             else:
                 tokens = up.forward_tokens(coarse, R)
         try:
             rgba, packed = self.render_tokens(tokens, smpl_params, cam_params, chunks=chunks, window_plan=window_plan)
-        except _WindowTooSmall:  # the refiner moved a point past the margin: full planes, once
+        except _WindowTooSmall:  # the refiner moved a point past the margin: full planes, once (under grad: under autograd)
             tokens = self.triplane_upsampler.forward_tokens(coarse, self.cfg.triplane_resolution)
             rgba, packed = self.render_tokens(tokens, smpl_params, cam_params, chunks=chunks)
         gaussians = self.unpack_gaussians(packed)
@@ -673,13 +689,23 @@ class TriplaneUpsampler(nn.Module):
         r = b[5](b[4](b[3](r)) * valid)
         return res.skip(x) + r
 
-    def forward_tokens_windowed(self, tokens, resolution, plan, out=None):
+    def forward_tokens_windowed(self, tokens, resolution, plan, out=None, differentiable=False):
         """Token slab [F,C,3 R^2] + plan_windows()' plan -> full-resolution slab [F,C,3 (2^n R)^2] whose texels inside
-        the active tiles are the upsampled planes (the rest keeps whatever the slab held: never sampled)."""
+        the active tiles are the upsampled planes (the rest keeps whatever the slab held: never sampled).
+        differentiable: the same evaluation as an autograd graph (under grad mode): the slab is a fresh zero tensor --
+        never the cached one, which earlier graphs may hold, and never `out` (refused) -- and the window cuts go through
+        ops.windows_cut_differentiable (HIP cut + transpose; pad / unfold / index for CPU tensors); crops, _run, the
+        mosaics, the validity masks and the placement of the tiles are torch and record their own graph.  Every
+        convolution's gradient has the shape of its activation, so the MAX_ACTIVATION_BYTES chunking of _run and
+        _mosaic bounds the backward's calls as it bounds the forward's."""
         F, C, _ = tokens.shape
         n = len(self.upsample_blocks)
         scale, s_in = 2 ** n, 2 ** (n - 1)
         r_out = resolution * scale
+        if differentiable:
+            if out is not None:
+                raise ValueError("forward_tokens_windowed: differentiable=True writes a slab of its own; `out` is refused")
+            out = torch.zeros(F, C, 3 * r_out * r_out, device=tokens.device, dtype=tokens.dtype)
         if out is None:
             cached = getattr(self, "_slab", None)
             if cached is None or cached.shape != (F, C, 3 * r_out * r_out) or cached.device != tokens.device:
@@ -703,11 +729,19 @@ class TriplaneUpsampler(nn.Module):
             tiles = tiles.to(tokens.device)
             f_idx, ty, tx = tiles[:, 0], tiles[:, 1], tiles[:, 2]
             extent = resolution * scale
+            if differentiable:  # the tiles as the cut's int32 arguments; tile (ty, tx) of frame f -> its index
+                frame32, ty32, tx32 = f_idx.int(), ty.int(), tx.int()
+                lattice = torch.full((F, g, g), -1, dtype=torch.int32, device=tokens.device)
+                lattice[f_idx, ty, tx] = torch.arange(tiles.shape[0], dtype=torch.int32, device=tokens.device)
 
             def tile_windows(x, level_scale, pad, size):
                 """[K,C,size,size]: for every active tile the window of `x` (level with `level_scale` texels per input
                 cell, cropped at (y0, x0), padded by `pad`) that starts `pad` texels before the tile."""
                 step = self.TILE_CELLS * level_scale
+                if differentiable:  # window (ty, tx) starts at ty step - y0 level_scale - pad: a lattice over the tiles
+                    off_y, off_x = -y0 * level_scale - pad, -x0 * level_scale - pad
+                    return ops.windows_cut_differentiable(x, frame32, ty32 * step + off_y, tx32 * step + off_x, size,
+                                                          (step, off_y, off_x, lattice))
                 xp = torch.nn.functional.pad(x, (pad, pad, pad, pad)) if pad else x
                 ay, ax = -(-(y0 * level_scale) // step), -(-(x0 * level_scale) // step)
                 wv = xp[:, :, ay * step - y0 * level_scale:].unfold(2, size, step).permute(0, 1, 2, 4, 3)

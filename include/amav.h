@@ -448,6 +448,28 @@ typedef struct amav_triplane_sample_backward_args {
 size_t amav_triplane_sample_features_backward_bytes(int num_frames, int num_points, int channels, int resolution);
 int amav_triplane_sample_features_backward(const amav_triplane_sample_backward_args *args, void *stream);
 
+/* Window cutting of the windowed triplane upsampler (TriplaneUpsampler.forward_tokens_windowed under autograd): K square
+ * windows of size x size out of x [F,C,h,w].  Window k belongs to frame frame[k] and has its top-left corner at
+ * (oy[k], ox[k]) in source coordinates; a corner may be negative and a window may reach past h / w.
+ *   out [K,C,size,size] = x[frame[k], c, oy[k] + i, ox[k] + j], exact zeros where that lies outside the source (or
+ *   frame[k] outside [0, F)).  Every element is written.  K = 0 or C = 0: nothing to do. */
+int amav_windows_cut(int num_frames, int channels, int height, int width, const float *x_dev, int num_windows, int size,
+                     const int32_t *frame_dev, const int32_t *oy_dev, const int32_t *ox_dev, float *out_dev,
+                     void *stream);
+/* Its transpose: grad_x[f,c,y,x] = sum over the windows k of frame f that cover (y, x) of
+ * grad_windows[k, c, y - oy_k, x - ox_k].  The corners lie on a lattice, oy = a * step + off_y and ox = b * step + off_x
+ * with 0 <= a < lattice_rows, 0 <= b < lattice_cols; lattice [F, lattice_rows, lattice_cols] int32 holds the window index
+ * at each position, or -1 (each window at one position; an index >= num_windows is never read).  A gather: one thread
+ * owns one element of grad_x, walks the <= ceil(size / step)^2 positions whose window covers it and adds them in
+ * ascending window index.  No float atomics: bitwise the same on every run.  Elements no window covers get +0.0; every
+ * element of grad_x [F,C,h,w] is written.
+ * Both refuse (AMAV_ERR_INVALID_ARG, before any launch) negative counts, size <= 0, step <= 0, h * w or size^2 beyond
+ * 2^31 - 1, a lattice whose corners leave the int32 range, and a NULL pointer to a non-empty array.  Element offsets are
+ * 64-bit.  No allocation and no host synchronisation. */
+int amav_windows_cut_backward(int num_frames, int channels, int height, int width, int num_windows, int size,
+                              const float *grad_windows_dev, int step, int off_y, int off_x, int lattice_rows,
+                              int lattice_cols, const int32_t *lattice_dev, float *grad_x_dev, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Stage-1 identity encoder: the point <-> triplane-cell reductions of
  * SMPLXTriplaneEncoder and the point -> pixel feature lookup, deterministic segment reductions.

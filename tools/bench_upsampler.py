@@ -2,7 +2,14 @@
 """Diagnostic: time of the TriplaneUpsampler (renderer.py:377-417) at the reference defaults (4 blocks, C=256,
 32^2 -> 512^2, three planes per frame) and of the default-config frame (upsampler + refiner at 30 000 points).
 
-    python tools/bench_upsampler.py [frames]
+    python tools/bench_upsampler.py [frames] [--backward] [--full-frames N] [--training-step]
+
+--backward: forward + backward of the upsampler under autograd (loss = weighted sum of the features sampled at the
+body's points), windowed (forward_tokens_windowed(differentiable=True)) against full planes (forward_tokens, on
+--full-frames frames, default 1), each with torch.cuda.max_memory_allocated and, for the windowed path, the share of the
+time spent in the two window-cutting kernels (HIP events around ops.windows_cut / ops.windows_cut_backward).
+--training-step: one full stage-2 AudioDrivenAvatar.training_step, forward + backward, at the reference's default
+renderer.yaml (upsampler + refiner, 30 000 points, every differentiable_* flag on) with its peak allocated memory.
 """
 import os
 import sys
@@ -18,7 +25,65 @@ from audio_motion_avatar_amd.config import RendererConfig  # noqa: E402
 from audio_motion_avatar_amd.renderer import Renderer  # noqa: E402
 from audio_motion_avatar_amd.synthetic import init_random_heads, make_render_inputs  # noqa: E402
 
-F = int(sys.argv[1]) if len(sys.argv) > 1 else 2
+from audio_motion_avatar_amd import ops  # noqa: E402
+
+_positional = [a for i, a in enumerate(sys.argv[1:], 1) if not a.startswith("--") and sys.argv[i - 1] != "--full-frames"]
+F = int(_positional[0]) if _positional else 2
+FULL_FRAMES = int(sys.argv[sys.argv.index("--full-frames") + 1]) if "--full-frames" in sys.argv else 1
+
+
+def training_step():
+    """tools/bench_attention_backward.py's training step with the reference's default renderer configuration."""
+    from audio_motion_avatar_amd.config import ModelConfig
+    from audio_motion_avatar_amd.harness import AudioDrivenAvatar
+
+    mcfg = ModelConfig()
+    rc = mcfg.renderer
+    rc.upsample_triplane, rc.no_point_refiner, rc.subdivide_steps = True, False, 2
+    rc.differentiable_smplx = rc.differentiable_refiner = rc.differentiable_refine_points = True
+    rc.differentiable_upsampler = True
+    model = AudioDrivenAvatar(mcfg)
+    init_random_heads(model.renderer)
+    model = model.cuda().eval()
+    with torch.no_grad():
+        model.renderer.point_refiner[-1].weight.normal_(0, 0.005)
+    a = mcfg.triplane_audio_net
+    T = a.triplane_output_frames
+    _, smpl, cam = make_render_inputs(T, rc, seed=1)
+    g = torch.Generator().manual_seed(2)
+    tri = torch.randn(1, a.triplane_input_frames, a.triplane_feature_dim, 3 * a.triplane_resolution ** 2, generator=g)
+    st = torch.randn(1, a.triplane_input_frames, a.smpl_token_dim, a.smpl_token_len, generator=g) * 0.2
+    audio = torch.randn(1, T, a.audio_feature_dim, generator=g)
+    target = torch.rand(1, T, 3, *rc.image_size, generator=g)
+    tri, st, audio, target = (t.cuda() for t in (tri, st, audio, target))
+
+    def step():
+        model.zero_grad(set_to_none=True)
+        loss, _ = model.training_step(tri, st, audio, cam, target, smpl)
+        loss.backward()
+
+    up = model.renderer.triplane_upsampler
+    full_plane_calls, full = [], up.forward_tokens
+    up.forward_tokens = lambda *args, **kw: (full_plane_calls.append(1), full(*args, **kw))[1]  # the fallback, if taken
+    step()
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    t0 = time.perf_counter()
+    reps = 2
+    for _ in range(reps):
+        step()
+    torch.cuda.synchronize()
+    dt = (time.perf_counter() - t0) / reps
+    missing = [k for k, p in up.named_parameters() if p.grad is None]
+    print(f"stage-2 training_step, reference default renderer ({T} frames, {model.renderer.num_verts} points, upsampler + "
+          f"refiner under autograd): {dt * 1e3:.0f} ms, peak allocated {torch.cuda.max_memory_allocated() / 2 ** 30:.1f} GiB; "
+          f"full-plane fallbacks in {reps + 1} steps: {len(full_plane_calls)}; upsampler parameters without a gradient: "
+          f"{missing}", flush=True)
+
+
+if "--training-step" in sys.argv:
+    training_step()
+    sys.exit(0)
 cfg = RendererConfig(image_size=(512, 512), subdivide_steps=0, predict_smplx_params=False, upsample_triplane=True,
                      num_upsample_blocks=4, device="cuda")
 r = init_random_heads(Renderer(cfg).eval())
@@ -70,3 +135,65 @@ with torch.no_grad():
 print(f"windowed: {dw * 1e3:.1f} ms per frame; crops {[w['crop'] for w in plan]} = {cells * 100:.0f} % of the cells for blocks 1-3, "
       f"{tiles * 100:.0f} % of the tiles for block 4 (tiled: {[w['tiles'] is not None for w in plan]}); "
       f"max |full - windowed| inside the active tiles {err:.2e}")
+
+if "--backward" in sys.argv:
+    del out, win, fv, wv
+    r.triplane_upsampler._slab = None
+    torch.cuda.empty_cache()
+    R, radius = cfg.triplane_resolution, cfg.radius
+    r_out = R * 2 ** cfg.num_upsample_blocks
+    cut_events = []
+
+    def timed_op(fn):
+        def wrapper(*a, **k):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            res = fn(*a, **k)
+            e1.record()
+            cut_events.append((e0, e1))
+            return res
+        return wrapper
+
+    ops.windows_cut, ops.windows_cut_backward = timed_op(ops.windows_cut), timed_op(ops.windows_cut_backward)
+
+    def run(label, frames, upsample):
+        g = torch.Generator().manual_seed(3)
+        tok = tokens[0, :frames].clone().requires_grad_()
+        points = pts[:frames].contiguous()
+        weights = torch.randn(frames, points.shape[1], 3 * cfg.triplane_feature_dim, generator=g).cuda()
+
+        def step():
+            r.zero_grad(set_to_none=True)
+            tok.grad = None
+            slab = upsample(tok, points)
+            planes = slab.view(frames, -1, 3, r_out, r_out).permute(0, 2, 1, 3, 4)
+            (ops.triplane_sample_features_differentiable(planes, points, radius) * weights).sum().backward()
+
+        step()
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        cut_events.clear()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            step()
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) / reps
+        cut = sum(a.elapsed_time(b) for a, b in cut_events) / reps
+        print(f"{label}: forward + backward {dt * 1e3 / frames:.1f} ms per frame ({frames} frames per call), peak allocated "
+              f"{torch.cuda.max_memory_allocated() / 2 ** 30:.2f} GiB; window cut kernels {cut:.2f} ms per call = "
+              f"{cut / (dt * 1e3) * 100:.2f} % of it ({len(cut_events) // reps} launches)", flush=True)
+        return {k: p.grad.clone() for k, p in up.named_parameters()}, tok.grad.clone()
+
+    def windowed(tok, points):
+        with torch.no_grad():
+            plan = up.plan_windows(points, R, radius)
+        return up.forward_tokens_windowed(tok, R, plan, differentiable=True)
+
+    gw, tw = run("windowed, autograd", F, windowed)
+    gw2, tw2 = run("windowed, autograd (again)", F, windowed)
+    same = all(torch.equal(gw[k], gw2[k]) for k in gw) and torch.equal(tw, tw2)
+    print(f"two windowed runs bit-identical: {same}" + ("" if same else "; worst relative difference " + format(max(
+        float((gw[k] - gw2[k]).abs().max() / gw[k].abs().max().clamp_min(1e-30)) for k in gw), ".2e")), flush=True)
+    del gw, gw2, tw, tw2
+    torch.cuda.empty_cache()
+    run("full planes, autograd", min(F, FULL_FRAMES), lambda tok, points: up.forward_tokens(tok, R))
