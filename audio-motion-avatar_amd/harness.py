@@ -115,7 +115,9 @@ class AudioDrivenAvatar(nn.Module):
         reach the SMPL-X decoder only with cfg.renderer.differentiable_smplx=True -- without it the renderer refuses a
         backward through the SMPL-X parameters (only transl is differentiable there).  The step runs in the module's
         current mode: the reference trains in .train(), which turns on the 0.1 dropout of SMPLXTemporalReducer's
-        attention; .eval() makes the step deterministic."""
+        attention; .eval() makes the step deterministic.  .train() also switches on gradient checkpointing of the audio
+        transformer's blocks (each keeps only its input and runs its forward again in the backward: a second forward
+        for a fraction of the activation memory, the same gradients)."""
         from .losses import l1_loss, smplx_param_loss, ssim
 
         images, _, pred_smplx_future, _, _ = self.audio_triplane(audio_features, triplanes, None, cam_params,

@@ -1539,6 +1539,123 @@ def _shaped(t, name, shape):
     return t
 
 
+# ------------------------------------------------------------------- the row kernels under autograd
+ROWS_CHUNK = 16  # rows per first-stage partial of rows_colsum and of the LayerNorm backward's dweight / dbias
+
+
+def rows_colsum(x, rows_per_group=None):
+    """x [rows, cols] fp32 (unit inner stride, row stride a multiple of 4, cols a multiple of 4) -> [groups, cols], the
+    column sums over consecutive groups of rows_per_group rows (None: one group), in the fixed two-stage order of
+    include/amav.h (chunks of ROWS_CHUNK rows ascending, then the chunk partials ascending): bit-identical between calls,
+    and a batch of groups equals the groups one by one."""
+    x = _need(x, "x")
+    if x.dim() != 2 or x.stride(1) != 1 or x.shape[1] % 4 or x.stride(0) % 4 or x.data_ptr() % 16:
+        raise AmavError("rows_colsum: need a 16-byte aligned [rows, cols] tensor, unit inner stride, cols a multiple of 4")
+    rows, cols = x.shape
+    per_group = rows if rows_per_group is None else int(rows_per_group)
+    if rows < 1 or per_group < 1 or rows % per_group:
+        raise AmavError(f"rows_colsum: rows={rows} is not a positive multiple of rows_per_group={per_group}")
+    ws = _scratch("amav_rows_colsum_workspace_bytes", x.device, rows, cols, per_group,
+                  rejected=f"rows={rows} cols={cols} rows_per_group={per_group}")
+    out = torch.empty(rows // per_group, cols, device=x.device)
+    _call("amav_rows_colsum", rows, cols, x.data_ptr(), x.stride(0), per_group, out.data_ptr(), ws.data_ptr(), ws.numel())
+    return out
+
+
+def geglu_backward(proj, bias, grad_out):
+    """amav_geglu_backward: proj [..., 2*inner] (contiguous; + bias [2*inner] or None) as geglu() read it and grad_out
+    [..., inner] -> d proj [..., 2*inner].  The bias gradient is rows_colsum of the result."""
+    proj, grad_out = _need(proj, "proj"), _contig(grad_out, "grad_out")
+    if not proj.is_contiguous() or proj.shape[-1] % 8:
+        raise AmavError("geglu_backward: need a contiguous [..., 2*inner] tensor with inner a multiple of 4")
+    inner = proj.shape[-1] // 2
+    rows = proj.numel() // proj.shape[-1]
+    if tuple(grad_out.shape) != tuple(proj.shape[:-1]) + (inner,):
+        raise AmavError(f"grad_out: expected {tuple(proj.shape[:-1]) + (inner,)}, got {tuple(grad_out.shape)}")
+    bias_ptr = None if bias is None else _shaped(bias, "bias", (2 * inner,)).data_ptr()
+    grad = torch.empty_like(proj)
+    _call("amav_geglu_backward", rows, inner, proj.data_ptr(), 2 * inner, bias_ptr, grad_out.data_ptr(), grad.data_ptr(),
+          2 * inner)
+    return grad
+
+
+def add_layernorm_backward(h, weight, eps, grad_norm, grad_h):
+    """amav_add_layernorm_backward: h [B,S,dim] = add_layernorm()'s first result, weight [dim], the upstream gradients of
+    its two results (either may be None = zero) -> (dh [B,S,dim], dweight [dim], dbias [dim]).  dh is the gradient of
+    `hidden` and of `add`; those of batch_row and add_bias are rows_colsum(dh) per batch item / over all rows."""
+    h = _need(h, "h")
+    if h.dim() != 3 or not h.is_contiguous():
+        raise AmavError("add_layernorm_backward: h must be a contiguous [B,S,dim] tensor")
+    B, S, dim = h.shape
+    ptr = lambda t, name: None if t is None else _shaped(t, name, (B, S, dim)).data_ptr()
+    ws = _scratch("amav_add_layernorm_backward_workspace_bytes", h.device, B * S, dim, rejected=f"rows={B * S} dim={dim}")
+    dh = torch.empty_like(h)
+    dweight, dbias = torch.empty(dim, device=h.device), torch.empty(dim, device=h.device)
+    _call("amav_add_layernorm_backward", B * S, dim, h.data_ptr(), _shaped(weight, "weight", (dim,)).data_ptr(), float(eps),
+          ptr(grad_norm, "grad_norm"), ptr(grad_h, "grad_h"), dh.data_ptr(), dweight.data_ptr(), dbias.data_ptr(),
+          ws.data_ptr(), ws.numel())
+    return dh, dweight, dbias
+
+
+class _Geglu(torch.autograd.Function):
+    """geglu (fp32 output) with amav_geglu_backward as the backward; only proj and bias are kept."""
+
+    @staticmethod
+    def forward(ctx, proj, bias):
+        ctx.save_for_backward(proj, bias)
+        return geglu(proj, bias=bias)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        proj, bias = ctx.saved_tensors
+        grad = geglu_backward(proj, bias, grad_out.float())
+        grad_bias = rows_colsum(grad.view(-1, grad.shape[-1]))[0] if bias is not None and ctx.needs_input_grad[1] else None
+        return (grad if ctx.needs_input_grad[0] else None), grad_bias
+
+
+def geglu_differentiable(proj, bias=None):
+    """geglu(proj, bias) as a torch.autograd.Function: the same values bit for bit, gradients for proj and bias from
+    amav_geglu_backward / amav_rows_colsum.  Saves proj and bias only (gelu(gate) is recomputed)."""
+    return _Geglu.apply(_need(proj, "proj").contiguous(), bias)
+
+
+class _AddLayerNorm(torch.autograd.Function):
+    """add_layernorm (fp32 rows) with amav_add_layernorm_backward as the backward; h and weight are kept, the normalised
+    rows are not."""
+
+    @staticmethod
+    def forward(ctx, hidden, add, batch_row, weight, bias, eps, add_bias):
+        h, norm = add_layernorm(hidden, add, batch_row, weight, bias, eps, add_bias=add_bias)
+        ctx.eps = float(eps)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(h, weight)
+        return h, norm
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_h, grad_norm):
+        h, weight = ctx.saved_tensors
+        B, S, dim = h.shape
+        ready = lambda g: None if g is None else g.float().contiguous()
+        dh, dweight, dbias = add_layernorm_backward(h, weight, ctx.eps, ready(grad_norm), ready(grad_h))
+        need = ctx.needs_input_grad
+        rows = dh.view(B * S, dim)
+        return (dh if need[0] else None, dh if need[1] else None,
+                rows_colsum(rows, S).view(B, 1, dim) if need[2] else None,
+                dweight if need[3] else None, dbias if need[4] else None, None,
+                rows_colsum(rows)[0] if need[6] else None)
+
+
+def add_layernorm_differentiable(hidden, add, batch_row, weight, bias, eps=1e-5, add_bias=None):
+    """add_layernorm(...) -> (h, norm) as a torch.autograd.Function: the same values bit for bit, gradients for hidden,
+    add, batch_row, weight, bias and add_bias from amav_add_layernorm_backward / amav_rows_colsum.  Saves h and weight;
+    mean, rstd and the normalised rows are recomputed."""
+    return _AddLayerNorm.apply(_need(hidden, "hidden").contiguous(), add if add is None else _need(add, "add").contiguous(),
+                               batch_row if batch_row is None else _need(batch_row, "batch_row").contiguous(),
+                               weight, bias, float(eps), add_bias)
+
+
 # -------------------------------------------------------------------------------------------------- point refiner
 def cloud_voxelize(points, cloud_of, clouds, resolution=100.0):
     """points [n,3] fp32, cloud_of int32 [n] (ascending) -> (grid int32 [n,3] from the cloud's own origin, cloud_depth

@@ -22,7 +22,11 @@ What runs where:
       - `linear()` on inputs without such a bound: three bf16 parts, six partial products, K' = 6 K (any finite input).
     Both are 2.5-3x / 1.5-2x faster than the library's fp32 GEMM and 2-3x closer to fp64 (tools/gemm_split_probe.py).
     AMAV_GEMM=f32 keeps the fp32 GEMMs, AMAV_GEMM=bf16 the bf16 format everywhere;
-  * GroupNorm, proj_in / proj_out, training / CPU: library kernels through torch (fp32 GEMMs).
+  * under autograd on the GPU (width 256..1024, single key): the row passes of a block -- residual adds + LayerNorm, GEGLU
+    -- on the same HIP kernels as inference, with HIP backwards (csrc/attention_rows_backward.hip); fp32 F.linear GEMMs.
+    AMAV_TRAIN_ROWS=library keeps the library's LayerNorm / gelu / mul there.  In .train() with
+    gradient_checkpointing=True every block is checkpointed, as in the reference;
+  * GroupNorm, proj_in / proj_out, CPU: library kernels through torch (fp32 GEMMs).
 """
 import math
 import os
@@ -32,6 +36,7 @@ import weakref
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+import torch.utils.checkpoint
 
 from . import ops, tuning
 
@@ -369,9 +374,29 @@ class BasicTransformerBlock(nn.Module):
             row = self.attn2(h[:, :1], encoder_hidden_states)[:, :1].contiguous()  # [B,1,dim]
             h, n3 = ops.add_layernorm(h.contiguous(), a1, row, self.norm3.weight, self.norm3.bias, self.norm3.eps)
             return self.ff(n3) + h
+        if single_key and self._train_rows_fused(h, encoder_hidden_states):
+            # autograd path on the row kernels: the passes of the inference branch above, each with its HIP backward
+            # (ops.add_layernorm_differentiable / geglu_differentiable).  The GEMMs stay F.linear;
+            # norm2 and attn2.to_q / to_k have no consumer with a single key and stay outside the graph.
+            ff_in, ff_out = self.ff.net[0].proj, self.ff.net[2]
+            h, n1 = ops.add_layernorm_differentiable(h, None, None, self.norm1.weight, self.norm1.bias, self.norm1.eps)
+            a1 = self.attn1._forward_differentiable(n1)
+            row = self.attn2(h[:, :1], encoder_hidden_states)[:, :1]   # [B,1,dim]; to_v / to_out get gradients
+            h, n3 = ops.add_layernorm_differentiable(h, a1, row, self.norm3.weight, self.norm3.bias, self.norm3.eps)
+            gated = ops.geglu_differentiable(F.linear(n3, ff_in.weight), bias=ff_in.bias)
+            return F.linear(gated, ff_out.weight, ff_out.bias) + h
         h = self.attn1(self.norm1(h)) + h
         h = self.attn2(self.norm2(h), encoder_hidden_states) + h
         return self.ff(self.norm3(h)) + h
+
+    def _train_rows_fused(self, h, context):
+        """Whether a single-key block under autograd runs its row passes on the HIP kernels (the default) instead of the
+        library's LayerNorm / add / gelu / mul.  AMAV_TRAIN_ROWS=library, read per call like AMAV_GEMM, keeps the library
+        path."""
+        if not (torch.is_grad_enabled() and h.is_cuda and h.dtype == torch.float32 and h.shape[-1] in (256, 512, 768, 1024)
+                and self.attn2.to_v.bias is None and os.environ.get("AMAV_TRAIN_ROWS", "fused") != "library"):
+            return False
+        return h.requires_grad or context.requires_grad or any(p.requires_grad for p in self.parameters())
 
 
 class Transformer1D_nn(nn.Module):
@@ -393,6 +418,7 @@ class Transformer1D_nn(nn.Module):
             BasicTransformerBlock(inner, num_attention_heads, attention_head_dim, dropout, cross_attention_dim)
             for _ in range(num_layers)])
         self.proj_out = nn.Linear(inner, in_channels)
+        self.gradient_checkpointing = bool(gradient_checkpointing)
         self._cross = None
 
     def _cross_rows(self, context):
@@ -426,6 +452,12 @@ class Transformer1D_nn(nn.Module):
                 h, pending = block.forward_fused(h, pending, row)
             last, last_bias = pending  # the last feed-forward output (+ its bias, when its GEMM ran without one)
             h = (last if last_bias is None else last + last_bias) + h
+        elif self.training and self.gradient_checkpointing and torch.is_grad_enabled():
+            # transformers.py:1044-1056: a block keeps its input only and runs its forward again in the backward.  The HIP
+            # Functions of a block are deterministic and keep no per-call state, so the second forward repeats the first
+            # bit for bit.
+            for block in self.transformer_blocks:
+                h = torch.utils.checkpoint.checkpoint(block, h, ctx, use_reentrant=False)
         else:
             for block in self.transformer_blocks:
                 h = block(h, ctx)

@@ -117,7 +117,7 @@ class SMPLXTriplaneEncoder(nn.Module):
             self.cross_attn = Transformer1D_nn(
                 num_layers=cfg.smplx_transformer_layers, attention_head_dim=cfg.smplx_transformer_head_dim,
                 in_channels=self.smpl_token_dim, num_attention_heads=cfg.smplx_transformer_num_heads,
-                cross_attention_dim=cfg.image_feature_dim, norm_type="layer_norm")
+                cross_attention_dim=cfg.image_feature_dim, norm_type="layer_norm", gradient_checkpointing=True)
             self.smpl_decoder = smpl_decoder
         self.actvn = nn.ReLU()
 
@@ -224,7 +224,8 @@ class FeatureFusionNetwork(nn.Module):
         self.transformer_cross = Transformer1D_nn(
             num_layers=cfg.cross_transformer_layers, attention_head_dim=cfg.cross_transformer_head_dim,
             in_channels=self.triplane_feature_dim, num_attention_heads=cfg.cross_transformer_num_heads,
-            cross_attention_dim=1536, norm_type="layer_norm")  # hard-coded in the reference too (:326)
+            cross_attention_dim=1536, norm_type="layer_norm",  # hard-coded in the reference too (:326)
+            gradient_checkpointing=True)
 
     def forward(self, geometry_triplane, image_features, smpl_tokens):
         B, T, _, C, H, W = geometry_triplane.shape

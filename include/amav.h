@@ -611,6 +611,39 @@ int amav_add_layernorm(int64_t rows, int dim, int64_t rows_per_batch, const floa
                        const float *weight_dev, const float *bias_dev, float eps, float *out_norm_dev,
                        void *out_norm_split_dev, int split_format, int split_scale_exp, void *stream);
 
+/* Backwards of the two row kernels above and the column sum their bias-like gradients need
+ * (csrc/attention_rows_backward.hip).  Deterministic bit for bit: no atomics, every sum in a fixed
+ * order that depends on the sizes alone.  Kernel launches only, no host synchronisation; all buffers 16-byte aligned, row
+ * strides in floats and multiples of 4.
+ *
+ * amav_rows_colsum     out [groups, cols] : out[g, c] = sum of x[r, c] over the rows_per_group rows of group g
+ *                      (groups = rows / rows_per_group, which must divide; cols a multiple of 4).  Two stages: the rows
+ *                      of a group in consecutive chunks of 16 (the last may be shorter; no chunk straddles a group), each
+ *                      summed in ascending row order; then a group's chunk partials added in ascending order.  workspace:
+ *                      amav_rows_colsum_workspace_bytes(rows, cols, rows_per_group) bytes (0 = bad sizes).
+ * amav_geglu_backward  with h = proj[:, :inner] + bias_h and g = proj[:, inner:] + bias_g (bias [2*inner] may be NULL),
+ *                      recomputed from proj: dproj [rows, 2*inner] = (dout gelu(g) | dout h (Phi(g) + g phi(g))), exact
+ *                      erf.  Nothing else of the forward is needed; the bias gradient is amav_rows_colsum(dproj), one group.
+ * amav_add_layernorm_backward  h [rows, dim] = the forward's hidden_out, dim in {256, 512, 768, 1024}.  mean and rstd are
+ *                      recomputed as the forward computes them; with xhat = (h - mean) rstd and t = dnorm * weight:
+ *                        dh = dhidden_out + rstd (t - mean_c(t) - xhat mean_c(t xhat))         [rows, dim]
+ *                        dweight[c] = sum_r dnorm xhat,  dbias[c] = sum_r dnorm                 [dim] each
+ *                      both in amav_rows_colsum's order with one group (a wave keeps the partials of its 16 rows in
+ *                      registers: dnorm is read once).  dnorm / dhidden_out [rows, dim] may be NULL (= zero); without dnorm
+ *                      dweight and dbias are +0.  dh must not alias an input.  The forward's other operands follow from
+ *                      dh: d add = d hidden = dh, d batch_row = amav_rows_colsum(dh, rows_per_group = rows_per_batch),
+ *                      d add_bias = amav_rows_colsum(dh, one group).  workspace:
+ *                      amav_add_layernorm_backward_workspace_bytes(rows, dim) bytes (0 = bad sizes). */
+size_t amav_rows_colsum_workspace_bytes(int64_t rows, int cols, int64_t rows_per_group);
+int amav_rows_colsum(int64_t rows, int cols, const float *x_dev, int64_t x_row_stride, int64_t rows_per_group,
+                     float *out_dev, void *workspace, size_t workspace_bytes, void *stream);
+int amav_geglu_backward(int64_t rows, int inner, const float *proj_dev, int64_t proj_row_stride, const float *bias_dev,
+                        const float *dout_dev, float *dproj_dev, int64_t dproj_row_stride, void *stream);
+size_t amav_add_layernorm_backward_workspace_bytes(int64_t rows, int dim);
+int amav_add_layernorm_backward(int64_t rows, int dim, const float *h_dev, const float *weight_dev, float eps,
+                                const float *dnorm_dev, const float *dhidden_out_dev, float *dh_dev, float *dweight_dev,
+                                float *dbias_dev, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Point refiner: the sparse / serialised operators of the reference's
  * PointTransformerV3 (src/models/point_transformer/pointtransformer_v3.py:81-145,328-499,618-759; point_encoder.py:25-40;
