@@ -36,6 +36,15 @@ inline int check_launch(const char *what) {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+inline unsigned blocks_for(long long threads) { return (unsigned)((threads + 255) / 256); }  // of 256 threads
+
+template <typename... P>
+inline bool aligned16(const P *...p) {
+    return ((... | reinterpret_cast<uintptr_t>(p)) & 15) == 0;
+}
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));  // a 32x32 MFMA accumulator
+
 // Tile-sparse wire format of the frame exchange (frames.hip has the description): shared with the rasterizer, which can
 // emit it directly (amav_raster_args.wire)
 constexpr int kWireHeaderInts = 16;

@@ -24,7 +24,6 @@
 namespace amav {
 namespace attn {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kD = 64;        // head dim
 constexpr int kBM = 128;      // queries per workgroup (4 waves x 32)

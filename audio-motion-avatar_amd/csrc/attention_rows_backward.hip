@@ -10,7 +10,6 @@
 // The order depends on (rows, rows_per_group) alone -- not on the grid, the clock or the batch around a group -- so two
 // calls are bit-identical and a batch of groups equals the groups one by one.
 #include <cmath>
-#include <initializer_list>
 
 #include "amav_common.h"
 
@@ -200,12 +199,6 @@ inline long long chunks_of(long long rows) { return (rows + kRowChunk - 1) / kRo
 
 using namespace amav;
 
-static bool aligned16(std::initializer_list<const void *> ptrs) {
-    uintptr_t bits = 0;
-    for (const void *p : ptrs) bits |= reinterpret_cast<uintptr_t>(p);
-    return (bits & 15) == 0;
-}
-
 extern "C" size_t amav_rows_colsum_workspace_bytes(int64_t rows, int cols, int64_t rows_per_group) {
     if (rows <= 0 || cols <= 0 || cols % 4 || rows_per_group <= 0 || rows % rows_per_group) return 0;
     const long long chunks = (rows / rows_per_group) * rows_bwd::chunks_of(rows_per_group);
@@ -221,7 +214,7 @@ extern "C" int amav_rows_colsum(int64_t rows, int cols, const float *x, int64_t 
                  (long long)rows_per_group);
     AMAV_REQUIRE(x && out, "amav_rows_colsum: NULL pointer");
     AMAV_REQUIRE(x_row_stride >= cols && x_row_stride % 4 == 0, "amav_rows_colsum: bad row stride");
-    AMAV_REQUIRE(aligned16({x, out, workspace}), "amav_rows_colsum: buffers must be 16-byte aligned");
+    AMAV_REQUIRE(aligned16(x, out, workspace), "amav_rows_colsum: buffers must be 16-byte aligned");
     const long long groups = rows / rows_per_group, per_group = rows_bwd::chunks_of(rows_per_group);
     AMAV_REQUIRE(groups <= 65535 && groups * per_group <= 65535, "amav_rows_colsum: grid too large");
     const size_t need = amav_rows_colsum_workspace_bytes(rows, cols, rows_per_group);
@@ -246,7 +239,7 @@ extern "C" int amav_geglu_backward(int64_t rows, int inner, const float *proj, i
     AMAV_REQUIRE(proj_row_stride >= 2LL * inner && proj_row_stride % 4 == 0 && dproj_row_stride >= 2LL * inner &&
                      dproj_row_stride % 4 == 0,
                  "amav_geglu_backward: bad row stride");
-    AMAV_REQUIRE(aligned16({proj, bias, dout, dproj}), "amav_geglu_backward: buffers must be 16-byte aligned");
+    AMAV_REQUIRE(aligned16(proj, bias, dout, dproj), "amav_geglu_backward: buffers must be 16-byte aligned");
     const long long quads = rows * (inner / 4);
     AMAV_REQUIRE((quads + 255) / 256 <= 0x7fffffffLL, "amav_geglu_backward: grid too large");
     rows_bwd::geglu_backward_kernel<<<(unsigned)((quads + 255) / 256), 256, 0, static_cast<hipStream_t>(stream)>>>(
@@ -267,7 +260,7 @@ extern "C" int amav_add_layernorm_backward(int64_t rows, int dim, const float *h
     AMAV_REQUIRE(rows > 0 && (dim == 256 || dim == 512 || dim == 768 || dim == 1024),
                  "amav_add_layernorm_backward: rows=%lld dim=%d (dim must be 256, 512, 768 or 1024)", (long long)rows, dim);
     AMAV_REQUIRE(h && weight && dh && dweight && dbias, "amav_add_layernorm_backward: NULL pointer");
-    AMAV_REQUIRE(aligned16({h, weight, dnorm, dhidden_out, dh, dweight, dbias, workspace}),
+    AMAV_REQUIRE(aligned16(h, weight, dnorm, dhidden_out, dh, dweight, dbias, workspace),
                  "amav_add_layernorm_backward: buffers must be 16-byte aligned");
     const size_t need = amav_add_layernorm_backward_workspace_bytes(rows, dim);
     if (workspace == nullptr || workspace_bytes < need)

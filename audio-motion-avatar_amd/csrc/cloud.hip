@@ -30,7 +30,6 @@
 namespace amav {
 namespace cloud {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 
 __device__ __forceinline__ float gelu(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
@@ -741,8 +740,6 @@ __global__ __launch_bounds__(256) void rows_norm_kernel(long long rows, const fl
 
 using namespace amav;
 
-static inline unsigned blocks_for(long long threads) { return (unsigned)((threads + 255) / 256); }
-static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 extern "C" int amav_cloud_voxelize(int64_t n, int clouds, const float *points, const int32_t *cloud_of, float resolution,
                                    int32_t *grid, int32_t *cloud_depth, int32_t *bounds, void *stream_) {

@@ -7,31 +7,28 @@
 //   amav_subm_pair_wgrad          dW[t] = sum over the pairs p of tap t of feat[src(p)]^T (x) g[dst(p)]: both operands
 //                                 gathered into LDS, the reduction dimension is the tap's pairs, split over chunks of
 //                                 pairs whose partial matrices a second pass adds in slice order
-//   amav_patch_attention_backward flash-attention-2 form through `order` / `patch_desc`: delta = rowsum(dO * O), a key-major
-//                                 pass for dK / dV and a query-major pass for dQ, probabilities recomputed from the row
-//                                 log-sum-exp of amav_patch_attention_lse.  A row is a query of exactly one patch (dQ is
-//                                 written once); it can be a key of two (its own and, as a borrowed slot, the cloud's last
-//                                 incomplete patch): the borrowed part is staged and added after the own part by a fixed pass
+//   amav_patch_attention_backward the flash-attention-2 backward of attention_backward_core.h through `order` /
+//                                 `patch_desc`, probabilities recomputed from the row log-sum-exp of
+//                                 amav_patch_attention_lse.  A row is a query of exactly one patch (dQ is written once);
+//                                 it can be a key of two (its own and, as a borrowed slot, the cloud's last incomplete
+//                                 patch): the borrowed part is staged and added after the own part by a fixed pass
 //   amav_cluster_max_backward     gelu(max * scale + shift): the whole gradient to the first member, in segment order, that
 //                                 attains the maximum; every row of dx written once
 //   amav_cluster_sum              out[j] = sum of x[members[r]] over segment j in segment order: the backward of the
 //                                 up[cluster] gather of amav_unpool_merge
 // No atomics, every sum in a fixed order: a call is deterministic bit for bit.  Products on v_mfma_f32_32x32x2_f32 (exact
-// fp32 products, fp32 sums).  MFMA layouts: csrc/attention_backward.hip.
+// fp32 products, fp32 sums).  MFMA layouts: csrc/attention_backward_core.h.
 #include <climits>
 #include <cmath>
 
-#include "amav_common.h"
+#include "attention_backward_core.h"
 
 namespace amav {
 namespace cloud_bwd {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using attn_bwd::acc_row;
 
-constexpr float kLog2e = 1.4426950408889634f;
 constexpr int kWgradChunk = 128;  // granularity of a split-K slice of amav_subm_pair_wgrad, in pairs
-
-__device__ __forceinline__ int acc_row(int t, int hh) { return (t & 3) + 8 * (t >> 2) + 4 * hh; }
 
 // ---- submanifold convolution ----------------------------------------------------------------------------------------
 // out[i] (+)= sum over r in [src_start[i], src_start[i+1]) with pair_lo <= src_pairs[r] < pair_hi of
@@ -124,258 +121,48 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(int taps, long long m
 }
 
 // ---- patch attention ------------------------------------------------------------------------------------------------
-// Slots, patch_desc and the borrowed tail: cloud.hip, patch_attention_kernel.  lse / delta are [n, heads] in point order.
-constexpr int kBT = 32;        // rows of the swept operand per LDS tile
-constexpr int kLd = kBT + 1;   // padded row of a transposed [d][row] tile
+// The kernels of attention_backward_core.h through `order` / `patch_desc` (slots and the borrowed tail: cloud.hip,
+// patch_attention_kernel).  A patch has K key slots, of which the first `own` are its queries; slot j >= own is borrowed:
+// row order[first + j - K] of the patch before.  Rows are [n, 3 C] of qkv / dqkv and [n, C] of out / dout, lse and delta
+// are [n, heads], all in point order.
+struct PatchRows {
+    const float *qkv;
+    const long long *order;
+    const int4 *desc;
+    const float *out, *dout, *lse;
+    float *delta, *dqkv, *stage;  // stage [n, 2 C]: dK | dV that a borrowed slot adds to its point
+    long long row_heads;          // n * heads
+    int C, heads, D;
+    int first, K, own;            // of the bound patch (bind)
 
-__device__ __forceinline__ long long slot_row(const long long *__restrict__ order, int first, int K, int own, int j) {
-    j = min(j, K - 1);
-    return order[first + j - (j >= own ? K : 0)];
-}
-
-// D / 4 threads per (row, head): out and dout are [n, heads * D] contiguous, so (row, head) number r starts at r * D
-template <int D>
-__global__ __launch_bounds__(256) void pa_delta_kernel(long long row_heads, const float *__restrict__ out,
-                                                       const float *__restrict__ dout, float *__restrict__ delta) {
-    constexpr int G = D / 4;
-    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long r = gid / G;
-    const int d4 = (int)(gid % G);
-    const bool live = r < row_heads;
-    float acc = 0.f;
-    if (live) {
-        const float4 o = *reinterpret_cast<const float4 *>(out + r * D + 4 * d4);
-        const float4 gg = *reinterpret_cast<const float4 *>(dout + r * D + 4 * d4);
-        acc = (o.x * gg.x + o.y * gg.y) + (o.z * gg.z + o.w * gg.w);
+    __device__ long long delta_rows() const { return row_heads; }
+    // out and dout are contiguous, so pair r = row * heads + head starts at r * D
+    __device__ void delta_io(long long r, const float *&o, const float *&g, float *&d) const {
+        o = out + r * D, g = dout + r * D, d = delta + r;
     }
-#pragma unroll
-    for (int o = G / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o, G);
-    if (live && d4 == 0) delta[r] = acc;
-}
-
-// grid (key slot blocks of 128, heads, patches).  Wave w owns key slots blockIdx.x * 128 + 32 w + (lane & 31) and sweeps
-// the patch's own queries (a borrowed slot's query result is dropped by the forward, so it has no gradient).
-template <int D>
-__global__ __launch_bounds__(256) void pa_dkdv_kernel(const float *__restrict__ qkv, const long long *__restrict__ order,
-                                                      const int4 *__restrict__ desc, const float *__restrict__ dout,
-                                                      const float *__restrict__ lse, const float *__restrict__ delta,
-                                                      float *__restrict__ dqkv, float *__restrict__ stage, int C, int heads,
-                                                      float scale) {
-    constexpr int DV = D < 32 ? 32 : D, NB = DV / 32, PER = D / 8;
-    __shared__ float Qt[DV * kLd];  // [d][query] of the current query tile (rows D.. stay zero)
-    __shared__ float Gt[DV * kLd];  // [d][query] of dO
-    __shared__ float Ls[kBT], Ds[kBT];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, c = lane & 31, hh = lane >> 5;
-    const int head = blockIdx.y;
-    const int4 pd = desc[blockIdx.z];
-    const int first = pd.x, K = pd.y, own = pd.z;
-    if ((int)blockIdx.x * 128 >= K) return;  // uniform over the workgroup
-    const int slot = blockIdx.x * 128 + wave * 32 + c;
-    const long long krow = slot_row(order, first, K, own, slot);
-    const long long rs = 3LL * C;
-    const float sl2 = scale * kLog2e;
-
-    float Kr[D / 2], Vr[D / 2];
-    {
-        const float *kp = qkv + krow * rs + C + head * D;
-#pragma unroll
-        for (int s = 0; s < D / 2; ++s) {
-            const float2 kt = *reinterpret_cast<const float2 *>(kp + 2 * s);
-            const float2 vt = *reinterpret_cast<const float2 *>(kp + C + 2 * s);
-            Kr[s] = (hh ? kt.y : kt.x) * sl2;
-            Vr[s] = hh ? vt.y : vt.x;
-        }
+    __device__ void bind(int head, int patch) {
+        const int4 pd = desc[patch];
+        first = pd.x, K = pd.y, own = pd.z;
+        qkv += head * D, dout += head * D, dqkv += head * D, stage += head * D;
+        lse += head, delta += head;
     }
-    if (D < 32) {
-        for (int t = tid; t < (DV - D) * kLd; t += 256) Qt[D * kLd + t] = 0.f, Gt[D * kLd + t] = 0.f;
+    __device__ int keys() const { return K; }
+    __device__ int queries() const { return own; }
+    __device__ long long slot_row(int j) const { return order[first + j - (j >= own ? K : 0)]; }
+    __device__ const float *q_row(int i) const { return qkv + slot_row(i) * 3 * C; }
+    __device__ const float *k_row(int j) const { return q_row(j) + C; }
+    __device__ const float *v_row(int j) const { return q_row(j) + 2 * C; }
+    __device__ const float *dout_row(int i) const { return dout + slot_row(i) * C; }
+    __device__ float lse_at(int i) const { return lse[slot_row(i) * heads]; }
+    __device__ float delta_at(int i) const { return delta[slot_row(i) * heads]; }
+    __device__ float *dq_row(int i) const { return dqkv + slot_row(i) * 3 * C; }
+    // an own slot writes the gradient row, a borrowed slot the staging row of the same point
+    __device__ float *dk_row(int j) const {
+        const long long row = slot_row(j);
+        return j < own ? dqkv + row * 3 * C + C : stage + row * 2 * C;
     }
-    f32x16 dV[NB], dK[NB];  // dV^T, dK^T: rows d, column = this lane's key slot
-#pragma unroll
-    for (int a = 0; a < NB; ++a)
-#pragma unroll
-        for (int t = 0; t < 16; ++t) dV[a][t] = 0.f, dK[a][t] = 0.f;
-
-    // staging: thread -> query tid / 8 of the tile, PER consecutive d at (tid % 8) * PER.  Queries past `own` are staged
-    // as zeros with L = delta = 0: P = 1 and dS = 0 meet a zero dO / Q row and add exact zeros
-    const int sq = tid >> 3, sd = (tid & 7) * PER;
-    const int ntiles = (own + kBT - 1) / kBT;
-    for (int qt = 0; qt < ntiles; ++qt) {
-        const int qi = qt * kBT + sq;
-        float av[PER], gv[PER];
-#pragma unroll
-        for (int e = 0; e < PER; ++e) av[e] = 0.f, gv[e] = 0.f;
-        if (qi < own) {
-            const long long r = slot_row(order, first, K, own, qi);
-            const float *qp = qkv + r * rs + head * D + sd;
-            const float *gp = dout + r * C + head * D + sd;
-#pragma unroll
-            for (int e = 0; e < PER; e += 2) {
-                const float2 a = *reinterpret_cast<const float2 *>(qp + e);
-                const float2 b = *reinterpret_cast<const float2 *>(gp + e);
-                av[e] = a.x, av[e + 1] = a.y, gv[e] = b.x, gv[e + 1] = b.y;
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < PER; ++e) Qt[(sd + e) * kLd + sq] = av[e], Gt[(sd + e) * kLd + sq] = gv[e];
-        if (tid < kBT) {
-            const int qq = qt * kBT + tid;
-            float l = 0.f, d = 0.f;
-            if (qq < own) {
-                const long long r = slot_row(order, first, K, own, qq);
-                l = lse[r * heads + head] * kLog2e, d = delta[r * heads + head];
-            }
-            Ls[tid] = l, Ds[tid] = d;
-        }
-        __syncthreads();
-
-        f32x16 Sa, dP;  // rows = queries r(t) + 4 hh of the tile, column = this lane's key slot
-#pragma unroll
-        for (int t = 0; t < 16; ++t) Sa[t] = 0.f, dP[t] = 0.f;
-#pragma unroll
-        for (int s = 0; s < D / 2; ++s) {
-            Sa = __builtin_amdgcn_mfma_f32_32x32x2f32(Qt[(2 * s + hh) * kLd + c], Kr[s], Sa, 0, 0, 0);
-            dP = __builtin_amdgcn_mfma_f32_32x32x2f32(Gt[(2 * s + hh) * kLd + c], Vr[s], dP, 0, 0, 0);
-        }
-        f32x16 P, dS;
-#pragma unroll
-        for (int t = 0; t < 16; ++t) {
-            const int qq = acc_row(t, hh);
-            P[t] = exp2f(Sa[t] - Ls[qq]);
-            dS[t] = P[t] * (dP[t] - Ds[qq]);
-        }
-        // dV^T += dO^T P, dK^T += Q^T dS: k-step t contracts over queries r(t), r(t) + 4
-#pragma unroll
-        for (int t = 0; t < 16; ++t) {
-            const int qq = acc_row(t, hh);
-#pragma unroll
-            for (int a = 0; a < NB; ++a) {
-                dV[a] = __builtin_amdgcn_mfma_f32_32x32x2f32(Gt[(c + 32 * a) * kLd + qq], P[t], dV[a], 0, 0, 0);
-                dK[a] = __builtin_amdgcn_mfma_f32_32x32x2f32(Qt[(c + 32 * a) * kLd + qq], dS[t], dK[a], 0, 0, 0);
-            }
-        }
-        __syncthreads();  // every wave is done with this tile before it is overwritten
-    }
-
-    if (slot < K) {  // an own slot writes the gradient row, a borrowed slot the staging row of the same point
-        float *kdst = slot < own ? dqkv + krow * rs + C + head * D : stage + krow * 2LL * C + head * D;
-        float *vdst = kdst + C;
-#pragma unroll
-        for (int a = 0; a < NB; ++a)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {  // registers 4g..4g+3 are 4 consecutive d: 32 a + 8 g + 4 hh + (0..3)
-                const int d = 32 * a + 8 * g + 4 * hh;
-                if (d < D) {
-                    *reinterpret_cast<float4 *>(vdst + d) =
-                        make_float4(dV[a][4 * g], dV[a][4 * g + 1], dV[a][4 * g + 2], dV[a][4 * g + 3]);
-                    *reinterpret_cast<float4 *>(kdst + d) = make_float4(dK[a][4 * g] * scale, dK[a][4 * g + 1] * scale,
-                                                                        dK[a][4 * g + 2] * scale, dK[a][4 * g + 3] * scale);
-                }
-            }
-    }
-}
-
-// grid (query slot blocks of 128, heads, patches).  Wave w owns query slots blockIdx.x * 128 + 32 w + (lane & 31) and
-// sweeps every key slot of the patch, borrowed ones included.
-template <int D>
-__global__ __launch_bounds__(256) void pa_dq_kernel(const float *__restrict__ qkv, const long long *__restrict__ order,
-                                                    const int4 *__restrict__ desc, const float *__restrict__ dout,
-                                                    const float *__restrict__ lse, const float *__restrict__ delta,
-                                                    float *__restrict__ dqkv, int C, int heads, float scale) {
-    constexpr int DV = D < 32 ? 32 : D, NB = DV / 32, PER = D / 8;
-    __shared__ float Kt[DV * kLd];  // [d][key] of the current key tile (rows D.. stay zero)
-    __shared__ float Vt[D * kLd];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, c = lane & 31, hh = lane >> 5;
-    const int head = blockIdx.y;
-    const int4 pd = desc[blockIdx.z];
-    const int first = pd.x, K = pd.y, own = pd.z;
-    if ((int)blockIdx.x * 128 >= K) return;
-    const int slot = blockIdx.x * 128 + wave * 32 + c;
-    const long long qrow = slot_row(order, first, K, own, slot);
-    const long long rs = 3LL * C;
-
-    float Qr[D / 2], Gr[D / 2];
-    {
-        const float *qp = qkv + qrow * rs + head * D;
-        const float *gp = dout + qrow * C + head * D;
-        const float sl2 = scale * kLog2e;
-#pragma unroll
-        for (int s = 0; s < D / 2; ++s) {
-            const float2 qt = *reinterpret_cast<const float2 *>(qp + 2 * s);
-            const float2 gt = *reinterpret_cast<const float2 *>(gp + 2 * s);
-            Qr[s] = (hh ? qt.y : qt.x) * sl2;
-            Gr[s] = hh ? gt.y : gt.x;
-        }
-    }
-    // a slot that is not an own query is computed and dropped: L = 1e30 makes its probabilities zero
-    const float Lq = slot < own ? lse[qrow * heads + head] * kLog2e : 1e30f, Dq = delta[qrow * heads + head];
-    if (D < 32) {
-        for (int t = tid; t < (DV - D) * kLd; t += 256) Kt[D * kLd + t] = 0.f;
-    }
-    f32x16 dQ[NB];  // dQ^T: rows d, column = this lane's query slot
-#pragma unroll
-    for (int a = 0; a < NB; ++a)
-#pragma unroll
-        for (int t = 0; t < 16; ++t) dQ[a][t] = 0.f;
-
-    const int sk = tid >> 3, sd = (tid & 7) * PER;
-    const int ntiles = (K + kBT - 1) / kBT;
-    for (int kt = 0; kt < ntiles; ++kt) {
-        const int kj = kt * kBT + sk;
-        float av[PER], bv[PER];
-#pragma unroll
-        for (int e = 0; e < PER; ++e) av[e] = 0.f, bv[e] = 0.f;
-        if (kj < K) {
-            const float *kp = qkv + slot_row(order, first, K, own, kj) * rs + C + head * D + sd;
-#pragma unroll
-            for (int e = 0; e < PER; e += 2) {
-                const float2 a = *reinterpret_cast<const float2 *>(kp + e);
-                const float2 b = *reinterpret_cast<const float2 *>(kp + C + e);
-                av[e] = a.x, av[e + 1] = a.y, bv[e] = b.x, bv[e + 1] = b.y;
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < PER; ++e) Kt[(sd + e) * kLd + sk] = av[e], Vt[(sd + e) * kLd + sk] = bv[e];
-        __syncthreads();
-
-        f32x16 St, dPt;  // rows = keys r(t) + 4 hh of the tile, column = this lane's query slot
-#pragma unroll
-        for (int t = 0; t < 16; ++t) St[t] = 0.f, dPt[t] = 0.f;
-#pragma unroll
-        for (int s = 0; s < D / 2; ++s) {
-            St = __builtin_amdgcn_mfma_f32_32x32x2f32(Kt[(2 * s + hh) * kLd + c], Qr[s], St, 0, 0, 0);
-            dPt = __builtin_amdgcn_mfma_f32_32x32x2f32(Vt[(2 * s + hh) * kLd + c], Gr[s], dPt, 0, 0, 0);
-        }
-        f32x16 dS;
-        const bool tail = (kt + 1) * kBT > K;
-#pragma unroll
-        for (int t = 0; t < 16; ++t) {
-            const float p = tail && kt * kBT + acc_row(t, hh) >= K ? 0.f : exp2f(St[t] - Lq);  // slots past K: P = 0
-            dS[t] = p * (dPt[t] - Dq);
-        }
-        // dQ^T += K^T dS^T: k-step t contracts over keys r(t), r(t) + 4
-#pragma unroll
-        for (int t = 0; t < 16; ++t) {
-            const int kk = acc_row(t, hh);
-#pragma unroll
-            for (int a = 0; a < NB; ++a)
-                dQ[a] = __builtin_amdgcn_mfma_f32_32x32x2f32(Kt[(c + 32 * a) * kLd + kk], dS[t], dQ[a], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-
-    if (slot < own) {
-        float *row = dqkv + qrow * rs + head * D;
-#pragma unroll
-        for (int a = 0; a < NB; ++a)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int d = 32 * a + 8 * g + 4 * hh;
-                if (d < D)
-                    *reinterpret_cast<float4 *>(row + d) = make_float4(dQ[a][4 * g] * scale, dQ[a][4 * g + 1] * scale,
-                                                                       dQ[a][4 * g + 2] * scale, dQ[a][4 * g + 3] * scale);
-            }
-    }
-}
+    __device__ float *dv_row(int j) const { return dk_row(j) + C; }
+};
 
 // dK | dV of every borrowed slot: own part (already in dqkv) + borrowed part (stage), in that order.  One thread per
 // (patch, slot, 4 floats of the 2 C); a point is borrowed by at most one patch, so no two threads meet.
@@ -461,9 +248,6 @@ __global__ __launch_bounds__(256) void cluster_sum_kernel(long long clusters, in
 }  // namespace amav
 
 using namespace amav;
-
-static inline unsigned blocks_for(long long threads) { return (unsigned)((threads + 255) / 256); }
-static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 extern "C" int amav_subm_pair_sum_csr(int64_t n, int channels, const float *products, int64_t pair_lo, int64_t pair_count,
                                       const int32_t *src_start, const int32_t *src_pairs, int accumulate, float *out,
@@ -552,13 +336,13 @@ extern "C" int amav_patch_attention_backward(int64_t n, int patches, int max_pat
     const long long *ord = reinterpret_cast<const long long *>(order);
     const int4 *pd = reinterpret_cast<const int4 *>(patch_desc);
     const dim3 grid((unsigned)((max_patch + 127) / 128), (unsigned)heads, (unsigned)patches);
-    const long long row_heads = (long long)n * heads;
-#define AMAV_PA_BWD(D_)                                                                                              \
-    {                                                                                                                \
-        cloud_bwd::pa_delta_kernel<D_><<<blocks_for(row_heads * (D_ / 4)), 256, 0, stream>>>(row_heads, out, grad_out, delta); \
-        cloud_bwd::pa_dkdv_kernel<D_><<<grid, 256, 0, stream>>>(qkv, ord, pd, grad_out, lse, delta, grad_qkv, stage, C,    \
-                                                               heads, scale);                                       \
-        cloud_bwd::pa_dq_kernel<D_><<<grid, 256, 0, stream>>>(qkv, ord, pd, grad_out, lse, delta, grad_qkv, C, heads, scale); \
+    const cloud_bwd::PatchRows rows = {qkv, ord, pd, out, grad_out, lse, delta, grad_qkv, stage, (long long)n * heads,
+                                       C, heads, head_dim, 0, 0, 0};
+#define AMAV_PA_BWD(D_)                                                                                          \
+    {                                                                                                            \
+        attn_bwd::delta_kernel<D_><<<blocks_for(rows.row_heads * (D_ / 4)), 256, 0, stream>>>(rows);             \
+        attn_bwd::dkdv_kernel<D_><<<grid, 256, 0, stream>>>(rows, scale);                                        \
+        attn_bwd::dq_kernel<D_><<<grid, 256, 0, stream>>>(rows, scale);                                          \
     }
     if (head_dim == 16) AMAV_PA_BWD(16)
     else if (head_dim == 32) AMAV_PA_BWD(32)

@@ -104,7 +104,6 @@ static const Plan *plan_for(long long rows, int n, int k3, int index, size_t ws_
 // Not on the product path: a base for the fused forms (GEGLU gate in the epilogue, next operand split in the epilogue)
 // that a library GEMM cannot express.
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr int kBM = 128, kBN = 128, kBK = 32;
 constexpr int kStageBytes = 2 * (kBM + kBN) * kBK * 2;  // both parts of both operands: 32 KB

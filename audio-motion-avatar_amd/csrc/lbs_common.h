@@ -30,7 +30,6 @@ struct PoseSource {
     const float *mean;              // [J*3] added to the concatenated pose, or NULL
 };
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kMfmaWaves = 4;                    // frame tiles (of 32) per block
 constexpr int kMfmaKC = 32;                      // table rows per staged chunk
 constexpr int kMfmaChunk4 = kMfmaKC * 96 / 4;    // float4 per chunk (768)

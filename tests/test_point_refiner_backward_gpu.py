@@ -216,6 +216,24 @@ def test_patch_attention_backward_borrowed_keys_carry_both_contributions():
     assert torch.equal(changed, want), (int(changed.sum()), int(want.sum()))
 
 
+@pytest.mark.parametrize("S", [5, 33, 129])
+def test_patch_attention_backward_of_one_patch_is_the_dense_backward(S):
+    """One cloud of S points in one patch without a borrowed slot is self-attention over qkv[order].  Both entries run the
+    kernels of csrc/attention_backward_core.h, so from the same out, lse and d out they agree bit for bit.  S: below one
+    tile of 32, one row past a tile, one row past a workgroup's 128."""
+    ops, _ = _mods()
+    heads, dim = 2, 64
+    qkv, order, dout, desc, max_patch = _attention_case(heads, dim, [S], 512)
+    assert desc.tolist() == [[0, S, S, 0]] and max_patch == S
+    qkv, order, dout = qkv.cuda(), order.cuda(), dout.cuda()
+    out, lse = ops.patch_attention_lse(qkv, order, desc, heads, max_patch)
+    got = ops.patch_attention_backward(qkv, order, desc, out, lse, dout, heads, max_patch)
+    dense = ops.selfattn_backward(qkv[order][None], out[order][None], lse[order].t()[None], dout[order][None], heads)
+    want = torch.empty_like(got)
+    want[order] = dense[0]
+    assert torch.equal(got, want)
+
+
 # --------------------------------------------------------------------------------------------- 3. segment kernels
 def _segments(gen, C):
     sizes = [1, 2, 3, 4, 5, 6, 7, 8, 1, 8, 2, 5]

@@ -41,7 +41,7 @@ def kernel_split(fn, repeats):
     times = {}
     for e in prof.events():
         if e.device_type.name == "CUDA" and "attn_bwd" in e.name:
-            key = e.name.split("(")[0].split("::")[-1]
+            key = e.name.split("(")[0].split("<")[0].split("::")[-1]  # "void ns::kernel<64, ns::Rows>(...)" -> kernel
             times.setdefault(key, []).append(e.device_time / 1e3 if hasattr(e, "device_time") else e.cuda_time / 1e3)
     return {k: round(statistics.median(v), 4) for k, v in times.items()}
 
