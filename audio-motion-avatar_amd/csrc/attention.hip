@@ -575,19 +575,32 @@ __device__ __forceinline__ int fp16_scale_exp(float amax) {
     return max(-100, min(100, 14 - ilogbf(amax)));
 }
 
+__device__ __forceinline__ float absmax4(float m, const float4 a) {
+    return fmaxf(m, fmaxf(fmaxf(fabsf(a.x), fabsf(a.y)), fmaxf(fabsf(a.z), fabsf(a.w))));
+}
+
+// kCross (cross-attention): q has its own row count and row stride (q_rows, q_row_stride) and is swept on its own;
+// `rows` and `row_stride` are then those of k and v.  Self-attention reads the three tensors in one sweep.
+template <bool kCross>
 __global__ __launch_bounds__(256) void absmax_kernel(const float *__restrict__ q, const float *__restrict__ k,
                                                      const float *__restrict__ v, long long rows, int row4,
-                                                     long long row_stride, unsigned *__restrict__ hdr) {
+                                                     long long row_stride, unsigned *__restrict__ hdr,
+                                                     long long q_rows = 0, long long q_row_stride = 0) {
     float mq = 0.f, mk = 0.f, mv = 0.f;
-    const long long total = rows * row4;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const long long total = rows * row4, first = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long step = (long long)gridDim.x * blockDim.x;
+    if (kCross) {
+        for (long long i = first; i < q_rows * row4; i += step) {
+            const long long row = i / row4;
+            mq = absmax4(mq, *reinterpret_cast<const float4 *>(q + row * q_row_stride + (i - row * row4) * 4));
+        }
+    }
+    for (long long i = first; i < total; i += step) {
         const long long row = i / row4;
         const size_t off = row * row_stride + (i - row * row4) * 4;
-        const float4 a = *reinterpret_cast<const float4 *>(q + off), b = *reinterpret_cast<const float4 *>(k + off);
-        const float4 c = *reinterpret_cast<const float4 *>(v + off);
-        mq = fmaxf(mq, fmaxf(fmaxf(fabsf(a.x), fabsf(a.y)), fmaxf(fabsf(a.z), fabsf(a.w))));
-        mk = fmaxf(mk, fmaxf(fmaxf(fabsf(b.x), fabsf(b.y)), fmaxf(fabsf(b.z), fabsf(b.w))));
-        mv = fmaxf(mv, fmaxf(fmaxf(fabsf(c.x), fabsf(c.y)), fmaxf(fabsf(c.z), fabsf(c.w))));
+        if (!kCross) mq = absmax4(mq, *reinterpret_cast<const float4 *>(q + off));
+        mk = absmax4(mk, *reinterpret_cast<const float4 *>(k + off));
+        mv = absmax4(mv, *reinterpret_cast<const float4 *>(v + off));
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -689,13 +702,16 @@ __device__ unsigned long long amav_attn_stamp_totals[8];
 #define AMAV_STAMP_FLUSH
 #endif
 
+// Sq queries attend Sk keys: Sq indexes the query tiles and the q, out, lse and part rows, Sk everything that sweeps
+// the keys (Kp / Vt, the tiles, the tail mask).  Self-attention passes Sq = Sk, cross-attention (amav_crossattn_forward)
+// any pair; row_stride is q's (k and v went through split_kv_f16_kernel with theirs).
 // kLse (amav_selfattn_forward_lse): with one key slice, the row's log-sum-exp also goes to lse [B, H, S] in natural
 // units, ln 2 (m + log2 l - 14) -- m and l are in the log2 domain and l carries the 2^14 of P'; with nsplit > 1
 // combine_kernel<., true> writes it.
 template <bool kLse = false>
 __global__ __launch_bounds__(256, 3) void selfattn_f16_kernel(const float *__restrict__ q, const _Float16 *__restrict__ Kp,
                                                            const _Float16 *__restrict__ Vt, float *__restrict__ out,
-                                                           int S, int Spad, long long row_stride,
+                                                           int Sq, int S, int Spad, long long row_stride,
                                                            long long out_row_stride, float scale_log2e, int nsplit,
                                                            float *__restrict__ part, const unsigned *__restrict__ hdr,
                                                            Magnitudes given, int H, int B, int q_tiles,
@@ -718,7 +734,7 @@ __global__ __launch_bounds__(256, 3) void selfattn_f16_kernel(const float *__res
 
     f16x8 Q1[4], Q2[4];
     {
-        const float *qrow = q + ((size_t)b * S + min(q0 + r, S - 1)) * row_stride + head * kD;
+        const float *qrow = q + ((size_t)b * Sq + min(q0 + r, Sq - 1)) * row_stride + head * kD;
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             const float4 lo = *reinterpret_cast<const float4 *>(qrow + 16 * s + 8 * hh);
@@ -863,8 +879,8 @@ __global__ __launch_bounds__(256, 3) void selfattn_f16_kernel(const float *__res
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);  // carries the 2^14 of P'
     const float unv = ldexpf(1.0f, -ev);
     if (nsplit > 1) {  // partial (O 2^14, m, l 2^14): the common factor cancels in combine_kernel
-        if (q0 + r < S) {
-            float *prow = part + ((((size_t)split * B + b) * H + head) * S + q0 + r) * (kD + 2);
+        if (q0 + r < Sq) {
+            float *prow = part + ((((size_t)split * B + b) * H + head) * Sq + q0 + r) * (kD + 2);
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int d = 8 * g + 4 * hh;
@@ -876,9 +892,9 @@ __global__ __launch_bounds__(256, 3) void selfattn_f16_kernel(const float *__res
         return;
     }
     const float inv = unv / l_tot;
-    if (q0 + r < S) {
-        if (kLse && hh == 0) lse[bh * S + q0 + r] = kLn2 * (m_run + log2f(l_tot) - 14.0f);
-        float *orow = out + ((size_t)b * S + q0 + r) * out_row_stride + head * kD;
+    if (q0 + r < Sq) {
+        if (kLse && hh == 0) lse[bh * Sq + q0 + r] = kLn2 * (m_run + log2f(l_tot) - 14.0f);
+        float *orow = out + ((size_t)b * Sq + q0 + r) * out_row_stride + head * kD;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const int d = 8 * g + 4 * hh;
@@ -892,11 +908,11 @@ __global__ __launch_bounds__(256, 3) void selfattn_f16_kernel(const float *__res
 
 // Key-range split that best balances the (q-tile, head, batch) workgroups over the chip: a CU runs two workgroups
 // at a time (LDS / registers), so the kernel lasts ceil(blocks * s / CUs) slices of 1/s of the key sweep.
-static int choose_split(int B, int S, int H, int num_cus) {
+static int choose_split(int B, int Sq, int Sk, int H, int num_cus) {
     static const int forced = getenv("AMAV_ATTN_SPLIT") ? atoi(getenv("AMAV_ATTN_SPLIT")) : 0;  // tuning aid
-    if (forced >= 1 && forced <= 16 && ((S + kBN - 1) / kBN) / forced >= 1) return forced;
-    const long long blocks = (long long)((S + kBM - 1) / kBM) * H * B;
-    const int ntiles = (S + kBN - 1) / kBN;
+    if (forced >= 1 && forced <= 16 && ((Sk + kBN - 1) / kBN) / forced >= 1) return forced;
+    const long long blocks = (long long)((Sq + kBM - 1) / kBM) * H * B;
+    const int ntiles = (Sk + kBN - 1) / kBN;
     int best = 1;
     double best_cost = (double)((blocks + num_cus - 1) / num_cus);
     for (int s = 2; s <= 8; ++s) {
@@ -942,15 +958,17 @@ static size_t attn_partial_bytes(int B, int S, int H, int ns) {
     return ns > 1 ? align_up((size_t)ns * B * H * S * (attn::kD + 2) * sizeof(float), 256) : 256;
 }
 static size_t attn_spad(int S) { return ((size_t)S + attn::kBN - 1) / attn::kBN * attn::kBN; }
+// [header] + K parts [parts][B H][S][64] + V^T parts [parts][B H][64][S_pad], 2-byte elements (S: the keys)
+static size_t attn_split_bytes(int B, int S, int H, size_t parts) {
+    return kAttnHeaderBytes + align_up(parts * B * H * S * attn::kD * 2, 256) +
+           align_up(parts * B * H * attn::kD * attn_spad(S) * 2, 256);
+}
 
 extern "C" size_t amav_selfattn_workspace_bytes(int B, int S, int H, int D) {
     if (B <= 0 || S <= 0 || H <= 0 || D != attn::kD) return 0;
-    const int ns = attn::choose_split(B, S, H, attn_num_cus());
+    const int ns = attn::choose_split(B, S, S, H, attn_num_cus());
     size_t need = attn_partial_bytes(B, S, H, ns);
-    const size_t parts = attn_variant() == 2 ? 2 : 3;
-    if (attn_use_split())  // [header] + K parts [parts][B H][S][64] + V^T parts [parts][B H][64][S_pad], 2-byte elements
-        need += kAttnHeaderBytes + align_up(parts * B * H * S * attn::kD * 2, 256) +
-                align_up(parts * B * H * attn::kD * attn_spad(S) * 2, 256);
+    if (attn_use_split()) need += attn_split_bytes(B, S, H, attn_variant() == 2 ? 2 : 3);
     return need;
 }
 
@@ -995,6 +1013,50 @@ extern "C" int amav_selfattn_forward_lse(int B, int S, int H, int D, const float
                                  lse, workspace, workspace_bytes, stream_);
 }
 
+// The fp16 x 2 kernels of one call, Sq queries over Sk keys, on a workspace laid out as [partial states of `ns` key
+// slices | header | K parts | V^T parts]: the magnitude pre-pass (unless the caller proved bounds: `proven`), the K / V
+// split and the attention kernel.  kCross: q has its own row count and stride.  The caller merges the slices
+// (combine_kernel) when ns > 1.  false: the header could not be cleared.
+template <bool kCross>
+static bool launch_f16(int B, int Sq, int Sk, int H, const float *q, int64_t q_row_stride, const float *k, const float *v,
+                       int64_t kv_row_stride, float *out, int64_t out_row_stride, float sl2, const attn::Magnitudes *proven,
+                       float *lse, int ns, char *ws, hipStream_t stream) {
+    const int Spad = (int)attn_spad(Sk);
+    unsigned *hdr = reinterpret_cast<unsigned *>(ws + attn_partial_bytes(B, Sq, H, ns));
+    char *kp = reinterpret_cast<char *>(hdr) + kAttnHeaderBytes;
+    char *vt = kp + align_up((size_t)2 * B * H * Sk * attn::kD * 2, 256);
+    const dim3 kv_grid((unsigned)(Spad / attn::kBN), H, B);
+    const int q_tiles = (Sq + attn::kBM - 1) / attn::kBM;
+    const long long rounds = ((long long)ns * H * B + 7) / 8;  // 8 slices (one per XCD) per round
+    const unsigned main_grid = (unsigned)(rounds * 8 * q_tiles);
+    attn::Magnitudes given = {0.f, 0.f, 0.f};
+    if (proven) {
+        given = *proven;
+        hdr = nullptr;  // the kernels scale from `given`
+    } else {            // measure max |q|, |k|, |v|
+        if (zero_async(hdr, 16, stream) != hipSuccess) return false;
+        const int row4 = H * attn::kD / 4;
+        const long long rows = (long long)B * Sk, q_rows = (long long)B * Sq;
+        const long long quads = std::max(rows, q_rows) * row4;
+        const unsigned blocks = (unsigned)std::min<long long>((quads + 255) / 256, 512);
+        if (kCross)
+            attn::absmax_kernel<true><<<blocks, 256, 0, stream>>>(q, k, v, rows, row4, kv_row_stride, hdr, q_rows, q_row_stride);
+        else
+            attn::absmax_kernel<false><<<blocks, 256, 0, stream>>>(q, k, v, rows, row4, kv_row_stride, hdr);
+    }
+    attn::split_kv_f16_kernel<<<kv_grid, 256, 0, stream>>>(k, v, Sk, Spad, kv_row_stride, hdr, given,
+                                                          reinterpret_cast<_Float16 *>(kp), reinterpret_cast<_Float16 *>(vt));
+    if (lse)
+        attn::selfattn_f16_kernel<true><<<main_grid, 256, 0, stream>>>(
+            q, reinterpret_cast<const _Float16 *>(kp), reinterpret_cast<const _Float16 *>(vt), out, Sq, Sk, Spad,
+            q_row_stride, out_row_stride, sl2, ns, reinterpret_cast<float *>(ws), hdr, given, H, B, q_tiles, lse);
+    else
+        attn::selfattn_f16_kernel<false><<<main_grid, 256, 0, stream>>>(
+            q, reinterpret_cast<const _Float16 *>(kp), reinterpret_cast<const _Float16 *>(vt), out, Sq, Sk, Spad,
+            q_row_stride, out_row_stride, sl2, ns, reinterpret_cast<float *>(ws), hdr, given, H, B, q_tiles);
+    return true;
+}
+
 static int selfattn_forward_impl(int B, int S, int H, int D, const float *q, const float *k, const float *v,
                                  int64_t row_stride, float *out, int64_t out_row_stride, float scale, float q_bound,
                                  float k_bound, float v_bound, void *out_split, int split_scale_exp, float *lse,
@@ -1017,7 +1079,7 @@ static int selfattn_forward_impl(int B, int S, int H, int D, const float *q, con
                    reinterpret_cast<uintptr_t>(out)) & 15) == 0,
                  "amav_selfattn_forward: q/k/v/out must be 16-byte aligned");
     AMAV_REQUIRE(H <= 65535 && B <= 65535, "amav_selfattn_forward: grid too large");
-    const int ns = attn::choose_split(B, S, H, attn_num_cus());
+    const int ns = attn::choose_split(B, S, S, H, attn_num_cus());
     const bool split = attn_use_split();
     const size_t need = split || ns > 1 ? amav_selfattn_workspace_bytes(B, S, H, D) : 0;
     if (need && (workspace == nullptr || workspace_bytes < need))
@@ -1038,26 +1100,9 @@ static int selfattn_forward_impl(int B, int S, int H, int D, const float *q, con
         const float sl2 = scale * 1.4426950408889634f;
         if (attn_variant() == 2) {
             const attn::Magnitudes given = {q_bound, k_bound, v_bound};
-            if (bounded) {
-                hdr = nullptr;  // the kernels scale from `given`
-            } else {            // measure max |q|, |k|, |v|
-                AMAV_REQUIRE(zero_async(hdr, 16, stream) == hipSuccess, "amav_selfattn_forward: header clear failed");
-                const long long rows = (long long)B * S;
-                const long long quads = rows * (H * attn::kD / 4);
-                attn::absmax_kernel<<<(unsigned)std::min<long long>((quads + 255) / 256, 512), 256, 0, stream>>>(
-                    q, k, v, rows, H * attn::kD / 4, row_stride, hdr);
-            }
-            attn::split_kv_f16_kernel<<<kv_grid, 256, 0, stream>>>(k, v, S, Spad, row_stride, hdr, given,
-                                                                  reinterpret_cast<_Float16 *>(kp),
-                                                                  reinterpret_cast<_Float16 *>(vt));
-            if (lse)
-                attn::selfattn_f16_kernel<true><<<main_grid, 256, 0, stream>>>(
-                    q, reinterpret_cast<const _Float16 *>(kp), reinterpret_cast<const _Float16 *>(vt), out, S, Spad,
-                    row_stride, out_row_stride, sl2, ns, static_cast<float *>(workspace), hdr, given, H, B, q_tiles, lse);
-            else
-                attn::selfattn_f16_kernel<false><<<main_grid, 256, 0, stream>>>(
-                    q, reinterpret_cast<const _Float16 *>(kp), reinterpret_cast<const _Float16 *>(vt), out, S, Spad,
-                    row_stride, out_row_stride, sl2, ns, static_cast<float *>(workspace), hdr, given, H, B, q_tiles);
+            if (!launch_f16<false>(B, S, S, H, q, row_stride, k, v, row_stride, out, out_row_stride, sl2, bounded ? &given : nullptr,
+                                   lse, ns, ws, stream))
+                return fail(AMAV_ERR_INVALID_ARG, "amav_selfattn_forward: header clear failed");
         } else {
             attn::split_kv_kernel<<<kv_grid, 256, 0, stream>>>(k, v, S, Spad, row_stride, reinterpret_cast<__bf16 *>(kp),
                                                               reinterpret_cast<__bf16 *>(vt));
@@ -1086,6 +1131,56 @@ static int selfattn_forward_impl(int B, int S, int H, int D, const float *q, con
         return amav_split_operand((int64_t)B * S, H * D, out, out_row_stride, 0, AMAV_SPLIT_FP16X2, split_scale_exp, out_split, stream_);
     }
     return check_launch("amav_selfattn_forward");
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Cross-attention of the stage-1 encoder (fusion network: 3152 queries, SMPL-X predictor: 80 queries, over the 4096
+// Sapiens tokens; 8 heads x 64): the fp16 x 2 kernels above with Sq != Sk, whatever the attn option selects -- the
+// bf16 x 3 and fp32 kernels are built for self-attention only.
+extern "C" int amav_crossattn_key_split(int B, int Sq, int Sk, int H) {
+    if (B <= 0 || Sq <= 0 || Sk <= 0 || H <= 0) return 0;
+    return attn::choose_split(B, Sq, Sk, H, attn_num_cus());
+}
+
+extern "C" size_t amav_crossattn_workspace_bytes(int B, int Sq, int Sk, int H, int D) {
+    if (B <= 0 || Sq <= 0 || Sk <= 0 || H <= 0 || D != attn::kD) return 0;
+    return attn_partial_bytes(B, Sq, H, amav_crossattn_key_split(B, Sq, Sk, H)) + attn_split_bytes(B, Sk, H, 2);
+}
+
+extern "C" int amav_crossattn_forward(int B, int Sq, int Sk, int H, int D, const float *q, int64_t q_row_stride,
+                                      const float *k, const float *v, int64_t kv_row_stride, float *out,
+                                      int64_t out_row_stride, float scale, float *lse, void *workspace,
+                                      size_t workspace_bytes, void *stream_) {
+    AMAV_REQUIRE(B > 0 && Sq > 0 && Sk > 0 && H > 0, "amav_crossattn_forward: bad sizes B=%d Sq=%d Sk=%d H=%d", B, Sq, Sk, H);
+    AMAV_REQUIRE(D == attn::kD, "amav_crossattn_forward: head_dim %d (only %d is built)", D, attn::kD);
+    AMAV_REQUIRE(q && k && v && out, "amav_crossattn_forward: NULL pointer");
+    const int64_t hd = (int64_t)H * D;
+    AMAV_REQUIRE(q_row_stride >= hd && kv_row_stride >= hd && out_row_stride >= hd && q_row_stride % 4 == 0 &&
+                     kv_row_stride % 4 == 0 && out_row_stride % 4 == 0,
+                 "amav_crossattn_forward: row strides must be multiples of 4 floats and >= H*D");
+    AMAV_REQUIRE(aligned16(q, k, v, out) && (reinterpret_cast<uintptr_t>(lse) & 3) == 0,
+                 "amav_crossattn_forward: q/k/v/out must be 16-byte aligned, lse 4-byte aligned");
+    AMAV_REQUIRE(std::isfinite(scale), "amav_crossattn_forward: scale must be finite");
+    AMAV_REQUIRE(H <= 65535 && B <= 65535, "amav_crossattn_forward: grid too large");
+    const int ns = amav_crossattn_key_split(B, Sq, Sk, H);
+    const size_t need = amav_crossattn_workspace_bytes(B, Sq, Sk, H, D);
+    if (workspace == nullptr || workspace_bytes < need)
+        return fail(AMAV_ERR_WORKSPACE, "amav_crossattn_forward: workspace %zu < required %zu", workspace_bytes, need);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!launch_f16<true>(B, Sq, Sk, H, q, q_row_stride, k, v, kv_row_stride, out, out_row_stride,
+                          scale * 1.4426950408889634f, nullptr, lse, ns, static_cast<char *>(workspace), stream))
+        return fail(AMAV_ERR_INVALID_ARG, "amav_crossattn_forward: header clear failed");
+    if (ns > 1) {
+        const unsigned blocks = blocks_for((long long)B * H * Sq * 16);
+        if (lse)
+            attn::combine_kernel<false, true><<<blocks, 256, 0, stream>>>(static_cast<const float *>(workspace), out, B, H, Sq,
+                                                                         ns, out_row_stride, nullptr, 1.0f,
+                                                                         attn::LseOut<true>{lse});
+        else
+            attn::combine_kernel<false><<<blocks, 256, 0, stream>>>(static_cast<const float *>(workspace), out, B, H, Sq, ns,
+                                                                   out_row_stride, nullptr, 1.0f);
+    }
+    return check_launch("amav_crossattn_forward");
 }
 
 

@@ -1,5 +1,5 @@
-// The flash-attention-2 backward that the audio transformer's self-attention (attention_backward.hip) and the point
-// refiner's patch attention (cloud_backward.hip) share; DESIGN.md section 4.10.  Given the forward's inputs, its output
+// The flash-attention-2 backward that the audio transformer's self-attention, the stage-1 encoder's cross-attention
+// (attention_backward.hip) and the point refiner's patch attention (cloud_backward.hip) share; DESIGN.md section 4.10.  Given the forward's inputs, its output
 // O, the row log-sum-exp L and dO = dLoss/dO, the gradients
 //     P = exp(scale Q K^T - L),  dP = dO V^T,  delta_i = rowsum(dO_i * O_i),  dS = P * (dP - delta)
 //     dV = P^T dO,  dK = scale dS^T Q,  dQ = scale dS K
@@ -23,7 +23,8 @@
 //     void delta_io(r, out, dout, delta)       the D floats of O and dO of pair r and where its delta is written
 //     void bind(blockIdx.y, blockIdx.z)        narrows the struct to one workgroup's head and batch item / patch; the
 //                                              calls below follow it and take a slot of that item
-//     int keys(), queries()                    key slots and query slots (query slot i is also key slot i)
+//     int keys(), queries()                    key slots and query slots (patch attention: query slot i is also key slot
+//                                              i; cross-attention: two row sets of any two sizes)
 //     const float *q_row(i), dout_row(i), k_row(j), v_row(j)     the D floats of the bound head
 //     float lse_at(i), delta_at(i)
 //     float *dk_row(j), dv_row(j), dq_row(i)   destinations
@@ -204,7 +205,7 @@ __global__ __launch_bounds__(256) void dq_kernel(Rows rows, float scale) {
     const int nk = rows.keys(), nq = rows.queries();
     if ((int)blockIdx.x * kBW >= nq) return;  // uniform over the workgroup
     const int query = blockIdx.x * kBW + wave * 32 + c;
-    const int qc = min(query, nk - 1);  // query slot i is key slot i, so the row exists; past nq its result is dropped
+    const int qc = min(query, nq - 1);  // a lane past the last query works on the last query's row; its result is dropped
 
     // B operands of S^T = K Q^T (Q pre-scaled to the log2 domain) and dP^T = V dO^T
     float Qr[D / 2], Gr[D / 2];

@@ -1428,6 +1428,116 @@ def selfattn_differentiable(qkv, heads, scale=None):
     return _SelfAttn.apply(qkv, int(heads), scale)
 
 
+def _rows(t, name, B=None, S=None, min_width=None, width=None):
+    """[B,S,C] fp32 device tensor with unit inner stride and dense batch stride, of the given sizes where given."""
+    _need(t, name)
+    if (t.dim() != 3 or t.stride(2) != 1 or t.stride(0) != t.shape[1] * t.stride(1)
+            or (B is not None and t.shape[0] != B) or (S is not None and t.shape[1] != S)
+            or (width is not None and t.shape[2] != width) or (min_width is not None and t.shape[2] < min_width)):
+        want = width if width is not None else f">={min_width}" if min_width is not None else "C"
+        raise AmavError(f"{name}: need [B,S,C] = [{B or 'B'},{S or 'S'},{want}] with unit inner stride and dense batch "
+                        f"stride, got {tuple(t.shape)} strides {tuple(t.stride())}")
+    return t
+
+
+def _kv_views(kv, heads):
+    """[B,Sk,2*H*D] fused k | v projection output -> (k, v) views sharing its row stride."""
+    _rows(kv, "kv")
+    if kv.shape[2] % (2 * heads):
+        raise AmavError(f"kv: need [B,Sk,2*H*D], got {tuple(kv.shape)} for {heads} heads")
+    HD = kv.shape[2] // 2
+    return kv[..., :HD], kv[..., HD:]
+
+
+def _crossattn(q, k, v, heads, scale, want_lse):
+    _rows(q, "q")
+    B, Sq, HD = q.shape
+    Sk = _rows(k, "k", B=B, width=HD).shape[1]
+    _rows(v, "v", B=B, S=Sk, width=HD)
+    if HD % heads or k.stride(1) != v.stride(1):
+        raise AmavError("crossattn: k and v must share shape and row stride, and H must divide the row width")
+    D = HD // heads
+    out = torch.empty(B, Sq, HD, device=q.device)
+    lse = torch.empty(B, heads, Sq, device=q.device) if want_lse else None
+    ws = _scratch("amav_crossattn_workspace_bytes", q.device, B, Sq, Sk, heads, D,
+                  rejected=f"B={B} Sq={Sq} Sk={Sk} H={heads} D={D}")
+    _call("amav_crossattn_forward", B, Sq, Sk, heads, D, q.data_ptr(), q.stride(1), k.data_ptr(), v.data_ptr(), k.stride(1),
+          out.data_ptr(), HD, float(scale if scale is not None else D ** -0.5), lse.data_ptr() if want_lse else None,
+          ws.data_ptr(), ws.numel())
+    return out, lse
+
+
+def crossattn(q, k, v, heads, scale=None):
+    """softmax(q k^T * scale) v for q [B,Sq,H*D] and k, v [B,Sk,H*D] sharing shape and row stride (e.g. the halves of a
+    fused k | v projection), any Sq and Sk, D = 64 -> [B,Sq,H*D] (amav_crossattn_forward).  Always the fp16 x 2 kernels,
+    whatever set_option("attn", ...) selects for self-attention."""
+    return _crossattn(q, k, v, heads, scale, False)[0]
+
+
+def crossattn_lse(q, kv, heads, scale=None):
+    """crossattn over a fused kv [B,Sk,2*H*D] (k | v, read in place) -> (out [B,Sq,H*D], lse [B,H,Sq]), lse the row
+    log-sum-exp in natural units that crossattn_backward needs.  `out` equals crossattn()'s bit for bit."""
+    return _crossattn(q, *_kv_views(kv, heads), heads, scale, True)
+
+
+def crossattn_backward(q, kv, out, lse, grad_out, heads, scale=None, grad_q=None, grad_kv=None):
+    """amav_crossattn_backward: (dq [B,Sq,H*D], dkv [B,Sk,2*H*D] = dk | dv) given the forward's out and lse
+    (crossattn_lse) and grad_out = dLoss/d out.  grad_q / grad_kv: optional [B,Sq,>=H*D] / [B,Sk,>=2*H*D] destination
+    views (their first H*D / 2*H*D columns are written)."""
+    k, v = _kv_views(kv, heads)
+    B, Sk, HD = k.shape
+    Sq = _rows(q, "q", B=B, width=HD).shape[1]
+    D = HD // heads
+    _rows(out, "out", B, Sq, width=HD), _rows(grad_out, "grad_out", B, Sq, width=HD)
+    lse = _contig(lse, "lse")
+    if tuple(lse.shape) != (B, heads, Sq):
+        raise AmavError(f"lse: need [B,H,Sq] = {(B, heads, Sq)}, got {tuple(lse.shape)}")
+    if grad_q is None:
+        grad_q = torch.empty(B, Sq, HD, device=q.device)
+    if grad_kv is None:
+        grad_kv = torch.empty(B, Sk, 2 * HD, device=q.device)
+    _rows(grad_q, "grad_q", B, Sq, min_width=HD), _rows(grad_kv, "grad_kv", B, Sk, min_width=2 * HD)
+    ws = _scratch("amav_crossattn_backward_workspace_bytes", q.device, B, Sq, heads, D,
+                  rejected=f"B={B} Sq={Sq} H={heads} D={D}")
+    _call("amav_crossattn_backward", B, Sq, Sk, heads, D, q.data_ptr(), q.stride(1), k.data_ptr(), v.data_ptr(),
+          kv.stride(1), out.data_ptr(), out.stride(1), lse.data_ptr(), grad_out.data_ptr(), grad_out.stride(1),
+          grad_q.data_ptr(), grad_q.stride(1), grad_kv.data_ptr(), grad_kv.stride(1),
+          float(scale if scale is not None else D ** -0.5), ws.data_ptr(), ws.numel())
+    return grad_q, grad_kv
+
+
+def _launchable(t):
+    """t, or a contiguous copy where its layout is not one the attention entry points read in place."""
+    if t.stride(2) != 1 or t.stride(0) != t.shape[1] * t.stride(1) or t.stride(1) % 4 or t.data_ptr() % 16:
+        return t.contiguous()
+    return t
+
+
+class _CrossAttn(torch.autograd.Function):
+    """crossattn_lse with amav_crossattn_backward as the backward; q, kv, the output and the row log-sum-exp are kept."""
+
+    @staticmethod
+    def forward(ctx, q, kv, heads, scale):
+        out, lse = crossattn_lse(q, kv, heads, scale)
+        ctx.heads, ctx.scale = heads, scale
+        ctx.save_for_backward(q, kv, out, lse)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        q, kv, out, lse = ctx.saved_tensors
+        dq, dkv = crossattn_backward(q, kv, out, lse, _launchable(grad_out.float()), ctx.heads, ctx.scale)
+        return dq, dkv, None, None
+
+
+def crossattn_differentiable(q, kv, heads, scale=None):
+    """softmax(q k^T * scale) v as a torch.autograd.Function over q [B,Sq,H*D] and a fused kv [B,Sk,2*H*D] (k | v along
+    the last axis, D = 64) -> [B,Sq,H*D]; the backward returns dq and d kv in the same fused layout
+    (amav_crossattn_backward), so the gradient of a fused to_k / to_v weight is one GEMM."""
+    return _CrossAttn.apply(_launchable(q), _launchable(kv), int(heads), scale)
+
+
 _GEMM_WS = {}
 
 

@@ -9,9 +9,14 @@ attention_bias=False, cross-attention to the audio token; triplane_audio_net.py:
 What runs where:
   * self-attention (attn1, S = 6304 tokens, 8 x 64): the hand-written MFMA flash kernel (csrc/attention.hip),
     fed by ONE fused q/k/v projection GEMM whose output it reads in place through a row stride;
-  * cross-attention (attn2): the context is a single audio token (triplane_audio_net.py:211), so softmax over one
-    key is exactly 1 and the layer is to_out(to_v(audio)) broadcast over the tokens -- computed exactly that way
+  * cross-attention (attn2) to one key: the context is a single audio token (triplane_audio_net.py:211), so softmax
+    over one key is exactly 1 and the layer is to_out(to_v(audio)) broadcast over the tokens -- computed exactly that way
     (two [1,768]x[768,512] products instead of 6304 x 512 x 2 of wasted Q/K work);
+  * cross-attention to many keys (stage 1: the fusion network's 3152 and the SMPL-X predictor's 80 queries over the 4096
+    Sapiens tokens): the same fp16 x 2 MFMA kernels with separate query and key counts (ops.crossattn, always fp16 x 2)
+    over q and ONE fused k | v projection, with the HIP backward under autograd (ops.crossattn_differentiable), for HIP
+    fp32 tensors, dim_head 64 and bias-free to_q / to_k / to_v.  Everything else (CPU, other dtypes or head dims,
+    biases) and AMAV_CROSS_ATTN=library (read per call) stay on the library's fused attention;
   * the four big projections of a block (q/k/v, to_out, both feed-forward layers) at inference: fp32-equivalent
     products on the low-precision matrix pipe -- both operands split into parts whose partial products are ONE library
     GEMM with fp32 accumulation over the parts concatenated along K (csrc/attention.hip, split_operand kernels):
@@ -147,7 +152,7 @@ class Attention(nn.Module):
         self.to_k = nn.Linear(ctx, inner, bias=bias)
         self.to_v = nn.Linear(ctx, inner, bias=bias)
         self.to_out = nn.ModuleList([nn.Linear(inner, query_dim), nn.Dropout(dropout)])
-        self._qkv = None
+        self._qkv = self._kv = None
 
     def _qkv_weight(self):
         ws = (self.to_q.weight, self.to_k.weight, self.to_v.weight)
@@ -155,6 +160,20 @@ class Attention(nn.Module):
         if self._qkv is None or self._qkv[0] != version:
             self._qkv = (version, torch.cat([w.detach() for w in ws], dim=0).contiguous())
         return self._qkv[1]
+
+    def _kv_weight(self):
+        ws = (self.to_k.weight, self.to_v.weight)
+        version = tuple((_version_of(w), w.data_ptr()) for w in ws)
+        if self._kv is None or self._kv[0] != version:
+            self._kv = (version, torch.cat([w.detach() for w in ws], dim=0).contiguous())
+        return self._kv[1]
+
+    def _cross_hip(self, hidden_states, context):
+        """Whether many-key cross-attention runs on the HIP kernels (module docstring)."""
+        return (hidden_states.is_cuda and context.is_cuda and hidden_states.dtype == context.dtype == torch.float32
+                and self.to_q.weight.dtype == torch.float32 and self.dim_head == 64
+                and self.to_q.bias is None and self.to_k.bias is None and self.to_v.bias is None
+                and os.environ.get("AMAV_CROSS_ATTN", "hip") != "library")
 
     def attend(self, qkv, out_bias=True, out_exp=None, bounds=None):
         """qkv [B,S,3*inner] (the fused projection's output, read in place) -> to_out(softmax(q k^T / sqrt(d)) v);
@@ -181,9 +200,10 @@ class Attention(nn.Module):
             qkv = linear(hidden_states, self._qkv_weight())            # [B,S,3*inner], one GEMM
             return self.attend(qkv)
         if encoder_hidden_states.shape[1] != 1:
-            # Many context tokens (stage 1: 4096 Sapiens tokens, triplane_net.py:104-113,320-329): a SURVEY 8(f)
-            # next-row, on the library's fused attention (the MFMA kernel of csrc/attention.hip is the self-attention
-            # of the audio net: equal query / key lengths).
+            # Many context tokens (stage 1: 4096 Sapiens tokens, triplane_net.py:104-113,320-329): the fp16 x 2 MFMA
+            # kernels with separate query and key counts (ops.crossattn), the library's fused attention elsewhere
+            if self._cross_hip(hidden_states, encoder_hidden_states):
+                return self._forward_cross(hidden_states, encoder_hidden_states)
             B, S, _ = hidden_states.shape
             split = lambda t: t.view(B, t.shape[1], self.heads, self.dim_head).transpose(1, 2)
             q = split(self.to_q(hidden_states))
@@ -193,6 +213,21 @@ class Attention(nn.Module):
         # one key: softmax == 1, so the output is to_out(to_v(context)) for every query
         ctx = self.to_out[0](self.to_v(encoder_hidden_states))        # [B,1,query_dim]
         return ctx.expand(-1, hidden_states.shape[1], -1)
+
+    def _forward_cross(self, hidden_states, context):
+        """Cross-attention to many keys on the GPU in fp32: k | v from one projection over the concatenated to_k / to_v
+        weights, read in place by the kernels.  Without grad the projections go through `linear`; under autograd they are
+        fp32 F.linear and the attention is ops.crossattn_differentiable, whose backward returns dq and a fused dk | dv."""
+        out_w, out_b = self.to_out[0].weight, self.to_out[0].bias
+        if torch.is_grad_enabled() and (hidden_states.requires_grad or context.requires_grad or any(
+                w.requires_grad for w in (self.to_q.weight, self.to_k.weight, self.to_v.weight, out_w, out_b))):
+            q = F.linear(hidden_states, self.to_q.weight)
+            kv = F.linear(context, torch.cat([self.to_k.weight, self.to_v.weight], dim=0))   # [B,Sk,2*inner]
+            return F.linear(ops.crossattn_differentiable(q, kv, self.heads, self.dim_head ** -0.5), out_w, out_b)
+        i = self.inner_dim
+        q = linear(hidden_states, self.to_q.weight)
+        kv = linear(context, self._kv_weight())
+        return linear(ops.crossattn(q, kv[..., :i], kv[..., i:], self.heads), out_w, out_b)
 
     def _forward_differentiable(self, hidden_states):
         """Self-attention under autograd: one fp32 F.linear over the concatenated q/k/v weights (so that gradients reach

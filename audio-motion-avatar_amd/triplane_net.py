@@ -15,7 +15,8 @@ correctness and determinism, on library kernels except where the reference's own
   * `points_projection` (pytorch3d point rasterizer + an index_put with duplicate indices: which pixel a point
     receives is undefined) -> z-buffer kernel with a fixed rule: the last pixel in (y, x) order that the point wins
     (what a sequential index_put does);
-  * cross-attention to the 4096 image tokens -> the library's fused attention; self-attention -> the MFMA kernel.
+  * cross-attention to the 4096 image tokens and self-attention -> the fp16 x 2 MFMA kernels of csrc/attention.hip,
+    forward and backward (transformer.py; AMAV_CROSS_ATTN=library keeps the library's fused attention for the former).
 
 `densify_smplx_verts` here means "append the face centres" (:266-272), not the Renderer's subdivision.
 """

@@ -576,6 +576,40 @@ int amav_selfattn_backward(int batch, int seq_len, int heads, int head_dim, cons
                            const float *lse_dev, const float *dout_dev, int64_t dout_row_stride, float *dqkv_dev,
                            int64_t dqkv_row_stride, float scale, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Cross-attention of the stage-1 encoder (diffusers Attention with encoder_hidden_states, as reached from
+ * BasicTransformerBlock.attn2: the fusion network's 3*32^2 + 80 = 3152 queries and the SMPL-X predictor's 80 queries
+ * over the 4096 Sapiens tokens, 8 heads x 64): softmax(Q K^T * scale) V, fp32 in/out, no mask, any q_len and kv_len.
+ * q [B, q_len, H*D] with row stride q_row_stride; k, v [B, kv_len, H*D] sharing kv_row_stride (so the halves of a fused
+ * k | v projection output can be passed without a copy); out [B, q_len, H*D] with out_row_stride; D must be 64.
+ *
+ * Always the fp16 x 2 kernels of the self-attention above (two fp16 parts per operand, three partial products,
+ * operands pre-scaled by powers of two from the measured max |q| over the B*q_len rows and max |k|, |v| over the
+ * B*kv_len rows), WHATEVER the attn option / AMAV_ATTN selects: the bf16 x 3 and fp32 kernels are self-attention only.
+ * With q_len = kv_len and one row stride the results equal amav_selfattn_forward_lse's bit for bit.
+ * lse_dev: NULL, or the row log-sum-exp [B, H, q_len] in natural units, which amav_crossattn_backward needs.
+ * amav_crossattn_key_split: the number of key slices a call takes (>= 1; 0 = bad sizes); above 1 the slices' partial
+ * softmax states pass through the workspace.  workspace: amav_crossattn_workspace_bytes bytes (0 = bad sizes).
+ * Pointers 16-byte aligned (lse 4), row strides multiples of 4 floats and >= H*D, scale finite, H, B <= 65535. */
+size_t amav_crossattn_workspace_bytes(int batch, int q_len, int kv_len, int heads, int head_dim);
+int amav_crossattn_key_split(int batch, int q_len, int kv_len, int heads);
+int amav_crossattn_forward(int batch, int q_len, int kv_len, int heads, int head_dim, const float *q_dev,
+                           int64_t q_row_stride, const float *k_dev, const float *v_dev, int64_t kv_row_stride,
+                           float *out_dev, int64_t out_row_stride, float scale, float *lse_dev, void *workspace,
+                           size_t workspace_bytes, void *stream);
+/* Cross-attention backward (the flash-attention-2 form of amav_selfattn_backward with two row sets): from the forward's
+ * q, k, v, out_dev, lse_dev and dout_dev = dLoss/d out ([B, q_len, H*D]) writes dq into dq_dev [B, q_len, >= H*D] and
+ * dk | dv into dkv_dev [B, kv_len, >= 2*H*D] (the gradient of a fused k | v projection's output; columns past the row
+ * width untouched).  Deterministic bit for bit (fixed-order sums, no atomics), batch items independent; exact fp32
+ * products on v_mfma_f32_32x32x2_f32.  Same alignment and stride rules; dkv_row_stride >= 2*H*D.
+ * workspace: amav_crossattn_backward_workspace_bytes(B, q_len, H, D) bytes (0 = bad sizes). */
+size_t amav_crossattn_backward_workspace_bytes(int batch, int q_len, int heads, int head_dim);
+int amav_crossattn_backward(int batch, int q_len, int kv_len, int heads, int head_dim, const float *q_dev,
+                            int64_t q_row_stride, const float *k_dev, const float *v_dev, int64_t kv_row_stride,
+                            const float *out_dev, int64_t out_row_stride, const float *lse_dev, const float *dout_dev,
+                            int64_t dout_row_stride, float *dq_dev, int64_t dq_row_stride, float *dkv_dev,
+                            int64_t dkv_row_stride, float scale, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Operand of an fp32-equivalent nn.Linear (src/models/transformers.py:70-84, 448, 505: the to_q/k/v, to_out and
  * feed-forward projections) computed as ONE low-precision GEMM with fp32 accumulation over operands split into parts
  * and concatenated along K.  x [rows, k] fp32 (row stride in floats, k a multiple of 8) -> out [rows, parts * k]:
