@@ -129,6 +129,8 @@ DecodeSource = STRUCTS["amav_decode_source"]
 BodyTables = STRUCTS["amav_body_tables"]
 PoseParts = STRUCTS["amav_pose_parts"]
 LbsBackwardArgs = STRUCTS["amav_lbs_backward_args"]
+ImageView = STRUCTS["amav_image_view"]  # element (n, y, x, c) at ptr[n * image + y * row + x * pixel + c * channel stride]
+ImageLossWindow = STRUCTS["amav_image_loss_window"]
 
 _lib = None
 

@@ -124,3 +124,36 @@ def smplx_param_loss(pred_params, gt_params, weights=None):
         losses["transl_smoothl1"] = F.smooth_l1_loss(pred_params["transl"], gt_params["transl"])
         total = total + weights["transl"] * losses["transl_smoothl1"]
     return total, losses
+
+
+def image_losses(img1, img2, size_average=True):
+    """(l1_loss(img1, img2), ssim(img1, img2, 11, size_average)) for training, from the fused HIP kernels
+    (ops.image_loss_differentiable; csrc/image_loss.hip): img1, img2 [B, T, H, W, C] on the device, C = 1..4, both read
+    in place whatever their strides (the renderer's rgba[..., :3] view, a permuted [B,T,C,H,W] target).  One forward and,
+    for whatever weights the caller puts on the two terms, one backward launch; the gradient reaches img1 only, and
+    img2 must not require one.  The functions above remain the CPU-capable statement of the reference; this one has no
+    CPU path.  l1 is the mean over everything; ssim the mean over everything, or per image [B*T] without size_average."""
+    from . import ops
+
+    if img1.dim() != 5 or img1.shape != img2.shape:
+        raise ValueError(f"image_losses: expected two [B,T,H,W,C] tensors of one shape, got {tuple(img1.shape)} and "
+                         f"{tuple(img2.shape)}")
+    l1_sum, ssim_sum = ops.image_loss_differentiable(img1.reshape(-1, *img1.shape[2:]),
+                                                     img2.reshape(-1, *img2.shape[2:]))
+    per_image = img1.shape[2] * img1.shape[3] * img1.shape[4]
+    l1 = l1_sum.sum() / (l1_sum.numel() * per_image)
+    return l1, (ssim_sum.sum() / (ssim_sum.numel() * per_image) if size_average else ssim_sum / per_image)
+
+
+IMAGE_LOSS_DEFAULT = "hip"   # tools/bench_image_loss.py: the fused path is the faster one at both training shapes
+
+
+def training_image_terms(rendered, target):
+    """(l1, 1 - ssim) of a training step: image_losses, or with AMAV_IMAGE_LOSS=library (read per call, like
+    AMAV_CROSS_ATTN) the two library evaluations l1_loss and ssim."""
+    import os
+
+    if os.environ.get("AMAV_IMAGE_LOSS", IMAGE_LOSS_DEFAULT) == "library":
+        return l1_loss(rendered, target), 1 - ssim(rendered, target)
+    l1, s = image_losses(rendered, target)
+    return l1, 1 - s

@@ -8,8 +8,8 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (AmavError, Attr, BodyTables, DecodeSource, LbsBackwardArgs, PoseParts, RasterArgs,
-                   RasterBackwardArgs, TriplaneDecodeBackwardArgs, TriplaneSampleBackwardArgs, check)
+from ._lib import (AmavError, Attr, BodyTables, DecodeSource, ImageLossWindow, ImageView, LbsBackwardArgs, PoseParts,
+                   RasterArgs, RasterBackwardArgs, TriplaneDecodeBackwardArgs, TriplaneSampleBackwardArgs, check)
 
 SCALE_BIAS = 3.9    # src/models/renderer.py:428
 OPACITY_BIAS = 0.0  # src/models/renderer.py:429
@@ -1130,6 +1130,90 @@ def windows_cut_differentiable(x, frame, oy, ox, size, lattice):
     if not x.is_cuda:
         return _windows_cut_torch(x, frame, oy, ox, int(size), lattice)
     return _WindowsCut.apply(x, frame, oy, ox, int(size), *lattice)
+
+
+# ------------------------------------------------------------------------------------------------------ image loss
+IMAGE_LOSS_WINDOW = 11   # the only window the kernels are built for (loss_utils.py:44)
+_image_loss_taps = None
+
+
+def _image_loss_window():
+    """The fp32 taps of losses.gaussian(11, 1.5): the very numbers create_window multiplies together."""
+    global _image_loss_taps
+    if _image_loss_taps is None:
+        from .losses import gaussian
+        taps = gaussian(IMAGE_LOSS_WINDOW, 1.5).float().tolist()
+        _image_loss_taps = ImageLossWindow((ctypes.c_float * IMAGE_LOSS_WINDOW)(*taps))
+    return _image_loss_taps
+
+
+def _image_pair(x, y, what):
+    """x, y [N,H,W,C] float32 on the device, any strides (both are read in place) -> (views, N, H, W, C)."""
+    _need(x, f"{what}: x")
+    _need(y, f"{what}: y")
+    if x.dim() != 4 or x.shape != y.shape:
+        raise AmavError(f"{what}: expected x and y [N,H,W,C] of one shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    if not 1 <= x.shape[3] <= 4:
+        raise AmavError(f"{what}: {x.shape[3]} channels; 1 to 4 are supported")
+    return (ImageView(x.data_ptr(), *x.stride()), ImageView(y.data_ptr(), *y.stride())), *x.shape
+
+
+def image_loss_sums(x, y, want_grad):
+    """x, y [N,H,W,C] (C = 1..4, any strides: a [..., :3] view of RGBA frames or a permuted planar target is read in
+    place) -> (sums [2,N], maps): sums[0] = per-image sum of |x - y|, sums[1] = per-image sum of the SSIM map of
+    losses.ssim (11-tap window, zero padding), by amav_image_loss_forward: one tile kernel and a fixed-order reduction,
+    bitwise the same on every run.  maps [3,N,H,W,C] is what image_loss_backward needs, or None without want_grad
+    (then nothing of that size is allocated)."""
+    (vx, vy), N, H, W, C = _image_pair(x, y, "image_loss_sums")
+    if N == 0 or H == 0 or W == 0:
+        return torch.zeros(2, N, device=x.device), (torch.empty(3, N, H, W, C, device=x.device) if want_grad else None)
+    sums = torch.empty(2, N, device=x.device)
+    maps = torch.empty(3, N, H, W, C, device=x.device) if want_grad else None
+    ws = _scratch("amav_image_loss_workspace_bytes", x.device, N, H, W, rejected=f"N={N} H={H} W={W}")
+    _call("amav_image_loss_forward", N, H, W, C, ctypes.byref(vx), ctypes.byref(vy), ctypes.byref(_image_loss_window()),
+          sums.data_ptr(), maps.data_ptr() if want_grad else None, ws.data_ptr(), ws.numel())
+    return sums, maps
+
+
+def image_loss_backward(x, y, maps, grad_l1, grad_ssim):
+    """Gradient of image_loss_sums with respect to x, [N,H,W,C] contiguous: grad_l1 / grad_ssim [N] are the gradients of
+    the per-image sums (read on the device), maps the forward's.  One launch (amav_image_loss_backward), a gather:
+    deterministic.  y gets no gradient."""
+    (vx, vy), N, H, W, C = _image_pair(x, y, "image_loss_backward")
+    maps = _need(maps, "image_loss_backward: maps")
+    if tuple(maps.shape) != (3, N, H, W, C) or not maps.is_contiguous():
+        raise AmavError(f"image_loss_backward: maps {tuple(maps.shape)}, expected contiguous {(3, N, H, W, C)}")
+    grad_l1, grad_ssim = _contig(grad_l1, "grad_l1"), _contig(grad_ssim, "grad_ssim")
+    if grad_l1.numel() != N or grad_ssim.numel() != N:
+        raise AmavError(f"image_loss_backward: {grad_l1.numel()} / {grad_ssim.numel()} gradients for {N} images")
+    grad_x = torch.empty(N, H, W, C, device=x.device)
+    _call("amav_image_loss_backward", N, H, W, C, ctypes.byref(vx), ctypes.byref(vy), ctypes.byref(_image_loss_window()),
+          maps.data_ptr(), grad_l1.data_ptr(), grad_ssim.data_ptr(), grad_x.data_ptr())
+    return grad_x
+
+
+class _ImageLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, want_grad):
+        sums, maps = image_loss_sums(x, y, want_grad)
+        if want_grad:
+            ctx.save_for_backward(x, y, maps)
+        return sums[0], sums[1]
+
+    @staticmethod
+    def backward(ctx, grad_l1, grad_ssim):
+        x, y, maps = ctx.saved_tensors   # an output nobody used arrives as zeros
+        return image_loss_backward(x, y, maps, grad_l1.float(), grad_ssim.float()), None, None
+
+
+def image_loss_differentiable(x, y):
+    """x, y [N,H,W,C] -> (l1_sum [N], ssim_sum [N]) under autograd: one Function with two outputs, so whatever weights
+    the caller puts on the two terms, the backward to x is one launch.  The target y must not require a gradient."""
+    _image_pair(x, y, "image_loss_differentiable")
+    if y.requires_grad and torch.is_grad_enabled():
+        raise AmavError("image_loss_differentiable: the target y requires a gradient; only x receives one")
+    # needs_input_grad does not see torch.no_grad(): decide here whether the derivative maps are written at all
+    return _ImageLoss.apply(x, y, x.requires_grad and torch.is_grad_enabled())
 
 # ---------------------------------------------------------------------------------------------- stage-1 reductions
 def cell_segments(cell_of, cells):

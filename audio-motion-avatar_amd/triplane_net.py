@@ -282,7 +282,8 @@ class TriplaneGaussianAvatar(nn.Module):
         ref_images / test_images [B,T,3,H,W] in [0,1], smpl_params the ground-truth dict of [B,T,...], cam_params /
         test_cam_params the camera dicts, image_tokens [B,T,4096,image_feature_dim] (the Sapiens output, from the
         caller as for forward).  parts: l1_train, ssim_train (= 1 - ssim), l1_test, ssim_test (0 without test images),
-        loss_smplx.  Call total.backward() for the gradients.
+        loss_smplx.  Call total.backward() for the gradients.  The image terms come from the fused HIP loss
+        (losses.image_losses); AMAV_IMAGE_LOSS=library, read per call, keeps the library's l1_loss and ssim.
 
         Every stage-1 parameter receives a gradient: ImageFeature.feature_reducer, the point network (fc_pos, blocks,
         fc_c) and vertex_emb through the HIP backwards of the encoder's reductions, the SMPL-X predictor (smpl_tokens,
@@ -290,19 +291,17 @@ class TriplaneGaussianAvatar(nn.Module):
         and the renderer's decoder heads.  The reference renders with the ground-truth parameters, so LBS sits outside
         the graph here.  The step runs in the module's current mode; .eval() and .train() differ only in the
         transformers' dropout, which is 0 at the reference's settings."""
-        from .losses import l1_loss, smplx_param_loss, ssim
+        from .losses import smplx_param_loss, training_image_terms
         from .renderer import render_multi_view
 
         rendered, gaussians, _, _, pred_smpl_1, pred_smpl_2, _ = self(ref_images, smpl_params, cam_params, image_tokens)
-        parts = {"l1_train": l1_loss(rendered, ref_images.permute(0, 1, 3, 4, 2)),
-                 "ssim_train": 1 - ssim(rendered, ref_images.permute(0, 1, 3, 4, 2))}
+        parts = dict(zip(("l1_train", "ssim_train"), training_image_terms(rendered, ref_images.permute(0, 1, 3, 4, 2))))
         if test_images is not None:
             B, T = test_images.shape[:2]
             args = type("Args", (), {"image_size": self.cfg.image_size, "rgb": True, "sh_degree": 3})()
             target = render_multi_view(gaussians, test_cam_params["intrinsic"].reshape(B, T, 3, 3),
                                        test_cam_params["extrinsic"].reshape(B, T, 4, 4), args)
-            parts["l1_test"] = l1_loss(target, test_images.permute(0, 1, 3, 4, 2))
-            parts["ssim_test"] = 1 - ssim(target, test_images.permute(0, 1, 3, 4, 2))
+            parts["l1_test"], parts["ssim_test"] = training_image_terms(target, test_images.permute(0, 1, 3, 4, 2))
         else:
             parts["l1_test"] = torch.zeros((), device=rendered.device)
             parts["ssim_test"] = torch.zeros((), device=rendered.device)

@@ -471,6 +471,45 @@ int amav_windows_cut_backward(int num_frames, int channels, int height, int widt
                               int lattice_cols, const int32_t *lattice_dev, float *grad_x_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Image loss of the two training steps: L1 and SSIM (src/utils/loss_utils.py:18-19, 24-84) of N images of H x W x C,
+ * forward and backward.  SSIM uses the reference's separable 11-tap window, zero padding of 5 (taps outside the image
+ * contribute 0, the window is not renormalised), C1 = 0.01^2, C2 = 0.03^2.
+ *
+ * Both images are read in place: element (n, y, x, c) of a view lives at
+ * ptr[n * image_stride + y * row_stride + x * pixel_stride + c * channel_stride] (strides in floats, 64-bit offsets), so
+ * a [..., :3] view of an RGBA frame, a planar [N,C,H,W] target and a contiguous [N,H,W,C] tensor need no copy. */
+typedef struct amav_image_view {
+    const float *ptr;
+    int64_t image_stride, row_stride, pixel_stride, channel_stride; /* floats */
+} amav_image_view;
+/* The 11 taps of the 1-D window, as fp32 (losses.gaussian(11, 1.5)): the 2-D window is their outer product. */
+typedef struct amav_image_loss_window {
+    float taps[11];
+} amav_image_loss_window;
+/* Bytes of the forward's workspace (one pair of partial sums per 16 x 16 tile and image); 0 for an empty problem or
+ * negative counts. */
+size_t amav_image_loss_workspace_bytes(int num_images, int height, int width);
+/* sums [2,N]: sums[n] = sum over image n of |x - y|, sums[N + n] = sum over image n of the SSIM map.  One workgroup per
+ * tile writes its pair of partial sums to its own workspace slot and a second kernel adds an image's slots in a fixed
+ * order: no float atomics, bitwise the same on every run.
+ * maps: NULL, or [3,N,H,W,C] (contiguous) receiving per element the derivatives of the SSIM map with respect to the
+ * window means E[x^2], E[xy] and mu_x, which amav_image_loss_backward reads.  With NULL nothing of that size is written.
+ * workspace: amav_image_loss_workspace_bytes(N, H, W) bytes; NULL or too small: AMAV_ERR_WORKSPACE. */
+int amav_image_loss_forward(int num_images, int height, int width, int channels, const amav_image_view *x,
+                            const amav_image_view *y, const amav_image_loss_window *window, float *sums_dev,
+                            float *maps_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+/* grad_x [N,H,W,C] (contiguous; every element written exactly once) =
+ *   grad_l1[n] * sign(x - y) + grad_ssim[n] * (conv(d_m1) + 2 x conv(d_e11) + y conv(d_e12))
+ * with conv the same zero-padded window over the forward's maps, sign(0) = 0, and grad_l1 / grad_ssim [N] the gradients
+ * of the per-image sums, read on the device.  The target y gets no gradient.  A gather: no atomics, deterministic.
+ * All three entry points refuse (AMAV_ERR_INVALID_ARG, before any launch) negative counts, channels outside 1..4, a
+ * per-image H * W * C beyond 2^31 - 1 and NULL pointers; N = 0, H = 0 or W = 0 is an empty problem (AMAV_OK, no pointer
+ * is looked at).  No allocation and no host synchronisation. */
+int amav_image_loss_backward(int num_images, int height, int width, int channels, const amav_image_view *x,
+                             const amav_image_view *y, const amav_image_loss_window *window, const float *maps_dev,
+                             const float *grad_l1_dev, const float *grad_ssim_dev, float *grad_x_dev, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Stage-1 identity encoder: the point <-> triplane-cell reductions of
  * SMPLXTriplaneEncoder and the point -> pixel feature lookup, deterministic segment reductions.
  * Replaces torch_scatter.scatter_max / scatter_mean as used at src/models/triplane_net.py:226-244 and the pytorch3d
