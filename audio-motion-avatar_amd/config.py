@@ -54,6 +54,7 @@ class RendererConfig:
     #                                   clouds, so larger passes cost less per frame (10 k points: 8 -> 2.26, 16 -> 1.85,
     #                                   32 -> 1.62 ms per frame); frames are independent, the split changes nothing
     refiner_points_per_pass: int = 320_000  # ... but a pass holds at most this many points (working set ~0.4 MB per 1 k points)
+    refiner_batch_statistics: bool = False  # in .train(): BatchNorm batch statistics + DropPath in the refiner
     differentiable_refiner: bool = False  # PTv3Encoder records an autograd graph (HIP backwards) when
     #                                       called under grad mode on its own; Renderer still refuses autograd with a refiner
     differentiable_refine_points: bool = False  # ... unless this is on too (needs differentiable_refiner): refine_points

@@ -2265,3 +2265,132 @@ def cluster_gather_differentiable(up, cluster, members, seg):
     """up[cluster] whose backward is cluster_sum over the clusters' member lists (members / seg of Level.pool()) instead
     of an atomic index_add."""
     return _ClusterGather.apply(up, cluster, members, seg)
+
+
+# ------------------------------------------------- point refiner: train-mode BatchNorm (DESIGN.md section 4.18)
+BN_CHUNK_ROWS = 64  # rows per first-stage partial of bn_batch_stats and of the train backward's column sums
+
+
+def refiner_bn_library():
+    """AMAV_REFINER_BN=library (read per call, like AMAV_CROSS_ATTN): F.batch_norm(training=True) + F.gelu under torch
+    autograd instead of the HIP statistics / backward kernels -- the comparison path of tools/bench_refiner_backward.py."""
+    return os.environ.get("AMAV_REFINER_BN", "hip") == "library"
+
+
+def bn_batch_stats(x):
+    """x [rows, C] (rows >= 2, C a multiple of 4) -> (mean [C], var [C]): the columns' mean and biased variance
+    (amav_bn_batch_stats: chunks of BN_CHUNK_ROWS rows about their first row, merged in a fixed order; bit-identical
+    between calls)."""
+    x = _contig(x, "x")
+    if x.dim() != 2:
+        raise AmavError(f"bn_batch_stats: expected [rows, C], got {tuple(x.shape)}")
+    rows, C = x.shape
+    ws = _scratch("amav_bn_batch_stats_workspace_bytes", x.device, rows, C,
+                  rejected=f"rows={rows} C={C} (batch statistics need at least 2 rows and C a multiple of 4)")
+    mean, var = torch.empty(C, device=x.device), torch.empty(C, device=x.device)
+    _call("amav_bn_batch_stats", rows, C, x.data_ptr(), mean.data_ptr(), var.data_ptr(), ws.data_ptr(), ws.numel())
+    return mean, var
+
+
+def bn_gelu_train_backward(x, mean, rstd, weight, bias, grad_out):
+    """amav_bn_gelu_train_backward: the backward of gelu(((x - mean) * rstd) * weight + bias) through the batch statistics
+    -> (grad_x [rows, C], grad_weight [C], grad_bias [C])."""
+    x = _contig(x, "x")
+    rows, C = x.shape
+    grad_out = _shaped(grad_out, "grad_out", (rows, C))
+    ws = _scratch("amav_bn_batch_stats_workspace_bytes", x.device, rows, C,
+                  rejected=f"rows={rows} C={C} (batch statistics need at least 2 rows and C a multiple of 4)")
+    grad_x = torch.empty_like(x)
+    grad_weight, grad_bias = torch.empty(C, device=x.device), torch.empty(C, device=x.device)
+    vec = lambda t, name: _shaped(t, name, (C,)).data_ptr()
+    _call("amav_bn_gelu_train_backward", rows, C, x.data_ptr(), vec(mean, "mean"), vec(rstd, "rstd"), vec(weight, "weight"),
+          vec(bias, "bias"), grad_out.data_ptr(), grad_x.data_ptr(), grad_weight.data_ptr(), grad_bias.data_ptr(),
+          ws.data_ptr(), ws.numel())
+    return grad_x, grad_weight, grad_bias
+
+
+def cluster_max_raw(x, members, seg):
+    """x [n,C], members int64 [n] (rows grouped by cluster), seg int64 [clusters+1] -> the segment maxima [clusters,C]."""
+    x, members, seg = _contig(x, "x"), _contig(members, "members", torch.int64), _contig(seg, "seg", torch.int64)
+    C = x.shape[1]
+    clusters = seg.shape[0] - 1
+    out = torch.empty(clusters, C, device=x.device)
+    _call("amav_cluster_max_raw", clusters, C, x.data_ptr(), members.data_ptr(), seg.data_ptr(), out.data_ptr())
+    return out
+
+
+def cluster_max_route(x, members, seg, grad_max):
+    """grad_max [clusters,C] -> grad_x [n,C]: each maximum's gradient on the first member, in segment order, that attains
+    it, +0 on the segment's other rows (rows that `members` does not list keep zeros)."""
+    x, members, seg = _contig(x, "x"), _contig(members, "members", torch.int64), _contig(seg, "seg", torch.int64)
+    C = x.shape[1]
+    clusters = seg.shape[0] - 1
+    grad_max = _shaped(grad_max, "grad_max", (clusters, C))
+    grad_x = torch.empty_like(x) if members.shape[0] == x.shape[0] else torch.zeros_like(x)
+    _call("amav_cluster_max_route", clusters, C, x.data_ptr(), members.data_ptr(), seg.data_ptr(), grad_max.data_ptr(),
+          grad_x.data_ptr())
+    return grad_x
+
+
+def bn_train_fold(x, weight, bias, eps):
+    """Train-mode BatchNorm of the rows x [rows, C] as the (scale, shift) that bn_gelu / unpool_merge take
+    -> (scale, shift, mean, var_biased, rstd); nothing here is differentiable."""
+    mean, var = bn_batch_stats(x)
+    rstd = torch.rsqrt(var + eps)
+    scale = weight.detach() * rstd
+    return scale, bias.detach() - mean * scale, mean, var, rstd
+
+
+class _BnGeluTrain(torch.autograd.Function):
+    """gelu(BatchNorm(x)) with the batch's own statistics: bn_batch_stats + bn_gelu forward, amav_bn_gelu_train_backward
+    backward.  Saves x, mean, rstd and the affine parameters (the normalised rows are recomputed)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps):
+        x = _contig(x, "x")
+        weight, bias = _contig(weight.detach(), "weight"), _contig(bias.detach(), "bias")
+        scale, shift, mean, var, rstd = bn_train_fold(x, weight, bias, eps)
+        ctx.save_for_backward(x, mean, rstd, weight, bias)
+        ctx.mark_non_differentiable(mean, var)
+        return bn_gelu(x, scale, shift), mean, var
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out, _grad_mean, _grad_var):
+        x, mean, rstd, weight, bias = ctx.saved_tensors
+        grad_x, grad_weight, grad_bias = bn_gelu_train_backward(x, mean, rstd, weight, bias, grad_out.float().contiguous())
+        return grad_x, grad_weight, grad_bias, None
+
+
+def bn_gelu_train_differentiable(x, weight, bias, eps):
+    """-> (gelu(BN_batch(x)), mean [C], var_biased [C]) for x [rows, C], rows >= 2: BatchNorm1d in training mode followed by
+    GELU, differentiable in x, weight and bias THROUGH the batch statistics; the two statistics outputs are not
+    differentiable (they feed the running buffers).  AMAV_REFINER_BN=library: the same function by F.batch_norm + F.gelu
+    under torch autograd."""
+    if refiner_bn_library():
+        F = torch.nn.functional
+        with torch.no_grad():
+            var, mean = torch.var_mean(x, 0, unbiased=False)
+        return F.gelu(F.batch_norm(x, None, None, weight, bias, True, 0.0, eps)), mean, var
+    return _BnGeluTrain.apply(x, weight, bias, float(eps))
+
+
+class _ClusterMaxRaw(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, members, seg):
+        x = _contig(x, "x")
+        ctx.save_for_backward(x, members, seg)
+        return cluster_max_raw(x, members, seg)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, members, seg = ctx.saved_tensors
+        return cluster_max_route(x, members, seg, grad_out.float().contiguous()), None, None
+
+
+def cluster_max_bn_train_differentiable(x, members, seg, weight, bias, eps):
+    """-> (gelu(BN_batch(segment maxima of x)), mean, var_biased): SerializedPooling's max + BatchNorm + GELU in training
+    mode -- raw maxima, their batch statistics, bn_gelu; the backward is the train backward followed by the routing of each
+    maximum's gradient to the first member that attains it.  Differentiable in x, weight and bias."""
+    return bn_gelu_train_differentiable(_ClusterMaxRaw.apply(x, members, seg), weight, bias, eps)

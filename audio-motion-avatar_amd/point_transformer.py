@@ -25,6 +25,14 @@ bias receive gradients), DropPath as the identity.  `.train()` changes nothing: 
 statistics, the reference's train-mode batch statistics and stochastic depth are not reproduced.  Gradients go to `feat`
 and to every floating-point parameter; `points` get none (the network sees coordinates through the integer grid only).
 Gradients are bitwise reproducible (no atomics).
+
+`PointTransformerV3(..., batch_statistics=True)` (cfg.refiner_batch_statistics for PTv3Encoder) opts into the reference's
+training function, and only while the module is in `.train()`: the 13 BatchNorm1d layers (stem, poolings, both branches
+of the unpoolings) normalise with the statistics of the batch -- every row of every cloud of one forward call, at a
+pooling the pooled rows --, differentiate through them (csrc/cloud_norm.hip) and update their
+running buffers on the device; every Block applies DropPath per point to its attention and MLP branches (not to the
+cpe branch) with rates rising to `drop_path`, the masks drawn from `drop_path_generator`.  With the flag on, `.eval()` is
+the forward described above bit for bit; with it off (the default) so is `.train()`.
 """
 import os
 from types import SimpleNamespace
@@ -119,6 +127,39 @@ def _bn(channels):
     return nn.BatchNorm1d(channels, eps=1e-3, momentum=0.01)  # pointtransformer_v3.py:857
 
 
+def _bn_track(bn, mean, var, rows):
+    """BatchNorm1d's train-mode buffer update from the batch's mean and BIASED variance over `rows` rows, on the device."""
+    if bn.momentum is None:
+        raise AmavError("train-mode BatchNorm: momentum=None (the cumulative average) is not built")
+    with torch.no_grad():
+        m = float(bn.momentum)
+        bn.running_mean.mul_(1.0 - m).add_(mean, alpha=m)
+        bn.running_var.mul_(1.0 - m).add_(var, alpha=m * rows / (rows - 1.0))
+        bn.num_batches_tracked += 1
+
+
+def _bn_rows(x, where):
+    rows = int(x.shape[0])
+    if rows < 2:
+        raise AmavError(f"{where}: {rows} row(s) -- train-mode BatchNorm needs at least 2 values per channel")
+    return rows
+
+
+def _bn_gelu_train(x, bn, where):
+    """gelu(BatchNorm(x)) with the statistics of the rows of x (differentiable through them when a graph is recorded),
+    and the update of bn's running buffers."""
+    rows = _bn_rows(x, where)
+    out, mean, var = ops.bn_gelu_train_differentiable(x, bn.weight, bn.bias, bn.eps)
+    _bn_track(bn, mean, var, rows)
+    return out
+
+
+def _drop_path_mask(n, rate, generator):
+    """The keep mask of DropPath over n points, float [n, 1] of 0 / 1: a point keeps a branch with probability 1 - rate
+    (timm's DropPath on `point.feat [N, C]`, pointtransformer_v3.py:591-610: one draw per row)."""
+    return torch.empty(n, 1, device=generator.device).bernoulli_(1.0 - rate, generator=generator)
+
+
 class MLP(nn.Module):
     def __init__(self, channels, hidden):
         super().__init__()
@@ -147,18 +188,27 @@ class SerializedAttention(nn.Module):
 
 
 class Block(nn.Module):
-    """pointtransformer_v3.py:528-615 (pre-norm; DropPath is the identity at inference)."""
+    """pointtransformer_v3.py:528-615 (pre-norm; DropPath is the identity at inference).  drop_path: the Block's rate,
+    applied only when forward is handed a generator (PointTransformerV3 with batch_statistics, in .train())."""
 
-    def __init__(self, channels, num_heads, patch_size, mlp_ratio, order_index):
+    def __init__(self, channels, num_heads, patch_size, mlp_ratio, order_index, drop_path=0.0):
         super().__init__()
+        self.drop_path = float(drop_path)
         self.cpe = nn.Sequential(SubMConv3d(channels, channels, 3), nn.Linear(channels, channels), nn.LayerNorm(channels))
         self.norm1 = nn.Sequential(nn.LayerNorm(channels))
         self.attn = SerializedAttention(channels, num_heads, patch_size, order_index)
         self.norm2 = nn.Sequential(nn.LayerNorm(channels))
         self.mlp = nn.Sequential(MLP(channels, int(channels * mlp_ratio)))
 
-    def forward(self, feat, level, conv_in=None, differentiable=False):
+    def forward(self, feat, level, conv_in=None, differentiable=False, drop_generator=None):
         x = self.cpe[0](feat if conv_in is None else conv_in, level, differentiable)
+        if drop_generator is not None and self.drop_path > 0.0:
+            keep = 1.0 - self.drop_path
+            feat = feat + self.cpe[2](self.cpe[1](x))
+            branch = self.attn(self.norm1(feat), level, differentiable)
+            feat = feat + branch * (_drop_path_mask(feat.shape[0], self.drop_path, drop_generator) / keep)
+            branch = self.mlp(self.norm2(feat))
+            return feat + branch * (_drop_path_mask(feat.shape[0], self.drop_path, drop_generator) / keep)
         # feat += LayerNorm(cpe linear); norm1 -- and feat += attention; norm2 -- as one pass over the rows each (the
         # fused pass normalises with one eps; it has no backward, so the differentiable path takes the library branch)
         if not differentiable and feat.shape[1] in (32, 64, 128, 256, 512) and self.cpe[2].eps == self.norm1[0].eps:
@@ -179,11 +229,21 @@ class SerializedPooling(nn.Module):
             raise AmavError(f"SerializedPooling: stride {stride} (the reference configures 2 everywhere)")
         self.proj = nn.Linear(in_channels, out_channels)
         self.norm = nn.Sequential(_bn(out_channels))
+        self.level = 1  # the level it pools into (PointTransformerV3 numbers its poolings), for error messages
 
-    def forward(self, feat, level, differentiable=False):
-        """-> (pooled features, child level, cluster, (members, seg): the clusters' member lists)."""
+    def forward(self, feat, level, differentiable=False, batch_stats=False):
+        """-> (pooled features, child level, cluster, (members, seg): the clusters' member lists).
+        batch_stats: BatchNorm with the statistics of the pooled rows (module docstring)."""
         child, cluster, seg = level.pool()
-        if differentiable:
+        if batch_stats:
+            bn = self.norm[0]
+            if child.n < 2:
+                raise AmavError(f"pooling into level {self.level}: {child.n} pooled row(s) -- train-mode BatchNorm needs at least 2 values per "
+                                "channel; use a larger cloud or fewer stages")
+            pooled, mean, var = ops.cluster_max_bn_train_differentiable(self.proj(feat), level.order[0], seg, bn.weight,
+                                                                        bn.bias, bn.eps)
+            _bn_track(bn, mean, var, child.n)
+        elif differentiable:
             pooled = ops.cluster_max_differentiable(self.proj(feat), level.order[0], seg, *_bn_live(self.norm[0]))
         else:
             pooled = ops.cluster_max(self.proj(feat), level.order[0], seg, *_bn_fold(self.norm[0]))
@@ -198,8 +258,23 @@ class SerializedUnpooling(nn.Module):
         self.proj = nn.Sequential(nn.Linear(in_channels, out_channels), _bn(out_channels))
         self.proj_skip = nn.Sequential(nn.Linear(skip_channels, out_channels), _bn(out_channels))
 
-    def forward(self, child_feat, parent_feat, cluster, members=None):
-        """members: (members, seg) of the pooling that made the child level -> the differentiable path."""
+    def forward(self, child_feat, parent_feat, cluster, members=None, batch_stats=False, where="unpooling"):
+        """members: (members, seg) of the pooling that made the child level -> the differentiable path.
+        batch_stats: both BatchNorms with the statistics of their own rows (module docstring)."""
+        if batch_stats and members is not None:
+            up = _bn_gelu_train(self.proj[0](child_feat), self.proj[1], where + " (proj)")
+            skip = _bn_gelu_train(self.proj_skip[0](parent_feat), self.proj_skip[1], where + " (proj_skip)")
+            return skip, skip + ops.cluster_gather_differentiable(up, cluster, *members)
+        if batch_stats:  # forward only: the statistics kernel, then the fused inference kernels on (scale, shift)
+            up = _bn_gelu_train(self.proj[0](child_feat), self.proj[1], where + " (proj)")
+            x, bn = self.proj_skip[0](parent_feat), self.proj_skip[1]
+            rows = _bn_rows(x, where + " (proj_skip)")
+            if ops.refiner_bn_library():
+                skip = _bn_gelu_train(x, bn, where + " (proj_skip)")
+                return skip, skip + up[cluster]
+            scale, shift, mean, var, _ = ops.bn_train_fold(x, bn.weight, bn.bias, bn.eps)
+            _bn_track(bn, mean, var, rows)
+            return ops.unpool_merge(x, scale, shift, up, cluster)
         if members is not None:
             up = _bn_gelu_live(self.proj[0](child_feat), self.proj[1])
             skip = _bn_gelu_live(self.proj_skip[0](parent_feat), self.proj_skip[1])
@@ -337,16 +412,24 @@ class Level:
 class PointTransformerV3(nn.Module):
     """pointtransformer_v3.py:795-991 (cls_mode=False, no PDNorm, no RPE, no flash): constructor arguments by the
     reference's names; `drop_path`, `shuffle_orders`, `enable_flash` are accepted and have no effect at inference /
-    are replaced by the deterministic semantics above.  `differentiable`: record an autograd graph when something
+    are replaced by the deterministic semantics above.  `batch_statistics`: in .train(), BatchNorm with batch statistics
+    and running-buffer updates, and DropPath with rates linspace(0, drop_path) over the encoder's blocks and over the
+    decoder's (reversed inside a stage, :879-937), masks from `drop_path_generator` (a torch.Generator on the device,
+    made on first use; assign or seed it to fix a run); off by default, and then .train() changes nothing.  `differentiable`: record an autograd graph when something
     requires grad (module docstring); off by default, and then `forward` is the inference path whatever the grad mode."""
 
     def __init__(self, in_channels=6, order=ORDERS, stride=(2, 2, 2, 2), enc_depths=(2, 2, 2, 6, 2),
                  enc_channels=(32, 64, 128, 256, 512), enc_num_head=(2, 4, 8, 16, 32),
                  enc_patch_size=(1024, 1024, 1024, 1024, 1024), dec_depths=(2, 2, 2, 2), dec_channels=(64, 64, 128, 256),
                  dec_num_head=(4, 4, 8, 16), dec_patch_size=(1024, 1024, 1024, 1024), mlp_ratio=4, drop_path=0.3,
-                 shuffle_orders=True, enable_flash=False, grid_resolution=100, differentiable=False):
+                 shuffle_orders=True, enable_flash=False, grid_resolution=100, differentiable=False, batch_statistics=False):
         super().__init__()
         self.differentiable = bool(differentiable)
+        self.batch_statistics = bool(batch_statistics)
+        self.drop_path = float(drop_path)
+        self.drop_path_generator = None
+        enc_rates = torch.linspace(0, self.drop_path, sum(enc_depths)).tolist()  # :879-881
+        dec_rates = torch.linspace(0, self.drop_path, sum(dec_depths)).tolist()  # :924-926
         if tuple(order) != ORDERS:
             raise AmavError(f"PointTransformerV3: orders {tuple(order)} (the kernels build {ORDERS})")
         stages = len(enc_depths)
@@ -364,18 +447,21 @@ class PointTransformerV3(nn.Module):
             enc = nn.Module()
             if s > 0:
                 enc.down = SerializedPooling(enc_channels[s - 1], enc_channels[s], stride[s - 1])
+                enc.down.level = s
+            rates = enc_rates[sum(enc_depths[:s]):sum(enc_depths[:s + 1])]
             for i in range(enc_depths[s]):
                 setattr(enc, f"block{i}", Block(enc_channels[s], enc_num_head[s], enc_patch_size[s], mlp_ratio,
-                                                i % len(ORDERS)))
+                                                i % len(ORDERS), rates[i]))
             setattr(self.enc, f"enc{s}", enc)
         self.dec = nn.Module()
         dec_channels = list(dec_channels) + [enc_channels[-1]]
         for s in reversed(range(stages - 1)):
             dec = nn.Module()
             dec.up = SerializedUnpooling(dec_channels[s + 1], enc_channels[s], dec_channels[s])
+            rates = dec_rates[sum(dec_depths[:s]):sum(dec_depths[:s + 1])][::-1]  # :931-934
             for i in range(dec_depths[s]):
                 setattr(dec, f"block{i}", Block(dec_channels[s], dec_num_head[s], dec_patch_size[s], mlp_ratio,
-                                                i % len(ORDERS)))
+                                                i % len(ORDERS), rates[i]))
             setattr(self.dec, f"dec{s}", dec)
         self.out_channels = dec_channels[0]
 
@@ -398,23 +484,33 @@ class PointTransformerV3(nn.Module):
         level = Level(grid, cloud_of, depth, np.full(Fc, N, dtype=np.int64), ops.cloud_codes(grid, cloud_of, depth))
         stem = self.embedding.stem
         x = stem.conv(feat.reshape(n, -1).float().contiguous(), level, diff)
-        x = _bn_gelu_live(x, stem.norm) if diff else ops.bn_gelu(x, *_bn_fold(stem.norm))
+        stats = self.batch_statistics and self.training  # the reference's training function (module docstring)
+        gen = None
+        if stats and self.drop_path > 0.0:
+            if self.drop_path_generator is None:
+                self.drop_path_generator = torch.Generator(device=dev)
+            gen = self.drop_path_generator
+        if stats:
+            x = _bn_gelu_train(x, stem.norm, "stem")
+        else:
+            x = _bn_gelu_live(x, stem.norm) if diff else ops.bn_gelu(x, *_bn_fold(stem.norm))
         stack = []
         for s in range(self.num_stages):
             enc = getattr(self.enc, f"enc{s}")
             if s > 0:
-                x_child, child, cluster, members = enc.down(x, level, diff)
+                x_child, child, cluster, members = enc.down(x, level, diff, stats)
                 stack.append((level, x, cluster, members))
                 level, x = child, x_child
             for i in range(self.enc_depths[s]):
-                x = getattr(enc, f"block{i}")(x, level, differentiable=diff)
+                x = getattr(enc, f"block{i}")(x, level, differentiable=diff, drop_generator=gen)
         for s in reversed(range(self.num_stages - 1)):
             dec = getattr(self.dec, f"dec{s}")
             parent, x_parent, cluster, members = stack.pop()
-            skip, x = dec.up(x, x_parent, cluster, members if diff else None)
+            skip, x = dec.up(x, x_parent, cluster, members if diff else None, stats, f"unpooling into level {s}")
             level = parent
             for i in range(self.dec_depths[s]):
-                x = getattr(dec, f"block{i}")(x, level, conv_in=skip if i == 0 else None, differentiable=diff)
+                x = getattr(dec, f"block{i}")(x, level, conv_in=skip if i == 0 else None, differentiable=diff,
+                                              drop_generator=gen)
         return x
 
 
@@ -422,7 +518,10 @@ class PTv3Encoder(nn.Module):
     """point_encoder.py:6-40.  cfg: input_dim, stride, enc_channels, enc_depths, dec_channels, dec_depths,
     enc_num_head, dec_num_head, enc_patch_size, dec_patch_size, enable_flash (reference names); optional
     `refiner_clouds_per_pass` bounds the working set (clouds are independent, so the split changes nothing); optional
-    `differentiable_refiner` (default False) builds the trainable network (module docstring)."""
+    `differentiable_refiner` (default False) builds the trainable network (module docstring); optional
+    `refiner_batch_statistics` (default False) is PointTransformerV3's batch_statistics: in .train() the population of a
+    BatchNorm statistic is every row of every cloud of one call -- the reference's batch --, so all clouds then run in ONE
+    pass whatever the two bounds say (a split would change the function) and memory is the caller's to bound."""
 
     def __init__(self, cfg=None):
         super().__init__()
@@ -435,7 +534,8 @@ class PTv3Encoder(nn.Module):
             dec_channels=cfg.dec_channels, dec_depths=cfg.dec_depths, enc_num_head=cfg.enc_num_head,
             dec_num_head=cfg.dec_num_head, enc_patch_size=cfg.enc_patch_size, dec_patch_size=cfg.dec_patch_size,
             enable_flash=getattr(cfg, "enable_flash", False),
-            differentiable=getattr(cfg, "differentiable_refiner", False))
+            differentiable=getattr(cfg, "differentiable_refiner", False),
+            batch_statistics=getattr(cfg, "refiner_batch_statistics", False))
         self.grid_resolution = 100
         self.clouds_per_pass = int(getattr(cfg, "refiner_clouds_per_pass", 32))
         self.points_per_pass = int(getattr(cfg, "refiner_points_per_pass", 320_000))
@@ -444,5 +544,7 @@ class PTv3Encoder(nn.Module):
         """pts [B,N,3], feats [B,N,C] -> [B*N, dec_channels[0]]."""
         B = pts.shape[0]
         step = max(1, min(self.clouds_per_pass, self.points_per_pass // max(int(pts.shape[1]), 1)))
+        if self.point_transformer.batch_statistics and self.point_transformer.training:
+            step = max(B, 1)  # batch statistics are over the whole call
         outs = [self.point_transformer(pts[s:s + step], feats[s:s + step]) for s in range(0, B, step)]
         return outs[0] if len(outs) == 1 else torch.cat(outs)

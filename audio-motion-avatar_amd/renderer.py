@@ -174,6 +174,9 @@ class Renderer(nn.Module):
         planes = triplane_tokens.view(F, triplane_tokens.shape[1], 3, R, R).permute(0, 2, 1, 3, 4)
         step = max(1, min(int(getattr(self.cfg, "refiner_clouds_per_pass", 32)),
                           int(getattr(self.cfg, "refiner_points_per_pass", 320_000)) // max(N, 1)))
+        ptv3 = self.point_encoder.point_transformer
+        if ptv3.batch_statistics and ptv3.training:
+            step = max(F, 1)  # cfg.refiner_batch_statistics: a BatchNorm statistic is over all frames of the call
         sample = ops.triplane_sample_features_differentiable if differentiable else ops.triplane_sample_features
         refined = []
         for s in range(0, F, step):

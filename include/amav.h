@@ -845,6 +845,47 @@ int amav_cluster_sum(int64_t clusters, int channels, const float *x_dev, const i
                      float *out_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Train-mode BatchNorm of the point refiner (csrc/cloud_norm.hip): the statistics of a batch of
+ * rows, the backward through them, and the pooling maximum on its own (in pooling the BatchNorm follows the maximum,
+ * pointtransformer_v3.py:693-719, so its statistics are over the pooled rows).  fp32, kernel launches only, no host
+ * synchronisation, no atomics; every sum in an order fixed by (rows, channels): a call is deterministic bit for bit.
+ * channels: a multiple of 4.  rows >= 2 (one value per channel has no batch statistics; torch refuses it too).
+ * The train-mode forward is amav_bn_gelu / amav_unpool_merge with scale = weight * rstd, shift = bias - mean * scale.
+ *
+ * amav_bn_batch_stats   mean [C], var [C] (biased: divided by rows) of the columns of x [rows, C].  Rows are cut into
+ *                       chunks of 64; a chunk is summed about its own first row (the pivot) and becomes (count, mean, M2);
+ *                       chunks are merged with the pairwise update of Chan, Golub & LeVeque, so a large common offset of a
+ *                       column costs no digits and a constant column has var = 0 exactly.  workspace:
+ *                       amav_bn_batch_stats_workspace_bytes(rows, channels) bytes (0 = bad sizes; one size serves this
+ *                       entry and the backward, whose fp64 partial sums are the larger need).
+ * amav_bn_gelu_train_backward  backward of y = gelu(xhat * weight + bias), xhat = (x - mean) * rstd, through the batch
+ *                       statistics.  With g = grad_out * gelu'(xhat * weight + bias) (exact erf, recomputed):
+ *                       grad_bias [C] = sum of g, grad_weight [C] = sum of g * xhat,
+ *                       grad_x [rows, C] = weight * rstd * (g - grad_bias / rows - xhat * grad_weight / rows).
+ *                       One pass over x and grad_out makes the column sums, a second pass makes grad_x.  The sums are
+ *                       accumulated in fp64 (grad_bias / grad_weight are their roundings) and grad_x is evaluated in fp64
+ *                       about the column means of g and of xhat, then rounded once: every column of grad_x sums to zero
+ *                       to 2^-24 of its absolute sum at any row count, two rows included.  workspace:
+ *                       amav_bn_batch_stats_workspace_bytes(rows, channels) bytes.
+ * amav_cluster_max_raw  out [clusters, C] = max over rows members[seg[j] .. seg[j+1]) of x: amav_cluster_max without scale,
+ *                       shift and GELU.
+ * amav_cluster_max_route  grad_x [n, C] from grad_max [clusters, C]: the whole gradient to the first member, in segment
+ *                       order, that attains the maximum, zero on every other row of the segment (amav_cluster_max_backward's
+ *                       rule; every row of a segment is written once).
+ */
+size_t amav_bn_batch_stats_workspace_bytes(int64_t rows, int channels);
+int amav_bn_batch_stats(int64_t rows, int channels, const float *x_dev, float *mean_dev, float *var_dev, void *workspace,
+                        size_t workspace_bytes, void *stream);
+int amav_bn_gelu_train_backward(int64_t rows, int channels, const float *x_dev, const float *mean_dev, const float *rstd_dev,
+                                const float *weight_dev, const float *bias_dev, const float *grad_out_dev, float *grad_x_dev,
+                                float *grad_weight_dev, float *grad_bias_dev, void *workspace, size_t workspace_bytes,
+                                void *stream);
+int amav_cluster_max_raw(int64_t clusters, int channels, const float *x_dev, const int64_t *members_dev,
+                         const int64_t *seg_dev, float *out_dev, void *stream);
+int amav_cluster_max_route(int64_t clusters, int channels, const float *x_dev, const int64_t *members_dev,
+                           const int64_t *seg_dev, const float *grad_max_dev, float *grad_x_dev, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Library GEMM of the fp16 x 2 split projections: out[rows, n] fp32 = alpha * a[rows, k3] x
  * w[n, k3]^T with fp16 operands and fp32 accumulation -- the three partial products of an fp32-equivalent nn.Linear
  * (src/models/transformers.py:70-84, 448, 505) concatenated along K.  hipBLASLt does the arithmetic; `algo_index` names

@@ -8,6 +8,10 @@ JSON line per measurement.
 
     timeout -k 10 900 python tools/bench_refiner_backward.py [--clouds 8] [--points 10000] [--iters 5]
 
+--train-mode measures the refiner's training function instead (batch_statistics=True, .train(), DESIGN.md section
+4.18): forward + backward with the HIP BatchNorm kernels against AMAV_REFINER_BN=library, alternated round by round in
+this one process, and each new kernel at the level-0 shape with its achieved bytes per second.
+
 Per-kernel times come from a trace run of their own (one step, no event timing):
 
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/bench_refiner_backward.py --once
@@ -142,12 +146,57 @@ def operator_bench(rc, pts, feat, iters):
     print(json.dumps(dict(kind="refiner_operators", **res)), flush=True)
 
 
+def train_mode_bench(rc, pts, feat, dout, iters, rounds=3):
+    torch.manual_seed(0)
+    net = PointTransformerV3(in_channels=3 * rc.triplane_feature_dim, differentiable=True, batch_statistics=True,
+                             drop_path=0.0, **{k: tuple(getattr(rc, k)) for k in PCFG_KEYS}).cuda().train()
+
+    def step():
+        net.zero_grad(set_to_none=True)
+        net(pts, feat.detach().requires_grad_()).backward(dout)
+
+    res = dict(clouds=int(pts.shape[0]), points=int(pts.shape[1]), iters=iters, rounds=rounds, hip=[], library=[])
+    for _ in range(rounds):  # A B A B ...: both sides see the same clocks and cache state
+        for mode in ("hip", "library"):
+            os.environ["AMAV_REFINER_BN"] = mode
+            res[mode].append(timed(step, iters)["median_ms"])
+    os.environ.pop("AMAV_REFINER_BN")
+    res["hip_median_ms"], res["library_median_ms"] = (sorted(res[m])[rounds // 2] for m in ("hip", "library"))
+    print(json.dumps(dict(kind="refiner_train_mode", **res)), flush=True)
+
+    n, C = pts.shape[0] * pts.shape[1], rc.enc_channels[0]
+    g = torch.Generator().manual_seed(3)
+    x, dy = torch.randn(n, C, generator=g).cuda(), torch.randn(n, C, generator=g).cuda()
+    w, b = torch.rand(C, generator=g).cuda() + 0.5, torch.randn(C, generator=g).cuda()
+    mean, var = ops.bn_batch_stats(x)
+    rstd = torch.rsqrt(var + 1e-3)
+    cloud_of = torch.arange(pts.shape[0], device="cuda", dtype=torch.int32).repeat_interleave(pts.shape[1])
+    grid, depth = ops.cloud_voxelize(pts.reshape(n, 3), cloud_of, pts.shape[0])
+    level = Level(grid, cloud_of, depth, np.full(pts.shape[0], pts.shape[1]), ops.cloud_codes(grid, cloud_of, depth))
+    _, _, seg = level.pool()
+    m = seg.shape[0] - 1
+    dm = torch.randn(m, C, generator=g).cuda()
+    rows = n * C * 4
+    ops_res = dict(rows=n, channels=C, clusters=m)
+    for name, fn, nbytes in (
+            ("bn_batch_stats", lambda: ops.bn_batch_stats(x), rows),
+            ("bn_gelu_train_backward", lambda: ops.bn_gelu_train_backward(x, mean, rstd, w, b, dy), 5 * rows),
+            ("cluster_max_raw", lambda: ops.cluster_max_raw(x, level.order[0], seg), rows + m * C * 4 + n * 8),
+            ("cluster_max_route", lambda: ops.cluster_max_route(x, level.order[0], seg, dm), 2 * rows + m * C * 4 + n * 8)):
+        t = timed(fn, max(iters, 20))
+        t["floor_bytes"] = nbytes
+        t["gb_per_s"] = round(nbytes / (t["median_ms"] * 1e-3) / 1e9, 1)
+        ops_res[name] = t
+    print(json.dumps(dict(kind="refiner_train_mode_operators", **ops_res)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--clouds", type=int, default=8)
     ap.add_argument("--points", type=int, default=10000)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--once", action="store_true", help="one warm-up and one forward + backward step (for a kernel trace)")
+    ap.add_argument("--train-mode", action="store_true", help="the batch-statistics training function, HIP against library")
     args = ap.parse_args()
     rc = RendererConfig()
     pts = body_points(args.clouds, args.points)
@@ -160,6 +209,9 @@ def main():
             net.zero_grad(set_to_none=True)
             net(pts, feat.detach().requires_grad_()).backward(dout)
         torch.cuda.synchronize()
+        return
+    if args.train_mode:
+        train_mode_bench(rc, pts, feat, dout, args.iters)
         return
     network_bench(net, pts, feat, dout, args.iters)
     operator_bench(rc, pts, feat, args.iters)
