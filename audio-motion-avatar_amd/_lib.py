@@ -22,7 +22,8 @@ class AmavError(RuntimeError):
 
 _SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
             "size_t": ctypes.c_size_t, "uint8_t": ctypes.c_uint8}
-_RETURNS = {("int", ""): ctypes.c_int, ("size_t", ""): ctypes.c_size_t, ("char", "*"): ctypes.c_char_p}
+_RETURNS = {("int", ""): ctypes.c_int, ("int64_t", ""): ctypes.c_int64, ("size_t", ""): ctypes.c_size_t,
+            ("char", "*"): ctypes.c_char_p}
 _STRUCT = re.compile(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*(\w+)\s*;")
 _FIELD = re.compile(r"(?:const\s+)?(\w+)\s+(.+)", re.S)
 _DECLARATOR = re.compile(r"(\*?)\s*(\w+)\s*(?:\[\s*(\d+)\s*\])?")

@@ -1250,6 +1250,97 @@ __global__ __launch_bounds__(256) void split_operand_f16_kernel(long long octs, 
         put(0, p2), put(1, p1), put(2, p1);
     }
 }
+// The bf16 x 3 operand of x^T (and, with out_rows, split_operand_kernel<false>'s operand of x from the same read): what
+// the two backward products of a linear layer contract over is the ROW dimension of their fp32 tensors (dW = g^T x over the
+// rows of both, dx = g W over the rows of W), and the library GEMM wants the contraction dimension innermost.
+// grid (row tiles, column tiles), 256 threads, one 64 x 64 fp32 tile: thread (pair = tid / 8, oct = tid % 8) reads rows
+// 2 pair, 2 pair + 1 x columns 8 oct .. 8 oct + 7 (four float4; rows past the end read as +0, whose parts are +0: the zero
+// tail of out_t), splits them in registers, writes the row-major operand with 16-byte stores, and stages each part in LDS
+// transposed: stage[part][column][dword d] = rows (2 d, 2 d + 1) of the tile.  A column's 32 dwords are eight 16-byte
+// slots, stored at slot ^ (column / 8):
+//   * writes (4 bytes; bank = dword % 32 over half a wave = 8 octs x 4 pairs of one slot): slot ^ oct takes 8 values, the
+//     pair's low bits the 4 dwords of a slot -- 32 banks, each once (unswizzled, all 8 octs would share 4 banks);
+//   * reads (16 bytes; bank = dword % 64 over the read's 16-lane groups): a wave reads the 8 columns of one column / 8, so
+//     the XOR permutes the slots of every column alike and keeps a 4-lane block on one half of a column; the groups' four
+//     blocks then sit on (even column, low half), (odd, high), (even, high), (odd, low) or the mirror image: 64 banks, each
+//     once.  A pad cannot serve both sides: 16-byte reads need a column stride that is a multiple of 4 dwords, and with any
+//     such stride the 8 octs of a write land on 4 banks.
+// out_t is written with 16-byte stores of 8 consecutive source rows, 8 lanes per column (128 contiguous bytes).
+template <bool kWeights>
+__global__ __launch_bounds__(256) void split_operand_transposed_kernel(long long rows, long long rows_padded, int k,
+                                                                       const float *__restrict__ x, long long row_stride,
+                                                                       __bf16 *__restrict__ out_rows,
+                                                                       __bf16 *__restrict__ out_t) {
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    __shared__ uint4 stage[3][64][8];
+    const int tid = threadIdx.x;
+    const long long row0 = (long long)blockIdx.x * 64;
+    const int col0 = blockIdx.y * 64;
+    {
+        const int pair = tid >> 3, oct = tid & 7;
+        const int col = col0 + 8 * oct;
+        float v[2][8];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const long long row = row0 + 2 * pair + h;
+            if (row < rows && col < k) {
+                const float *src = x + row * row_stride + col;
+                const float4 lo = *reinterpret_cast<const float4 *>(src), hi = *reinterpret_cast<const float4 *>(src + 4);
+                v[h][0] = lo.x, v[h][1] = lo.y, v[h][2] = lo.z, v[h][3] = lo.w;
+                v[h][4] = hi.x, v[h][5] = hi.y, v[h][6] = hi.z, v[h][7] = hi.w;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[h][j] = 0.0f;
+            }
+        }
+        bf16x8 p[2][3];
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                __bf16 a, b, cc;
+                split3(v[h][j], a, b, cc);
+                p[h][0][j] = a, p[h][1][j] = b, p[h][2][j] = cc;
+            }
+        if (out_rows && col < k) {  // activation order, as split_operand_kernel<false>
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const long long row = row0 + 2 * pair + h;
+                if (row >= rows) continue;
+                __bf16 *dst = out_rows + row * 6 * k + col;
+                auto put = [&](int block, const bf16x8 &q) { *reinterpret_cast<bf16x8 *>(dst + (long long)block * k) = q; };
+                put(0, p[h][2]), put(1, p[h][1]), put(2, p[h][0]), put(3, p[h][1]), put(4, p[h][0]), put(5, p[h][0]);
+            }
+        }
+        unsigned *words = reinterpret_cast<unsigned *>(&stage[0][0][0]);
+        const int dword = (((pair >> 2) ^ oct) << 2) | (pair & 3);
+#pragma unroll
+        for (int part = 0; part < 3; ++part)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                bf16x2 two;
+                two[0] = p[0][part][j], two[1] = p[1][part][j];
+                words[(part * 64 + 8 * oct + j) * 32 + dword] = __builtin_bit_cast(unsigned, two);
+            }
+    }
+    __syncthreads();
+    const int slot = tid & 7;
+    const long long row = row0 + 8 * slot;  // the first of this lane's 8 source rows
+    if (row >= rows_padded) return;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        const int c = 32 * half + (tid >> 3);
+        if (col0 + c >= k) continue;
+        const uint4 p1 = stage[0][c][slot ^ (c >> 3)], p2 = stage[1][c][slot ^ (c >> 3)], p3 = stage[2][c][slot ^ (c >> 3)];
+        __bf16 *dst = out_t + (long long)(col0 + c) * 6 * rows_padded + row;
+        auto put = [&](int block, const uint4 &q) { *reinterpret_cast<uint4 *>(dst + block * rows_padded) = q; };
+        if (kWeights) {
+            put(0, p1), put(1, p2), put(2, p3), put(3, p1), put(4, p2), put(5, p1);
+        } else {
+            put(0, p3), put(1, p2), put(2, p1), put(3, p2), put(4, p1), put(5, p1);
+        }
+    }
+}
 }  // namespace attn
 }  // namespace amav
 
@@ -1284,6 +1375,33 @@ extern "C" int amav_split_operand(int64_t rows, int k, const float *x, int64_t x
                                                                         static_cast<__bf16 *>(out));
     }
     return check_launch("amav_split_operand");
+}
+
+extern "C" int64_t amav_split_transposed_rows(int64_t rows) { return rows > 0 ? (rows + 7) / 8 * 8 : 0; }
+
+extern "C" int amav_split_operand_transposed(int64_t rows, int k, const float *x, int64_t x_row_stride, int weights,
+                                             void *out_rows, void *out_t, void *stream_) {
+    AMAV_REQUIRE(rows > 0 && k > 0 && k % 8 == 0,
+                 "amav_split_operand_transposed: rows=%lld k=%d (k must be a multiple of 8)", (long long)rows, k);
+    AMAV_REQUIRE(x && out_t, "amav_split_operand_transposed: NULL pointer");
+    AMAV_REQUIRE(x_row_stride >= k && x_row_stride % 4 == 0, "amav_split_operand_transposed: bad row stride");
+    AMAV_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out_rows) |
+                   reinterpret_cast<uintptr_t>(out_t)) & 15) == 0,
+                 "amav_split_operand_transposed: buffers must be 16-byte aligned");
+    const long long row_tiles = (rows + 63) / 64, col_tiles = (k + 63) / 64;
+    AMAV_REQUIRE(row_tiles <= 0x7fffffffLL && col_tiles <= 65535,
+                 "amav_split_operand_transposed: rows=%lld k=%d exceed the launch grid", (long long)rows, k);
+    const dim3 grid((unsigned)row_tiles, (unsigned)col_tiles);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const long long rows_padded = amav_split_transposed_rows(rows);
+    __bf16 *o_rows = static_cast<__bf16 *>(out_rows), *o_t = static_cast<__bf16 *>(out_t);
+    if (weights)
+        amav::attn::split_operand_transposed_kernel<true><<<grid, 256, 0, stream>>>(rows, rows_padded, k, x, x_row_stride,
+                                                                                  o_rows, o_t);
+    else
+        amav::attn::split_operand_transposed_kernel<false><<<grid, 256, 0, stream>>>(rows, rows_padded, k, x, x_row_stride,
+                                                                                   o_rows, o_t);
+    return check_launch("amav_split_operand_transposed");
 }
 
 

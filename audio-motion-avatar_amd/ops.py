@@ -1706,6 +1706,24 @@ def split_operand(x, weights=False, fmt=SPLIT_BF16X3, scale_exp=0):
     return out
 
 
+def split_operand_transposed(x, weights=False, also_rows=False):
+    """x [rows, k] fp32 (as split_operand takes it) -> the bf16 x 3 activation (default) or weight operand of x^T,
+    [k, 6 Rp] bf16 with Rp = rows rounded up to a multiple of 8: part p of column c at [c, p Rp : p Rp + rows], zeros after
+    it.  With also_rows -> (split_operand(x), that operand) from one read of x; the row-major one is the ACTIVATION operand
+    whatever `weights` is.  include/amav.h, amav_split_operand_transposed."""
+    x = _need(x, "x")
+    if x.dim() != 2 or x.stride(1) != 1 or x.shape[1] % 8 or x.stride(0) % 4 or x.data_ptr() % 16:
+        raise AmavError("split_operand_transposed: need a 16-byte aligned [rows, k] tensor, unit inner stride, k a "
+                        "multiple of 8")
+    rows, k = x.shape
+    padded = _lib.lib().amav_split_transposed_rows(rows)
+    out_t = torch.empty(k, 6 * padded, dtype=torch.bfloat16, device=x.device)
+    out_rows = _split_buffer(rows, k, SPLIT_BF16X3, x.device) if also_rows else None
+    _call("amav_split_operand_transposed", rows, k, x.data_ptr(), x.stride(0), int(bool(weights)),
+          out_rows.data_ptr() if also_rows else None, out_t.data_ptr())
+    return (out_rows, out_t) if also_rows else out_t
+
+
 def add_layernorm(hidden, add, batch_row, weight, bias, eps=1e-5, add_bias=None, split=None, split_exp=0):
     """hidden [B,S,dim] (contiguous), add [B,S,dim] or None (+ add_bias [dim]: the bias of the projection that produced
     it), batch_row [B,1,dim] or None -> (h = batch_row + ((add + add_bias) + hidden), LayerNorm(h) * weight + bias), two
@@ -1848,6 +1866,100 @@ def add_layernorm_differentiable(hidden, add, batch_row, weight, bias, eps=1e-5,
     return _AddLayerNorm.apply(_need(hidden, "hidden").contiguous(), add if add is None else _need(add, "add").contiguous(),
                                batch_row if batch_row is None else _need(batch_row, "batch_row").contiguous(),
                                weight, bias, float(eps), add_bias)
+
+
+# --------------------------------------------------- linear layers on bf16 x 3 split products under autograd
+def _rows_2d(t, width):
+    """t [..., width] -> a [rows, width] view (a copy where the kernels could not read it in place)."""
+    t = t.reshape(-1, width)
+    if t.stride(1) != 1 or t.stride(0) % 4 or t.stride(0) < width:
+        t = t.contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+class _LinearSplit(torch.autograd.Function):
+    """x W^T (+ b) and both of its backward products as bf16 x 3 split GEMMs (those named in `library`: the library's fp32
+    GEMM); x and W are kept in fp32, as F.linear keeps them, and every split operand is rebuilt where it is used."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, weight_split, weight_split_t, library):
+        N, K = weight.shape
+        if "forward" in library:
+            y = torch.nn.functional.linear(_rows_2d(x, K), weight, bias)
+        else:
+            b = weight_split() if weight_split else split_operand(weight.detach(), weights=True)
+            a = split_operand(_rows_2d(x, K))
+            if bias is None:
+                y = torch.mm(a, b.t(), out_dtype=torch.float32)
+            else:
+                y = torch.addmm(bias, a, b.t(), out_dtype=torch.float32)
+        ctx.weight_split_t, ctx.library = weight_split_t, library
+        ctx.has_bias = bias is not None
+        ctx.save_for_backward(x, weight)
+        return y.view(*x.shape[:-1], N)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, weight = ctx.saved_tensors
+        N, K = weight.shape
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        g = _rows_2d(grad_out.float(), N)  # [rows, N]; an expanded gradient becomes a real one here
+        grad_x = grad_w = grad_b = None
+        split_x, split_w = need_x and "dgrad" not in ctx.library, need_w and "wgrad" not in ctx.library
+        g_rows = g_t = None
+        if split_x and split_w:
+            g_rows, g_t = split_operand_transposed(g, also_rows=True)  # both forms from one read of g
+        elif split_x:
+            g_rows = split_operand(g)
+        elif split_w:
+            g_t = split_operand_transposed(g)
+        if split_x:  # dx = g W: contraction over the rows of W, so W^T's weight operand [K, 6 N]
+            make = ctx.weight_split_t
+            wt = make() if make else split_operand_transposed(weight.detach(), weights=True)
+            grad_x = torch.mm(g_rows, wt.t(), out_dtype=torch.float32).view(x.shape)
+        elif need_x:
+            grad_x = torch.mm(g, weight).view(x.shape)
+        if split_w:  # dW = g^T x: contraction over the (padded) rows of both
+            xt = split_operand_transposed(_rows_2d(x, K), weights=True)
+            grad_w = torch.mm(g_t, xt.t(), out_dtype=torch.float32)
+        elif need_w:
+            grad_w = torch.mm(g.t(), _rows_2d(x, K))
+        if ctx.has_bias and need_b:
+            grad_b = rows_colsum(g)[0]
+        return grad_x, grad_w, grad_b, None, None, None
+
+
+LINEAR_PRODUCTS = ("forward", "dgrad", "wgrad")
+
+
+def linear_split_differentiable(x, weight, bias=None, weight_split=None, weight_split_t=None, library=()):
+    """F.linear(x, weight, bias) for HIP fp32 tensors (x [..., K], weight [N, K], K and N multiples of 8) as a
+    torch.autograd.Function whose three products are fp32-equivalent bf16 x 3 split GEMMs:
+        y  = mm(split_operand(x), split_operand(W, weights=True)^T) + b     -- transformer.linear's values, bit for bit
+        dx = mm(split_operand(g), split_operand_transposed(W, weights=True)^T)
+        dW = mm(split_operand_transposed(g), split_operand_transposed(x, weights=True)^T)      (K' = 6 rows)
+        db = rows_colsum(g)
+    with both operands of g from one read when dx and dW are both wanted, and no product for an input that needs no
+    gradient.  weight_split / weight_split_t: zero-argument callables returning the two weight operands (a caller's
+    cache, looked up only when the operand is needed); None builds them per call.  Always the split path for
+    the sizes it accepts; `library` names the products (of LINEAR_PRODUCTS) a caller has measured slower there and wants
+    as the library's fp32 GEMM inside the same Function -- transformer.train_linear's choice, () here."""
+    x, weight = _need(x, "x"), _need(weight, "weight")
+    if weight.dim() != 2 or x.dim() < 1 or x.shape[-1] != weight.shape[1] or x.numel() == 0:
+        raise AmavError(f"linear_split_differentiable: x {tuple(x.shape)} does not match weight {tuple(weight.shape)}")
+    N, K = weight.shape
+    if K % 8 or N % 8:
+        raise AmavError(f"linear_split_differentiable: K={K} and N={N} must be multiples of 8")
+    if bias is not None:
+        _shaped(bias, "bias", (N,))
+    if any(f is not None and not callable(f) for f in (weight_split, weight_split_t)):
+        raise AmavError("linear_split_differentiable: weight_split / weight_split_t are zero-argument callables or None")
+    library = frozenset(library)
+    if not library <= set(LINEAR_PRODUCTS):
+        raise AmavError(f"linear_split_differentiable: unknown products {sorted(library - set(LINEAR_PRODUCTS))}")
+    weight = weight if weight.is_contiguous() else weight.contiguous()
+    return _LinearSplit.apply(x, weight, bias, weight_split, weight_split_t, library)
 
 
 # -------------------------------------------------------------------------------------------------- point refiner

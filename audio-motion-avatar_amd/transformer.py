@@ -28,8 +28,13 @@ What runs where:
     Both are 2.5-3x / 1.5-2x faster than the library's fp32 GEMM and 2-3x closer to fp64 (tools/gemm_split_probe.py).
     AMAV_GEMM=f32 keeps the fp32 GEMMs, AMAV_GEMM=bf16 the bf16 format everywhere;
   * under autograd on the GPU (width 256..1024, single key): the row passes of a block -- residual adds + LayerNorm, GEGLU
-    -- on the same HIP kernels as inference, with HIP backwards (csrc/attention_rows_backward.hip); fp32 F.linear GEMMs.
-    AMAV_TRAIN_ROWS=library keeps the library's LayerNorm / gelu / mul there.  In .train() with
+    -- on the same HIP kernels as inference, with HIP backwards (csrc/attention_rows_backward.hip).
+    AMAV_TRAIN_ROWS=library keeps the library's LayerNorm / gelu / mul there.  The projections under autograd (q|k|v,
+    to_out, both feed-forward layers, the three of many-key cross-attention) go through `train_linear`:
+    AMAV_TRAIN_GEMM=f32 (the default) is the library's fp32 F.linear; AMAV_TRAIN_GEMM=split runs them as bf16 x 3 split
+    products over operands from the split kernels, the backward's from the transposing one
+    (ops.linear_split_differentiable: forward, dgrad and wgrad), except the products measured slower than the library's
+    fp32 GEMM at the reference shapes -- today every wgrad.  In .train() with
     gradient_checkpointing=True every block is checkpointed, as in the reference;
   * GroupNorm, proj_in / proj_out, CPU: library kernels through torch (fp32 GEMMs).
 """
@@ -49,6 +54,14 @@ _MEMO = {}  # (name, ids of the tensors it was derived from) -> (their versions,
 SPLIT_GEMM_MIN_ROWS = 256  # below this the operand split costs more than the faster GEMM saves
 SPLIT_GEMM_MAX_K = 1024    # bf16 x 3 format only: the 2048 -> 512 feed-forward output projection ran 126 + 35 (split) us
 #                            against 120 us for the tuned fp32 GEMM (6304 rows; K' = 12288 leaves ~100 output tiles)
+# train_linear under AMAV_TRAIN_GEMM=split, per product (6304 rows, split path with its split kernels against the library's
+# fp32 GEMM; tools/bench_train_gemm.py).  The forward obeys SPLIT_GEMM_MAX_K: 2048 -> 512 ran 126.7
+# against 118.7 us here too.
+TRAIN_SPLIT_DGRAD_MAX_N = 1536  # dgrad contracts over N: 91.9 against 119.6 us at N = 1536 (K = 512), 317.9 against 229.6 us
+#                                 at N = 4096 (K = 512; K' = 24576 leaves ~200 output tiles)
+TRAIN_SPLIT_WGRAD = False       # wgrad contracts over 6 x rows = 37824 into an [N, K] result of 16..128 tiles: 205.1 / 124.0 /
+#                                 430.9 / 219.2 us against 90.3 / 49.2 / 182.8 / 100.7 us (512 -> 1536, 512 -> 512, 512 -> 4096,
+#                                 2048 -> 512): it loses at every reference shape and stays on the library
 FP16_TARGET = 32768.0      # a tensor's bound is scaled to at most this (fp16 max 65504: 2x margin for rounding)
 # The fp16 x 2 parts keep a value exact down to 2^-17 of the scaled bound (absolute error bound * 2^-40 below that).  With
 # the largest actual value at bound * 2^-k, a 2048-term dot product stays at the fp32 level (2^-22 of its largest term)
@@ -138,6 +151,42 @@ def linear(x, weight, bias=None):
     return linear_presplit(ops.split_operand(x2), weight, bias).view(*x.shape[:-1], weight.shape[0])
 
 
+def _train_gemm_split(x, weight, bias):
+    """Whether train_linear sends this product down the split path."""
+    if os.environ.get("AMAV_TRAIN_GEMM", "f32") != "split":
+        return False
+    N, K = weight.shape
+    return (x.is_cuda and weight.is_cuda and x.dtype == weight.dtype == torch.float32
+            and (bias is None or (bias.is_cuda and bias.dtype == torch.float32))
+            and x.numel() // K >= SPLIT_GEMM_MIN_ROWS and K % 8 == 0 and N % 8 == 0)
+
+
+def train_linear(x, weight, bias=None, sources=None):
+    """F.linear(x, weight, bias) under autograd, the sibling of `linear`.  AMAV_TRAIN_GEMM, read per call like
+    AMAV_TRAIN_ROWS: `f32` (the default) is F.linear itself; `split` runs the forward and both backward products of HIP
+    fp32 tensors with at least SPLIT_GEMM_MIN_ROWS rows and K, N multiples of 8 as bf16 x 3 split GEMMs
+    (ops.linear_split_differentiable) and everything else as F.linear.  A product measured slower
+    than the library's at the reference shapes stays an fp32 GEMM (SPLIT_GEMM_MAX_K, TRAIN_SPLIT_DGRAD_MAX_N,
+    TRAIN_SPLIT_WGRAD).  Both weight operands are memoised on `sources`, the parameters `weight` was made from (default:
+    `weight` itself; the concatenated q | k | v and k | v weights are new tensors every call), so an optimizer step or an
+    in-place update rebuilds them."""
+    if not _train_gemm_split(x, weight, bias):
+        return F.linear(x, weight, bias)
+    N, K = weight.shape
+    library = tuple(name for name, lost in (("forward", K > SPLIT_GEMM_MAX_K), ("dgrad", N > TRAIN_SPLIT_DGRAD_MAX_N),
+                                            ("wgrad", not TRAIN_SPLIT_WGRAD)) if lost)
+    if len(library) == 3:
+        return F.linear(x, weight, bias)
+    keys = (weight,) if sources is None else tuple(sources)
+    name = "bf16x3" if sources is None else "bf16x3_cat"  # one parameter: the operand `linear` memoises too
+    w = weight.detach()
+    return ops.linear_split_differentiable(
+        x, weight, bias,
+        weight_split=lambda: _memo(name, keys, lambda: ops.split_operand(w, weights=True)),
+        weight_split_t=lambda: _memo(name + "_t", keys, lambda: ops.split_operand_transposed(w, weights=True)),
+        library=library)
+
+
 class Attention(nn.Module):
     """diffusers `Attention` as configured by the reference: q/k/v without bias, out with
     bias, scale 1/sqrt(dim_head), no mask."""
@@ -217,24 +266,25 @@ class Attention(nn.Module):
     def _forward_cross(self, hidden_states, context):
         """Cross-attention to many keys on the GPU in fp32: k | v from one projection over the concatenated to_k / to_v
         weights, read in place by the kernels.  Without grad the projections go through `linear`; under autograd they are
-        fp32 F.linear and the attention is ops.crossattn_differentiable, whose backward returns dq and a fused dk | dv."""
+        `train_linear` and the attention is ops.crossattn_differentiable, whose backward returns dq and a fused dk | dv."""
         out_w, out_b = self.to_out[0].weight, self.to_out[0].bias
         if torch.is_grad_enabled() and (hidden_states.requires_grad or context.requires_grad or any(
                 w.requires_grad for w in (self.to_q.weight, self.to_k.weight, self.to_v.weight, out_w, out_b))):
-            q = F.linear(hidden_states, self.to_q.weight)
-            kv = F.linear(context, torch.cat([self.to_k.weight, self.to_v.weight], dim=0))   # [B,Sk,2*inner]
-            return F.linear(ops.crossattn_differentiable(q, kv, self.heads, self.dim_head ** -0.5), out_w, out_b)
+            q = train_linear(hidden_states, self.to_q.weight)
+            kv = train_linear(context, torch.cat([self.to_k.weight, self.to_v.weight], dim=0),
+                              sources=(self.to_k.weight, self.to_v.weight))                   # [B,Sk,2*inner]
+            return train_linear(ops.crossattn_differentiable(q, kv, self.heads, self.dim_head ** -0.5), out_w, out_b)
         i = self.inner_dim
         q = linear(hidden_states, self.to_q.weight)
         kv = linear(context, self._kv_weight())
         return linear(ops.crossattn(q, kv[..., :i], kv[..., i:], self.heads), out_w, out_b)
 
     def _forward_differentiable(self, hidden_states):
-        """Self-attention under autograd: one fp32 F.linear over the concatenated q/k/v weights (so that gradients reach
+        """Self-attention under autograd: one `train_linear` over the concatenated q/k/v weights (so that gradients reach
         all three), the MFMA flash kernel with its HIP backward on the GPU (ops.selfattn_differentiable), the library's
         SDPA on the CPU, then to_out."""
-        w = torch.cat([self.to_q.weight, self.to_k.weight, self.to_v.weight], dim=0)
-        qkv = F.linear(hidden_states, w)                                # [B,S,3*inner]
+        ws = (self.to_q.weight, self.to_k.weight, self.to_v.weight)
+        qkv = train_linear(hidden_states, torch.cat(ws, dim=0), sources=ws)   # [B,S,3*inner]
         if qkv.is_cuda and qkv.dtype == torch.float32:
             out = ops.selfattn_differentiable(qkv, self.heads, self.dim_head ** -0.5)
         elif qkv.is_cuda:
@@ -243,7 +293,7 @@ class Attention(nn.Module):
             B, S, _ = qkv.shape
             q, k, v = (t.view(B, S, self.heads, self.dim_head).transpose(1, 2) for t in qkv.split(self.inner_dim, -1))
             out = F.scaled_dot_product_attention(q, k, v).transpose(1, 2).reshape(B, S, self.inner_dim)
-        return F.linear(out, self.to_out[0].weight, self.to_out[0].bias)
+        return train_linear(out, self.to_out[0].weight, self.to_out[0].bias)
 
 
 class GEGLU(nn.Module):
@@ -411,15 +461,16 @@ class BasicTransformerBlock(nn.Module):
             return self.ff(n3) + h
         if single_key and self._train_rows_fused(h, encoder_hidden_states):
             # autograd path on the row kernels: the passes of the inference branch above, each with its HIP backward
-            # (ops.add_layernorm_differentiable / geglu_differentiable).  The GEMMs stay F.linear;
+            # (ops.add_layernorm_differentiable / geglu_differentiable).  The GEMMs are
+            # train_linear: the library's fp32 products, or split products under AMAV_TRAIN_GEMM=split (section 4.19);
             # norm2 and attn2.to_q / to_k have no consumer with a single key and stay outside the graph.
             ff_in, ff_out = self.ff.net[0].proj, self.ff.net[2]
             h, n1 = ops.add_layernorm_differentiable(h, None, None, self.norm1.weight, self.norm1.bias, self.norm1.eps)
             a1 = self.attn1._forward_differentiable(n1)
             row = self.attn2(h[:, :1], encoder_hidden_states)[:, :1]   # [B,1,dim]; to_v / to_out get gradients
             h, n3 = ops.add_layernorm_differentiable(h, a1, row, self.norm3.weight, self.norm3.bias, self.norm3.eps)
-            gated = ops.geglu_differentiable(F.linear(n3, ff_in.weight), bias=ff_in.bias)
-            return F.linear(gated, ff_out.weight, ff_out.bias) + h
+            gated = ops.geglu_differentiable(train_linear(n3, ff_in.weight), bias=ff_in.bias)
+            return train_linear(gated, ff_out.weight, ff_out.bias) + h
         h = self.attn1(self.norm1(h)) + h
         h = self.attn2(self.norm2(h), encoder_hidden_states) + h
         return self.ff(self.norm3(h)) + h

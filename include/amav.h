@@ -664,6 +664,21 @@ int amav_crossattn_backward(int batch, int q_len, int kv_len, int heads, int hea
 int amav_split_operand(int64_t rows, int k, const float *x_dev, int64_t x_row_stride, int weights, int format,
                        int scale_exp, void *out_dev, void *stream);
 
+/* The AMAV_SPLIT_BF16X3 operand of x^T, for the products whose contraction runs over the ROWS of an fp32 tensor: both
+ * backward products of a linear layer (dW = g^T x over the rows of g and x, dx = g W over the rows
+ * of W).  x [rows, k] fp32, the same rules on k, stride and alignment as amav_split_operand.  With
+ * Rp = amav_split_transposed_rows(rows) = rows rounded up to a multiple of 8 (0 for rows <= 0):
+ *   out_t_dev     [k, 6 Rp] bf16: part p of column c at out_t[c, p Rp : p Rp + rows], the Rp - rows entries after it
+ *                 written as +0; part order as amav_split_operand ([x3 x2 x1 x2 x1 x1] for weights = 0, [x1 x2 x3 x1 x2 x1]
+ *                 for weights = 1) and the same three-way split, so every part equals that kernel's bit for bit.
+ *   out_rows_dev  NULL, or [rows, 6 k] bf16: the ACTIVATION operand of x from the same read, bit-identical to
+ *                 amav_split_operand(..., weights = 0, AMAV_SPLIT_BF16X3, ...) whatever `weights` is (a backward needs its
+ *                 upstream gradient in both forms).
+ * One kernel, no atomics, no workspace. */
+int64_t amav_split_transposed_rows(int64_t rows);
+int amav_split_operand_transposed(int64_t rows, int k, const float *x_dev, int64_t x_row_stride, int weights,
+                                  void *out_rows_dev /* may be NULL */, void *out_t_dev, void *stream);
+
 /* GEGLU gate of the transformer feed-forward (src/models/transformers.py:484-508, exact-erf GELU):
  * proj [rows, 2*inner] (row stride in floats) -> [rows, inner] = proj[:, :inner] * gelu(proj[:, inner:]).
  * bias [2*inner] (may be NULL) is added to proj first: the projection's bias when its GEMM ran without one.
