@@ -130,6 +130,19 @@ class AudioDrivenAvatar(nn.Module):
         total = 10 * parts["loss_target"] + 0.05 * parts["smpl_loss_future"]
         return total, parts
 
+    def configure_optimizers(self, lr=1e-4, total_steps=200000, max_grad_norm=1.0):
+        """lightning_model_wrapper.py:642-658 (`AudioDrivenTriplaneAvatarLightning.configure_optimizers`: Adam over
+        self.parameters() at the configured lr, LinearLR from 1.0 to 0.01 over the run's steps, stepped every step) with
+        the Trainer's gradient_clip_val = 1.0 (trainer_factory.py:44-45) inside the optimizer's step: returns
+        (optim.Adam over the parameters that require grad, the LinearLR scheduler).  One iteration is
+
+            loss, _ = model.training_step(...); loss.backward(); optimizer.step(); scheduler.step(); optimizer.zero_grad()
+
+        optimizer.grad_norm holds the norm before the clip (a device tensor; reading it is the caller's only wait)."""
+        from .optim import configure_optimizers
+
+        return configure_optimizers(self, lr, total_steps, max_grad_norm)
+
     # ---- chained windows (demo) ------------------------------------------------------------------------------------
     @torch.no_grad()
     def rollout(self, triplanes, smplx_tokens, audio_features, cam_params, num_windows=None):

@@ -11,6 +11,8 @@ from . import _lib
 from ._lib import (AmavError, Attr, BodyTables, DecodeSource, ImageLossWindow, ImageView, LbsBackwardArgs, PoseParts,
                    RasterArgs, RasterBackwardArgs, TriplaneDecodeBackwardArgs, TriplaneSampleBackwardArgs, check)
 
+OptimTensor, OptimChunk, OptimGroup = (_lib.STRUCTS["amav_optim_" + n] for n in ("tensor", "chunk", "group"))
+
 SCALE_BIAS = 3.9    # src/models/renderer.py:428
 OPACITY_BIAS = 0.0  # src/models/renderer.py:429
 SCALE_MAX = 0.1     # src/models/renderer.py:532
@@ -2506,3 +2508,86 @@ def cluster_max_bn_train_differentiable(x, members, seg, weight, bias, eps):
     mode -- raw maxima, their batch statistics, bn_gelu; the backward is the train backward followed by the routing of each
     maximum's gradient to the first member that attains it.  Differentiable in x, weight and bias."""
     return bn_gelu_train_differentiable(_ClusterMaxRaw.apply(x, members, seg), weight, bias, eps)
+
+
+# ------------------------------------------------------------------------------------------ optimizer (optimizer.hip)
+OPTIM_CHUNK = 16384  # elements per chunk = per work-group visit: 64 iterations of 256 lanes x 16 B in each array
+OPTIM_MAX_GROUPS = _lib.DEFINES["AMAV_OPTIM_MAX_GROUPS"]
+
+
+def optimizer_tables(numels, groups, chunk=OPTIM_CHUNK):
+    """The two tables of amav_grad_norm_clip / amav_adam_step as host arrays (ctypes arrays of the header's structs):
+    tensors[i] = (numel numels[i], group groups[i], addresses still 0) and the chunks (tensor, start) that cut every
+    tensor into pieces of at most `chunk` elements, ascending by (tensor, start); a tensor of 0 elements gets no chunk.
+    Pure Python: nothing here touches a device."""
+    if len(numels) != len(groups):
+        raise ValueError(f"optimizer_tables: {len(numels)} element counts for {len(groups)} group indices")
+    if int(chunk) <= 0:
+        raise ValueError(f"optimizer_tables: chunk={chunk}, expected a positive element count")
+    chunk = int(chunk)
+    tensors = (OptimTensor * len(numels))()
+    starts = []
+    for i, (n, g) in enumerate(zip(numels, groups)):
+        if n < 0 or g < 0:
+            raise ValueError(f"optimizer_tables: tensor {i} has numel={n} group={g}")
+        tensors[i].numel, tensors[i].group = int(n), int(g)
+        starts += [(i, s) for s in range(0, int(n), chunk)]
+    chunks = (OptimChunk * len(starts))()
+    for c, (i, s) in zip(chunks, starts):
+        c.tensor, c.start = i, s
+    return tensors, chunks
+
+
+def optimizer_group(lr, betas, eps, weight_decay, step):
+    """amav_optim_group of torch.optim.Adam's hyper-parameters at step count `step` (>= 1): the bias corrections are
+    formed in double, as torch's single-tensor path forms them, and rounded once."""
+    beta1, beta2 = betas
+    return OptimGroup(lr / (1.0 - beta1 ** step), 1.0 / (1.0 - beta2 ** step) ** 0.5, beta1, beta2, 1.0 - beta1, 1.0 - beta2,
+                      eps, weight_decay)
+
+
+def optimizer_table_to_device(table, device):
+    """A host table (ctypes array) -> uint8 device tensor, through a pinned staging copy that the stream reads later:
+    the host does not wait (torch's pinned allocator keeps the staging block alive until the copy has run)."""
+    nbytes = ctypes.sizeof(table)
+    if nbytes == 0:
+        return torch.empty(0, dtype=torch.uint8, device=device)
+    host = torch.frombuffer(table, dtype=torch.uint8).pin_memory()
+    return torch.empty(nbytes, dtype=torch.uint8, device=device).copy_(host, non_blocking=True)
+
+
+def _optimizer_table(t, name, struct, count):
+    t = _contig(t, name, torch.uint8)
+    if t.numel() < count * ctypes.sizeof(struct):
+        raise AmavError(f"{name}: {t.numel()} bytes hold fewer than {count} entries of {ctypes.sizeof(struct)} bytes")
+    return t.data_ptr()
+
+
+def grad_norm_clip(tensors_dev, num_tensors, chunks_dev, num_chunks, chunk, max_norm, partial=None, norm=None):
+    """amav_grad_norm_clip over device tables (uint8 tensors, optimizer_table_to_device) -> norm, fp32 [2] on the device:
+    norm[0] = the L2 norm of all gradients, norm[1] = min(1, max_norm / (norm[0] + 1e-6)).  No host synchronisation.
+    `partial` (fp64, >= num_chunks) and `norm` are reused when given."""
+    tp = _optimizer_table(tensors_dev, "tensors_dev", OptimTensor, num_tensors)
+    cp = _optimizer_table(chunks_dev, "chunks_dev", OptimChunk, num_chunks)
+    if partial is None:
+        partial = torch.empty(max(num_chunks, 1), dtype=torch.float64, device=tensors_dev.device)
+    elif _need(partial, "partial", torch.float64).numel() < num_chunks or not partial.is_contiguous():
+        raise AmavError(f"partial: {partial.numel()} contiguous fp64 values needed for {num_chunks} chunks")
+    norm = torch.empty(2, device=tensors_dev.device) if norm is None else _shaped(norm, "norm", (2,))
+    _call("amav_grad_norm_clip", tp, num_tensors, cp, num_chunks, chunk, float(max_norm), partial.data_ptr(),
+          norm.data_ptr())
+    return norm
+
+
+def adam_step(tensors_dev, num_tensors, chunks_dev, num_chunks, chunk, groups, coef=None, zero_grad=False):
+    """amav_adam_step over device tables: one fused pass of torch.optim.Adam's update on every chunk.  groups: a sequence
+    of OptimGroup (optimizer_group), indexed by the tensors' group field; coef: None (1) or a one-element fp32 device
+    tensor the gradients are multiplied by on the way in (grad_norm_clip(...)[1:]); zero_grad: also store zeros to the
+    gradients.  The caller bumps the version counters of what was written."""
+    tp = _optimizer_table(tensors_dev, "tensors_dev", OptimTensor, num_tensors)
+    cp = _optimizer_table(chunks_dev, "chunks_dev", OptimChunk, num_chunks)
+    if len(groups) > OPTIM_MAX_GROUPS:
+        raise AmavError(f"adam_step: {len(groups)} groups, at most {OPTIM_MAX_GROUPS}")
+    table = (OptimGroup * len(groups))(*groups)
+    coef_ptr = None if coef is None else _need(coef, "coef").data_ptr()
+    _call("amav_adam_step", tp, num_tensors, cp, num_chunks, chunk, table, len(groups), coef_ptr, int(bool(zero_grad)))

@@ -920,6 +920,71 @@ int amav_gemm_split_fp16_tune(int64_t rows, int n, int k3, const void *a_fp16, c
                               float *heuristic_ms, void *stream);
 const char *amav_gemm_library_version(void);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * The tail of a training step (csrc/optimizer.hip): Lightning's clip of the global L2 norm of all
+ * gradients (trainer_factory.py:44-45, gradient_clip_val = 1.0 -> torch.nn.utils.clip_grad_norm_) and torch.optim.Adam's
+ * update (lightning_model_wrapper.py:366-382, 642-658), over any number of fp32 tensors in three launches.  No atomics,
+ * no host synchronisation, every sum in an order fixed by the tables: a call is deterministic bit for bit.
+ *
+ * Tables (device memory, written by the caller, never read on the host -- the contract below is the caller's):
+ *   tensors [num_tensors] amav_optim_tensor: the four addresses of a tensor (4-byte aligned is enough; 16-byte aligned
+ *                         addresses take the 16-byte path), its element count and the index of its amav_optim_group.
+ *   chunks  [num_chunks]  amav_optim_chunk: elements [start, min(start + chunk, numel)) of tensor `tensor`.  The chunks
+ *                         partition every tensor (no element twice: two chunks of one update must not overlap), ordered
+ *                         by (tensor, start); a tensor of 0 elements has no chunk.  One work-group handles one chunk;
+ *                         with more than 2048 chunks work-group b takes chunks b, b + 2048, ... .  A chunk whose tensor,
+ *                         start or group index is out of range is skipped by the kernels (it adds 0 to the norm).
+ * `chunk` (elements, > 0) is the caller's choice: it sets the granularity of the work and of the partial sums.
+ *
+ * amav_grad_norm_clip   partial[c] (fp64 [num_chunks], `partial_dev`) = the sum of grad^2 over chunk c, accumulated in
+ *                       fp64 from exact fp64 squares: per lane in element order, a shuffle tree inside the wave, the 4 waves
+ *                       in order.  Then one work-group adds the partials (fp64; lane l takes l, l + 256, ... in order, then
+ *                       the same tree) and writes norm_dev[0] = (float)sqrt(sum) and
+ *                       norm_dev[1] = min(1, max_norm / (norm_dev[0] + 1e-6f)) in fp32 (clip_grad_norm_'s coefficient; a NaN
+ *                       norm gives a NaN coefficient, as torch.clamp does).  num_tensors == 0 or num_chunks == 0: no table is
+ *                       needed and norm_dev = {0, 1}.
+ * amav_adam_step        per element, fp32, with h = groups[tensor.group] and c = *coef_dev (NULL: 1):
+ *                           g = grad * c;  if (h.weight_decay != 0) g += h.weight_decay * param
+ *                           exp_avg    += h.one_minus_beta1 * (g - exp_avg)
+ *                           exp_avg_sq  = h.beta2 * exp_avg_sq + h.one_minus_beta2 * g * g
+ *                           param      -= h.step_size * (exp_avg / (sqrt(exp_avg_sq) * h.inv_sqrt_bc2 + h.eps))
+ *                       torch.optim.Adam's single-tensor formula (eps outside the bias-corrected root).  `groups` is a HOST
+ *                       array of num_groups <= AMAV_OPTIM_MAX_GROUPS entries, passed to the kernel by value: the caller
+ *                       computes step_size = lr / (1 - beta1^t) and inv_sqrt_bc2 = 1 / sqrt(1 - beta2^t) in double per step
+ *                       and nothing has to be uploaded.  grad is only read (the clipped gradient is never stored), unless
+ *                       zero_grad != 0: then the same pass stores zeros to it.  28 bytes of traffic per element (32 with
+ *                       zero_grad) after the norm's 4.  The version counters of the tensors are the caller's to bump.
+ */
+#define AMAV_OPTIM_MAX_GROUPS 16
+typedef struct amav_optim_tensor {
+    float *param;
+    float *grad;
+    float *exp_avg;
+    float *exp_avg_sq;
+    int64_t numel;
+    int32_t group;
+    int32_t reserved;
+} amav_optim_tensor;
+typedef struct amav_optim_chunk {
+    int64_t start;
+    int32_t tensor;
+    int32_t reserved;
+} amav_optim_chunk;
+typedef struct amav_optim_group {
+    float step_size;    /* lr / (1 - beta1^t) */
+    float inv_sqrt_bc2; /* 1 / sqrt(1 - beta2^t) */
+    float beta1;
+    float beta2;
+    float one_minus_beta1;
+    float one_minus_beta2;
+    float eps;
+    float weight_decay;
+} amav_optim_group;
+int amav_grad_norm_clip(const void *tensors_dev, int num_tensors, const void *chunks_dev, int num_chunks, int chunk,
+                        float max_norm, void *partial_dev, float *norm_dev, void *stream);
+int amav_adam_step(const void *tensors_dev, int num_tensors, const void *chunks_dev, int num_chunks, int chunk,
+                   const amav_optim_group *groups, int num_groups, const float *coef_dev, int zero_grad, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
