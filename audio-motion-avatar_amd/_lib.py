@@ -132,6 +132,7 @@ PoseParts = STRUCTS["amav_pose_parts"]
 LbsBackwardArgs = STRUCTS["amav_lbs_backward_args"]
 ImageView = STRUCTS["amav_image_view"]  # element (n, y, x, c) at ptr[n * image + y * row + x * pixel + c * channel stride]
 ImageLossWindow = STRUCTS["amav_image_loss_window"]
+Conv3x3Args = STRUCTS["amav_conv3x3_args"]
 
 _lib = None
 

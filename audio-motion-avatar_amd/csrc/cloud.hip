@@ -26,6 +26,7 @@
 #include <cmath>
 
 #include "amav_common.h"
+#include "split_f16.h"
 
 namespace amav {
 namespace cloud {
@@ -283,18 +284,8 @@ __global__ __launch_bounds__(256) void pair_gemm_kernel(const float *__restrict_
 // accumulation -- the fp32 product to 2^-22 at a third of the matrix time.  Scaling (exact powers of two): the weights
 // by one exponent from their largest magnitude (static: subm_weights_split_kernel writes it into the prepared buffer's
 // header), the features by one exponent from the largest |feature| of the call (feat_absmax_kernel -> `scratch`).
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-constexpr size_t kSplitHeader = 256;  // prepared weights: [0] float largest |w|, [1] int scale exponent
-
-__device__ __forceinline__ int f16_scale_exp(float amax) {
-    if (!(amax > 0.f)) return 0;
-    return max(-100, min(100, 14 - ilogbf(amax)));
-}
-__device__ __forceinline__ void split2(float x, _Float16 &a, _Float16 &b) {
-    a = (_Float16)x;
-    b = (_Float16)__builtin_fmaf((float)a, -1.0f, x);
-}
+// f16x8 / f16x4, f16_scale_exp and split2: split_f16.h
+using amav::kSplitHeader;
 
 __global__ __launch_bounds__(256) void absmax_kernel(const float4 *__restrict__ x4, long long n4, unsigned *__restrict__ out) {
     float m = 0.f;

@@ -8,7 +8,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (AmavError, Attr, BodyTables, DecodeSource, ImageLossWindow, ImageView, LbsBackwardArgs, PoseParts,
+from ._lib import (AmavError, Attr, BodyTables, Conv3x3Args, DecodeSource, ImageLossWindow, ImageView, LbsBackwardArgs, PoseParts,
                    RasterArgs, RasterBackwardArgs, TriplaneDecodeBackwardArgs, TriplaneSampleBackwardArgs, check)
 
 OptimTensor, OptimChunk, OptimGroup = (_lib.STRUCTS["amav_optim_" + n] for n in ("tensor", "chunk", "group"))
@@ -2049,6 +2049,72 @@ def subm_pair_gemm_split(feat, pair_src, tap_start, tile_start, tiles, weights_s
           pair_src.data_ptr(), tap_start.data_ptr(), tile_start.data_ptr(), weights_split.data_ptr(),
           scratch.data_ptr(), products.data_ptr())
     return products
+
+
+def _no_autograd(name, *tensors):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise AmavError(f"{name} carries no autograd: an input requires grad (call it under torch.no_grad())")
+
+
+def conv3x3_prepare_weights(weight, out_scale=None):
+    """torch's convolution weight [C_out,C_in,3,3] (times out_scale [C_out] per output channel when given) -> uint8 device
+    buffer: two scaled fp16 parts in MFMA fragment order (include/amav.h, amav_conv3x3_prepare_weights_split), the
+    `weights_split` of conv3x3_cells."""
+    _no_autograd("conv3x3_prepare_weights", weight, out_scale)
+    weight = _contig(weight, "weight")
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        raise AmavError(f"conv3x3_prepare_weights: expected [C_out,C_in,3,3], got {tuple(weight.shape)}")
+    cout, cin = weight.shape[:2]
+    nbytes = _lib.lib().amav_conv3x3_weights_split_bytes(cin, cout)
+    if nbytes == 0:
+        raise AmavError(f"conv3x3_prepare_weights: channels must be multiples of 32, got {cin} -> {cout}")
+    out = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
+    _call("amav_conv3x3_prepare_weights_split", cin, cout, weight.data_ptr(),
+          None if out_scale is None else _shaped(out_scale, "out_scale", (cout,)).data_ptr(), out.data_ptr(), nbytes)
+    return out
+
+
+def conv3x3_cells(x, weights_split, cout, bias=None, *, upsample_input=False, in_scale=None, in_shift=None, origin=None,
+                  extent=0, relu_out=False, residual=None):
+    """3x3 convolution (stride 1, zero padding 1) over independent channels-last cells on the 16-bit matrix pipe
+    (include/amav.h, amav_conv3x3_cells): x [K,h,w,C_in] -> [K,H,W,cout], H = 2h with upsample_input (nearest x2 folded
+    into the gather).  in_scale / in_shift [C_in]: relu(in_scale x + in_shift) in front; origin int32 [K,2] + extent: taps
+    outside the plane read zero; bias [cout], relu_out, residual [K,H,W,cout]: the epilogue, in that order."""
+    _no_autograd("conv3x3_cells", x, bias, in_scale, in_shift, residual)
+    x = _contig(x, "x")
+    if x.dim() != 4:
+        raise AmavError(f"conv3x3_cells: x must be [K,h,w,C_in], got {tuple(x.shape)}")
+    K, h, w, cin = x.shape
+    H, W = (2 * h, 2 * w) if upsample_input else (h, w)
+    cout = int(cout)
+    need = _lib.lib().amav_conv3x3_weights_split_bytes(cin, cout)
+    if need == 0 or _need(weights_split, "weights_split", torch.uint8).numel() != need:
+        raise AmavError(f"conv3x3_cells: weights_split was not prepared for {cin} -> {cout} channels")
+    if (in_scale is None) != (in_shift is None):
+        raise AmavError("conv3x3_cells: in_scale and in_shift come together")
+    a = Conv3x3Args()
+    a.cells, a.height, a.width, a.cin, a.cout = K, H, W, cin, cout
+    a.upsample_input, a.relu_out, a.extent = int(bool(upsample_input)), int(bool(relu_out)), int(extent)
+    a.x_dev, a.weights_split_dev, a.weights_split_bytes = x.data_ptr(), weights_split.data_ptr(), need
+    if in_scale is not None:
+        a.in_scale_dev = _shaped(in_scale, "in_scale", (cin,)).data_ptr()
+        a.in_shift_dev = _shaped(in_shift, "in_shift", (cin,)).data_ptr()
+    if origin is not None:
+        origin = _contig(origin, "origin", torch.int32)
+        if tuple(origin.shape) != (K, 2):
+            raise AmavError(f"conv3x3_cells: origin must be int32 [{K},2], got {tuple(origin.shape)}")
+        a.origin_dev = origin.data_ptr()
+    if bias is not None:
+        a.bias_dev = _shaped(bias, "bias", (cout,)).data_ptr()
+    if residual is not None:
+        a.residual_dev = _shaped(residual, "residual", (K, H, W, cout)).data_ptr()
+    out = torch.empty(K, H, W, cout, device=x.device)
+    workspace = _scratch("amav_conv3x3_workspace_bytes", x.device)
+    a.out_dev, a.workspace_dev, a.workspace_bytes = out.data_ptr(), workspace.data_ptr(), workspace.numel()
+    if K == 0:
+        return out
+    _call("amav_conv3x3_cells", ctypes.byref(a))
+    return out
 
 
 def subm_pair_sum(products, pair_of, bias=None):

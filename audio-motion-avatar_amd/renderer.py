@@ -717,6 +717,7 @@ class TriplaneUpsampler(nn.Module):
             out = cached
         planes = tokens.view(F, C, 3, resolution, resolution)
         ov = out.view(F, C, 3, r_out, r_out)
+        hip = self._use_hip_conv(tokens, differentiable)
         t_in, t_out, g = self.TILE_CELLS * s_in, self.TILE_CELLS * scale, resolution // self.TILE_CELLS
         P = t_in + 4
         for p, w in enumerate(plan):
@@ -752,15 +753,20 @@ class TriplaneUpsampler(nn.Module):
                 return wv[f_idx, :, ty - ay, :, tx - ax, :]
 
             def validity(step, first, length):
-                """float [K,1,length,length] (or None when all ones): 1 where row ty step + first + j and the matching
-                column lie inside the plane at that level (plane size = extent / t_out * step)."""
+                """float [K,1,length,length] (or, on the library path, None when all ones): 1 where row ty step + first + j
+                and the matching column lie inside the plane at that level (plane size = extent / t_out * step)."""
                 size = extent // t_out * step
                 pos = torch.arange(length, device=tokens.device) + first
                 vy = ((ty * step)[:, None] + pos >= 0) & ((ty * step)[:, None] + pos < size)
                 vx = ((tx * step)[:, None] + pos >= 0) & ((tx * step)[:, None] + pos < size)
-                if bool(vy.all() and vx.all()):
+                if not hip and bool(vy.all() and vx.all()):  # (host sync; the HIP branch multiplies unconditionally)
                     return None
                 return (vy[:, :, None] & vx[:, None, :]).to(tokens.dtype)[:, None]
+
+            def origins(step, first):
+                """int32 [K,2]: the plane position (y, x) of every cell's first texel, what validity(step, first, .)
+                encodes as a mask image."""
+                return torch.stack((ty * step + first, tx * step + first), 1).int()
 
             chain = n >= 2 and bool(getattr(self.cfg, "upsample_tile_chain", True))
             if chain:
@@ -769,8 +775,13 @@ class TriplaneUpsampler(nn.Module):
                 s2 = 2 ** (n - 2)
                 t2 = self.TILE_CELLS * s2
                 act2, skip2 = self._run(crop, 0, n - 2)
-                res = self._mosaic(self.upsample_blocks[n - 2], tile_windows(act2, s2, 3, t2 + 6),
-                                   validity(t_in, -6, 2 * (t2 + 6)), p, 0)[:, :, 4:-4, 4:-4]           # [K,C,P,P]
+                if hip:
+                    res = self._tile_block_hip(self.upsample_blocks[n - 2], tile_windows(act2, s2, 3, t2 + 6),
+                                               origins(t_in, -6), extent // t_out * t_in)
+                else:
+                    res = self._mosaic(self.upsample_blocks[n - 2], tile_windows(act2, s2, 3, t2 + 6),
+                                       validity(t_in, -6, 2 * (t2 + 6)), p, 0)
+                res = res[:, :, 4:-4, 4:-4]                                                             # [K,C,P,P]
                 skip1 = self.skip_connections[n - 2](tile_windows(skip2, s2, 1, t2 + 2))                # [K,C,P,P]
                 cells = res + skip1
                 inside = validity(t_in, -2, P)   # the padded tile's positions outside the plane are zero padding
@@ -782,10 +793,80 @@ class TriplaneUpsampler(nn.Module):
                 # the padding is only ever read where the crop ends at the plane's own border: zeros, as the reference pads
                 cells = tile_windows(act, s_in, 2, P)
                 skips = tile_windows(skip, s_in, 0, t_in)
-            vals = self._mosaic(self.upsample_blocks[n - 1], cells, validity(t_out, -4, 2 * P), p, 1)
+            if hip:
+                vals = self._tile_block_hip(self.upsample_blocks[n - 1], cells, origins(t_out, -4), extent)
+            else:
+                vals = self._mosaic(self.upsample_blocks[n - 1], cells, validity(t_out, -4, 2 * P), p, 1)
             vals = vals[:, :, 4:4 + t_out, 4:4 + t_out] + self.skip_connections[n - 1](skips)
             ov.view(F, C, 3, g, t_out, g, t_out)[f_idx, :, p, ty, :, tx, :] = vals
         return out
+
+    def _use_hip_conv(self, tokens, differentiable):
+        """True when the tile stages run on ops.conv3x3_cells: AMAV_UPSAMPLER_CONV=hip (read per call; unset:
+        cfg.upsample_conv), and nothing the kernel lacks is asked for -- no autograd, device tensors, eval-mode BatchNorm,
+        channels a multiple of 32.  Otherwise the library path runs."""
+        mode = os.environ.get("AMAV_UPSAMPLER_CONV") or getattr(self.cfg, "upsample_conv", "library")
+        if mode not in ("library", "hip"):
+            raise ValueError(f"AMAV_UPSAMPLER_CONV / cfg.upsample_conv: expected 'library' or 'hip', got {mode!r}")
+        if mode != "hip" or differentiable or self.training or not tokens.is_cuda or tokens.shape[1] % 32:
+            return False
+        if tokens.dtype != torch.float32 or any(not q.is_cuda for q in self.parameters()):
+            return False
+        return not (torch.is_grad_enabled() and (tokens.requires_grad or any(q.requires_grad for q in self.parameters())))
+
+    @staticmethod
+    def _bn_fold(bn):
+        """Eval-mode BatchNorm as (scale, shift), folded in fp64."""
+        scale = torch.rsqrt(bn.running_var.double() + bn.eps)
+        if bn.weight is not None:
+            scale = scale * bn.weight.double()
+        shift = -bn.running_mean.double() * scale
+        if bn.bias is not None:
+            shift = shift + bn.bias.double()
+        return scale, shift
+
+    def _prepared_block(self, block):
+        """Split weights and folded vectors of one UpsampleBlock for _tile_block_hip, memoised on the version counter and
+        address of every tensor they derive from (optim.Adam and load_state_dict update in place and bump the version)."""
+        _, conv1, _, res = block.upsample
+        bn0, _, conv_a, bn1, _, conv_b = res.block
+        assert isinstance(res.skip, nn.Identity), "UpsampleBlock of the upsampler keeps its width: ResBlock.skip is Identity"
+        sources = [t for m in (conv1, conv_a, conv_b) for t in (m.weight, m.bias)]
+        sources += [t for bn in (bn0, bn1) for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)]
+        key = tuple((ops.tensor_version(t), t.data_ptr()) for t in sources if t is not None)
+        if not hasattr(self, "_conv_memo"):
+            self._conv_memo = {}
+        hit = self._conv_memo.get(id(block))
+        if hit is None or hit[0] != key:
+            with torch.no_grad():
+                s0, t0 = self._bn_fold(bn0)
+                s1, t1 = self._bn_fold(bn1)
+                bias_a = t1 if conv_a.bias is None else s1 * conv_a.bias.double() + t1
+                prepared = dict(
+                    w1=ops.conv3x3_prepare_weights(conv1.weight.detach()), b1=conv1.bias,
+                    in_scale=s0.float().contiguous(), in_shift=t0.float().contiguous(),
+                    wa=ops.conv3x3_prepare_weights(conv_a.weight.detach(), s1.float().contiguous()),
+                    ba=bias_a.float().contiguous(),
+                    wb=ops.conv3x3_prepare_weights(conv_b.weight.detach()), bb=conv_b.bias)
+            hit = (key, prepared)
+            self._conv_memo[id(block)] = hit
+        return hit[1]
+
+    def _tile_block_hip(self, block, cells, origin, extent):
+        """One UpsampleBlock over independent cells [K,C,P,P] -> [K,C,2P,2P] (a channels-last view) in three launches of
+        ops.conv3x3_cells, what _mosaic + _last_block compute on the library: every cell is zero padded on its own (the
+        mosaic's neighbours only ever reach the halo the caller cuts away), and `origin` int32 [K,2] / `extent` state
+        where a cell lies in its plane, so that positions outside the plane are the reference's zero padding for the
+        second and third convolution (the `valid` images of _last_block).  Eval-mode BatchNorm: bn0 is the second
+        launch's prologue, bn1 is folded into conv_a's prepared weights and bias."""
+        w = self._prepared_block(block)
+        C = cells.shape[1]
+        with torch.no_grad():
+            x = ops.conv3x3_cells(cells.permute(0, 2, 3, 1), w["w1"], C, w["b1"], upsample_input=True, relu_out=True)
+            r = ops.conv3x3_cells(x, w["wa"], C, w["ba"], in_scale=w["in_scale"], in_shift=w["in_shift"], origin=origin,
+                                  extent=extent, relu_out=True)
+            out = ops.conv3x3_cells(r, w["wb"], C, w["bb"], origin=origin, extent=extent, residual=x)
+        return out.permute(0, 3, 1, 2)
 
     def _mosaic(self, block, cells, valid, plane, stage):
         """One UpsampleBlock over cells [K,C,p,p] -> [K,C,2p,2p].  The cells are laid out as ONE mosaic image, 8 cells

@@ -470,6 +470,56 @@ int amav_windows_cut_backward(int num_frames, int channels, int height, int widt
                               const float *grad_windows_dev, int step, int off_y, int off_x, int lattice_rows,
                               int lattice_cols, const int32_t *lattice_dev, float *grad_x_dev, void *stream);
 
+/* 3x3 convolution, stride 1, over K independent cells in channels-last layout: the two tile stages of the windowed
+ * triplane upsampler (three nn.Conv2d(C, C, 3, padding=1) per UpsampleBlock, src/models/renderer.py:348-375) without the
+ * mosaic image the library needed.  x [K,h,w,Cin] -> out [K,H,W,Cout], fp32, zero padding of 1 around every cell; an
+ * implicit GEMM of K H W rows, Cout columns and a contraction of 9 Cin on the 16-bit MFMA pipe: both operands as two fp16
+ * parts scaled by one power of two each, three partial products per fp32 product, fp32 accumulation (the arithmetic of
+ * amav_subm_pair_gemm_split).  The weights' exponent is in the prepared buffer's header; the activations' comes from the
+ * largest magnitude of the operand after the prologue, found by one sweep inside the call (into the workspace).
+ *
+ * amav_conv3x3_weights_split_bytes: size of the prepared weights (256-byte header + 9 cin cout x 2 fp16); 0 = channels
+ *   that are not positive multiples of 32.
+ * amav_conv3x3_prepare_weights_split: weights [cout,cin,3,3] (torch's layout), out_scale NULL or [cout]: weight
+ *   [co,:,:,:] is multiplied by out_scale[co] before the split (an eval-mode BatchNorm behind the convolution folds
+ *   into it).  out: 256-byte aligned, out_bytes >= the size above (else AMAV_ERR_WORKSPACE).
+ * amav_conv3x3_cells, in the order the operand is built:
+ *   upsample_input   x is [K,H/2,W/2,Cin] and tap (y + dy, x + dx) reads input texel ((y + dy) >> 1, (x + dx) >> 1): a
+ *                    nearest x2 folded into the gather.  H and W must be even.
+ *   in_scale, in_shift  [Cin], both or neither: the prologue relu(in_scale x + in_shift) on every texel read.
+ *   zeros            a tap outside the cell, [0,H) x [0,W) at the OUTPUT resolution, reads 0; with origin int32 [K,2]
+ *                    (the cell's first texel (y, x) in plane coordinates at the output level; may be negative) so does a
+ *                    tap whose plane position is outside [0, extent) on either axis.  Both are zeros of the
+ *                    convolution's operand: they apply after the prologue (a padded tap is 0, not relu(in_shift)).
+ *   epilogue         out = acc (+ bias [Cout]) -> max(., 0) if relu_out -> + residual [K,H,W,Cout] if given.
+ * workspace: amav_conv3x3_workspace_bytes() bytes, 16-byte aligned.  Refused with an error code before any launch: NULL
+ * args / x / weights_split / out, sizes <= 0, channels that are not multiples of 32, odd H or W with upsample_input,
+ * in_scale without in_shift (or the reverse), origin with extent <= 0, misaligned x / in_scale / in_shift, a
+ * weights_split_bytes or workspace below the required size (AMAV_ERR_WORKSPACE).  Element offsets are 64-bit.  No float
+ * atomics: bitwise the same on every run.  No allocation and no host synchronisation. */
+typedef struct amav_conv3x3_args {
+    int64_t cells;                   /* K */
+    int32_t height, width;           /* H, W of the output */
+    int32_t cin, cout;
+    int32_t upsample_input, relu_out;
+    int32_t extent;                  /* plane size at the output level; read only with origin_dev */
+    const float *x_dev;              /* [K,H,W,Cin], or [K,H/2,W/2,Cin] with upsample_input */
+    const void *weights_split_dev;   /* from amav_conv3x3_prepare_weights_split */
+    size_t weights_split_bytes;
+    const float *in_scale_dev, *in_shift_dev; /* [Cin] or NULL */
+    const int32_t *origin_dev;       /* [K,2] or NULL */
+    const float *bias_dev;           /* [Cout] or NULL */
+    const float *residual_dev;       /* [K,H,W,Cout] or NULL */
+    float *out_dev;                  /* [K,H,W,Cout] */
+    void *workspace_dev;
+    size_t workspace_bytes;
+} amav_conv3x3_args;
+size_t amav_conv3x3_weights_split_bytes(int cin, int cout);
+size_t amav_conv3x3_workspace_bytes(void);
+int amav_conv3x3_prepare_weights_split(int cin, int cout, const float *weights_dev, const float *out_scale_dev,
+                                       void *out_dev, size_t out_bytes, void *stream);
+int amav_conv3x3_cells(const amav_conv3x3_args *args, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Image loss of the two training steps: L1 and SSIM (src/utils/loss_utils.py:18-19, 24-84) of N images of H x W x C,
  * forward and backward.  SSIM uses the reference's separable 11-tap window, zero padding of 5 (taps outside the image

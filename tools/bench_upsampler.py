@@ -2,12 +2,16 @@
 """Diagnostic: time of the TriplaneUpsampler (renderer.py:377-417) at the reference defaults (4 blocks, C=256,
 32^2 -> 512^2, three planes per frame) and of the default-config frame (upsampler + refiner at 30 000 points).
 
-    python tools/bench_upsampler.py [frames] [--backward] [--full-frames N] [--training-step]
+    python tools/bench_upsampler.py [frames] [--backward] [--full-frames N] [--training-step] [--conv library|hip|both]
 
 --backward: forward + backward of the upsampler under autograd (loss = weighted sum of the features sampled at the
 body's points), windowed (forward_tokens_windowed(differentiable=True)) against full planes (forward_tokens, on
 --full-frames frames, default 1), each with torch.cuda.max_memory_allocated and, for the windowed path, the share of the
 time spent in the two window-cutting kernels (HIP events around ops.windows_cut / ops.windows_cut_backward).
+--conv: only the windowed evaluation, with its tile stages on the library's convolutions (the mosaic images) or on the HIP
+3x3 cell convolution (AMAV_UPSAMPLER_CONV).  `both` alternates the two in one process on one plan
+and prints ms per frame for each, the largest difference inside the active tiles and, for the HIP launches, their
+HIP-event time and the FLOP they issue (3 partial products x 2 M 9 C_in C_out) against the dense 16-bit MFMA peak.
 --training-step: one full stage-2 AudioDrivenAvatar.training_step, forward + backward, at the reference's default
 renderer.yaml (upsampler + refiner, 30 000 points, every differentiable_* flag on) with its peak allocated memory.
 """
@@ -27,9 +31,14 @@ from audio_motion_avatar_amd.synthetic import init_random_heads, make_render_inp
 
 from audio_motion_avatar_amd import ops  # noqa: E402
 
-_positional = [a for i, a in enumerate(sys.argv[1:], 1) if not a.startswith("--") and sys.argv[i - 1] != "--full-frames"]
+_positional = [a for i, a in enumerate(sys.argv[1:], 1)
+               if not a.startswith("--") and sys.argv[i - 1] not in ("--full-frames", "--conv")]
 F = int(_positional[0]) if _positional else 2
 FULL_FRAMES = int(sys.argv[sys.argv.index("--full-frames") + 1]) if "--full-frames" in sys.argv else 1
+CONV = sys.argv[sys.argv.index("--conv") + 1] if "--conv" in sys.argv else None
+if CONV not in (None, "library", "hip", "both"):
+    sys.exit("--conv takes library, hip or both")
+MFMA_16BIT_PEAK_TFLOPS = 2516.6  # bench.py: dense fp16 MFMA, 32x32x16 in 32 cycles per SIMD, 1024 SIMDs, 2.4 GHz
 
 
 def training_step():
@@ -98,6 +107,68 @@ def flops():
         total += 3 * (2.0 * res * res * c * c * 9) + (2.0 * (res // 2) ** 2 * c * c if i == 0 else 0.0)
     return 3 * total  # three planes
 
+
+def compare_conv():
+    """The windowed evaluation under AMAV_UPSAMPLER_CONV = library / hip, alternating on one plan."""
+    modes = ("library", "hip") if CONV == "both" else (CONV,)
+    R, rounds = cfg.triplane_resolution, 5
+    launches = []  # (start event, stop event, issued FLOP) of every HIP convolution
+    conv = ops.conv3x3_cells
+
+    def timed_conv(x, weights_split, cout, *a, **k):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        y = conv(x, weights_split, cout, *a, **k)
+        e1.record()
+        launches.append((e0, e1, 3 * 2.0 * y.shape[0] * y.shape[1] * y.shape[2] * 9 * x.shape[3] * cout))
+        return y
+
+    ops.conv3x3_cells = timed_conv
+    with torch.no_grad():
+        pts = r.get_smpl_vertices(smpl)
+        plan = up.plan_windows(pts, R, cfg.radius)
+        slabs, times = {}, {m: [] for m in modes}
+        for m in modes:  # warm-up: kernel selection of the library, prepared weights of the HIP path
+            os.environ["AMAV_UPSAMPLER_CONV"] = m
+            for _ in range(2):
+                slabs[m] = up.forward_tokens_windowed(tokens[0], R, plan).clone()
+        torch.cuda.synchronize()
+        launches.clear()
+        for _ in range(rounds):
+            for m in modes:
+                os.environ["AMAV_UPSAMPLER_CONV"] = m
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                up.forward_tokens_windowed(tokens[0], R, plan)
+                torch.cuda.synchronize()
+                times[m].append((time.perf_counter() - t0) * 1e3 / F)
+    os.environ.pop("AMAV_UPSAMPLER_CONV", None)
+    ops.conv3x3_cells = conv
+    tiles = sum(len(w["tiles"]) for w in plan if w["tiles"] is not None)
+    print(f"windowed upsampler, {F} frames, {tiles} active tiles, {rounds} alternating rounds (median, min .. max):")
+    for m in modes:
+        t = sorted(times[m])
+        print(f"  {m:8s} {t[len(t) // 2]:7.2f} ms per frame ({t[0]:.2f} .. {t[-1]:.2f})")
+    if launches:
+        ms = sum(a.elapsed_time(b) for a, b, _ in launches) / rounds
+        flop = sum(f for _, _, f in launches) / rounds
+        tf = flop / (ms * 1e-3) / 1e12
+        print(f"  hip convolutions: {len(launches) // rounds} launches, {ms / F:.2f} ms per frame by HIP events (the operand sweep "
+              f"included), {flop / F / 1e12:.3f} TFLOP issued per frame -> {tf:.0f} TFLOP/s = "
+              f"{tf / MFMA_16BIT_PEAK_TFLOPS * 100:.1f} % of the 16-bit MFMA peak ({MFMA_16BIT_PEAK_TFLOPS:.0f}); "
+              f"fp32-equivalent {tf / 3:.0f} TFLOP/s")
+    if CONV == "both":
+        r_out, t = R * 2 ** cfg.num_upsample_blocks, 4 * 2 ** cfg.num_upsample_blocks
+        a, b = (slabs[m].view(F, -1, 3, r_out, r_out) for m in modes)
+        err = max(float((a[f, :, p, ty * t:(ty + 1) * t, tx * t:(tx + 1) * t]
+                         - b[f, :, p, ty * t:(ty + 1) * t, tx * t:(tx + 1) * t]).abs().max())
+                  for p, w in enumerate(plan) if w["tiles"] is not None for f, ty, tx in w["tiles"].tolist())
+        print(f"  max |library - hip| inside the active tiles {err:.2e} (largest |value| {float(a.abs().max()):.2e})")
+
+
+if CONV:
+    compare_conv()
+    sys.exit(0)
 
 with torch.no_grad():
     for _ in range(2):
