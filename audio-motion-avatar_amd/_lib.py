@@ -133,6 +133,7 @@ LbsBackwardArgs = STRUCTS["amav_lbs_backward_args"]
 ImageView = STRUCTS["amav_image_view"]  # element (n, y, x, c) at ptr[n * image + y * row + x * pixel + c * channel stride]
 ImageLossWindow = STRUCTS["amav_image_loss_window"]
 Conv3x3Args = STRUCTS["amav_conv3x3_args"]
+Conv3x3BackwardArgs = STRUCTS["amav_conv3x3_backward_args"]
 
 _lib = None
 

@@ -33,6 +33,9 @@ class RendererConfig:
     upsample_windows: bool = True     # upsample only the plane regions the body's points can sample (renderer.py, TriplaneUpsampler)
     upsample_conv: str = "library"    # the tile stages' convolutions: "library" | "hip" (3x3 split-product kernel, DESIGN.md
     #                                   section 4.6); the environment variable AMAV_UPSAMPLER_CONV, read per call, overrides
+    upsample_conv_grad: str = "library"  # the tile stages under differentiable_upsampler: "library" | "hip" (the same kernel
+    #                                   under autograd with a HIP backward, deterministic); the
+    #                                   environment variable AMAV_UPSAMPLER_CONV_GRAD, read per call, overrides
     upsample_frames_per_pass: int = 8    # Renderer.forward splits longer calls (upsampled planes: 805 MB per frame)
     upsample_window_margin: float = 0.05  # metres kept free around the points for the refiner's offsets (checked; falls back)
     densify_smplx_verts: bool = True

@@ -8,7 +8,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (AmavError, Attr, BodyTables, Conv3x3Args, DecodeSource, ImageLossWindow, ImageView, LbsBackwardArgs, PoseParts,
+from ._lib import (AmavError, Attr, BodyTables, Conv3x3Args, Conv3x3BackwardArgs, DecodeSource, ImageLossWindow, ImageView, LbsBackwardArgs, PoseParts,
                    RasterArgs, RasterBackwardArgs, TriplaneDecodeBackwardArgs, TriplaneSampleBackwardArgs, check)
 
 OptimTensor, OptimChunk, OptimGroup = (_lib.STRUCTS["amav_optim_" + n] for n in ("tensor", "chunk", "group"))
@@ -2115,6 +2115,144 @@ def conv3x3_cells(x, weights_split, cout, bias=None, *, upsample_input=False, in
         return out
     _call("amav_conv3x3_cells", ctypes.byref(a))
     return out
+
+
+def conv3x3_prepare_weights_transposed(weight):
+    """torch's convolution weight [C_out,C_in,3,3] -> the prepared weights of conv3x3_cells' DATA gradient
+    (amav_conv3x3_prepare_weights_split_transposed): W'[ci,co,a,b] = W[co,ci,2-a,2-b], split as conv3x3_prepare_weights."""
+    _no_autograd("conv3x3_prepare_weights_transposed", weight)
+    weight = _contig(weight, "weight")
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        raise AmavError(f"conv3x3_prepare_weights_transposed: expected [C_out,C_in,3,3], got {tuple(weight.shape)}")
+    cout, cin = weight.shape[:2]
+    nbytes = _lib.lib().amav_conv3x3_weights_split_bytes(cout, cin)
+    if nbytes == 0:
+        raise AmavError(f"conv3x3_prepare_weights_transposed: channels must be multiples of 32, got {cin} -> {cout}")
+    out = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
+    _call("amav_conv3x3_prepare_weights_split_transposed", cin, cout, weight.data_ptr(), out.data_ptr(), nbytes)
+    return out
+
+
+def conv3x3_cells_backward(grad_out, x, weights_split_t=None, *, out=None, upsample_input=False, in_scale=None, in_shift=None,
+                           origin=None, extent=0, relu_out=False, want_x=True, want_weight=True, want_bias=True,
+                           want_prologue=None, wgrad_slices=0):
+    """Backward of conv3x3_cells (include/amav.h, amav_conv3x3_cells_backward): grad_out [K,H,W,C_out], the forward's x
+    and options, `out` the forward's result when relu_out, weights_split_t from conv3x3_prepare_weights_transposed (read
+    for grad_x and the prologue's gradients).  -> (grad_x, grad_weight [C_out,C_in,3,3], grad_bias, grad_in_scale,
+    grad_in_shift), None for what was not wanted (want_prologue None: wanted when there is a prologue).  wgrad_slices:
+    split-K slices of the weight gradient, 0 = the library's heuristic.  Fixed summation orders: deterministic."""
+    _no_autograd("conv3x3_cells_backward", grad_out, x, in_scale, in_shift, out)
+    grad_out, x = _contig(grad_out, "grad_out"), _contig(x, "x")
+    if x.dim() != 4 or grad_out.dim() != 4:
+        raise AmavError(f"conv3x3_cells_backward: x must be [K,h,w,C_in] and grad_out [K,H,W,C_out], got {tuple(x.shape)}, "
+                        f"{tuple(grad_out.shape)}")
+    K, h, w, cin = x.shape
+    H, W = (2 * h, 2 * w) if upsample_input else (h, w)
+    cout = grad_out.shape[3]
+    if tuple(grad_out.shape) != (K, H, W, cout):
+        raise AmavError(f"conv3x3_cells_backward: grad_out {tuple(grad_out.shape)} does not match x {tuple(x.shape)}")
+    need = _lib.lib().amav_conv3x3_weights_split_bytes(cout, cin)
+    if need == 0:
+        raise AmavError(f"conv3x3_cells_backward: channels must be multiples of 32, got {cin} -> {cout}")
+    if (in_scale is None) != (in_shift is None):
+        raise AmavError("conv3x3_cells_backward: in_scale and in_shift come together")
+    want_prologue = in_scale is not None if want_prologue is None else bool(want_prologue)
+    if want_prologue and in_scale is None:
+        raise AmavError("conv3x3_cells_backward: want_prologue without a prologue")
+    if not (want_x or want_weight or want_bias or want_prologue):
+        raise AmavError("conv3x3_cells_backward: no gradient asked for")
+    a = Conv3x3BackwardArgs()
+    a.cells, a.height, a.width, a.cin, a.cout = K, H, W, cin, cout
+    a.upsample_input, a.relu_out, a.extent, a.wgrad_slices = int(bool(upsample_input)), int(bool(relu_out)), int(extent), int(wgrad_slices)
+    a.x_dev, a.grad_out_dev = x.data_ptr(), grad_out.data_ptr()
+    if want_x or want_prologue:
+        if weights_split_t is None or _need(weights_split_t, "weights_split_t", torch.uint8).numel() != need:
+            raise AmavError(f"conv3x3_cells_backward: weights_split_t was not prepared for {cin} -> {cout} channels")
+        a.weights_split_t_dev, a.weights_split_t_bytes = weights_split_t.data_ptr(), need
+    if in_scale is not None:
+        a.in_scale_dev = _shaped(in_scale, "in_scale", (cin,)).data_ptr()
+        a.in_shift_dev = _shaped(in_shift, "in_shift", (cin,)).data_ptr()
+    if origin is not None:
+        origin = _contig(origin, "origin", torch.int32)
+        if tuple(origin.shape) != (K, 2):
+            raise AmavError(f"conv3x3_cells_backward: origin must be int32 [{K},2], got {tuple(origin.shape)}")
+        a.origin_dev = origin.data_ptr()
+    if relu_out:
+        if out is None:
+            raise AmavError("conv3x3_cells_backward: relu_out needs the forward's out")
+        a.out_dev = _shaped(out, "out", (K, H, W, cout)).data_ptr()
+    dev = x.device
+    grad_x = torch.empty(K, h, w, cin, device=dev) if want_x else None
+    grad_weight = torch.empty(cout, cin, 3, 3, device=dev) if want_weight else None
+    grad_bias = torch.empty(cout, device=dev) if want_bias else None
+    grad_scale = torch.empty(cin, device=dev) if want_prologue else None
+    grad_shift = torch.empty(cin, device=dev) if want_prologue else None
+    result = (grad_x, grad_weight, grad_bias, grad_scale, grad_shift)
+    if K == 0:
+        for t in result[1:]:
+            if t is not None:
+                t.zero_()
+        return result
+    for field, t in zip(("grad_x_dev", "grad_weight_dev", "grad_bias_dev", "grad_in_scale_dev", "grad_in_shift_dev"), result):
+        if t is not None:
+            setattr(a, field, t.data_ptr())
+    nbytes = _lib.lib().amav_conv3x3_backward_workspace_bytes(ctypes.byref(a), int(wgrad_slices))
+    if nbytes == 0:
+        raise AmavError("amav_conv3x3_backward_workspace_bytes rejected the call: " + _lib.lib().amav_last_error().decode())
+    workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    a.workspace_dev, a.workspace_bytes = workspace.data_ptr(), nbytes
+    _call("amav_conv3x3_cells_backward", ctypes.byref(a))
+    return result
+
+
+class _Conv3x3Cells(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, in_scale, in_shift, residual, origin, upsample_input, extent, relu_out):
+        x = _contig(x, "x")
+        out = conv3x3_cells(x, conv3x3_prepare_weights(weight), weight.shape[0], bias, upsample_input=upsample_input,
+                            in_scale=in_scale, in_shift=in_shift, origin=origin, extent=extent, relu_out=relu_out,
+                            residual=residual)
+        ctx.options = dict(upsample_input=upsample_input, extent=extent, relu_out=relu_out)
+        ctx.origin = origin
+        ctx.save_for_backward(x, weight, in_scale, in_shift, out if relu_out else None)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, weight, in_scale, in_shift, out = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        grad_out = grad_out.float().contiguous()
+        grads = [None] * 5
+        if any(need[:5]):
+            data = need[0] or need[3] or need[4]
+            grads = conv3x3_cells_backward(
+                grad_out, x, conv3x3_prepare_weights_transposed(weight) if data else None, out=out, in_scale=in_scale,
+                in_shift=in_shift, origin=ctx.origin, want_x=need[0], want_weight=need[1], want_bias=need[2],
+                want_prologue=need[3] or need[4], **ctx.options)
+        gx, gw, gb, gs, gt = grads
+        return (gx, gw, gb, gs if need[3] else None, gt if need[4] else None, grad_out if need[5] else None, None, None,
+                None, None)
+
+
+def conv3x3_cells_differentiable(x, weight, bias=None, *, upsample_input=False, in_scale=None, in_shift=None, origin=None,
+                                 extent=0, relu_out=False, residual=None):
+    """conv3x3_cells under autograd, over the plain fp32 weight [C_out,C_in,3,3]: the forward prepares the split weights
+    and runs the HIP kernel, the backward is conv3x3_cells_backward (the same kernel on the transposed, flipped weights
+    for the data gradient, a split-product MFMA GEMM for the weight gradient, fixed-order column sums for bias and
+    prologue; deterministic).  Gradients flow to x, weight, bias, in_scale, in_shift and residual, to those that require
+    them.  relu_out together with residual is refused: the backward gates on the saved output's sign."""
+    if relu_out and residual is not None:
+        raise AmavError("conv3x3_cells_differentiable: relu_out together with residual is not differentiable here "
+                        "(the ReLU's gate is read from the saved output)")
+    _need(x, "x"), _need(weight, "weight")
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or x.dim() != 4 or weight.shape[1] != x.shape[3]:
+        raise AmavError(f"conv3x3_cells_differentiable: expected x [K,h,w,C_in] and weight [C_out,C_in,3,3], got "
+                        f"{tuple(x.shape)}, {tuple(weight.shape)}")
+    if weight.shape[0] % 32 or weight.shape[1] % 32 or weight.shape[0] == 0 or weight.shape[1] == 0:
+        raise AmavError(f"conv3x3_cells_differentiable: channels must be multiples of 32, got {weight.shape[1]} -> {weight.shape[0]}")
+    return _Conv3x3Cells.apply(x, weight, bias, in_scale, in_shift, residual, origin, bool(upsample_input), int(extent),
+                               bool(relu_out))
 
 
 def subm_pair_sum(products, pair_of, bias=None):

@@ -718,6 +718,9 @@ class TriplaneUpsampler(nn.Module):
         planes = tokens.view(F, C, 3, resolution, resolution)
         ov = out.view(F, C, 3, r_out, r_out)
         hip = self._use_hip_conv(tokens, differentiable)
+        hip_grad = self._use_hip_conv_grad(tokens, differentiable)
+        tile_block = self._tile_block_hip_grad if hip_grad else self._tile_block_hip
+        hip = hip or hip_grad
         t_in, t_out, g = self.TILE_CELLS * s_in, self.TILE_CELLS * scale, resolution // self.TILE_CELLS
         P = t_in + 4
         for p, w in enumerate(plan):
@@ -776,8 +779,8 @@ class TriplaneUpsampler(nn.Module):
                 t2 = self.TILE_CELLS * s2
                 act2, skip2 = self._run(crop, 0, n - 2)
                 if hip:
-                    res = self._tile_block_hip(self.upsample_blocks[n - 2], tile_windows(act2, s2, 3, t2 + 6),
-                                               origins(t_in, -6), extent // t_out * t_in)
+                    res = tile_block(self.upsample_blocks[n - 2], tile_windows(act2, s2, 3, t2 + 6),
+                                     origins(t_in, -6), extent // t_out * t_in)
                 else:
                     res = self._mosaic(self.upsample_blocks[n - 2], tile_windows(act2, s2, 3, t2 + 6),
                                        validity(t_in, -6, 2 * (t2 + 6)), p, 0)
@@ -794,7 +797,7 @@ class TriplaneUpsampler(nn.Module):
                 cells = tile_windows(act, s_in, 2, P)
                 skips = tile_windows(skip, s_in, 0, t_in)
             if hip:
-                vals = self._tile_block_hip(self.upsample_blocks[n - 1], cells, origins(t_out, -4), extent)
+                vals = tile_block(self.upsample_blocks[n - 1], cells, origins(t_out, -4), extent)
             else:
                 vals = self._mosaic(self.upsample_blocks[n - 1], cells, validity(t_out, -4, 2 * P), p, 1)
             vals = vals[:, :, 4:4 + t_out, 4:4 + t_out] + self.skip_connections[n - 1](skips)
@@ -813,6 +816,18 @@ class TriplaneUpsampler(nn.Module):
         if tokens.dtype != torch.float32 or any(not q.is_cuda for q in self.parameters()):
             return False
         return not (torch.is_grad_enabled() and (tokens.requires_grad or any(q.requires_grad for q in self.parameters())))
+
+    def _use_hip_conv_grad(self, tokens, differentiable):
+        """True when a differentiable evaluation runs its tile stages on ops.conv3x3_cells_differentiable (HIP forward and
+        backward, deterministic gradients): AMAV_UPSAMPLER_CONV_GRAD=hip (read per call; unset: cfg.upsample_conv_grad),
+        device fp32 tensors and parameters, channels a multiple of 32, eval-mode BatchNorm.  Otherwise the library path
+        runs.  AMAV_UPSAMPLER_CONV does not bear on it."""
+        mode = os.environ.get("AMAV_UPSAMPLER_CONV_GRAD") or getattr(self.cfg, "upsample_conv_grad", "library")
+        if mode not in ("library", "hip"):
+            raise ValueError(f"AMAV_UPSAMPLER_CONV_GRAD / cfg.upsample_conv_grad: expected 'library' or 'hip', got {mode!r}")
+        if mode != "hip" or not differentiable or self.training or not tokens.is_cuda or tokens.shape[1] % 32:
+            return False
+        return tokens.dtype == torch.float32 and all(q.is_cuda and q.dtype == torch.float32 for q in self.parameters())
 
     @staticmethod
     def _bn_fold(bn):
@@ -866,6 +881,24 @@ class TriplaneUpsampler(nn.Module):
             r = ops.conv3x3_cells(x, w["wa"], C, w["ba"], in_scale=w["in_scale"], in_shift=w["in_shift"], origin=origin,
                                   extent=extent, relu_out=True)
             out = ops.conv3x3_cells(r, w["wb"], C, w["bb"], origin=origin, extent=extent, residual=x)
+        return out.permute(0, 3, 1, 2)
+
+    def _tile_block_hip_grad(self, block, cells, origin, extent):
+        """_tile_block_hip under autograd: the same three convolutions through ops.conv3x3_cells_differentiable.  The
+        eval-mode BatchNorms are folded in torch (fp64, as _bn_fold, then fp32) inside the graph -- bn0 as the second
+        convolution's prologue vectors, bn1 into conv_a's weight and bias -- so their affine parameters, trainable in
+        eval mode, get their gradients from autograd's chain through the fold."""
+        _, conv1, _, res = block.upsample
+        bn0, _, conv_a, bn1, _, conv_b = res.block
+        assert isinstance(res.skip, nn.Identity), "UpsampleBlock of the upsampler keeps its width: ResBlock.skip is Identity"
+        s0, t0 = self._bn_fold(bn0)
+        s1, t1 = self._bn_fold(bn1)
+        w_a = (s1[:, None, None, None] * conv_a.weight.double()).float()
+        b_a = (t1 if conv_a.bias is None else s1 * conv_a.bias.double() + t1).float()
+        conv = ops.conv3x3_cells_differentiable
+        x = conv(cells.permute(0, 2, 3, 1), conv1.weight, conv1.bias, upsample_input=True, relu_out=True)
+        r = conv(x, w_a, b_a, in_scale=s0.float(), in_shift=t0.float(), origin=origin, extent=extent, relu_out=True)
+        out = conv(r, conv_b.weight, conv_b.bias, origin=origin, extent=extent, residual=x)
         return out.permute(0, 3, 1, 2)
 
     def _mosaic(self, block, cells, valid, plane, stage):

@@ -520,6 +520,58 @@ int amav_conv3x3_prepare_weights_split(int cin, int cout, const float *weights_d
                                        void *out_dev, size_t out_bytes, void *stream);
 int amav_conv3x3_cells(const amav_conv3x3_args *args, void *stream);
 
+/* Backward of amav_conv3x3_cells.  With Z = inside o relu(in_scale up(x) + in_shift) the forward's operand (prologue and
+ * up optional; `inside`: the cell's zero padding and the plane rule), y = conv(Z, W) + bias, out = relu(y) if relu_out,
+ * and g = grad_out [K,H,W,Cout]:
+ *   ga           = g where out > 0 with relu_out (the gate reads out_dev, the forward's saved result; a forward that also
+ *                  added a residual cannot be gated from it, so the two do not combine), else g.  grad_residual = g.
+ *   grad_bias    [Cout] = column sum of ga.
+ *   gZ           = the same 3x3 cell convolution of ga (the cell's own zero padding, no prologue, no plane rule) with the
+ *                  weights W'[ci,co,a,b] = W[co,ci,2-a,2-b]: amav_conv3x3_cells' kernel on weights_split_t_dev from
+ *                  amav_conv3x3_prepare_weights_split_transposed, ga built while the operand is staged; the sweep for
+ *                  its exponent sees ga.
+ *   grad_x       [K,h,w,Cin] = in_scale * pool(gZ m), m = inside o [in_scale up(x) + in_shift > 0]; pool adds the 2 x 2
+ *                  fine texels of a coarse one in row-major order (upsample_input only).
+ *   grad_in_scale, grad_in_shift [Cin] = column sums of gZ m up(x) and of gZ m.
+ *   grad_weight  [Cout,Cin,3,3] (torch's layout) = sum over all texels of ga[co] Z[ci] shifted by the tap: a split-product
+ *                  MFMA GEMM over K H W texels.  Split-K: the (cell, tile) pairs are cut into `wgrad_slices` contiguous
+ *                  ranges (0: a heuristic that fills the CUs within 64 MiB of workspace; at most 4096), each range
+ *                  writes its own partial, a second kernel adds the partials in ascending order.
+ * Every sum has a fixed order and nothing is accumulated with atomics: bitwise the same on every run.  A NULL gradient
+ * pointer skips that gradient's work; grad_in_scale and grad_in_shift come together and need the prologue.
+ * amav_conv3x3_backward_workspace_bytes: the workspace this call needs (it depends on which gradients are asked for and
+ * on the slice count); 0 = the arguments would be refused.  Refused with an error code before any launch: everything
+ * amav_conv3x3_cells refuses, NULL grad_out, relu_out without out_dev, misaligned grad_out / out / gradients, a slice
+ * count outside [0, 4096], no gradient asked for at all, a workspace below the required size (AMAV_ERR_WORKSPACE).
+ * Element offsets are 64-bit.  No allocation and no host synchronisation.
+ * amav_conv3x3_prepare_weights_split_transposed: weights [cout,cin,3,3] -> the prepared weights of the data gradient
+ * (amav_conv3x3_weights_split_bytes(cout, cin) bytes, 256-byte aligned). */
+typedef struct amav_conv3x3_backward_args {
+    int64_t cells;                   /* K */
+    int32_t height, width;           /* H, W of the output */
+    int32_t cin, cout;
+    int32_t upsample_input, relu_out;
+    int32_t extent;
+    int32_t wgrad_slices;            /* 0 = heuristic */
+    const float *x_dev;              /* the forward's x */
+    const void *weights_split_t_dev; /* from amav_conv3x3_prepare_weights_split_transposed; read for grad_x / in_scale */
+    size_t weights_split_t_bytes;
+    const float *in_scale_dev, *in_shift_dev;
+    const int32_t *origin_dev;
+    const float *out_dev;            /* the forward's result [K,H,W,Cout]; read only with relu_out */
+    const float *grad_out_dev;       /* [K,H,W,Cout] */
+    float *grad_x_dev;               /* [K,h,w,Cin] or NULL */
+    float *grad_weight_dev;          /* [Cout,Cin,3,3] or NULL */
+    float *grad_bias_dev;            /* [Cout] or NULL */
+    float *grad_in_scale_dev, *grad_in_shift_dev; /* [Cin], both or neither */
+    void *workspace_dev;
+    size_t workspace_bytes;
+} amav_conv3x3_backward_args;
+int amav_conv3x3_prepare_weights_split_transposed(int cin, int cout, const float *weights_dev, void *out_dev,
+                                                  size_t out_bytes, void *stream);
+size_t amav_conv3x3_backward_workspace_bytes(const amav_conv3x3_backward_args *args, int wgrad_slices);
+int amav_conv3x3_cells_backward(const amav_conv3x3_backward_args *args, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Image loss of the two training steps: L1 and SSIM (src/utils/loss_utils.py:18-19, 24-84) of N images of H x W x C,
  * forward and backward.  SSIM uses the reference's separable 11-tap window, zero padding of 5 (taps outside the image

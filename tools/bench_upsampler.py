@@ -12,6 +12,10 @@ time spent in the two window-cutting kernels (HIP events around ops.windows_cut 
 3x3 cell convolution (AMAV_UPSAMPLER_CONV).  `both` alternates the two in one process on one plan
 and prints ms per frame for each, the largest difference inside the active tiles and, for the HIP launches, their
 HIP-event time and the FLOP they issue (3 partial products x 2 M 9 C_in C_out) against the dense 16-bit MFMA peak.
+--backward --conv library|hip|both: forward + backward of the windowed evaluation with its tile stages' gradients on the
+library or on the HIP backward (AMAV_UPSAMPLER_CONV_GRAD); `both` alternates the two in one
+process on one plan: ms per frame (median, range) and peak allocated memory for each, and, for the HIP path, HIP-event
+times of its data-gradient and weight-gradient launches replayed one by one, with the FLOP they issue.
 --training-step: one full stage-2 AudioDrivenAvatar.training_step, forward + backward, at the reference's default
 renderer.yaml (upsampler + refiner, 30 000 points, every differentiable_* flag on) with its peak allocated memory.
 """
@@ -166,8 +170,80 @@ def compare_conv():
         print(f"  max |library - hip| inside the active tiles {err:.2e} (largest |value| {float(a.abs().max()):.2e})")
 
 
+def compare_conv_grad():
+    """Forward + backward of the windowed evaluation under AMAV_UPSAMPLER_CONV_GRAD = library / hip, alternating on one
+    plan; then every HIP backward call of one step replayed alone: its data gradient (with the column sums and the
+    operand's row kernel) and its weight gradient under HIP events."""
+    modes = ("library", "hip") if CONV == "both" else (CONV,)
+    R, rounds = cfg.triplane_resolution, 3
+    r_out = R * 2 ** cfg.num_upsample_blocks
+    with torch.no_grad():
+        pts = r.get_smpl_vertices(smpl).contiguous()
+        plan = up.plan_windows(pts, R, cfg.radius)
+    tok = tokens[0].clone().requires_grad_()
+    weights = torch.randn(F, pts.shape[1], 3 * cfg.triplane_feature_dim, generator=torch.Generator().manual_seed(3)).cuda()
+
+    def step():
+        r.zero_grad(set_to_none=True)
+        tok.grad = None
+        slab = up.forward_tokens_windowed(tok, R, plan, differentiable=True)
+        planes = slab.view(F, -1, 3, r_out, r_out).permute(0, 2, 1, 3, 4)
+        (ops.triplane_sample_features_differentiable(planes, pts, cfg.radius) * weights).sum().backward()
+
+    times, peaks = {m: [] for m in modes}, {m: 0.0 for m in modes}
+    for m in modes:
+        os.environ["AMAV_UPSAMPLER_CONV_GRAD"] = m
+        step()
+    for _ in range(rounds):
+        for m in modes:
+            os.environ["AMAV_UPSAMPLER_CONV_GRAD"] = m
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            t0 = time.perf_counter()
+            step()
+            torch.cuda.synchronize()
+            times[m].append((time.perf_counter() - t0) * 1e3 / F)
+            peaks[m] = max(peaks[m], torch.cuda.max_memory_allocated() / 2 ** 30)
+    tiles = sum(len(w["tiles"]) for w in plan if w["tiles"] is not None)
+    print(f"windowed upsampler, forward + backward, {F} frames per call, {tiles} active tiles, {rounds} alternating rounds "
+          f"(median, min .. max):")
+    for m in modes:
+        t = sorted(times[m])
+        print(f"  {m:8s} {t[len(t) // 2]:7.2f} ms per frame ({t[0]:.2f} .. {t[-1]:.2f}), peak allocated {peaks[m]:.2f} GiB", flush=True)
+    if "hip" in modes:
+        os.environ["AMAV_UPSAMPLER_CONV_GRAD"] = "hip"
+        backward, recorded = ops.conv3x3_cells_backward, []
+        ops.conv3x3_cells_backward = lambda *a, **k: (recorded.append((a, k)), backward(*a, **k))[1]
+        step()
+        ops.conv3x3_cells_backward = backward
+        torch.cuda.synchronize()
+        totals = {"data": [0.0, 0.0], "weight": [0.0, 0.0]}  # ms, FLOP
+        with torch.no_grad():
+            for a, k in recorded:
+                K, H, W, cout = a[0].shape
+                flop = 3 * 2.0 * K * H * W * 9 * a[1].shape[3] * cout
+                parts = {"data": dict(k, want_weight=False), "weight": dict(k, want_x=False, want_bias=False, want_prologue=False)}
+                for name, kw in parts.items():
+                    if not (kw["want_x"] or kw["want_weight"] or kw["want_bias"] or kw["want_prologue"]):
+                        continue
+                    backward(*a, **kw)  # warm-up
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    backward(*a, **kw)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    totals[name][0] += e0.elapsed_time(e1)
+                    totals[name][1] += flop if (name == "weight" or kw["want_x"] or kw["want_prologue"]) else 0.0
+        for name, (ms, flop) in totals.items():
+            tf = flop / max(ms, 1e-9) / 1e9
+            print(f"  hip {name} gradient: {len(recorded)} calls, {ms / F:.2f} ms per frame by HIP events (sweeps, column sums and "
+                  f"workspace allocation included), {flop / F / 1e12:.3f} TFLOP issued per frame -> {tf:.0f} TFLOP/s = "
+                  f"{tf / MFMA_16BIT_PEAK_TFLOPS * 100:.1f} % of the 16-bit MFMA peak ({MFMA_16BIT_PEAK_TFLOPS:.0f})")
+    os.environ.pop("AMAV_UPSAMPLER_CONV_GRAD", None)
+
+
 if CONV:
-    compare_conv()
+    compare_conv_grad() if "--backward" in sys.argv else compare_conv()
     sys.exit(0)
 
 with torch.no_grad():
