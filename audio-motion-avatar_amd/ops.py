@@ -1457,10 +1457,26 @@ def selfattn_lse(qkv, heads, scale=None):
     return out, lse
 
 
-def selfattn_backward(qkv, out, lse, grad_out, heads, scale=None, grad_qkv=None):
+def _attn_backward_split(arithmetic):
+    """False for the exact-fp32 attention backward, True for the fp16 x 2 split products (amav_*attn_backward_split).
+    arithmetic: "f32" | "split"; None follows AMAV_ATTN_BACKWARD (read per call, like AMAV_CROSS_ATTN; default f32)."""
+    chosen = arithmetic if arithmetic is not None else os.environ.get("AMAV_ATTN_BACKWARD", "f32")
+    if chosen == "f32":
+        return False
+    if chosen == "split":
+        return True
+    where = "arithmetic" if arithmetic is not None else "AMAV_ATTN_BACKWARD"
+    raise AmavError(f"attention backward: {where} must be 'f32' or 'split', got {chosen!r}")
+
+
+def selfattn_backward(qkv, out, lse, grad_out, heads, scale=None, grad_qkv=None, arithmetic=None):
     """amav_selfattn_backward: the gradient [B,S,3*H*D] (dq | dk | dv) of a fused qkv given the forward's out and lse
     (selfattn_lse) and grad_out = dLoss/d out.  out / grad_out: [B,S,H*D] with unit inner stride and dense batch stride;
-    grad_qkv: optional [B,S,>=3*H*D] destination view (its first 3*H*D columns are written)."""
+    grad_qkv: optional [B,S,>=3*H*D] destination view (its first 3*H*D columns are written).  arithmetic: "f32" (exact
+    fp32 products) or "split" (amav_selfattn_backward_split: fp16 x 2 split products); None follows AMAV_ATTN_BACKWARD."""
+    sizer, entry = (("amav_selfattn_backward_split_workspace_bytes", "amav_selfattn_backward_split")
+                    if _attn_backward_split(arithmetic) else
+                    ("amav_selfattn_backward_workspace_bytes", "amav_selfattn_backward"))
     B, S, HD, D = _qkv_views(qkv, heads)
     for name, t in (("out", out), ("grad_out", grad_out)):
         _need(t, name)
@@ -1475,10 +1491,10 @@ def selfattn_backward(qkv, out, lse, grad_out, heads, scale=None, grad_qkv=None)
     if (grad_qkv.dim() != 3 or tuple(grad_qkv.shape[:2]) != (B, S) or grad_qkv.shape[2] < 3 * HD
             or grad_qkv.stride(2) != 1 or grad_qkv.stride(0) != S * grad_qkv.stride(1)):
         raise AmavError(f"grad_qkv: need [B,S,>=3*H*D] with unit inner stride, got {tuple(grad_qkv.shape)}")
-    ws = _scratch("amav_selfattn_backward_workspace_bytes", qkv.device, B, S, heads, D,
+    ws = _scratch(sizer, qkv.device, B, S, heads, D,
                   rejected=f"B={B} S={S} H={heads} D={D}")
     p = qkv.data_ptr()
-    _call("amav_selfattn_backward", B, S, heads, D, p, p + 4 * HD, p + 8 * HD, qkv.stride(1), out.data_ptr(),
+    _call(entry, B, S, heads, D, p, p + 4 * HD, p + 8 * HD, qkv.stride(1), out.data_ptr(),
           out.stride(1), lse.data_ptr(), grad_out.data_ptr(), grad_out.stride(1), grad_qkv.data_ptr(),
           grad_qkv.stride(1), float(scale if scale is not None else D ** -0.5), ws.data_ptr(), ws.numel())
     return grad_qkv
@@ -1566,10 +1582,14 @@ def crossattn_lse(q, kv, heads, scale=None):
     return _crossattn(q, *_kv_views(kv, heads), heads, scale, True)
 
 
-def crossattn_backward(q, kv, out, lse, grad_out, heads, scale=None, grad_q=None, grad_kv=None):
+def crossattn_backward(q, kv, out, lse, grad_out, heads, scale=None, grad_q=None, grad_kv=None, arithmetic=None):
     """amav_crossattn_backward: (dq [B,Sq,H*D], dkv [B,Sk,2*H*D] = dk | dv) given the forward's out and lse
     (crossattn_lse) and grad_out = dLoss/d out.  grad_q / grad_kv: optional [B,Sq,>=H*D] / [B,Sk,>=2*H*D] destination
-    views (their first H*D / 2*H*D columns are written)."""
+    views (their first H*D / 2*H*D columns are written).  arithmetic: as selfattn_backward's
+    (amav_crossattn_backward_split)."""
+    sizer, entry = (("amav_crossattn_backward_split_workspace_bytes", "amav_crossattn_backward_split")
+                    if _attn_backward_split(arithmetic) else
+                    ("amav_crossattn_backward_workspace_bytes", "amav_crossattn_backward"))
     k, v = _kv_views(kv, heads)
     B, Sk, HD = k.shape
     Sq = _rows(q, "q", B=B, width=HD).shape[1]
@@ -1583,9 +1603,9 @@ def crossattn_backward(q, kv, out, lse, grad_out, heads, scale=None, grad_q=None
     if grad_kv is None:
         grad_kv = torch.empty(B, Sk, 2 * HD, device=q.device)
     _rows(grad_q, "grad_q", B, Sq, min_width=HD), _rows(grad_kv, "grad_kv", B, Sk, min_width=2 * HD)
-    ws = _scratch("amav_crossattn_backward_workspace_bytes", q.device, B, Sq, heads, D,
+    ws = _scratch(sizer, q.device, B, Sq, heads, D,
                   rejected=f"B={B} Sq={Sq} H={heads} D={D}")
-    _call("amav_crossattn_backward", B, Sq, Sk, heads, D, q.data_ptr(), q.stride(1), k.data_ptr(), v.data_ptr(),
+    _call(entry, B, Sq, Sk, heads, D, q.data_ptr(), q.stride(1), k.data_ptr(), v.data_ptr(),
           kv.stride(1), out.data_ptr(), out.stride(1), lse.data_ptr(), grad_out.data_ptr(), grad_out.stride(1),
           grad_q.data_ptr(), grad_q.stride(1), grad_kv.data_ptr(), grad_kv.stride(1),
           float(scale if scale is not None else D ** -0.5), ws.data_ptr(), ws.numel())

@@ -751,6 +751,28 @@ int amav_crossattn_backward(int batch, int q_len, int kv_len, int heads, int hea
                             int64_t dout_row_stride, float *dq_dev, int64_t dq_row_stride, float *dkv_dev,
                             int64_t dkv_row_stride, float scale, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The two backwards above on fp16 x 2 split products ("split arithmetic"): the same three
+ * passes, arguments, strides, alignment rules and errors, with all seven products on v_mfma_f32_32x32x16_f16 -- two
+ * fp16 parts per operand, three partial products per fp32 product, fp32 sums.  Q, K, V and dO are scaled by powers of
+ * two from their measured call-wide maxima, P by 2^14 and dS by a power of two from the proven bound |dS_ij| <=
+ * 2 max_i |dO_i|_2 max_j |v_j|_2; the maxima are reduced on the device into a header in the workspace (integer atomicMax
+ * on bit patterns: order-independent).  Deterministic bit for bit; because the scales are measured per call, a batch of
+ * two is not bitwise two single calls.  No float atomics, no host synchronisation, HIP-graph capturable.
+ * workspace: the matching ..._split_workspace_bytes (header + delta; 0 = bad sizes). */
+size_t amav_selfattn_backward_split_workspace_bytes(int batch, int seq_len, int heads, int head_dim);
+int amav_selfattn_backward_split(int batch, int seq_len, int heads, int head_dim, const float *q_dev, const float *k_dev,
+                                 const float *v_dev, int64_t row_stride, const float *out_dev, int64_t out_row_stride,
+                                 const float *lse_dev, const float *dout_dev, int64_t dout_row_stride, float *dqkv_dev,
+                                 int64_t dqkv_row_stride, float scale, void *workspace, size_t workspace_bytes,
+                                 void *stream);
+size_t amav_crossattn_backward_split_workspace_bytes(int batch, int q_len, int heads, int head_dim);
+int amav_crossattn_backward_split(int batch, int q_len, int kv_len, int heads, int head_dim, const float *q_dev,
+                                  int64_t q_row_stride, const float *k_dev, const float *v_dev, int64_t kv_row_stride,
+                                  const float *out_dev, int64_t out_row_stride, const float *lse_dev,
+                                  const float *dout_dev, int64_t dout_row_stride, float *dq_dev, int64_t dq_row_stride,
+                                  float *dkv_dev, int64_t dkv_row_stride, float scale, void *workspace,
+                                  size_t workspace_bytes, void *stream);
+
 /* Operand of an fp32-equivalent nn.Linear (src/models/transformers.py:70-84, 448, 505: the to_q/k/v, to_out and
  * feed-forward projections) computed as ONE low-precision GEMM with fp32 accumulation over operands split into parts
  * and concatenated along K.  x [rows, k] fp32 (row stride in floats, k a multiple of 8) -> out [rows, parts * k]:

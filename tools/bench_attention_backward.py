@@ -3,7 +3,13 @@
 row log-sum-exp, backward, and the backward's three kernels (delta pre-pass, key-major dK/dV, query-major dQ) -- and one
 full stage-2 training step (AudioDrivenAvatar.training_step forward + backward, 6 output frames, 8 layers, 512^2
 frames, B = 1) with its peak allocated memory.  Times are medians over repeats between HIP events; the per-kernel split
-is the profiler's device time of each kernel, median over the same repeats.  Prints one JSON line."""
+is the profiler's device time of each kernel, median over the same repeats.  Prints one JSON line.
+
+--arithmetics [rounds]: instead, the exact-fp32 backward and the fp16 x 2 split-product backward (arithmetic="f32" /
+"split") alternating in one process, `rounds` rounds (default 3) of medians of 10 calls each, at the
+self-attention reference shape and the two stage-1 cross-attention shapes (Sq = 3152 and 80 over Sk = 4096, B = 1,
+H = 8): per arithmetic the median over the rounds, the spread between them and the per-kernel split; with --step also
+the stage-2 training step under AMAV_ATTN_BACKWARD=f32 and =split, alternating."""
 import json
 import os
 import statistics
@@ -61,6 +67,63 @@ def attention_numbers(repeats):
             "backward_tflops_fp32": round(flop / (bwd * 1e-3) / 1e12, 1)}
 
 
+def alternate(sides, rounds, repeats=10):
+    """{name: fn} timed in turn, `rounds` times -> {name: {"ms": median of the rounds, "spread_ms": max - min}}."""
+    seen = {name: [] for name in sides}
+    for _ in range(rounds):
+        for name, fn in sides.items():
+            seen[name].append(timed(fn, repeats))
+    return {name: {"ms": round(statistics.median(v), 4), "spread_ms": round(max(v) - min(v), 4)} for name, v in seen.items()}
+
+
+def arithmetic_numbers(rounds):
+    """f32 and split backwards alternating at (B, Sq, Sk, H) = the self-attention reference shape and the two stage-1
+    cross-attention shapes."""
+    H, HD = 8, 8 * 64
+    g = torch.Generator().manual_seed(0)
+    res = {}
+    S = 6304
+    qkv = torch.randn(1, S, 3 * HD, generator=g).cuda()
+    dout = torch.randn(1, S, HD, generator=g).cuda()
+    out, lse = ops.selfattn_lse(qkv, H)
+    grad = torch.empty(1, S, 3 * HD, device="cuda")
+    sides = {a: (lambda a=a: ops.selfattn_backward(qkv, out, lse, dout, H, grad_qkv=grad, arithmetic=a))
+             for a in ("f32", "split")}
+    res[f"self_{S}"] = alternate(sides, rounds)
+    for a, fn in sides.items():
+        res[f"self_{S}"][a]["kernels_ms"] = kernel_split(fn, 10)
+    for Sq, Sk in ((3152, 4096), (80, 4096)):
+        q = torch.randn(1, Sq, HD, generator=g).cuda()
+        kv = torch.randn(1, Sk, 2 * HD, generator=g).cuda()
+        xdout = torch.randn(1, Sq, HD, generator=g).cuda()
+        xout, xlse = ops.crossattn_lse(q, kv, H)
+        dq, dkv = torch.empty(1, Sq, HD, device="cuda"), torch.empty(1, Sk, 2 * HD, device="cuda")
+        sides = {a: (lambda a=a: ops.crossattn_backward(q, kv, xout, xlse, xdout, H, grad_q=dq, grad_kv=dkv, arithmetic=a))
+                 for a in ("f32", "split")}
+        res[f"cross_{Sq}x{Sk}"] = alternate(sides, rounds)
+        for a, fn in sides.items():
+            res[f"cross_{Sq}x{Sk}"][a]["kernels_ms"] = kernel_split(fn, 10)
+    return res
+
+
+def arithmetic_step_numbers(rounds):
+    """The stage-2 training step under AMAV_ATTN_BACKWARD=f32 and =split (read per call), alternating."""
+    step, info = stage2_step()
+
+    def under(value):
+        def run():
+            os.environ["AMAV_ATTN_BACKWARD"] = value
+            try:
+                return step()
+            finally:
+                os.environ.pop("AMAV_ATTN_BACKWARD", None)
+        return run
+
+    under("f32")()
+    torch.cuda.synchronize()
+    return {**alternate({"f32": under("f32"), "split": under("split")}, rounds, repeats=3), **info}
+
+
 def stage2_step(train_transformer=False):
     """-> (step, info): step() runs one AudioDrivenAvatar.training_step forward + backward at the reference configuration
     (B = 1) on seeded inputs.  The model is in .eval(); train_transformer puts .train() on audio_triplane.transformer
@@ -108,7 +171,15 @@ def training_step_numbers(repeats):
 
 
 if __name__ == "__main__":
-    repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 10
+    if "--arithmetics" in sys.argv:
+        at = sys.argv.index("--arithmetics")
+        rounds = int(sys.argv[at + 1]) if len(sys.argv) > at + 1 and sys.argv[at + 1].isdigit() else 3
+        res = {"attention_backward_arithmetics": arithmetic_numbers(rounds)}
+        if "--step" in sys.argv:
+            res["training_step_ms"] = arithmetic_step_numbers(rounds)
+        print(json.dumps(res))
+        sys.exit(0)
+    repeats = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 10
     res = {"attention": attention_numbers(repeats)}
     if "--no-step" not in sys.argv:
         res["training_step"] = training_step_numbers(max(3, repeats // 3))
