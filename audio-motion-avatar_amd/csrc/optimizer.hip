@@ -15,12 +15,17 @@
 //   norm_finish_kernel  one work-group: lane l adds partials l, l + 256, ... in order (fp64), the same tree, and lane 0
 //                       writes norm and coefficient with ordinary vector stores.
 //   adam_kernel         one pass: reads p, g, m, v, writes p, m, v (28 B per element); with `zero` also g (32 B).
+//   pack_kernel         the data-parallel step's fourth launch: scale * g of every tensor into one bucket, which the
+//                       collective then averages in place and the two kernels above read through a second table.
+//   fingerprint_kernel  a wrap-around sum of the bit patterns of one of the four arrays (replicas still in step?), with
+//                       fingerprint_finish_kernel in the two stages of the norm.
 //
 // 16-byte path: when the chunk's first element is 16-byte aligned in every array the kernel touches, lanes move float4;
 // the up to 3 elements left over, and every chunk of a tensor that is not aligned (a view at an odd offset), go one
 // float per lane.  Loads in flight: the Adam pass has 4 x 16 B per lane outstanding per iteration, 4 KiB per wave and
 // 128 KiB per CU at its 8 waves per SIMD; the norm pass has one load per iteration and is unrolled by 4 for the same reason.
 #include <climits>
+#include <cmath>
 
 #include "amav_common.h"
 
@@ -186,7 +191,125 @@ __global__ __launch_bounds__(kBlock) void adam_kernel(const amav_optim_tensor *_
     }
 }
 
-// the checks the two entry points share; `what` names the entry point.  *empty: nothing to launch over
+// Data-parallel step: every gradient times `scale` into one bucket (the buffer the all-reduce runs on), tensor t at
+// bucket[offsets[t]].  8 B per element (a read and a write), 12 with kZero; a tensor without a gradient costs the write.
+// Only [offsets[t], offsets[t] + numel) is ever written: the gaps between tensors belong to the caller.
+__device__ __forceinline__ f32x4 scaled(f32x4 x, float s) {  // one rounding per element, contracted with nothing
+    return f32x4{__fmul_rn(x.x, s), __fmul_rn(x.y, s), __fmul_rn(x.z, s), __fmul_rn(x.w, s)};
+}
+
+template <bool kZero>
+__global__ __launch_bounds__(kBlock) void pack_kernel(const amav_optim_tensor *__restrict__ tensors, int num_tensors,
+                                                      const amav_optim_chunk *__restrict__ chunks, int num_chunks,
+                                                      int chunk, const int64_t *__restrict__ offsets,
+                                                      float *__restrict__ bucket, int64_t bucket_numel, float scale) {
+    for (int ci = blockIdx.x; ci < num_chunks; ci += gridDim.x) {
+        const Piece pc = piece_of(tensors, num_tensors, chunks, ci, chunk);
+        if (pc.count == 0) continue;
+        const int64_t off = offsets[chunks[ci].tensor];
+        if (off < 0 || off > bucket_numel || pc.t.numel > bucket_numel - off) continue;
+        float *dst = bucket + off + pc.start;
+        const gfloat_p __restrict__ out = (gfloat_p)dst;
+        const gfloat4_p __restrict__ out4 = (gfloat4_p)out;
+        const int n4 = pc.count / 4;
+        int done = 0;
+        if (pc.t.grad == nullptr) {  // not used on this rank: zeros travel
+            if (lanes_aligned16(dst)) {
+                for (int i = threadIdx.x; i < n4; i += kBlock) out4[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+                done = n4 * 4;
+            }
+            for (int i = done + threadIdx.x; i < pc.count; i += kBlock) out[i] = 0.0f;
+            continue;
+        }
+        // source and destination never overlap (include/amav.h)
+        const gfloat_p __restrict__ g = (gfloat_p)(pc.t.grad + pc.start);
+        if (lanes_aligned16(pc.t.grad + pc.start, dst)) {
+            const gfloat4_p __restrict__ g4 = (gfloat4_p)g;
+            const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
+            int i = threadIdx.x;
+            // four loads per lane in flight before the first store: written out, since the compiler's own unrolling
+            // keeps every load behind the store in front of it
+            for (; i + 3 * kBlock < n4; i += 4 * kBlock) {
+                const f32x4 x0 = g4[i], x1 = g4[i + kBlock], x2 = g4[i + 2 * kBlock], x3 = g4[i + 3 * kBlock];
+                out4[i] = scaled(x0, scale);
+                out4[i + kBlock] = scaled(x1, scale);
+                out4[i + 2 * kBlock] = scaled(x2, scale);
+                out4[i + 3 * kBlock] = scaled(x3, scale);
+                if (kZero) g4[i] = g4[i + kBlock] = g4[i + 2 * kBlock] = g4[i + 3 * kBlock] = zero;
+            }
+            for (; i < n4; i += kBlock) {
+                out4[i] = scaled(g4[i], scale);
+                if (kZero) g4[i] = zero;
+            }
+            done = n4 * 4;
+        }
+#pragma unroll 4
+        for (int i = done + threadIdx.x; i < pc.count; i += kBlock) {
+            out[i] = __fmul_rn(g[i], scale);
+            if (kZero) g[i] = 0.0f;
+        }
+    }
+}
+
+// the sum over the work-group, returned to every thread; modulo 2^64, so the order does not matter
+__device__ __forceinline__ unsigned long long block_sum_u64(unsigned long long v, unsigned long long *wave_sums) {
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
+    if (threadIdx.x % kWave == 0) wave_sums[threadIdx.x / kWave] = v;
+    __syncthreads();
+    unsigned long long s = 0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) s += wave_sums[w];
+    __syncthreads();
+    return s;
+}
+
+// partial[c] = the sum of the 32-bit patterns of chunk c's elements in array `which`, modulo 2^64
+__global__ __launch_bounds__(kBlock) void fingerprint_kernel(const amav_optim_tensor *__restrict__ tensors, int num_tensors,
+                                                             const amav_optim_chunk *__restrict__ chunks, int num_chunks,
+                                                             int chunk, int which,
+                                                             unsigned long long *__restrict__ partial) {
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    __shared__ unsigned long long wave_sums[kWaves];
+    for (int c = blockIdx.x; c < num_chunks; c += gridDim.x) {
+        const Piece pc = piece_of(tensors, num_tensors, chunks, c, chunk);
+        unsigned long long a = 0;
+        if (pc.count > 0) {
+            const float *base = which == 0 ? pc.t.param : which == 1 ? pc.t.grad : which == 2 ? pc.t.exp_avg : pc.t.exp_avg_sq;
+            if (base != nullptr) {
+                const AMAV_GLOBAL unsigned *x = (const AMAV_GLOBAL unsigned *)(base + pc.start);
+                int done = 0;
+                if (lanes_aligned16(base + pc.start)) {
+                    const AMAV_GLOBAL u32x4 *x4 = (const AMAV_GLOBAL u32x4 *)x;
+                    const int n4 = pc.count / 4;
+#pragma unroll 4
+                    for (int i = threadIdx.x; i < n4; i += kBlock) {
+                        const u32x4 q = x4[i];
+                        a += ((unsigned long long)q.x + q.y) + ((unsigned long long)q.z + q.w);
+                    }
+                    done = n4 * 4;
+                }
+#pragma unroll 4
+                for (int i = done + threadIdx.x; i < pc.count; i += kBlock) a += x[i];
+            }
+        }
+        const unsigned long long s = block_sum_u64(a, wave_sums);
+        if (threadIdx.x == 0) partial[c] = s;
+    }
+}
+
+// one work-group; out[0] = the sum of the partials
+__global__ __launch_bounds__(kBlock) void fingerprint_finish_kernel(int num_chunks,
+                                                                    const unsigned long long *__restrict__ partial,
+                                                                    unsigned long long *__restrict__ out) {
+    __shared__ unsigned long long wave_sums[kWaves];
+    unsigned long long a = 0;
+    for (int c = threadIdx.x; c < num_chunks; c += kBlock) a += partial[c];
+    const unsigned long long s = block_sum_u64(a, wave_sums);
+    if (threadIdx.x == 0) out[0] = s;
+}
+
+// the checks the entry points share; `what` names the entry point.  *empty: nothing to launch over
 inline int check_tables(const char *what, const void *tensors, int num_tensors, const void *chunks, int num_chunks,
                         int chunk, bool *empty) {
     AMAV_REQUIRE(num_tensors >= 0 && num_chunks >= 0, "%s: negative count num_tensors=%d num_chunks=%d", what, num_tensors,
@@ -246,4 +369,46 @@ extern "C" int amav_adam_step(const void *tensors_dev, int num_tensors, const vo
         adam_kernel<false><<<grid_for(num_chunks), kBlock, 0, stream>>>(tensors, num_tensors, chunks, num_chunks, chunk,
                                                                         by_value, num_groups, coef_dev);
     return check_launch("amav_adam_step: adam_kernel");
+}
+
+extern "C" int amav_grads_pack(const void *tensors_dev, int num_tensors, const void *chunks_dev, int num_chunks, int chunk,
+                               const int64_t *offsets_dev, float *bucket_dev, int64_t bucket_numel, float scale,
+                               int zero_source, void *stream_) {
+    bool empty;
+    if (int rc = check_tables("amav_grads_pack", tensors_dev, num_tensors, chunks_dev, num_chunks, chunk, &empty)) return rc;
+    AMAV_REQUIRE(bucket_numel >= 0, "amav_grads_pack: bucket_numel=%lld is negative", (long long)bucket_numel);
+    AMAV_REQUIRE(std::isfinite(scale), "amav_grads_pack: scale=%g is not finite", (double)scale);
+    if (empty) return AMAV_OK;
+    AMAV_REQUIRE(offsets_dev && bucket_dev, "amav_grads_pack: NULL pointer (offsets / bucket)");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const amav_optim_tensor *tensors = static_cast<const amav_optim_tensor *>(tensors_dev);
+    const amav_optim_chunk *chunks = static_cast<const amav_optim_chunk *>(chunks_dev);
+    if (zero_source)
+        pack_kernel<true><<<grid_for(num_chunks), kBlock, 0, stream>>>(tensors, num_tensors, chunks, num_chunks, chunk,
+                                                                       offsets_dev, bucket_dev, bucket_numel, scale);
+    else
+        pack_kernel<false><<<grid_for(num_chunks), kBlock, 0, stream>>>(tensors, num_tensors, chunks, num_chunks, chunk,
+                                                                        offsets_dev, bucket_dev, bucket_numel, scale);
+    return check_launch("amav_grads_pack: pack_kernel");
+}
+
+extern "C" int amav_tensors_fingerprint(const void *tensors_dev, int num_tensors, const void *chunks_dev, int num_chunks,
+                                        int chunk, int which, void *partial_dev, void *out_dev, void *stream_) {
+    bool empty;
+    if (int rc = check_tables("amav_tensors_fingerprint", tensors_dev, num_tensors, chunks_dev, num_chunks, chunk, &empty))
+        return rc;
+    AMAV_REQUIRE(which >= 0 && which <= 3, "amav_tensors_fingerprint: which=%d outside 0..3", which);
+    AMAV_REQUIRE(out_dev, "amav_tensors_fingerprint: NULL pointer (out)");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!empty) {
+        AMAV_REQUIRE(partial_dev, "amav_tensors_fingerprint: NULL pointer (partial)");
+        fingerprint_kernel<<<grid_for(num_chunks), kBlock, 0, stream>>>(
+            static_cast<const amav_optim_tensor *>(tensors_dev), num_tensors, static_cast<const amav_optim_chunk *>(chunks_dev),
+            num_chunks, chunk, which, static_cast<unsigned long long *>(partial_dev));
+        if (int rc = check_launch("amav_tensors_fingerprint: fingerprint_kernel")) return rc;
+    }
+    fingerprint_finish_kernel<<<1, kBlock, 0, stream>>>(empty ? 0 : num_chunks,
+                                                        static_cast<const unsigned long long *>(partial_dev),
+                                                        static_cast<unsigned long long *>(out_dev));
+    return check_launch("amav_tensors_fingerprint: fingerprint_finish_kernel");
 }

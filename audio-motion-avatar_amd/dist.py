@@ -14,6 +14,9 @@ The autoregressive token generator does not shard in time.  Two modes (SURVEY.md
 rolls its own chain from the same reference tokens and nothing but frames is exchanged; "sequential" -- one rank runs
 the exact chain of the demo loop and hands each rank its block of tokens (send_frames / recv_frames / scatter_frames,
 3.2 MB per frame), so only the rendering scales.
+
+Data-parallel training needs one thing from this layer: broadcast_module, which makes the replicas equal before the first
+step; the gradient all-reduce itself lives in optim.Adam(process_group=...).
 """
 import torch
 import torch.distributed as dist
@@ -75,6 +78,22 @@ def scatter_frames(full, total_frames: int, trailing_shape, dtype, device, src: 
         return mine
     s, e = shard_range(total_frames, world, rank)
     return recv_frames((e - s, *trailing_shape), dtype, device, src, group)
+
+
+@torch.no_grad()
+def broadcast_module(module, src=0, group=None, buffers=True):
+    """Rank `src`'s parameters (and, with `buffers`, its buffers) to every rank of the group, in place: the start of a
+    data-parallel run (optim.Adam(process_group=...) keeps replicas equal, it does not make them so).  `src` is a
+    global rank, as in torch.distributed.broadcast.  What was written then has its version counter bumped
+    (torch.autograd.graph.increment_version), since the package's caches of split and packed weights are keyed on it and
+    a collective that writes through the address does not have to move it.  Returns the module."""
+    tensors = list(module.parameters()) + (list(module.buffers()) if buffers else [])
+    if any(t.is_cuda for t in tensors) and dist.get_backend(group) != "nccl":
+        torch.cuda.current_stream().synchronize()  # host-side backend: see send_frames()
+    for t in tensors:
+        dist.broadcast(t, src=src, group=group)
+    torch.autograd.graph.increment_version(tensors)
+    return module
 
 
 class FrameAllGather:

@@ -130,7 +130,7 @@ class AudioDrivenAvatar(nn.Module):
         total = 10 * parts["loss_target"] + 0.05 * parts["smpl_loss_future"]
         return total, parts
 
-    def configure_optimizers(self, lr=1e-4, total_steps=200000, max_grad_norm=1.0):
+    def configure_optimizers(self, lr=1e-4, total_steps=200000, max_grad_norm=1.0, process_group=None):
         """lightning_model_wrapper.py:642-658 (`AudioDrivenTriplaneAvatarLightning.configure_optimizers`: Adam over
         self.parameters() at the configured lr, LinearLR from 1.0 to 0.01 over the run's steps, stepped every step) with
         the Trainer's gradient_clip_val = 1.0 (trainer_factory.py:44-45) inside the optimizer's step: returns
@@ -138,10 +138,11 @@ class AudioDrivenAvatar(nn.Module):
 
             loss, _ = model.training_step(...); loss.backward(); optimizer.step(); scheduler.step(); optimizer.zero_grad()
 
-        optimizer.grad_norm holds the norm before the clip (a device tensor; reading it is the caller's only wait)."""
+        optimizer.grad_norm holds the norm before the clip (a device tensor; reading it is the caller's only wait).
+        process_group: a torch.distributed group for the data-parallel step of optim.Adam; None: one process."""
         from .optim import configure_optimizers
 
-        return configure_optimizers(self, lr, total_steps, max_grad_norm)
+        return configure_optimizers(self, lr, total_steps, max_grad_norm, process_group)
 
     # ---- chained windows (demo) ------------------------------------------------------------------------------------
     @torch.no_grad()

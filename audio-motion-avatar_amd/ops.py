@@ -2815,3 +2815,62 @@ def adam_step(tensors_dev, num_tensors, chunks_dev, num_chunks, chunk, groups, c
     table = (OptimGroup * len(groups))(*groups)
     coef_ptr = None if coef is None else _need(coef, "coef").data_ptr()
     _call("amav_adam_step", tp, num_tensors, cp, num_chunks, chunk, table, len(groups), coef_ptr, int(bool(zero_grad)))
+
+
+# ------------------------------------------------------------------- the data-parallel step's bucket (optimizer.hip)
+def bucket_offsets(numels, align=64):
+    """Where each tensor starts in the bucket of the data-parallel step -> (offsets, total), in elements: an offset is
+    the previous tensor's end rounded up to a multiple of `align`, and so is `total`.  align=64 elements = 256 bytes, the
+    allocator's own granule: a tensor's first element is then 16-byte aligned in the bucket as it is in an allocation of
+    its own, so whether a chunk of the norm / Adam kernels takes their 16-byte path depends on the parameter alone, and a
+    step that reads its gradients from the bucket adds in the order of a step that reads them from ordinary allocations.
+    Pure Python: nothing here touches a device."""
+    align = int(align)
+    if align < 4:
+        raise ValueError(f"bucket_offsets: align={align}, expected at least 4 elements (16 bytes)")
+    offsets, end = [], 0
+    for i, n in enumerate(numels):
+        if n < 0:
+            raise ValueError(f"bucket_offsets: tensor {i} has numel={n}")
+        offsets.append(end)
+        end = -(-(end + int(n)) // align) * align
+    return offsets, end
+
+
+def grads_pack(tensors_dev, num_tensors, chunks_dev, num_chunks, chunk, offsets, bucket, scale=1.0, zero_source=False):
+    """amav_grads_pack over device tables: bucket[offsets[t] + i] = scale * grad_t[i] (one rounding), zeros for a tensor
+    whose grad address is NULL; zero_source: the gradients are zeroed in the same pass.  offsets: int64 device tensor
+    [num_tensors] (bucket_offsets); bucket: contiguous fp32, only the tensors' own ranges are written.  No host
+    synchronisation.  The caller bumps the version counters of gradients it had zeroed."""
+    tp = _optimizer_table(tensors_dev, "tensors_dev", OptimTensor, num_tensors)
+    cp = _optimizer_table(chunks_dev, "chunks_dev", OptimChunk, num_chunks)
+    if _need(offsets, "offsets", torch.int64).numel() < num_tensors or not offsets.is_contiguous():
+        raise AmavError(f"offsets: {offsets.numel()} contiguous int64 values needed for {num_tensors} tensors")
+    if not _need(bucket, "bucket").is_contiguous():
+        raise AmavError("bucket: expected a contiguous fp32 tensor")
+    _call("amav_grads_pack", tp, num_tensors, cp, num_chunks, chunk, offsets.data_ptr(), bucket.data_ptr(), bucket.numel(),
+          float(scale), int(bool(zero_source)))
+    return bucket
+
+
+FINGERPRINT_OF = {"param": 0, "grad": 1, "exp_avg": 2, "exp_avg_sq": 3}
+
+
+def tensors_fingerprint(tensors_dev, num_tensors, chunks_dev, num_chunks, chunk, which, partial=None, out=None):
+    """amav_tensors_fingerprint over device tables -> out, a 0-dim int64 device tensor holding the uint64 sum, modulo
+    2^64, of the 32-bit patterns of every element of the array `which` ("param" | "grad" | "exp_avg" | "exp_avg_sq", or
+    0..3).  No host synchronisation.  `partial` (int64, >= num_chunks) and `out` are reused when given.  Equal values do
+    not prove equal arrays (two swapped elements give the same sum); different values prove different arrays."""
+    tp = _optimizer_table(tensors_dev, "tensors_dev", OptimTensor, num_tensors)
+    cp = _optimizer_table(chunks_dev, "chunks_dev", OptimChunk, num_chunks)
+    which = FINGERPRINT_OF.get(which, which)
+    if partial is None:
+        partial = torch.empty(max(num_chunks, 1), dtype=torch.int64, device=tensors_dev.device)
+    elif _need(partial, "partial", torch.int64).numel() < num_chunks or not partial.is_contiguous():
+        raise AmavError(f"partial: {partial.numel()} contiguous int64 values needed for {num_chunks} chunks")
+    if out is None:
+        out = torch.empty((), dtype=torch.int64, device=tensors_dev.device)
+    elif _need(out, "out", torch.int64).numel() != 1:
+        raise AmavError(f"out: expected one int64 value, got {tuple(out.shape)}")
+    _call("amav_tensors_fingerprint", tp, num_tensors, cp, num_chunks, chunk, int(which), partial.data_ptr(), out.data_ptr())
+    return out

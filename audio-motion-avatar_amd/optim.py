@@ -14,10 +14,15 @@ split weights are keyed on (transformer.py, renderer.py, point_transformer.py, b
 
 AMAV_OPTIMIZER=library (or backend="library") runs clip_grad_norm_ and the library's Adam inside step() instead: the
 comparison path of the tests and of tools/time_optimizer.py.
+
+Data-parallel training (one process per GPU, every rank holding a replica): Adam(..., process_group=group) averages the
+gradients over the group inside step() -- a fourth launch packs them into one bucket, one all-reduce, and the norm and
+the update read the averaged gradient where the collective left it ("Data-parallel step").
 """
 import os
 
 import torch
+import torch.distributed
 from torch.optim.adam import adam as _library_adam  # the functional form behind torch.optim.Adam.step
 
 from . import ops
@@ -40,10 +45,19 @@ class Adam(torch.optim.Optimizer):
     also stores zeros to the gradients it read, and a following zero_grad(set_to_none=False) finds nothing left to do.
     Parameters: fp32, CUDA, contiguous, one device.  Not supported: amsgrad, maximize, sparse gradients, graph capture of
     step(), more than ops.OPTIM_MAX_GROUPS distinct (parameter group, step count) pairs in one step.
+
+    process_group (a torch.distributed group, world size 1 allowed; None: the single-process step, unchanged): step()
+    averages the gradients over the group before the clip, so grad_norm is the norm of the averaged gradient, which is
+    what Lightning clips under DDP.  The participation rule differs from the single-process step: EVERY parameter of the
+    optimizer takes part in EVERY step, whether or not it has a gradient on this rank -- the ranks must agree on the
+    bucket's layout without talking to each other.  State is created for all of them in the first step; a parameter
+    without a gradient here contributes zeros to the average, and one that no rank used receives a zero gradient (its
+    step count advances and its moments decay; from fresh state its value does not move).  Every rank must call step()
+    the same number of times, on replicas that started equal (dist.broadcast_module).
     """
 
     def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0, backend=None,
-                 zero_grads_in_step=False):
+                 zero_grads_in_step=False, process_group=None):
         if max_grad_norm is not None and not max_grad_norm >= 0.0:
             raise ValueError(f"max_grad_norm={max_grad_norm}: expected None or a value >= 0")
         backend = default_backend() if backend is None else backend
@@ -69,6 +83,8 @@ class Adam(torch.optim.Optimizer):
         self._partial = self._norm = None
         self._zeroed = []        # (gradient, its version) of the last step, when that step zeroed them
         self._counts = {}        # parameter -> its step count as an int: state["step"] without a tensor read per step
+        self.process_group = process_group
+        self._replicas = None    # the data-parallel step's bucket and tables (_Replicas), built in its first step
 
     def _check_groups(self):
         for i, group in enumerate(self.param_groups):
@@ -91,6 +107,7 @@ class Adam(torch.optim.Optimizer):
                 s["step"] = torch.tensor(float(step), dtype=torch.float32) if not torch.is_tensor(step) else step.float().cpu()
         self._counts = {p: int(s["step"].item()) for p, s in self.state.items() if "step" in s}
         self._signature = None
+        self._replicas = None
 
     # ---- the step ------------------------------------------------------------------------------------------------
     def _participants(self):
@@ -181,14 +198,153 @@ class Adam(torch.optim.Optimizer):
             self._zeroed = [(g, g._version) for g in grads]
         torch.autograd.graph.increment_version(written)
 
+    # ---- the data-parallel step ----------------------------------------------------------------------------------
+    def _all_reduce(self, t):
+        """SUM over the group, in place, ordered on the current stream.  RCCL orders itself behind the stream that wrote
+        `t`; a host-side backend (gloo) reads the memory from the CPU, so that stream is drained first (dist.send_frames)."""
+        if torch.distributed.get_backend(self.process_group) != "nccl":
+            torch.cuda.current_stream(self._device).synchronize()
+        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.SUM, group=self.process_group)
+
+    def _everyone(self):
+        """[(group index, parameter, state)] of every parameter, with the state created where it is missing."""
+        found = []
+        for gi, group in enumerate(self.param_groups):
+            for p in group["params"]:
+                state = self.state[p]
+                if len(state) == 0:
+                    state["step"] = torch.tensor(0.0, dtype=torch.float32)
+                    state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    self._counts[p] = 0
+                found.append((gi, p, state))
+        return found
+
+    def _replica_tables(self, everyone, group_of):
+        """The bucket and the step table (grad addresses inside the bucket), uploaded again only when a parameter or
+        state address or a group index changed; the pack table's entries are refreshed by the caller."""
+        r = self._replicas
+        numels = tuple(p.numel() for _, p, _ in everyone)
+        signature = (numels, tuple(group_of), tuple((p.data_ptr(), s["exp_avg"].data_ptr(), s["exp_avg_sq"].data_ptr())
+                                                     for _, p, s in everyone))
+        if r is None or r.numels != numels:
+            r = self._replicas = _Replicas(numels, self._device)
+        if r.signature != signature:
+            base = r.bucket.data_ptr()
+            for entry, group, offset, (param, exp_avg, exp_avg_sq) in zip(r.step_host, group_of, r.offsets, signature[2]):
+                entry.param, entry.grad, entry.exp_avg, entry.exp_avg_sq = param, base + 4 * offset, exp_avg, exp_avg_sq
+                entry.group = group
+            r.step_dev = ops.optimizer_table_to_device(r.step_host, self._device)
+            r.signature = signature
+        return r
+
+    def _step_replicas_hip(self):
+        everyone = self._everyone()
+        keys, group_of, counts = {}, [], self._counts
+        for gi, p, _ in everyone:
+            counts[p] = step = counts[p] + 1
+            group_of.append(keys.setdefault((gi, step), len(keys)))
+        torch._foreach_add_([state["step"] for _, _, state in everyone], 1.0)
+        if len(keys) > ops.OPTIM_MAX_GROUPS:
+            raise RuntimeError(f"optim.Adam: {len(keys)} distinct (parameter group, step count) pairs in one step, at most "
+                               f"{ops.OPTIM_MAX_GROUPS}")
+        groups = []
+        for gi, step in keys:
+            group = self.param_groups[gi]
+            groups.append(ops.optimizer_group(group["lr"], group["betas"], group["eps"], group["weight_decay"], step))
+        r = self._replica_tables(everyone, group_of)
+        # the pack table follows the allocator: this step's gradient addresses, NULL where the rank has none
+        sources = []
+        for _, p, _ in everyone:
+            g = p.grad
+            if g is not None:
+                if g.is_sparse:
+                    raise RuntimeError("optim.Adam does not support sparse gradients")
+                if g.dtype != torch.float32 or not g.is_contiguous():
+                    g = g.to(torch.float32).contiguous()
+            sources.append(g)
+        addresses = tuple(None if g is None else g.data_ptr() for g in sources)
+        if addresses != r.pack_signature:
+            for entry, address in zip(r.pack_host, addresses):
+                entry.grad = address
+            r.pack_dev = ops.optimizer_table_to_device(r.pack_host, self._device)
+            r.pack_signature = addresses
+        n, world = len(everyone), torch.distributed.get_world_size(self.process_group)
+        ops.grads_pack(r.pack_dev, n, r.chunks_dev, r.num_chunks, ops.OPTIM_CHUNK, r.offsets_dev, r.bucket,
+                       scale=1.0 / world, zero_source=self.zero_grads_in_step)
+        self._all_reduce(r.bucket)
+        coef = None
+        if self.max_grad_norm is not None:
+            ops.grad_norm_clip(r.step_dev, n, r.chunks_dev, r.num_chunks, ops.OPTIM_CHUNK, self.max_grad_norm,
+                               partial=r.partial, norm=r.norm)
+            self.grad_norm, coef = r.norm[0], r.norm[1:]
+        # the pack has zeroed the gradients where that was asked for: zeroing here would only clear the bucket
+        ops.adam_step(r.step_dev, n, r.chunks_dev, r.num_chunks, ops.OPTIM_CHUNK, groups, coef=coef, zero_grad=False)
+        if self.zero_grads_in_step:
+            grads = []
+            for (_, p, _), g in zip(everyone, sources):
+                if g is not None:
+                    if g is not p.grad:  # the kernel zeroed a converted copy
+                        p.grad.zero_()
+                    grads.append(p.grad)
+            torch.autograd.graph.increment_version(grads)
+            self._zeroed = [(g, g._version) for g in grads]
+        torch.autograd.graph.increment_version([t for _, p, s in everyone for t in (p, s["exp_avg"], s["exp_avg_sq"])])
+
+    def _step_replicas_library(self):
+        """The comparison path: every p.grad (zeros where None) summed over the group and divided by its size, then the
+        library step over all of them."""
+        world = torch.distributed.get_world_size(self.process_group)
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.grad is None:
+                    p.grad = torch.zeros_like(p)
+                self._all_reduce(p.grad)
+                p.grad.div_(world)
+        self._step_library(self._participants())
+
+    def replicas_in_sync(self):
+        """True iff every rank of the group holds the same parameters and moments, as far as a fingerprint can tell: the
+        three wrap-around sums of the bit patterns of param, exp_avg and exp_avg_sq (ops.tensors_fingerprint) are
+        all-gathered, 3 x 8 bytes per rank, and compared.  Synchronises: meant for every N-th step and for tests.  The
+        limit: a sum does not see two elements swapped, nor changes that cancel; replicas that drifted apart through
+        arithmetic differ in it."""
+        if self.process_group is None:
+            raise RuntimeError("optim.Adam.replicas_in_sync: constructed without a process_group")
+        with torch.no_grad():
+            everyone = self._everyone()
+            r = self._replicas
+            # the fingerprint reads no group index: the last step's stand (before the first step: zeros) keeps the table
+            known = r is not None and r.signature is not None and len(r.signature[1]) == len(everyone)
+            r = self._replica_tables(everyone, r.signature[1] if known else [0] * len(everyone))
+            mine = torch.empty(3, dtype=torch.int64, device=self._device)
+            for i, which in enumerate(("param", "exp_avg", "exp_avg_sq")):
+                ops.tensors_fingerprint(r.step_dev, len(everyone), r.chunks_dev, r.num_chunks, ops.OPTIM_CHUNK, which,
+                                        partial=r.fingerprint_partial, out=mine[i])
+            world = torch.distributed.get_world_size(self.process_group)
+            everyones = torch.empty(world, 3, dtype=torch.int64, device=self._device)
+            if torch.distributed.get_backend(self.process_group) != "nccl":
+                torch.cuda.current_stream(self._device).synchronize()
+            torch.distributed.all_gather_into_tensor(everyones.view(-1), mine, group=self.process_group)
+            return bool((everyones == everyones[0]).all().item())
+
     @torch.no_grad()
     def step(self, closure=None):
-        """One clipped Adam update of every parameter that has a gradient; no host synchronisation."""
+        """One clipped Adam update of every parameter that has a gradient (with a process_group: of every parameter, on
+        the gradients averaged over the group); no host synchronisation on a stream-ordered backend."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
         self._zeroed = []
+        if self.process_group is not None:
+            if self.max_grad_norm is None:
+                self.grad_norm = None
+            if self.backend == "library":
+                self._step_replicas_library()
+            else:
+                self._step_replicas_hip()
+            return loss
         found = self._participants()
         if self.max_grad_norm is None:
             self.grad_norm = None
@@ -218,10 +374,32 @@ class Adam(torch.optim.Optimizer):
                     p.grad.zero_()
 
 
-def configure_optimizers(module, lr=1e-4, total_steps=200000, max_grad_norm=1.0):
+class _Replicas:
+    """What the data-parallel step keeps between steps, for one cut of the parameters: the bucket (zero-filled once: the
+    gaps between tensors are never written and stay zero), the chunk table and the offsets (uploaded once), the pack
+    table (follows the gradients' addresses) and the step table (its grad addresses point into the bucket)."""
+
+    def __init__(self, numels, device):
+        self.numels = numels
+        self.offsets, total = ops.bucket_offsets(numels)
+        self.bucket = torch.zeros(total, dtype=torch.float32, device=device)
+        self.offsets_dev = torch.tensor(self.offsets, dtype=torch.int64).pin_memory().to(device, non_blocking=True)
+        self.pack_host, chunks = ops.optimizer_tables(numels, [0] * len(numels), ops.OPTIM_CHUNK)
+        self.step_host, _ = ops.optimizer_tables(numels, [0] * len(numels), ops.OPTIM_CHUNK)
+        self.chunks_dev, self.num_chunks = ops.optimizer_table_to_device(chunks, device), len(chunks)
+        self.pack_dev = self.step_dev = None
+        self.pack_signature = self.signature = None
+        self.partial = torch.empty(max(self.num_chunks, 1), dtype=torch.float64, device=device)
+        self.fingerprint_partial = torch.empty(max(self.num_chunks, 1), dtype=torch.int64, device=device)
+        self.norm = torch.empty(2, device=device)
+
+
+def configure_optimizers(module, lr=1e-4, total_steps=200000, max_grad_norm=1.0, process_group=None):
     """The reference's `configure_optimizers` plus its Trainer's clip, for `module`: (Adam over the parameters that
     require grad, LinearLR(start_factor=1.0, end_factor=0.01, total_iters=total_steps)).  The scheduler is the library's:
-    scheduler.step() after every optimizer.step() rewrites param_group["lr"] on the host and the next step reads it."""
-    optimizer = Adam([p for p in module.parameters() if p.requires_grad], lr=lr, max_grad_norm=max_grad_norm)
+    scheduler.step() after every optimizer.step() rewrites param_group["lr"] on the host and the next step reads it.
+    process_group: handed to Adam (the data-parallel step); None keeps the single-process step."""
+    optimizer = Adam([p for p in module.parameters() if p.requires_grad], lr=lr, max_grad_norm=max_grad_norm,
+                     process_group=process_group)
     scheduler = torch.optim.lr_scheduler.LinearLR(optimizer, start_factor=1.0, end_factor=0.01, total_iters=total_steps)
     return optimizer, scheduler

@@ -310,11 +310,12 @@ class TriplaneGaussianAvatar(nn.Module):
                  + 0.01 * parts["loss_smplx"])
         return total, parts
 
-    def configure_optimizers(self, lr=1e-4, total_steps=200000, max_grad_norm=1.0):
+    def configure_optimizers(self, lr=1e-4, total_steps=200000, max_grad_norm=1.0, process_group=None):
         """lightning_model_wrapper.py:366-382 (`TriplaneGaussianAvatarLightning.configure_optimizers`: Adam over
         self.parameters(), LinearLR from 1.0 to 0.01 over the run's steps, stepped every step) with the Trainer's
         gradient_clip_val = 1.0 (trainer_factory.py:44-45) inside the optimizer's step: returns (optim.Adam over the
-        parameters that require grad, the LinearLR scheduler); see AudioDrivenAvatar.configure_optimizers."""
+        parameters that require grad, the LinearLR scheduler); see AudioDrivenAvatar.configure_optimizers.
+        process_group: a torch.distributed group for the data-parallel step of optim.Adam; None: one process."""
         from .optim import configure_optimizers
 
-        return configure_optimizers(self, lr, total_steps, max_grad_norm)
+        return configure_optimizers(self, lr, total_steps, max_grad_norm, process_group)

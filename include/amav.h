@@ -1109,6 +1109,34 @@ int amav_grad_norm_clip(const void *tensors_dev, int num_tensors, const void *ch
 int amav_adam_step(const void *tensors_dev, int num_tensors, const void *chunks_dev, int num_chunks, int chunk,
                    const amav_optim_group *groups, int num_groups, const float *coef_dev, int zero_grad, void *stream);
 
+/* The data-parallel step ("Data-parallel step"): the gradients of every tensor, scaled, into one
+ * bucket that a collective averages in place; the two entry points above then run from a second table whose grad
+ * addresses point into the bucket.  Same tables, same chunk rules, same skip of out-of-range entries as above.
+ *
+ * amav_grads_pack           bucket[offsets[t] + i] = scale * tensors[t].grad[i] for every element of every chunk: one
+ *                           correctly rounded fp32 multiply.  A tensor whose grad is NULL contributes zeros (the parameter
+ *                           was not used on this rank).  zero_source != 0: store 0 to grad[i] after reading it.
+ *                           offsets_dev: int64 [num_tensors], in elements.  A chunk is skipped when its tensor index or
+ *                           start is out of range, or when offsets[t] is negative or offsets[t] + numel exceeds
+ *                           bucket_numel.  Only elements [offsets[t], offsets[t] + numel) are written, never the gaps
+ *                           between tensors; the bucket overlaps no gradient.  16-byte loads and stores where the chunk's
+ *                           first element is 16-byte aligned in the gradient and in the bucket (ops.bucket_offsets keeps
+ *                           the bucket side aligned).  8 bytes of traffic per element, 12 with zero_source.  Nothing to
+ *                           pack (num_tensors == 0 or num_chunks == 0): returns 0 without a launch or a table.
+ * amav_tensors_fingerprint  out_dev[0] (uint64) = the sum over all elements of all chunks of the element's 32 bits,
+ *                           zero-extended to 64 bits, modulo 2^64, of the array `which`: 0 param, 1 grad, 2 exp_avg,
+ *                           3 exp_avg_sq; a NULL address contributes 0.  partial_dev: uint64 [num_chunks], one sum per
+ *                           chunk, which one work-group then adds.  num_tensors == 0 or num_chunks == 0: out_dev[0] = 0,
+ *                           no table and no partial_dev needed.  Equal fingerprints do not prove equal arrays: the sum does
+ *                           not see two elements swapped.
+ * Neither uses atomics.
+ */
+int amav_grads_pack(const void *tensors_dev, int num_tensors, const void *chunks_dev, int num_chunks, int chunk,
+                    const int64_t *offsets_dev, float *bucket_dev, int64_t bucket_numel, float scale, int zero_source,
+                    void *stream);
+int amav_tensors_fingerprint(const void *tensors_dev, int num_tensors, const void *chunks_dev, int num_chunks, int chunk,
+                             int which, void *partial_dev, void *out_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

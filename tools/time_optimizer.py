@@ -19,7 +19,16 @@ medians.  Next to `hip`: the traffic model of DESIGN.md section 4.20 -- 4 B per 
 -- at the 6.29 TB/s a float4 copy reaches on the MI355X, and the fraction of that rate the step achieves.
 Prints one JSON line.
 
-usage: time_optimizer.py [rounds] [repeats] [--no-survey]"""
+--data-parallel: the data-parallel step instead ("Data-parallel step"), on the `model` set in a
+one-rank RCCL group -- what the step costs a rank apart from the wire, which one GPU cannot show:
+
+  hip                optim.Adam(backend="hip") as above
+  hip_data_parallel  optim.Adam(backend="hip", process_group=<the one-rank group>): pack + all-reduce + the three launches
+  pack_launch        amav_grads_pack alone over tables built once: 8 B per parameter (a read and a write)
+
+The same rounds, the same events; next to pack_launch its fraction of the float4 copy rate.
+
+usage: time_optimizer.py [rounds] [repeats] [--no-survey] [--data-parallel]"""
 import json
 import os
 import statistics
@@ -73,13 +82,21 @@ def launches_only(params, chunk):
     return step, lambda: ops.grad_norm_clip(*tables, 1.0, partial=partial, norm=norm)
 
 
-def numbers(params, rounds, repeats):
-    g = torch.Generator(device="cuda").manual_seed(0)
-    for p in params:
-        p.grad = torch.randn(p.shape, generator=g, device="cuda") * 1e-3
-    paths = {"library": optim.Adam(params, lr=1e-4, backend="library").step, "library_fused": library_fused(params),
-             "hip": optim.Adam(params, lr=1e-4, backend="hip").step}
-    paths["hip_launches"], paths["hip_norm_launches"] = launches_only(params, ops.OPTIM_CHUNK)
+def pack_only(params, chunk):
+    """amav_grads_pack over tables built once from the gradients of `params`, into a bucket of its own."""
+    tensors, chunk_table = ops.optimizer_tables([p.numel() for p in params], [0] * len(params), chunk)
+    for t, p in zip(tensors, params):
+        t.grad = p.grad.data_ptr()
+    offsets, total = ops.bucket_offsets([p.numel() for p in params])
+    bucket = torch.zeros(total, device="cuda")
+    offsets_dev = torch.tensor(offsets, dtype=torch.int64, device="cuda")
+    tables = (ops.optimizer_table_to_device(tensors, "cuda"), len(tensors), ops.optimizer_table_to_device(chunk_table, "cuda"),
+              len(chunk_table), chunk)
+    return lambda: ops.grads_pack(*tables, offsets_dev, bucket, scale=1.0)
+
+
+def rounds_of(paths, rounds, repeats):
+    """Warm every path up, then let them alternate -> {name: the round medians}."""
     for step in paths.values():   # warm-up: code objects, the state, the tables, the allocator
         for _ in range(3):
             step()
@@ -88,6 +105,45 @@ def numbers(params, rounds, repeats):
     for _ in range(rounds):
         for name, step in paths.items():
             medians[name].append(step_ms(step, repeats))
+    return medians
+
+
+def data_parallel_numbers(params, rounds, repeats):
+    import tempfile
+
+    import torch.distributed as dist
+
+    g = torch.Generator(device="cuda").manual_seed(0)
+    for p in params:
+        p.grad = torch.randn(p.shape, generator=g, device="cuda") * 1e-3
+    with tempfile.TemporaryDirectory() as d:
+        dist.init_process_group("nccl", init_method=f"file://{os.path.join(d, 'rendezvous')}", rank=0, world_size=1)
+        try:
+            paths = {"hip": optim.Adam(params, lr=1e-4, backend="hip").step,
+                     "hip_data_parallel": optim.Adam(params, lr=1e-4, backend="hip", process_group=dist.group.WORLD).step,
+                     "pack_launch": pack_only(params, ops.OPTIM_CHUNK)}
+            medians = rounds_of(paths, rounds, repeats)
+        finally:
+            dist.destroy_process_group()
+    count = sum(p.numel() for p in params)
+    res = {"tensors": len(params), "parameters": count}
+    for name, m in medians.items():
+        ms = statistics.median(m)
+        res[name] = {"ms": round(ms, 4), "spread_ms": round(max(m) - min(m), 4)}
+    ms, model_ms = res["pack_launch"]["ms"], count * 8 / (COPY_TB_PER_S * 1e12) * 1e3
+    res["pack_launch"].update(model_ms_at_copy_rate=round(model_ms, 4), tb_per_s=round(count * 8 / (ms * 1e-3) / 1e12, 3),
+                              fraction_of_copy_rate=round(model_ms / ms, 3))
+    return res
+
+
+def numbers(params, rounds, repeats):
+    g = torch.Generator(device="cuda").manual_seed(0)
+    for p in params:
+        p.grad = torch.randn(p.shape, generator=g, device="cuda") * 1e-3
+    paths = {"library": optim.Adam(params, lr=1e-4, backend="library").step, "library_fused": library_fused(params),
+             "hip": optim.Adam(params, lr=1e-4, backend="hip").step}
+    paths["hip_launches"], paths["hip_norm_launches"] = launches_only(params, ops.OPTIM_CHUNK)
+    medians = rounds_of(paths, rounds, repeats)
     count = sum(p.numel() for p in params)
     res = {"tensors": len(params), "parameters": count}
     for name, m in medians.items():
@@ -110,6 +166,10 @@ if __name__ == "__main__":
 
     res = {"rounds": rounds, "repeats": repeats, "chunk": ops.OPTIM_CHUNK}
     model = AudioDrivenAvatar()
+    if "--data-parallel" in sys.argv:
+        res["model_data_parallel"] = data_parallel_numbers([p for p in model.parameters() if p.requires_grad], rounds, repeats)
+        print(json.dumps(res))
+        raise SystemExit(0)
     res["model"] = numbers([p for p in model.parameters() if p.requires_grad], rounds, repeats)
     del model
     torch.cuda.empty_cache()
