@@ -12,6 +12,9 @@ What the reference's demo does, and where it lives here:
   * windows of T_out frames chained through `out[:, -2:]` (main2.py:179-203), optionally as the even / odd pair of
     stride-2 chains zipped together (main2.py:160-311)                             -> harness.rollout(_interleaved)
   * frames -> 24 fps mp4 + the clip's audio muxed in by ffmpeg (main2.py:342-384) -> FrameWriter (below)
+  * the second clip, `smplx_sequence.mp4`: every frame stacked on the same frame with the predicted SMPL-X mesh drawn
+    over it (main2.py:213-220,296-303,342-384) -> `--smplx-out`: mesh_overlay.draw_smplx_on_image, one call per clip,
+    into a second FrameWriter of height 2H
 
 FrameWriter needs no OpenCV: frames leave the GPU as uint8 RGB (`(frame * 255).astype(uint8)`, main2.py:351, done by
 `amav_frames_to_rgb8`) and go as raw `rgb24` into a pipe.  With an `.mp4` / `.mkv` / `.mov` target the pipe is an
@@ -128,6 +131,8 @@ def main(argv=None):
                          "(what a released checkpoint was trained with); default is BASELINE's 10 000-Gaussian renderer")
     ap.add_argument("--fps", type=float, default=24.0)
     ap.add_argument("--out", default="demo.rgb", help=".rgb (raw frames + .json), .mp4 / .mkv / .mov (needs ffmpeg) or - for stdout")
+    ap.add_argument("--smplx-out", help="also write the mesh clip there: every frame above the same frame with the predicted "
+                                        "SMPL-X mesh drawn over it (height 2H; same suffix rules and audio as --out)")
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--seed", type=int, default=42)
     args = ap.parse_args(argv)
@@ -156,15 +161,32 @@ def main(argv=None):
     _, _, cam = make_render_inputs(n, rcfg, seed=args.seed, device=args.device)
     seeds = _load_tokens(args.tokens, cfg, args.device, args.seed)
     target = sys.stdout.buffer if args.out == "-" else args.out
+    want_mesh = args.smplx_out is not None
     with FrameWriter(target, H, W, fps=args.fps, audio_path=args.audio) as writer:
         if args.interleave:
             if len(seeds) < 2:
                 raise SystemExit("--interleave needs two token pairs (even and odd chain)")
-            writer.write(model.rollout_interleaved((seeds[0], seeds[1]), audio, cam)[:args.frames])
+            frames = model.rollout_interleaved((seeds[0], seeds[1]), audio, cam, return_smplx=want_mesh)
+            frames, smplx = frames if want_mesh else (frames, None)
         else:
-            out = model.rollout(seeds[0][0], seeds[0][1], audio, cam)
-            writer.write(out["images"][0, :args.frames])
+            out = model.rollout(seeds[0][0], seeds[0][1], audio, cam, return_smplx=want_mesh)
+            frames, smplx = out["images"][0], {k: v[0] for k, v in out["smplx_params"].items()} if want_mesh else None
+        frames = frames[:args.frames]
+        writer.write(frames)
     print(f"wrote {writer.frames} frames of {W}x{H} at {args.fps} fps to {args.out}", file=sys.stderr)
+    if want_mesh:
+        from .mesh_overlay import SimpleMeshRenderer, draw_smplx_on_image
+
+        n = frames.shape[0]
+        body = model.renderer.smplx_model
+        stacked = draw_smplx_on_image(frames[None, ..., :3].permute(0, 1, 4, 2, 3),
+                                      {k: v[None, :n] for k, v in smplx.items()}, cam["intrinsic"][:, :n],
+                                      cam["extrinsic"][:, :n], body, SimpleMeshRenderer(body.faces, H, W))
+        mesh_target = sys.stdout.buffer if args.smplx_out == "-" else args.smplx_out
+        with FrameWriter(mesh_target, 2 * H, W, fps=args.fps, audio_path=args.audio) as mesh_writer:
+            mesh_writer.write(stacked)
+        print(f"wrote {mesh_writer.frames} frames of {W}x{2 * H} (frame over mesh overlay) to {args.smplx_out}",
+              file=sys.stderr)
     return 0
 
 

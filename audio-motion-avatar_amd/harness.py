@@ -146,31 +146,41 @@ class AudioDrivenAvatar(nn.Module):
 
     # ---- chained windows (demo) ------------------------------------------------------------------------------------
     @torch.no_grad()
-    def rollout(self, triplanes, smplx_tokens, audio_features, cam_params, num_windows=None):
+    def rollout(self, triplanes, smplx_tokens, audio_features, cam_params, num_windows=None, return_smplx=False):
         """main2.py:179-203.  audio_features [B, W*T_out(+), 768], cam_params [B, W*T_out, ...] -> dict with
-        images [B, W*T_out, H, W, 3] plus the final two token sets (to continue the clip later)."""
+        images [B, W*T_out, H, W, 3] plus the final two token sets (to continue the clip later).  return_smplx: also
+        smplx_params, every window's predicted SMPL-X parameters (the net's `pred_smplx_future`, a dict of [B,T_out,...])
+        concatenated along time: what mesh_overlay.draw_smplx_on_image draws (main2.py:213-220)."""
         T = self.audio_triplane.T_output
         W = audio_features.shape[1] // T if num_windows is None else num_windows
         if W < 1 or audio_features.shape[1] < W * T or cam_params["intrinsic"].shape[1] < W * T:
             raise ValueError(f"need {W * T} audio tokens and cameras for {W} windows of {T} frames")
-        images = []
+        images, smplx = [], []
         for w in range(W):
             sl = slice(w * T, (w + 1) * T)
             cam = {k: v[:, sl] for k, v in cam_params.items()}
             out = self.audio_triplane(audio_features[:, sl], triplanes, None, cam, smplx_tokens)
             images.append(out[0])
+            smplx.append(out[2])
             triplanes, smplx_tokens = out[3][:, -2:], out[4][:, -2:]  # chain into the next window
-        return {"images": torch.cat(images, dim=1), "triplanes": triplanes, "smplx_tokens": smplx_tokens}
+        result = {"images": torch.cat(images, dim=1), "triplanes": triplanes, "smplx_tokens": smplx_tokens}
+        if return_smplx:
+            if smplx[0] is None:
+                raise ValueError("rollout(return_smplx=True): the renderer predicts no SMPL-X parameters "
+                                 "(predict_smplx_params is off)")
+            result["smplx_params"] = {k: torch.cat([s[k] for s in smplx], dim=1) for k in smplx[0]}
+        return result
 
     @torch.no_grad()
-    def rollout_interleaved(self, seeds, audio_features, cam_params, num_windows=None):
+    def rollout_interleaved(self, seeds, audio_features, cam_params, num_windows=None, return_smplx=False):
         """The demo's two interleaved chains (main2.py:160-311).  Every dataset item is a stride-2 clip
         (dataset_speech_vid.py:150), so the demo rolls an "even" chain over frames 0,2,4,... seeded from item 0 and an
         "odd" chain over frames 1,3,5,... seeded from item 1, and zips the two frame lists (main2.py:301-311).
 
         seeds = ((triplanes_even, smplx_tokens_even), (triplanes_odd, smplx_tokens_odd)), each [1,2,...];
         audio_features [1, 2*W*T_out, 768] and cam_params [1, 2*W*T_out, ...] are per output frame of the zipped clip.
-        The chains are independent, so they run as ONE batch of two.  Returns images [2*W*T_out, H, W, 3]."""
+        The chains are independent, so they run as ONE batch of two.  Returns images [2*W*T_out, H, W, 3]; with
+        return_smplx, (images, smplx_params): the predicted SMPL-X parameters [2*W*T_out, ...], zipped like the frames."""
         (tri_e, smpl_e), (tri_o, smpl_o) = seeds
         T = self.audio_triplane.T_output
         n = audio_features.shape[1]
@@ -178,9 +188,12 @@ class AudioDrivenAvatar(nn.Module):
         if W < 1 or n < 2 * W * T or cam_params["intrinsic"].shape[1] < 2 * W * T:
             raise ValueError(f"need {2 * W * T} audio tokens and cameras for 2 x {W} windows of {T} frames")
         unzip = lambda x: torch.cat([x[:, 0:2 * W * T:2], x[:, 1:2 * W * T:2]], dim=0)  # [2, W*T, ...]: even, odd
-        out = self.rollout(torch.cat([tri_e, tri_o]), torch.cat([smpl_e, smpl_o]), unzip(audio_features),
-                           {k: unzip(v) for k, v in cam_params.items()}, num_windows=W)["images"]
-        return torch.stack([out[0], out[1]], dim=1).reshape(2 * W * T, *out.shape[2:])  # e0, o0, e1, o1, ...
+        res = self.rollout(torch.cat([tri_e, tri_o]), torch.cat([smpl_e, smpl_o]), unzip(audio_features),
+                           {k: unzip(v) for k, v in cam_params.items()}, num_windows=W, return_smplx=return_smplx)
+        zipped = lambda x: torch.stack([x[0], x[1]], dim=1).reshape(2 * W * T, *x.shape[2:])  # e0, o0, e1, o1, ...
+        if return_smplx:
+            return zipped(res["images"]), {k: zipped(v) for k, v in res["smplx_params"].items()}
+        return zipped(res["images"])
 
     @torch.no_grad()
     def rollout_tokens(self, triplanes, smplx_tokens, audio_features, num_windows):

@@ -3,6 +3,7 @@
 Every function requires CUDA(HIP) float32 tensors and raises on anything else: there is no CPU path.
 """
 import ctypes
+import math
 import os
 
 import torch
@@ -2873,4 +2874,77 @@ def tensors_fingerprint(tensors_dev, num_tensors, chunks_dev, num_chunks, chunk,
     elif _need(out, "out", torch.int64).numel() != 1:
         raise AmavError(f"out: expected one int64 value, got {tuple(out.shape)}")
     _call("amav_tensors_fingerprint", tp, num_tensors, cp, num_chunks, chunk, int(which), partial.data_ptr(), out.data_ptr())
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------- mesh overlay
+MeshOverlayArgs = _lib.STRUCTS["amav_mesh_overlay_args"]
+MESH_SMALL_BOX = _lib.DEFINES["AMAV_MESH_SMALL_BOX"]
+MESH_DIFFUSE = 0.96  # 1 - F0 of a dielectric at l = v: pyrender's metallic-roughness diffuse weight at metallic = 0
+
+
+def mesh_overlay(vertices, faces, K, E, height, width, frames=None, transl=None, base_color=(0.8, 0.8, 0.8),
+                 light_intensity=5.0, znear=0.05, cull_backfaces=True, background=(1, 1, 1), want_depth=False,
+                 want_face_index=False, want_screen=False, workspace=None, want_shade=False, small_box=None):
+    """Flat-shaded, z-buffered triangle mesh over a batch of frames (include/amav.h, amav_mesh_overlay; DESIGN.md
+    section 4.21): vertices [F,V,3] world, faces [T,3] int32 (int64 is converted), K [F,3,3], E [F,4,4] world-to-camera,
+    frames fp32 [F,H,W,3|4] or None (composite over `background`), transl [F,3] or None.  Returns a dict: rgb
+    [F,H,W,3]; depth [F,H,W] (0 where no face covers the pixel), face_index int32 [F,H,W] (-1 there), screen int32
+    [F,V,2] (the vertices snapped to 1/256 px) and shade [F,T,3] when asked for, else None; status int32 [F,2]: the faces
+    dropped at the near plane and at the guard band, left on the device.  The shade is min(1, k max(0, n . l)) with
+    k = 0.96 base_color light_intensity / pi and the camera's headlight.  workspace: a uint8 tensor of at least
+    amav_mesh_overlay_workspace_bytes, reused when given.  small_box: pixel centres a face's own thread may visit
+    (None: AMAV_MESH_SMALL_BOX; 0 sends every face to the wave-per-face tier; the result does not depend on it)."""
+    vertices = _contig(vertices, "vertices")
+    if vertices.dim() != 3 or vertices.shape[2] != 3:
+        raise AmavError(f"mesh_overlay: vertices {tuple(vertices.shape)}, expected [F,V,3]")
+    F, V, _ = vertices.shape
+    if not isinstance(faces, torch.Tensor) or not faces.is_cuda:
+        raise AmavError("mesh_overlay: faces must be a tensor on the HIP device (this package only runs on an MI355X)")
+    if faces.dtype == torch.int64:
+        faces = faces.to(torch.int32)
+    faces = _contig(faces, "faces", torch.int32)
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise AmavError(f"mesh_overlay: faces {tuple(faces.shape)}, expected [T,3]")
+    T, H, W = faces.shape[0], int(height), int(width)
+    K, E = _contig(K.reshape(-1, 3, 3), "K"), _contig(E.reshape(-1, 4, 4), "E")
+    if K.shape[0] != F or E.shape[0] != F:
+        raise AmavError(f"mesh_overlay: {F} frames of vertices, {K.shape[0]} intrinsics, {E.shape[0]} extrinsics")
+    dev = vertices.device
+    a = MeshOverlayArgs()
+    a.num_frames, a.num_verts, a.num_faces, a.height, a.width = F, V, T, H, W
+    a.cull_backfaces, a.small_box = int(bool(cull_backfaces)), -1 if small_box is None else int(small_box)
+    a.vertices, a.faces, a.K, a.E = vertices.data_ptr(), faces.data_ptr(), K.data_ptr(), E.data_ptr()
+    if transl is not None:
+        transl = _contig(transl.reshape(-1, 3), "transl")
+        if transl.shape[0] != F:
+            raise AmavError(f"mesh_overlay: transl {tuple(transl.shape)}, expected [{F},3]")
+        a.transl = transl.data_ptr()
+    if frames is not None:
+        frames = _contig(frames, "frames")
+        if frames.dim() != 4 or tuple(frames.shape[:3]) != (F, H, W) or frames.shape[3] not in (3, 4):
+            raise AmavError(f"mesh_overlay: frames {tuple(frames.shape)}, expected [{F},{H},{W},3|4]")
+        a.frames, a.frame_channels = frames.data_ptr(), frames.shape[3]
+    for c in range(3):
+        a.background[c] = float(background[c])
+        a.shade_k[c] = MESH_DIFFUSE * float(base_color[c]) * float(light_intensity) / math.pi
+    a.znear = float(znear)
+    if workspace is None:
+        workspace = _scratch("amav_mesh_overlay_workspace_bytes", dev, F, V, T, H, W,
+                             rejected=f"F={F} V={V} T={T} H={H} W={W}")
+    else:
+        workspace = _contig(workspace, "workspace", torch.uint8)
+    out = {"rgb": torch.empty(F, H, W, 3, device=dev),
+           "depth": torch.empty(F, H, W, device=dev) if want_depth else None,
+           "face_index": torch.empty(F, H, W, dtype=torch.int32, device=dev) if want_face_index else None,
+           "screen": torch.empty(F, V, 2, dtype=torch.int32, device=dev) if want_screen else None,
+           "shade": torch.empty(F, T, 3, device=dev) if want_shade else None,
+           "status": torch.empty(F, 2, dtype=torch.int32, device=dev)}
+    a.out_rgb, a.out_status = out["rgb"].data_ptr(), out["status"].data_ptr()
+    for field, key in (("out_depth", "depth"), ("out_face_index", "face_index"), ("out_screen", "screen"),
+                       ("out_shade", "shade")):
+        if out[key] is not None:
+            setattr(a, field, out[key].data_ptr())
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    _call("amav_mesh_overlay", ctypes.byref(a))
     return out

@@ -1137,6 +1137,69 @@ int amav_grads_pack(const void *tensors_dev, int num_tensors, const void *chunks
 int amav_tensors_fingerprint(const void *tensors_dev, int num_tensors, const void *chunks_dev, int num_chunks, int chunk,
                              int which, void *partial_dev, void *out_dev, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * SMPL-X mesh overlay: the demo's second clip (src/main2.py:213-220,296-303; draw_smplx_on_image and
+ * SimpleMeshRenderer.render_mesh, src/utils/graphic_utils.py:782-944, there pyrender on an offscreen GL context with one
+ * scene and one host round trip per frame).  A z-buffered triangle rasterizer with flat shading and a composite over
+ * the rendered frames, a whole batch of frames per call.
+ *
+ * Conventions of amav_points_project: E [F,4,4] row-major world-to-camera (OpenCV: x right, y down, z forward), K
+ * [F,3,3] in pixels, the centre of pixel (r, c) at (c + 0.5, r + 0.5).  Five launches on the caller's stream:
+ *   fill     every key of the [F,H,W] uint64 z-buffer to all ones, the counters to 0
+ *   project  one thread per (frame, vertex): p_cam = E (v + transl_f), u = fx x / z + cx, v = fy y / z + cy, snapped to
+ *            1/256 px as int32 fixed point (round to nearest even); everything downstream works on the snapped integers
+ *   setup    one thread per (frame, face).  A face with a vertex at z < znear is dropped and counted in status[f][0]
+ *            (no clipping at the near plane); otherwise a face with a snapped |u| or |v| above 2^22 units (16384 px) is
+ *            dropped and counted in status[f][1] (with that guard the edge functions stay below 2^48 in int64).  A face
+ *            with a vertex id outside [0, V) or with zero doubled area is skipped without a count.  Front faces have a
+ *            NEGATIVE doubled area (x1-x0)(y2-y0) - (x2-x0)(y1-y0) in pixel coordinates: SMPL-X's outward,
+ *            counter-clockwise-from-outside faces as the OpenCV camera sees them.  cull_backfaces != 0 drops the others;
+ *            0 keeps them with their normal reversed.  Shade, per channel: min(1, shade_k[c] * max(0, n . l)) with n the
+ *            unit normal of the face in camera space (from the edges E (v_k - v_0): the differences are taken in world
+ *            space, where they do not cancel) and l = (0, 0, -1) the camera's headlight (pyrender's
+ *            metallic-roughness diffuse term at metallic 0, roughness 1 is shade_k = 0.96 * base_color * intensity / pi;
+ *            its specular lobe is left out).  A face whose clipped bounding box holds at most small_box pixel centres is
+ *            rasterized by its thread; the others go to a per-frame list (integer atomicAdd, capacity T)
+ *   large    a fixed grid of waves strides over that list (its length is read on the device): one wave per face, the
+ *            lanes stride over the pixel centres of the box
+ *   resolve  one thread per pixel: the winner's shade, or the frame's RGB (the background colour without frames)
+ * Coverage is exact: int64 edge functions at (256 c + 128, 256 r + 128) with the top-left fill rule (a centre exactly on
+ * an edge belongs to the face only if the interior lies to the right of the edge, or below a horizontal one), so two
+ * faces that share an edge never both own a pixel and never both miss it.  Depth is perspective-correct, z = 1 / sum
+ * b_i / z_i with b_i the edge value over the doubled area in fp32; the pixel keeps the smallest key
+ * (bits(z) << 32) | face under integer atomicMin: nearest face, lowest id on exact ties, independent of the order the
+ * faces arrive in.  No float atomics: results are bitwise reproducible and a frame does not depend on the others of
+ * the batch.  Every check below is made before the first launch; no allocation, no host synchronisation. */
+#define AMAV_MESH_SMALL_BOX 256
+typedef struct amav_mesh_overlay_args {
+    int32_t num_frames, num_verts, num_faces, height, width;
+    int32_t frame_channels;    /* floats per pixel of `frames`: 3 or 4 (ignored without frames) */
+    int32_t cull_backfaces;
+    int32_t small_box;         /* pixel centres a face's own thread may visit; < 0: AMAV_MESH_SMALL_BOX; 0: every face
+                                  takes the large tier */
+    const float *vertices;     /* [F,V,3] world */
+    const int32_t *faces;      /* [T,3] */
+    const float *transl;       /* [F,3] added to every vertex of the frame, or NULL */
+    const float *K;            /* [F,3,3] */
+    const float *E;            /* [F,4,4] */
+    const float *frames;       /* [F,H,W,frame_channels] contiguous; NULL: composite over `background` */
+    float background[3];
+    float shade_k[3];
+    float znear;               /* > 0 */
+    float *out_rgb;            /* [F,H,W,3] */
+    float *out_depth;          /* [F,H,W] camera-space z in metres, 0 where no face covers the pixel; or NULL */
+    int32_t *out_face_index;   /* [F,H,W], -1 where no face covers the pixel; or NULL */
+    int32_t *out_screen;       /* [F,V,2] the snapped (u, v) in 1/256 px; or NULL */
+    int32_t *out_status;       /* [F,2] faces dropped at the near plane / at the guard band; or NULL */
+    float *out_shade;          /* [F,T,3] the shade of every rasterized face, 0 for a dropped one; or NULL */
+    void *workspace;           /* 16-byte aligned */
+    size_t workspace_bytes;
+} amav_mesh_overlay_args;
+/* 8 F H W (keys) + 12 F V (camera z, snapped coordinates) + 16 F T (shade, list) + 12 F (counters), every slab rounded up to
+ * 256 bytes; 0 on a non-positive size, H or W above 16384, F above 65535 or F H W above 2^38. */
+size_t amav_mesh_overlay_workspace_bytes(int num_frames, int num_verts, int num_faces, int height, int width);
+int amav_mesh_overlay(const amav_mesh_overlay_args *args, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
