@@ -98,6 +98,10 @@ class Stage1Config(RendererConfig):
     cross_transformer_num_heads: int = 8
     image_feature_dim: int = 1536
     sample_feature: bool = True
+    # With upsample_triplane (one flag for both halves, as in the reference's flattened config: renderer.yaml's `true`
+    # overrides triplane_net.yaml's `false`, so the reference as shipped runs stage 1 with it) the encoder scatters into
+    # (triplane_resolution * upsample_factor)^2 cells and TriplaneDownsampler returns them to triplane_resolution^2;
+    # at least 2.  AMAV_STAGE1_DOWNSAMPLER=library, read per call, keeps the library's operators (triplane_net.py).
     upsample_factor: int = 3
 
 

@@ -1985,6 +1985,195 @@ def linear_split_differentiable(x, weight, bias=None, weight_split=None, weight_
     return _LinearSplit.apply(x, weight, bias, weight_split, weight_split_t, library)
 
 
+# ------------------------------------------------------------------ stage-1 TriplaneDownsampler
+DWCONV_MIN_CHANNELS, DWCONV_MAX_CHANNELS = 64, 512  # amav_dwconv7_layernorm: a multiple of 64 in this range
+
+
+def dwconv7_channels_ok(channels) -> bool:
+    """Whether amav_dwconv7_layernorm is built for this width."""
+    return DWCONV_MIN_CHANNELS <= channels <= DWCONV_MAX_CHANNELS and channels % 64 == 0
+
+
+def _planes(x, name):
+    x = _need(x, name)
+    if x.dim() != 4 or not x.is_contiguous():
+        raise AmavError(f"{name}: expected contiguous channels-last planes [K,H,W,C], got {tuple(x.shape)}")
+    return x
+
+
+def _split_out(rows, k, split, device):
+    """(fp32 [rows, k] or None, split operand or None) for the kernels that write exactly one of them."""
+    if split is None:
+        return torch.empty(rows, k, device=device), None
+    return None, _split_buffer(rows, k, split, device)
+
+
+def dwconv7_layernorm(x, dw_weight, dw_bias, ln_weight, ln_bias, eps=1e-6, split=None, split_exp=0, want_y=False):
+    """ConvNeXtBlock's dwconv -> LayerNorm (triplane_net.py:414-424) in one kernel: x [K,H,W,C] channels-last planes,
+    dw_weight [C,1,7,7] (nn.Conv2d, groups=C), dw_bias / ln_weight / ln_bias [C] -> the normalised rows [K*H*W, C], fp32
+    or (split = SPLIT_BF16X3 / SPLIT_FP16X2) the activation operand of the projection that follows.  want_y: also return
+    y [K,H,W,C], the convolution before the norm -> (rows, y).  include/amav.h, amav_dwconv7_layernorm."""
+    x = _planes(x, "x")
+    K, H, W, C = x.shape
+    w = _shaped(dw_weight, "dw_weight", (C, 1, 7, 7))
+    out, out_split = _split_out(K * H * W, C, split, x.device)
+    y = torch.empty_like(x) if want_y else None
+    _call("amav_dwconv7_layernorm", K, H, W, C, x.data_ptr(), w.data_ptr(), _shaped(dw_bias, "dw_bias", (C,)).data_ptr(),
+          _shaped(ln_weight, "ln_weight", (C,)).data_ptr(), _shaped(ln_bias, "ln_bias", (C,)).data_ptr(), float(eps),
+          None if y is None else y.data_ptr(), None if out is None else out.data_ptr(),
+          None if out_split is None else out_split.data_ptr(), int(split or 0), int(split_exp))
+    rows = out if out_split is None else out_split
+    return (rows, y) if want_y else rows
+
+
+def dwconv7_layernorm_backward(x, y, dw_weight, ln_weight, eps, grad_norm):
+    """amav_dwconv7_layernorm_backward: x, y [K,H,W,C] (the forward's input and its y), grad_norm [K*H*W, C] ->
+    (dx [K,H,W,C], d dw_weight [C,1,7,7], d dw_bias [C], d ln_weight [C], d ln_bias [C])."""
+    x, y = _planes(x, "x"), _planes(y, "y")
+    K, H, W, C = x.shape
+    if y.shape != x.shape:
+        raise AmavError(f"dwconv7_layernorm_backward: y {tuple(y.shape)} does not match x {tuple(x.shape)}")
+    g = _shaped(grad_norm, "grad_norm", (K * H * W, C))
+    ws = _scratch("amav_dwconv7_layernorm_backward_workspace_bytes", x.device, K, H, W, C,
+                  rejected=f"planes={K} height={H} width={W} channels={C}")
+    dx, d_w = torch.empty_like(x), torch.empty(C, 1, 7, 7, device=x.device)
+    d_b, d_lw, d_lb = (torch.empty(C, device=x.device) for _ in range(3))
+    _call("amav_dwconv7_layernorm_backward", K, H, W, C, x.data_ptr(), y.data_ptr(),
+          _shaped(dw_weight, "dw_weight", (C, 1, 7, 7)).data_ptr(), _shaped(ln_weight, "ln_weight", (C,)).data_ptr(),
+          float(eps), g.data_ptr(), dx.data_ptr(), d_w.data_ptr(), d_b.data_ptr(), d_lw.data_ptr(), d_lb.data_ptr(),
+          ws.data_ptr(), ws.numel())
+    return dx, d_w, d_b, d_lw, d_lb
+
+
+def _proj_rows(proj, name):
+    proj = _need(proj, "proj")
+    if proj.dim() < 1 or not proj.is_contiguous() or proj.shape[-1] % 4 or proj.numel() == 0:
+        raise AmavError(f"{name}: need a contiguous [..., inner] tensor with inner a multiple of 4")
+    return proj, proj.numel() // proj.shape[-1], proj.shape[-1]
+
+
+def gelu_bias(proj, bias=None, split=None, split_exp=0):
+    """proj [..., inner] (contiguous fp32; + bias [inner], when the projection's GEMM ran without it) -> gelu(proj + bias),
+    exact erf: fp32 [..., inner], or with split the activation operand [rows, 6 inner] bf16 / [rows, 3 inner] fp16 of the
+    next projection.  include/amav.h, amav_gelu_bias."""
+    proj, rows, inner = _proj_rows(proj, "gelu_bias")
+    out, out_split = _split_out(rows, inner, split, proj.device)
+    _call("amav_gelu_bias", rows, inner, proj.data_ptr(), inner,
+          None if bias is None else _shaped(bias, "bias", (inner,)).data_ptr(), None if out is None else out.data_ptr(),
+          None if out_split is None else out_split.data_ptr(), int(split or 0), int(split_exp))
+    return out.view(proj.shape) if out_split is None else out_split
+
+
+def gelu_bias_backward(proj, bias, grad_out):
+    """amav_gelu_bias_backward: proj (+ bias) as gelu_bias() read it and grad_out of proj's shape -> d proj.  The bias
+    gradient is rows_colsum of the result."""
+    proj, rows, inner = _proj_rows(proj, "gelu_bias_backward")
+    grad_out = _shaped(_contig(grad_out, "grad_out"), "grad_out", proj.shape)
+    grad = torch.empty_like(proj)
+    _call("amav_gelu_bias_backward", rows, inner, proj.data_ptr(), inner,
+          None if bias is None else _shaped(bias, "bias", (inner,)).data_ptr(), grad_out.data_ptr(), grad.data_ptr(), inner)
+    return grad
+
+
+def patch4_out_size(n, stride):
+    """Output size of Conv2d(kernel 4, stride, padding 1) along an axis of n pixels."""
+    return (int(n) - 2) // int(stride) + 1
+
+
+def patch4_gather(x, stride, split=None, split_exp=0):
+    """The im2col of Conv2d(C, C, 4, stride, padding 1) over channels-last planes: x [K,H,W,C] -> [K*Ho*Wo, 16*C], tap-major
+    (column (4 ky + kx) C + c), zero outside the plane; fp32, or with split the activation operand of the product with
+    the weight permuted to [C_out, ky, kx, C_in].  include/amav.h, amav_patch4_gather."""
+    x = _planes(x, "x")
+    K, H, W, C = x.shape
+    if int(stride) < 2 or H < 2 or W < 2:
+        raise AmavError(f"patch4_gather: stride={stride} height={H} width={W} (stride >= 2, height and width >= 2)")
+    rows = K * patch4_out_size(H, stride) * patch4_out_size(W, stride)
+    out, out_split = _split_out(rows, 16 * C, split, x.device)
+    _call("amav_patch4_gather", K, H, W, C, int(stride), x.data_ptr(), None if out is None else out.data_ptr(),
+          None if out_split is None else out_split.data_ptr(), int(split or 0), int(split_exp))
+    return out if out_split is None else out_split
+
+
+def patch4_gather_backward(grad_cols, shape, stride):
+    """amav_patch4_gather_backward: grad_cols [K*Ho*Wo, 16*C] -> d x of `shape` = (K,H,W,C): every pixel adds the windows
+    that cover it in ascending window index; exactly 0 where none does."""
+    K, H, W, C = (int(s) for s in shape)
+    rows = K * patch4_out_size(H, stride) * patch4_out_size(W, stride)
+    g = _shaped(_contig(grad_cols, "grad_cols"), "grad_cols", (rows, 16 * C))
+    dx = torch.empty(K, H, W, C, device=g.device)
+    _call("amav_patch4_gather_backward", K, H, W, C, int(stride), g.data_ptr(), dx.data_ptr())
+    return dx
+
+
+class _DwConv7LayerNorm(torch.autograd.Function):
+    """dwconv7_layernorm (fp32 rows) with amav_dwconv7_layernorm_backward as the backward; x, y and the two weights are
+    kept (y is stored, not recomputed: DESIGN.md section 4.22), mean / rstd / the normalised rows are recomputed."""
+
+    @staticmethod
+    def forward(ctx, x, dw_weight, dw_bias, ln_weight, ln_bias, eps):
+        rows, y = dwconv7_layernorm(x, dw_weight, dw_bias, ln_weight, ln_bias, eps, want_y=True)
+        ctx.eps = float(eps)
+        ctx.save_for_backward(x, y, dw_weight, ln_weight)
+        return rows
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_rows):
+        x, y, dw_weight, ln_weight = ctx.saved_tensors
+        grads = dwconv7_layernorm_backward(x, y, dw_weight, ln_weight, ctx.eps, grad_rows.float().contiguous())
+        return tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad)) + (None,)
+
+
+def dwconv7_layernorm_differentiable(x, dw_weight, dw_bias, ln_weight, ln_bias, eps=1e-6):
+    """dwconv7_layernorm(...) -> fp32 rows [K*H*W, C] as a torch.autograd.Function: the same values bit for bit, gradients
+    for x and the four parameters from amav_dwconv7_layernorm_backward."""
+    return _DwConv7LayerNorm.apply(_planes(x, "x"), dw_weight, dw_bias, ln_weight, ln_bias, float(eps))
+
+
+class _GeluBias(torch.autograd.Function):
+    """gelu_bias (fp32 output) with amav_gelu_bias_backward as the backward; only proj and bias are kept."""
+
+    @staticmethod
+    def forward(ctx, proj, bias):
+        ctx.save_for_backward(proj, bias)
+        return gelu_bias(proj, bias)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        proj, bias = ctx.saved_tensors
+        grad = gelu_bias_backward(proj, bias, grad_out.float())
+        grad_bias = rows_colsum(grad.view(-1, grad.shape[-1]))[0] if bias is not None and ctx.needs_input_grad[1] else None
+        return (grad if ctx.needs_input_grad[0] else None), grad_bias
+
+
+def gelu_bias_differentiable(proj, bias=None):
+    """gelu_bias(proj, bias) as a torch.autograd.Function: the same values bit for bit, gradients for proj and bias from
+    amav_gelu_bias_backward / amav_rows_colsum.  Saves proj and bias only."""
+    return _GeluBias.apply(_need(proj, "proj").contiguous(), bias)
+
+
+class _Patch4Gather(torch.autograd.Function):
+    """patch4_gather (fp32 columns) with its transpose as the backward; nothing of the forward is kept but the shape."""
+
+    @staticmethod
+    def forward(ctx, x, stride):
+        ctx.shape, ctx.stride = tuple(x.shape), int(stride)
+        return patch4_gather(x, stride)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_cols):
+        return patch4_gather_backward(grad_cols.float(), ctx.shape, ctx.stride), None
+
+
+def patch4_gather_differentiable(x, stride):
+    """patch4_gather(x, stride) -> fp32 [K*Ho*Wo, 16*C] as a torch.autograd.Function: the same values bit for bit, the
+    gradient of x from amav_patch4_gather_backward."""
+    return _Patch4Gather.apply(_planes(x, "x"), int(stride))
+
+
 # -------------------------------------------------------------------------------------------------- point refiner
 def cloud_voxelize(points, cloud_of, clouds, resolution=100.0):
     """points [n,3] fp32, cloud_of int32 [n] (ascending) -> (grid int32 [n,3] from the cloud's own origin, cloud_depth

@@ -16,11 +16,18 @@ correctness and determinism, on library kernels except where the reference's own
     receives is undefined) -> z-buffer kernel with a fixed rule: the last pixel in (y, x) order that the point wins
     (what a sequential index_put does);
   * cross-attention to the 4096 image tokens and self-attention -> the fp16 x 2 MFMA kernels of csrc/attention.hip,
-    forward and backward (transformer.py; AMAV_CROSS_ATTN=library keeps the library's fused attention for the former).
+    forward and backward (transformer.py; AMAV_CROSS_ATTN=library keeps the library's fused attention for the former);
+  * with cfg.upsample_triplane -- what the reference runs: renderer.yaml's `upsample_triplane: true` overrides
+    triplane_net.yaml's false in the flattened config (config_loader.py:190-234) -- the encoder scatters into
+    (R * upsample_factor)^2 cells and `TriplaneDownsampler` (:411-451: two ConvNeXtBlocks and a 4x4 stride-s convolution)
+    brings the planes back to R^2: depthwise 7x7 + LayerNorm, bias + GELU and the convolution's patch gather are HIP
+    kernels with HIP backwards (csrc/convnext.hip), its three matrix products per block go
+    through transformer.linear / train_linear; AMAV_STAGE1_DOWNSAMPLER=library keeps the library's operators.
 
 `densify_smplx_verts` here means "append the face centres" (:266-272), not the Renderer's subdivision.
 """
 import math
+import os
 
 import torch
 import torch.nn as nn
@@ -31,7 +38,7 @@ from ._lib import AmavError
 from .body_model import BodyModel
 from .renderer import Renderer
 from .smplx_decoder import SMPLXDecoder
-from .transformer import Transformer1D_nn
+from .transformer import Transformer1D_nn, _memo, linear_presplit, split_gemm_ok, train_linear
 
 POINT_RADIUS_NDC = 0.0075  # graphic_utils.py:280 (pytorch3d NDC: the shorter image side spans [-1, 1])
 
@@ -92,9 +99,126 @@ class ImageFeature(nn.Module):
         return torch.cat([rgb.reshape(B * Nv, *rgb.shape[2:]), f], dim=1).reshape(B, Nv, -1, H, W)
 
 
+class ConvNeXtBlock(nn.Module):
+    """triplane_net.py:411-429: x + pwconv2(gelu(pwconv1(LayerNorm(dwconv(x))))), the norm and the projections over the
+    channels.  `forward` takes the reference's [B,C,H,W]; `forward_planes` channels-last planes [K,H,W,C], on the HIP
+    kernels (hip=True) or the library's operators."""
+
+    def __init__(self, dim):
+        super().__init__()
+        self.dwconv = nn.Conv2d(dim, dim, kernel_size=7, padding=3, groups=dim)
+        self.norm = nn.LayerNorm(dim, eps=1e-6)
+        self.pwconv1 = nn.Linear(dim, 4 * dim)
+        self.act = nn.GELU()
+        self.pwconv2 = nn.Linear(4 * dim, dim)
+
+    def forward(self, x):
+        return self.forward_planes(x.permute(0, 2, 3, 1), hip=False).permute(0, 3, 1, 2)
+
+    def forward_planes(self, x, hip, grad=False):
+        dw, norm, pw1, pw2 = self.dwconv, self.norm, self.pwconv1, self.pwconv2
+        K, H, W, C = x.shape
+        if not hip:
+            y = F.conv2d(x.permute(0, 3, 1, 2), dw.weight, dw.bias, padding=3, groups=C).permute(0, 2, 3, 1)
+            n = F.layer_norm(y, (C,), norm.weight, norm.bias, norm.eps)
+            return F.linear(F.gelu(F.linear(n, pw1.weight, pw1.bias)), pw2.weight, pw2.bias) + x
+        x = x.contiguous()
+        if grad:
+            n = ops.dwconv7_layernorm_differentiable(x, dw.weight, dw.bias, norm.weight, norm.bias, norm.eps)
+            h = ops.gelu_bias_differentiable(train_linear(n, pw1.weight), pw1.bias)  # pwconv1's bias: added by the GELU pass
+            return train_linear(h, pw2.weight, pw2.bias).view(K, H, W, C) + x
+        args = (x, dw.weight, dw.bias, norm.weight, norm.bias, norm.eps)
+        p = _linear_after(lambda split: ops.dwconv7_layernorm(*args, split=split), K * H * W, pw1.weight)
+        return _linear_after(lambda split: ops.gelu_bias(p, pw1.bias, split=split), K * H * W, pw2.weight,
+                             pw2.bias).view(K, H, W, C) + x
+
+
+def _linear_after(rows_kernel, rows, weight, bias=None):
+    """F.linear over the rows a HIP kernel produces, without autograd: where transformer.linear would take the bf16 x 3
+    split GEMM (split_gemm_ok) the kernel writes the activation operand itself (rows_kernel(SPLIT_BF16X3)), so the rows
+    never pass through HBM as fp32; elsewhere fp32 rows and the library's GEMM."""
+    if split_gemm_ok(rows, weight.shape[1]):
+        return linear_presplit(rows_kernel(ops.SPLIT_BF16X3), weight, bias)
+    return F.linear(rows_kernel(None), weight, bias)
+
+
+DOWNSAMPLER_DEFAULT = "hip"  # tools/bench_stage1_downsampler.py (DESIGN.md section 4.22)
+DOWNSAMPLER_FRAMES_PER_PASS = 8  # frames (x 3 planes) per pass: the 4C hidden rows of a frame are 113 MB at C = 256, R = 96
+
+
+class TriplaneDownsampler(nn.Module):
+    """triplane_net.py:431-451: two ConvNeXtBlocks, then Conv2d(C, C, 4, stride=upsample_factor, padding=1), applied to
+    every plane on its own.  Parameter names and layouts are the reference's (blocks.{0,1}.*, down.*).
+
+    AMAV_STAGE1_DOWNSAMPLER, read per call: `hip` (the default) runs HIP fp32 planes of a width the kernels are built
+    for (ops.dwconv7_channels_ok) on csrc/convnext.hip -- under autograd (grad=True) through the autograd Functions of
+    ops, so every parameter and the input receive gradients; `library`, and every other input (CPU, other dtypes or
+    widths), evaluates the same module with F.conv2d / F.layer_norm / F.gelu / F.linear."""
+
+    def __init__(self, cfg):
+        super().__init__()
+        self.cfg = cfg
+        self.scale = int(cfg.upsample_factor)
+        if self.scale < 2:
+            raise AmavError(f"TriplaneDownsampler: upsample_factor={cfg.upsample_factor} must be at least 2 (the 4x4 "
+                            "padding-1 convolution returns R - 1 cells at stride 1)")
+        C = cfg.triplane_feature_dim
+        self.blocks = nn.ModuleList([ConvNeXtBlock(C) for _ in range(2)])
+        self.down = nn.Conv2d(C, C, kernel_size=4, stride=self.scale, padding=1)
+
+    def _hip(self, x):
+        return (x.is_cuda and x.dtype == torch.float32 and self.down.weight.dtype == torch.float32
+                and ops.dwconv7_channels_ok(x.shape[-1])
+                and os.environ.get("AMAV_STAGE1_DOWNSAMPLER", DOWNSAMPLER_DEFAULT) != "library")
+
+    def _down_weight(self):
+        """down.weight [C_out, C_in, 4, 4] as the [C_out, 16 C_in] matrix of the tap-major patch rows, permuted once per
+        version of the parameter."""
+        w = self.down.weight
+        return _memo("down_rows", (w,), lambda: w.detach().permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous())
+
+    def forward_planes(self, x, grad=False):
+        """x [K,H,W,C] channels-last planes -> [K,Ho,Wo,C]."""
+        hip = self._hip(x)
+        outs = []
+        for part in x.split(3 * DOWNSAMPLER_FRAMES_PER_PASS):
+            for blk in self.blocks:
+                part = blk.forward_planes(part, hip, grad)
+            K, H, W, C = part.shape
+            if not hip:
+                outs.append(F.conv2d(part.permute(0, 3, 1, 2), self.down.weight, self.down.bias, stride=self.scale,
+                                     padding=1).permute(0, 2, 3, 1))
+                continue
+            Ho, Wo = ops.patch4_out_size(H, self.scale), ops.patch4_out_size(W, self.scale)
+            if grad:
+                w = self.down.weight.permute(0, 2, 3, 1).reshape(C, 16 * C)
+                y = train_linear(ops.patch4_gather_differentiable(part, self.scale), w, self.down.bias,
+                                 sources=(self.down.weight,))
+            else:
+                y = _linear_after(lambda split, part=part: ops.patch4_gather(part, self.scale, split=split), K * Ho * Wo,
+                                  self._down_weight(), self.down.bias)
+            outs.append(y.view(K, Ho, Wo, C))
+        return outs[0] if len(outs) == 1 else torch.cat(outs)
+
+    def forward(self, x, grad=None):
+        """x [F,3,C,H,W] (the reference's layout) -> [F,3,C,H/s,W/s]; channels-last planes [K,H,W,C] -> [K,H/s,W/s,C].
+        grad: whether the HIP path records an autograd graph (None: grad mode is on and the input or a parameter
+        requires grad)."""
+        if grad is None:
+            grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+        if x.dim() == 4:
+            return self.forward_planes(x, grad)
+        Fr, P, C, H, W = x.shape
+        y = self.forward_planes(x.permute(0, 1, 3, 4, 2).reshape(Fr * P, H, W, C), grad)
+        return y.view(Fr, P, *y.shape[1:]).permute(0, 1, 4, 2, 3)
+
+
 class SMPLXTriplaneEncoder(nn.Module):
     """triplane_net.py:66-352: a posed SMPL-X mesh (+ per-vertex embedding, + image features under the projected
-    vertices) -> PointNet with triplane-cell max pooling -> per-cell mean -> geometry triplanes [B,T,3,C,R,R]."""
+    vertices) -> PointNet with triplane-cell max pooling -> per-cell mean -> geometry triplanes [B,T,3,C,R,R].  With
+    cfg.upsample_triplane the cells are those of an (R * upsample_factor)^2 grid and `triplane_downsampler` returns the
+    planes to R^2 (:96-97, 176-205); self.triplane_resolution stays R (the reference multiplies and divides it on every
+    call), and any number of frames B * T works (the reference's .squeeze(1) needs T = 1)."""
 
     def __init__(self, cfg, smpl_decoder=None):
         super().__init__()
@@ -109,9 +233,10 @@ class SMPLXTriplaneEncoder(nn.Module):
         self.blocks = nn.ModuleList([ResnetBlockFC(2 * C, C) for _ in range(3)])
         self.fc_c = nn.Linear(C, C)
         self.vertex_emb = nn.Embedding(self.num_verts, C // 2 if cfg.sample_feature else C)
+        self.cell_resolution = self.triplane_resolution
         if getattr(cfg, "upsample_triplane", False):
-            raise NotImplementedError("stage 1 with upsample_triplane (TriplaneDownsampler, triplane_net.py:432-451) "
-                                      "is not built; the reference's triplane_net.yaml has it off")
+            self.triplane_downsampler = TriplaneDownsampler(cfg)
+            self.cell_resolution = self.triplane_resolution * self.triplane_downsampler.scale
         if cfg.predict_smplx_params:
             self.smpl_token_len, self.smpl_token_dim = cfg.smpl_token_len, cfg.smpl_token_dim
             self.smpl_tokens = nn.Parameter(torch.randn(self.smpl_token_dim, self.smpl_token_len))
@@ -152,8 +277,9 @@ class SMPLXTriplaneEncoder(nn.Module):
         return torch.cat([vertices, centers], dim=1)
 
     def cell_indices(self, verts):
-        """:163-183: clamp to the cube, normalise to [0,1), cell = x + R * y for (x,y), (x,z), (y,z) -> int32 [BT,3,N]."""
-        R, rad = self.triplane_resolution, self.cfg.radius
+        """:163-183: clamp to the cube, normalise to [0,1), cell = x + R * y for (x,y), (x,z), (y,z) -> int32 [BT,3,N]; R is
+        the cell grid's resolution (triplane_resolution, times upsample_factor with upsample_triplane)."""
+        R, rad = self.cell_resolution, self.cfg.radius
         pos = (torch.clamp(verts, -rad + 1e-6, rad - 1e-6) + rad) / (2 * rad)
         cells = []
         for a, b in ((0, 1), (0, 2), (1, 2)):
@@ -198,7 +324,7 @@ class SMPLXTriplaneEncoder(nn.Module):
             verts_feat = verts_emb
         net = self.blocks[0](self.fc_pos(torch.cat([verts, verts_feat], dim=-1)))
         cell_of = self.cell_indices(verts)
-        cells = self.triplane_resolution ** 2
+        cells = self.cell_resolution ** 2
         segments = ops.cell_segments(cell_of, cells)
         for block in self.blocks[1:]:                                                # :185-188
             pooled = pool(net, cell_of, cells, segments)
@@ -207,8 +333,13 @@ class SMPLXTriplaneEncoder(nn.Module):
         planes = [splat(c, cell_of[:, p].contiguous(), cells,
                         (segments[0][:, p].contiguous(), segments[1][:, p].contiguous()))
                   for p in range(3)]
-        R = self.triplane_resolution
+        R = self.cell_resolution
         smplx_triplanes = torch.stack(planes, dim=1).view(B, T, 3, -1, R, R)
+        if self.cell_resolution != self.triplane_resolution:                         # :202-205, for any B * T
+            C = smplx_triplanes.shape[3]
+            fine = smplx_triplanes.view(B * T * 3, C, R, R).permute(0, 2, 3, 1)      # channels-last planes [K,R,R,C]
+            coarse = self.triplane_downsampler(fine, grad=grad)                      # [K,r,r,C]
+            smplx_triplanes = coarse.permute(0, 3, 1, 2).reshape(B, T, 3, C, *coarse.shape[1:3])
         return smplx_triplanes, smpl_tokens, pred_smpl_params
 
 

@@ -857,6 +857,61 @@ int amav_add_layernorm_backward(int64_t rows, int dim, const float *h_dev, const
                                 float *dbias_dev, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Stage-1 TriplaneDownsampler (src/models/triplane_net.py:411-451: two ConvNeXtBlocks and Conv2d(C, C, 4, stride s,
+ * padding 1)): everything of it that is not a matrix product (csrc/convnext.hip).  fp32, planes
+ * channels-last [planes, height, width, channels] with planes = frames x 3; deterministic bit for bit (no atomics, every
+ * sum in an order fixed by the sizes alone), planes independent of each other; kernel launches only; all buffers 16-byte
+ * aligned.  Results that feed a projection go to exactly one of an fp32 buffer and out_split, the ACTIVATION operand of
+ * amav_split_operand in split_format / split_scale_exp (the rule of amav_add_layernorm); the other is NULL.
+ *
+ * amav_dwconv7_layernorm   ConvNeXtBlock's dwconv -> permute -> norm (:414-424).  y = depthwise 7x7 convolution of x
+ *                      (padding 3, taps outside the plane read zero; dw_weight [channels, 49], nn.Conv2d's [C,1,7,7]) +
+ *                      dw_bias: bias first, then the taps in (ky, kx) order, one fma each.  out [planes*height*width,
+ *                      channels] = LayerNorm over the channels of y (two-pass mean / variance, eps as given; the
+ *                      reference uses 1e-6) * ln_weight + ln_bias.  y_dev: NULL, or [planes, height, width, channels],
+ *                      receives y -- what the backward reads.  channels: a multiple of 64 in [64, 512].
+ * ..._backward         from x, the stored y and dnorm = dLoss/d out [planes*height*width, channels]: LayerNorm backward
+ *                      with mean and rstd recomputed as the forward computes them (amav_add_layernorm_backward's
+ *                      formulas), then dx = the same stencil over dy with the flipped kernel, d_dw_weight [channels, 49],
+ *                      d_dw_bias, d_ln_weight, d_ln_bias [channels].  The four parameter gradients are two-stage sums
+ *                      in amav_rows_colsum's scheme: LayerNorm's over chunks of 16 rows (ascending rows, then ascending
+ *                      chunks); the depthwise ones over the 8 x 8 pixel tiles of the stencil (inside a tile row-major,
+ *                      two rows per wave, then the four waves in order; then the tiles ascending over plane, tile row,
+ *                      tile column).  dx of a plane does not depend on the other planes of the call.  workspace:
+ *                      amav_dwconv7_layernorm_backward_workspace_bytes bytes (0 = bad sizes).
+ * amav_gelu_bias       ConvNeXtBlock's act (:417, exact erf): out [rows, inner] = gelu(proj + bias); proj [rows, inner]
+ *                      with row stride proj_row_stride floats (a multiple of 4), bias [inner] may be NULL; inner a
+ *                      multiple of 4 (of 8 for a split operand).
+ * ..._backward         dproj = dout (Phi(g) + g phi(g)) with g = proj + bias recomputed; the bias gradient is
+ *                      amav_rows_colsum(dproj), one group.
+ * amav_patch4_gather   the im2col of the strided convolution: out [planes*Ho*Wo, 16*channels], column (4 ky + kx) *
+ *                      channels + c of window (k, oy, ox) = x[k, oy*stride - 1 + ky, ox*stride - 1 + kx, c], +0 outside
+ *                      the plane; Ho = (height - 2) / stride + 1, Wo likewise.  The convolution is out times the weight
+ *                      permuted to [C_out, ky, kx, C_in].  stride >= 2, height, width >= 2, channels a multiple of 4 (of 8
+ *                      for a split operand).
+ * ..._backward         the transpose: dx [planes, height, width, channels] = the sum of dcols over the at most
+ *                      ceil(4 / stride)^2 windows that cover the pixel, in ascending window index; +0 where no window
+ *                      does (stride > 4, or rows / columns past the last window). */
+int amav_dwconv7_layernorm(int planes, int height, int width, int channels, const float *x_dev,
+                           const float *dw_weight_dev, const float *dw_bias_dev, const float *ln_weight_dev,
+                           const float *ln_bias_dev, float eps, float *y_dev /* may be NULL */, float *out_dev,
+                           void *out_split_dev, int split_format, int split_scale_exp, void *stream);
+size_t amav_dwconv7_layernorm_backward_workspace_bytes(int planes, int height, int width, int channels);
+int amav_dwconv7_layernorm_backward(int planes, int height, int width, int channels, const float *x_dev,
+                                    const float *y_dev, const float *dw_weight_dev, const float *ln_weight_dev, float eps,
+                                    const float *dnorm_dev, float *dx_dev, float *d_dw_weight_dev, float *d_dw_bias_dev,
+                                    float *d_ln_weight_dev, float *d_ln_bias_dev, void *workspace, size_t workspace_bytes,
+                                    void *stream);
+int amav_gelu_bias(int64_t rows, int inner, const float *proj_dev, int64_t proj_row_stride, const float *bias_dev,
+                   float *out_dev, void *out_split_dev, int split_format, int split_scale_exp, void *stream);
+int amav_gelu_bias_backward(int64_t rows, int inner, const float *proj_dev, int64_t proj_row_stride, const float *bias_dev,
+                            const float *dout_dev, float *dproj_dev, int64_t dproj_row_stride, void *stream);
+int amav_patch4_gather(int planes, int height, int width, int channels, int stride, const float *x_dev, float *out_dev,
+                       void *out_split_dev, int split_format, int split_scale_exp, void *stream);
+int amav_patch4_gather_backward(int planes, int height, int width, int channels, int stride, const float *dcols_dev,
+                                float *dx_dev, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Point refiner: the sparse / serialised operators of the reference's
  * PointTransformerV3 (src/models/point_transformer/pointtransformer_v3.py:81-145,328-499,618-759; point_encoder.py:25-40;
  * called from src/models/renderer.py:143-151) over a batch of CLOUDS (one per frame; n = all their points, a

@@ -1,0 +1,201 @@
+"""The TriplaneDownsampler kernels (csrc/convnext.hip) on the MI355X against the fp64 restatement
+of tests/downsampler_cases.py: depthwise 7x7 + LayerNorm, bias + GELU, the 4x4 stride-s patch gather, and their backwards.
+
+Bounds (downsampler_cases.bound): the library's own fp32 error against the same fp64 restatement (F.conv2d,
+F.layer_norm, F.gelu and their autograd; the larger of the CPU and the MI355X measurement, rounded up to one digit), times
+4 for the different summation order over 49 taps and C channels; relative to max |reference| per tensor.  Measured over
+the cases of this file (downsampler_cases.measure_library; every test prints its own figure):
+
+    kind     library fp32, CPU   library fp32, MI355X   HIP kernels, MI355X   bound
+    conv         2.8e-7              2.7e-7                 3.1e-7             1.2e-6
+    norm         2.4e-7              3.5e-7                 2.7e-7             1.6e-6
+    gelu         1.0e-7              6.2e-8                 6.2e-8             8.0e-7
+    dx           2.1e-7              2.6e-7                 2.1e-7             1.2e-6
+    dparam       4.9e-7              3.7e-7                 2.2e-7             2.0e-6
+    dgelu        1.4e-7              7.3e-8                 7.3e-8             8.0e-7
+
+The gather and its transpose copy and add at most four fp32 terms in the reference's order: compared exactly."""
+import pytest
+import torch
+
+import downsampler_cases as dc
+
+pytestmark = pytest.mark.gpu
+
+
+def check(kind, got, want, what):
+    err = dc.rel_err(got, want)
+    print(f"{what}: {kind} error {err:.3e} (bound {dc.bound(kind):.1e})")
+    assert err <= dc.bound(kind), f"{what}: {err:.3e} > {dc.bound(kind):.1e}"
+
+
+def cuda(ts):
+    return [t.cuda() for t in ts]
+
+
+# ------------------------------------------------------------------------------------------ depthwise 7x7 + LayerNorm
+@pytest.mark.parametrize("case", dc.DW_CASES, ids=lambda c: "x".join(map(str, c)))
+def test_dwconv7_layernorm_matches_the_restatement(case):
+    from audio_motion_avatar_amd import ops
+
+    args, (y, n) = dc.dw_case(*case)
+    rows, got_y = ops.dwconv7_layernorm(*cuda(args), want_y=True)
+    check("conv", got_y, y, f"{case} y")
+    check("norm", rows, n, f"{case} norm")
+    plain = ops.dwconv7_layernorm(*cuda(args))
+    assert torch.equal(plain, rows)                                    # with and without the stored y
+    # the split outputs are amav_split_operand's operands of the fp32 rows, part for part
+    bf = ops.dwconv7_layernorm(*cuda(args), split=ops.SPLIT_BF16X3)
+    assert torch.equal(bf.float(), ops.split_operand(rows).float())
+    fp = ops.dwconv7_layernorm(*cuda(args), split=ops.SPLIT_FP16X2, split_exp=9)
+    assert torch.equal(fp.float(), ops.split_operand(rows, fmt=ops.SPLIT_FP16X2, scale_exp=9).float())
+
+
+def test_dwconv7_layernorm_planes_do_not_bleed():
+    """K = 2 with a NaN-poisoned neighbour plane: plane 0 is finite and equals the call on plane 0 alone, bit for bit."""
+    from audio_motion_avatar_amd import ops
+
+    for C in (64, 256):
+        args, _ = dc.dw_case(2, 9, 13, C)
+        x, params = args[0].cuda(), cuda(args[1:])
+        alone, y_alone = ops.dwconv7_layernorm(x[:1].contiguous(), *params, want_y=True)
+        for poisoned in (1, 0):
+            xp = x.clone()
+            xp[poisoned] = float("nan")
+            rows, y = ops.dwconv7_layernorm(xp, *params, want_y=True)
+            rows = rows.view(2, 9 * 13, C)
+            clean = 1 - poisoned
+            assert bool(torch.isfinite(rows[clean]).all()) and bool(torch.isfinite(y[clean]).all())
+            assert bool(torch.isnan(rows[poisoned]).all())
+            if clean == 0:
+                assert torch.equal(rows[0], alone) and torch.equal(y[0], y_alone[0])
+
+
+@pytest.mark.parametrize("C", (64, 256))
+def test_impulse_returns_the_flipped_kernel_and_zero_input_the_norm_bias(C):
+    from audio_motion_avatar_amd import ops
+
+    H, W = 9, 13
+    w = dc.randn(7, C, 1, 7, 7).cuda()
+    zeros, ones = torch.zeros(C, device="cuda"), torch.ones(C, device="cuda")
+    ln_b = dc.randn(8, C).cuda()
+    x = torch.zeros(1, H, W, C, device="cuda")
+    x[0, 4, 6] = 1.0
+    _, y = ops.dwconv7_layernorm(x, w, zeros, ones, ln_b, want_y=True)
+    # y[4 + dy, 6 + dx] = w[3 - dy, 3 - dx]: the kernel flipped about the impulse, exactly (every other term is 0 * w)
+    want = torch.zeros_like(y)
+    want[0, 1:8, 3:10] = w[:, 0].flip(1, 2).permute(1, 2, 0)
+    assert torch.equal(y, want)
+    # all-zero input, constant bias: zero variance, the output is the norm's bias exactly
+    rows, y = ops.dwconv7_layernorm(torch.zeros_like(x), w, 0.5 * ones, 1.0 + dc.randn(9, C).cuda(), ln_b, want_y=True)
+    assert bool((y == 0.5).all()) and torch.equal(rows, ln_b.expand(H * W, C))
+
+
+@pytest.mark.parametrize("case", dc.DW_CASES, ids=lambda c: "x".join(map(str, c)))
+def test_dwconv7_layernorm_backward_matches_fp64_autograd(case):
+    from audio_motion_avatar_amd import ops
+
+    args, g, want = dc.dw_backward_case(*case)
+    x, dw_w, dw_b, ln_w, ln_b = cuda(args)
+    _, y = ops.dwconv7_layernorm(x, dw_w, dw_b, ln_w, ln_b, want_y=True)
+    got = ops.dwconv7_layernorm_backward(x, y, dw_w, ln_w, 1e-6, g.cuda())
+    for name, a, b in zip(("dx", "d dw_weight", "d dw_bias", "d ln_weight", "d ln_bias"), got, want):
+        check("dx" if name == "dx" else "dparam", a, b, f"{case} {name}")
+    again = ops.dwconv7_layernorm_backward(x, y, dw_w, ln_w, 1e-6, g.cuda())
+    assert all(torch.equal(a, b) for a, b in zip(got, again))          # two calls bit-equal
+    # under autograd: the forward is the plain call bit for bit and backward() returns the same gradients
+    leaves = [t.clone().requires_grad_(True) for t in (x, dw_w, dw_b, ln_w, ln_b)]
+    rows = ops.dwconv7_layernorm_differentiable(*leaves)
+    assert torch.equal(rows.detach(), ops.dwconv7_layernorm(x, dw_w, dw_b, ln_w, ln_b))
+    rows.backward(g.cuda())
+    assert all(torch.equal(t.grad, a) for t, a in zip(leaves, got))
+
+
+def test_dwconv7_layernorm_backward_of_a_batch_equals_its_halves():
+    """dx of a K = 4 call is bit-equal to two K = 2 calls (planes are independent); the parameter gradients are sums
+    over all planes and only have to agree to rounding."""
+    from audio_motion_avatar_amd import ops
+
+    args, g, _ = dc.dw_backward_case(2, 9, 13, 256)
+    args2, g2, _ = dc.dw_backward_case(2, 9, 13, 256, seed=50)
+    x = torch.cat([args[0], args2[0]]).cuda()
+    grad = torch.cat([g, g2]).cuda()
+    dw_w, dw_b, ln_w, ln_b = cuda(args[1:])
+    _, y = ops.dwconv7_layernorm(x, dw_w, dw_b, ln_w, ln_b, want_y=True)
+    full = ops.dwconv7_layernorm_backward(x, y, dw_w, ln_w, 1e-6, grad)
+    rows = 2 * 9 * 13
+    halves = [ops.dwconv7_layernorm_backward(x[i:i + 2].contiguous(), y[i:i + 2].contiguous(), dw_w, ln_w, 1e-6,
+                                             grad[i // 2 * rows:(i // 2 + 1) * rows].contiguous()) for i in (0, 2)]
+    assert torch.equal(full[0], torch.cat([halves[0][0], halves[1][0]]))
+    for a, b, c in zip(full[1:], halves[0][1:], halves[1][1:]):
+        check("dparam", a, (b.double() + c.double()), "K = 4 parameter gradient against the sum of two K = 2 calls")
+
+
+# ------------------------------------------------------------------------------------------------------ bias + GELU
+@pytest.mark.parametrize("rows", dc.GELU_ROWS)
+def test_gelu_bias_and_its_backward(rows):
+    from audio_motion_avatar_amd import ops
+
+    (proj, bias, g), (out, d_proj, d_bias) = dc.gelu_case(rows)
+    proj, bias, g = cuda((proj, bias, g))
+    got = ops.gelu_bias(proj, bias)
+    check("gelu", got, out, f"rows={rows} gelu")
+    check("gelu", ops.gelu_bias(proj + bias), out, f"rows={rows} gelu without a bias")
+    bf = ops.gelu_bias(proj, bias, split=ops.SPLIT_BF16X3)
+    assert torch.equal(bf.float(), ops.split_operand(got).float())
+    fp = ops.gelu_bias(proj, bias, split=ops.SPLIT_FP16X2, split_exp=10)
+    assert torch.equal(fp.float(), ops.split_operand(got, fmt=ops.SPLIT_FP16X2, scale_exp=10).float())
+    grad = ops.gelu_bias_backward(proj, bias, g)
+    check("dgelu", grad, d_proj, f"rows={rows} d proj")
+    assert torch.equal(grad, ops.gelu_bias_backward(proj, bias, g))
+    leaves = [proj.clone().requires_grad_(True), bias.clone().requires_grad_(True)]
+    y = ops.gelu_bias_differentiable(*leaves)
+    assert torch.equal(y.detach(), got)
+    y.backward(g)
+    assert torch.equal(leaves[0].grad, grad)
+    check("dparam", leaves[1].grad, d_bias, f"rows={rows} d bias")
+    if rows > 1:  # a batch of rows equals its parts: the kernel is row-wise
+        assert torch.equal(grad[:32], ops.gelu_bias_backward(proj[:32].contiguous(), bias, g[:32].contiguous()))
+
+
+# ------------------------------------------------------------------------------- 4x4 stride-s patch gather / transpose
+@pytest.mark.parametrize("stride,H,W", [(2, 9, 12), (3, 12, 12), (3, 10, 13), (4, 10, 14), (5, 13, 16)])
+def test_patch4_gather_and_its_transpose(stride, H, W):
+    """s = 2: the bottom / right taps leave the plane; s = 5: some pixels lie in no window and get exactly 0."""
+    from audio_motion_avatar_amd import ops
+
+    K, C = 4, 64
+    x = dc.randn(60 + stride, K, H, W, C)
+    want = dc.patch4_gather(x, stride)
+    Ho, Wo = ops.patch4_out_size(H, stride), ops.patch4_out_size(W, stride)
+    assert want.shape == (K * Ho * Wo, 16 * C)
+    got = ops.patch4_gather(x.cuda(), stride)
+    assert torch.equal(got.cpu(), want)
+    assert torch.equal(ops.patch4_gather(x.cuda(), stride, split=ops.SPLIT_BF16X3).float(), ops.split_operand(got).float())
+    assert torch.equal(ops.patch4_gather(x.cuda(), stride, split=ops.SPLIT_FP16X2, split_exp=11).float(),
+                       ops.split_operand(got, fmt=ops.SPLIT_FP16X2, scale_exp=11).float())
+    # the product with the permuted weight is the convolution
+    w, b = dc.randn(70, C, C, 4, 4, scale=0.03), dc.randn(71, C, scale=0.1)
+    conv = torch.nn.functional.conv2d(x.double().permute(0, 3, 1, 2), w.double(), b.double(), stride=stride, padding=1)
+    mine = got.cpu().double() @ w.double().permute(0, 2, 3, 1).reshape(C, -1).t() + b.double()
+    assert dc.rel_err(mine.view(K, Ho, Wo, C), conv.permute(0, 2, 3, 1)) < 1e-12
+    # transpose: fp64 autograd of the restatement; at most four terms per pixel, added in the same (window) order
+    g = dc.randn(80 + stride, *want.shape)
+    leaf = x.double().requires_grad_(True)
+    (dx,) = torch.autograd.grad(dc.patch4_gather(leaf, stride), leaf, g.double())
+    got_dx = ops.patch4_gather_backward(g.cuda(), x.shape, stride)
+    # <= 4 fp32 terms: three additions, each rounding a partial sum of magnitude <= 4 max |g| to 2^-24 of itself
+    assert dc.rel_err(got_dx, dx) <= 3 * 2.0 ** -24 * 4 * float(g.abs().max()) / float(dx.abs().max())
+    covered = lambda n, no: torch.tensor([any(o * stride - 1 <= i <= o * stride + 2 for o in range(no)) for i in range(n)])
+    uncovered = ~(covered(H, Ho)[:, None] & covered(W, Wo)[None, :])    # past the last window, or between windows (s = 5)
+    assert torch.equal(got_dx.cpu().abs().sum(-1) == 0, uncovered.expand(K, H, W))
+    assert bool(uncovered.any()) == ((stride, H, W) in ((3, 10, 13), (5, 13, 16)))
+    assert torch.equal(got_dx, ops.patch4_gather_backward(g.cuda(), x.shape, stride))
+    rows = 2 * Ho * Wo
+    halves = [ops.patch4_gather_backward(g[i * rows:(i + 1) * rows].cuda(), (2, H, W, C), stride) for i in (0, 1)]
+    assert torch.equal(got_dx, torch.cat(halves))                       # K = 4 equals two K = 2 calls
+    leaf = x.cuda().requires_grad_(True)
+    cols = ops.patch4_gather_differentiable(leaf, stride)
+    assert torch.equal(cols.detach(), got)
+    cols.backward(g.cuda())
+    assert torch.equal(leaf.grad, got_dx)
