@@ -21,9 +21,15 @@ FrameWriter needs no OpenCV: frames leave the GPU as uint8 RGB (`(frame * 255).a
 `ffmpeg` child process that encodes the video and muxes the audio in the same pass (the reference writes a silent mp4
 with cv2 and re-muxes it); without ffmpeg on PATH that target is refused, and a `.rgb` target (raw frames + a JSON
 side-car with width / height / fps) or any writable binary stream works everywhere.
+
+An `.avi` target needs no encoder process: the frames are JPEG-encoded on the device (ops.jpeg_encode; fp32 RGBA frames
+never become rgb24) and only the streams cross to the host, into a Motion-JPEG AVI with the clip's audio as 16-bit PCM
+(mjpeg.AviWriter).  `.mjpeg` is the bare concatenation of the JPEGs, and `--frames-dir` the reference's per-frame
+image dump (main2.py:231-236) as frame_000.jpg ... from the same streams.
 """
 import argparse
 import json
+import os
 import shutil
 import subprocess
 import sys
@@ -33,19 +39,35 @@ import torch
 from . import ops
 
 VIDEO_SUFFIXES = (".mp4", ".mkv", ".mov")
+JPEG_CHUNK = 64  # frames per ops.jpeg_encode call: bounds the encoder's workspace for long clips
 
 
 class FrameWriter:
     """Sink of rendered frames: `write(frames)` takes fp32 [..., H, W, 3|4] in [0, 1] on the HIP device (or uint8 RGB
-    on any device) and appends them; `close()` finishes the file (and waits for ffmpeg)."""
+    on any device) and appends them; `close()` finishes the file (and waits for ffmpeg).  `.avi` / `.mjpeg` targets
+    and `frames_dir` take the frames through the device's JPEG encoder (`jpeg_quality`, `jpeg_subsampling`)."""
 
-    def __init__(self, target, height, width, fps=24.0, audio_path=None, ffmpeg="ffmpeg"):
+    def __init__(self, target, height, width, fps=24.0, audio_path=None, ffmpeg="ffmpeg", jpeg_quality=90,
+                 jpeg_subsampling="420", frames_dir=None, device="cuda"):
         self.height, self.width, self.fps = int(height), int(width), float(fps)
         self.frames = 0
         self.proc = None
         self.sidecar = None
+        self.avi = None
         self._close_stream = False
-        if hasattr(target, "write"):
+        self.jpeg_quality, self.jpeg_subsampling, self.device = int(jpeg_quality), str(jpeg_subsampling), device
+        self.frames_dir = frames_dir
+        if frames_dir is not None:
+            os.makedirs(frames_dir, exist_ok=True)
+        suffix = "" if hasattr(target, "write") else os.path.splitext(str(target))[1].lower()
+        self.bare_jpeg = suffix == ".mjpeg"
+        if suffix == ".avi":
+            from .mjpeg import AviWriter, load_pcm16
+
+            self.stream = None
+            self.avi = AviWriter(str(target), self.height, self.width, self.fps,
+                                 audio=load_pcm16(audio_path) if audio_path else None)
+        elif hasattr(target, "write"):
             self.stream = target
         elif str(target).lower().endswith(VIDEO_SUFFIXES):
             exe = shutil.which(ffmpeg)
@@ -62,18 +84,45 @@ class FrameWriter:
         else:
             self.stream = open(target, "wb")
             self._close_stream = True
-            self.sidecar = str(target) + ".json"
+            self.sidecar = None if self.bare_jpeg else str(target) + ".json"
+
+    def _write_jpeg(self, frames):
+        """Encode on the device, copy the streams (not the frames) to the host and hand every frame's JPEG on."""
+        frames = frames.reshape(-1, self.height, self.width, frames.shape[-1])
+        if not frames.is_cuda:
+            frames = frames.to(self.device)
+        for at in range(0, frames.shape[0], JPEG_CHUNK):
+            stream, offsets = ops.jpeg_encode(frames[at:at + JPEG_CHUNK].contiguous(), quality=self.jpeg_quality,
+                                              subsampling=self.jpeg_subsampling)
+            data, offsets = stream.cpu().numpy().tobytes(), offsets.tolist()
+            for i in range(len(offsets) - 1):
+                jpeg = data[offsets[i]:offsets[i + 1]]
+                if self.avi is not None:
+                    self.avi.write_frame(jpeg)
+                elif self.bare_jpeg:
+                    self.stream.write(jpeg)
+                if self.frames_dir is not None:
+                    with open(os.path.join(self.frames_dir, f"frame_{self.frames + at + i:03d}.jpg"), "wb") as fh:
+                        fh.write(jpeg)
 
     def write(self, frames):
-        if frames.dtype != torch.uint8:
-            if frames.shape[-1] == 3:  # the reference's [B,T,H,W,3] images: add the alpha the packing kernel skips
-                frames = torch.cat([frames, torch.ones_like(frames[..., :1])], dim=-1)
-            frames = ops.frames_to_rgb8(frames.contiguous())
-        frames = frames.reshape(-1, self.height, self.width, 3)
-        self.stream.write(frames.cpu().numpy().tobytes())
-        self.frames += frames.shape[0]
+        if frames.dtype != torch.uint8 and frames.shape[-1] == 3:
+            # the reference's [B,T,H,W,3] images: add the alpha the packing kernels skip
+            frames = torch.cat([frames, torch.ones_like(frames[..., :1])], dim=-1)
+        count = frames.numel() // (self.height * self.width * frames.shape[-1])
+        jpeg = self.avi is not None or self.bare_jpeg
+        if jpeg or self.frames_dir is not None:
+            self._write_jpeg(frames)
+        if not jpeg:
+            if frames.dtype != torch.uint8:
+                frames = ops.frames_to_rgb8(frames.contiguous())
+            self.stream.write(frames.reshape(-1, self.height, self.width, 3).cpu().numpy().tobytes())
+        self.frames += count
 
     def close(self):
+        if self.avi is not None:
+            self.avi.close()
+            return
         if self.proc is not None:
             self.stream.close()
             if self.proc.wait() != 0:
@@ -130,9 +179,13 @@ def main(argv=None):
                     help="the reference's default renderer.yaml: triplane upsampler x16, PTv3 point refiner, 30 000 Gaussians "
                          "(what a released checkpoint was trained with); default is BASELINE's 10 000-Gaussian renderer")
     ap.add_argument("--fps", type=float, default=24.0)
-    ap.add_argument("--out", default="demo.rgb", help=".rgb (raw frames + .json), .mp4 / .mkv / .mov (needs ffmpeg) or - for stdout")
+    ap.add_argument("--out", default="demo.rgb", help=".rgb (raw frames + .json), .avi (Motion-JPEG + PCM audio, encoded on the "
+                                                      "device), .mjpeg (bare JPEGs), .mp4 / .mkv / .mov (needs ffmpeg) or - for stdout")
     ap.add_argument("--smplx-out", help="also write the mesh clip there: every frame above the same frame with the predicted "
                                         "SMPL-X mesh drawn over it (height 2H; same suffix rules and audio as --out)")
+    ap.add_argument("--jpeg-quality", type=int, default=90, help="quality 1..100 of .avi / .mjpeg / --frames-dir output")
+    ap.add_argument("--jpeg-subsampling", choices=("420", "444"), default="420")
+    ap.add_argument("--frames-dir", help="also write every frame of --out there as frame_000.jpg ... (main2.py:231-236)")
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--seed", type=int, default=42)
     args = ap.parse_args(argv)
@@ -162,7 +215,8 @@ def main(argv=None):
     seeds = _load_tokens(args.tokens, cfg, args.device, args.seed)
     target = sys.stdout.buffer if args.out == "-" else args.out
     want_mesh = args.smplx_out is not None
-    with FrameWriter(target, H, W, fps=args.fps, audio_path=args.audio) as writer:
+    jpeg = dict(jpeg_quality=args.jpeg_quality, jpeg_subsampling=args.jpeg_subsampling, device=args.device)
+    with FrameWriter(target, H, W, fps=args.fps, audio_path=args.audio, frames_dir=args.frames_dir, **jpeg) as writer:
         if args.interleave:
             if len(seeds) < 2:
                 raise SystemExit("--interleave needs two token pairs (even and odd chain)")
@@ -183,7 +237,7 @@ def main(argv=None):
                                       {k: v[None, :n] for k, v in smplx.items()}, cam["intrinsic"][:, :n],
                                       cam["extrinsic"][:, :n], body, SimpleMeshRenderer(body.faces, H, W))
         mesh_target = sys.stdout.buffer if args.smplx_out == "-" else args.smplx_out
-        with FrameWriter(mesh_target, 2 * H, W, fps=args.fps, audio_path=args.audio) as mesh_writer:
+        with FrameWriter(mesh_target, 2 * H, W, fps=args.fps, audio_path=args.audio, **jpeg) as mesh_writer:
             mesh_writer.write(stacked)
         print(f"wrote {mesh_writer.frames} frames of {W}x{2 * H} (frame over mesh overlay) to {args.smplx_out}",
               file=sys.stderr)

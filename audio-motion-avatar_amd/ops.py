@@ -495,6 +495,99 @@ def frames_tile_state(num_buffers, F, H, W, device):
     return torch.full((num_buffers * F * tile_count(H, W),), -1, dtype=torch.int32, device=device)
 
 
+# ----------------------------------------------------------------------------------------------------------- JPEG
+JPEG_SUBSAMPLING = {"420": _lib.DEFINES["AMAV_JPEG_420"], "444": _lib.DEFINES["AMAV_JPEG_444"]}
+
+
+def _jpeg_args(frames, subsampling, tile_hint, background, who):
+    """(frames, F, H, W, is_rgba_f32, subsampling code, hint pointer, background) of a JPEG call: fp32 RGBA [F,H,W,4]
+    or uint8 RGB [F,H,W,3], contiguous, on the device."""
+    if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
+        raise AmavError(f"{who}: frames must be a tensor on the HIP device")
+    rgba = frames.dtype == torch.float32
+    if frames.dim() != 4 or not frames.is_contiguous() or frames.dtype not in (torch.float32, torch.uint8) or \
+            frames.shape[-1] != (4 if rgba else 3):
+        raise AmavError(f"{who}: need contiguous fp32 RGBA [F,H,W,4] or uint8 RGB [F,H,W,3] frames, got "
+                        f"{frames.dtype} {tuple(frames.shape)}")
+    if str(subsampling) not in JPEG_SUBSAMPLING:
+        raise AmavError(f"{who}: unknown subsampling {subsampling!r} (420 or 444)")
+    F, H, W = (int(x) for x in frames.shape[:3])
+    hint_ptr, bg3 = None, None
+    if tile_hint is not None:
+        tile_hint = _need(tile_hint, "tile_hint", torch.int32)
+        if not tile_hint.is_contiguous() or tile_hint.numel() != F * tile_count(H, W):
+            raise AmavError(f"{who}: tile_hint must be a contiguous int32 [F * tiles] tensor")
+        hint_ptr = tile_hint.data_ptr()
+        bg3 = (ctypes.c_float * 3)(*[float(c) for c in (background if background is not None else (1.0, 1.0, 1.0))])
+    return frames, F, H, W, int(rgba), JPEG_SUBSAMPLING[str(subsampling)], hint_ptr, bg3
+
+
+def jpeg_coefficients(frames, quality=90, subsampling="420", tile_hint=None, background=None):
+    """The encoder's transform stage alone: frames -> int16 levels [F, blocks per frame, 64] (blocks in MCU-interleaved
+    scan order, coefficients in zigzag order; include/amav.h has the arithmetic).  `tile_hint` / `background` as in
+    frames_pack_tiles (background defaults to white)."""
+    frames, F, H, W, rgba, sub, hint_ptr, bg3 = _jpeg_args(frames, subsampling, tile_hint, background, "jpeg_coefficients")
+    blocks = int(_lib.lib().amav_jpeg_num_blocks(F, H, W, sub))
+    if blocks == 0:
+        raise AmavError(f"jpeg_coefficients: sizes F={F} H={H} W={W} are outside the encoder's limits")
+    levels = torch.empty(F, blocks // F, 64, dtype=torch.int16, device=frames.device)
+    ws = torch.empty(_lib.DEFINES["AMAV_JPEG_HINT_WORKSPACE"], dtype=torch.uint8, device=frames.device)
+    _call("amav_jpeg_coefficients", F, H, W, frames.data_ptr(), rgba, int(quality), sub, hint_ptr, bg3,
+          levels.data_ptr(), levels.numel() * 2, ws.data_ptr(), ws.numel())
+    return levels
+
+
+def jpeg_stream_bound(F, H, W, subsampling="420", restart_rows=1):
+    n = _lib.lib().amav_jpeg_stream_bound(int(F), int(H), int(W), JPEG_SUBSAMPLING[str(subsampling)], int(restart_rows))
+    if n == 0:
+        raise AmavError(f"jpeg_stream_bound: bad sizes F={F} H={H} W={W} restart_rows={restart_rows}")
+    return int(n)
+
+
+def jpeg_encode_into(frames, stream, quality=90, subsampling="420", restart_rows=1, tile_hint=None, background=None,
+                     capacity=None, frame_offsets=None, status=None):
+    """One amav_jpeg_encode call into the caller's uint8 `stream` buffer (its first `capacity` bytes; default: all of
+    it).  Returns (frame_offsets int64 [F+1], status int32 [1]) on the device; no host synchronisation.  status != 0:
+    the stream needed frame_offsets[F] > capacity bytes, and nothing at or beyond the capacity was written."""
+    frames, F, H, W, rgba, sub, hint_ptr, bg3 = _jpeg_args(frames, subsampling, tile_hint, background, "jpeg_encode")
+    if not isinstance(stream, torch.Tensor) or stream.dtype != torch.uint8 or not stream.is_contiguous() or \
+            stream.device != frames.device:
+        raise AmavError("jpeg_encode: stream must be a contiguous uint8 tensor on the frames' device")
+    capacity = stream.numel() if capacity is None else int(capacity)
+    if not 0 <= capacity <= stream.numel():
+        raise AmavError(f"jpeg_encode: capacity {capacity} outside the {stream.numel()}-byte stream buffer")
+    if frame_offsets is None:
+        frame_offsets = torch.empty(F + 1, dtype=torch.int64, device=frames.device)
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=frames.device)
+    ws = _scratch("amav_jpeg_workspace_bytes", frames.device, F, H, W, sub, int(restart_rows),
+                  rejected=f"F={F} H={H} W={W} restart_rows={restart_rows}")
+    _call("amav_jpeg_encode", F, H, W, frames.data_ptr(), rgba, int(quality), sub, int(restart_rows), hint_ptr, bg3,
+          stream.data_ptr(), capacity, frame_offsets.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel())
+    return frame_offsets, status
+
+
+def jpeg_encode(frames, quality=90, subsampling="420", restart_rows=1, tile_hint=None, background=None, capacity=None):
+    """Frames (fp32 RGBA [F,H,W,4] as the rasterizer leaves them, or uint8 RGB [F,H,W,3]) -> baseline JPEG, one complete
+    file per frame, packed back to back: (stream uint8 [bytes] on the device, frame_offsets int64 [F+1] on the host);
+    frame f is stream[frame_offsets[f]:frame_offsets[f + 1]].
+
+    `capacity` (default: the raw rgb24 size F*H*W*3) is the buffer the first attempt encodes into; when the stream does
+    not fit, the call is repeated once at amav_jpeg_stream_bound.  Reading frame_offsets (the size) back is the call's
+    single host synchronisation; jpeg_encode_into() is the form without any."""
+    F, H, W = (int(x) for x in frames.shape[:3])
+    kw = dict(quality=quality, subsampling=subsampling, restart_rows=restart_rows, tile_hint=tile_hint, background=background)
+    capacity = F * H * W * 3 if capacity is None else int(capacity)
+    stream = torch.empty(capacity, dtype=torch.uint8, device=frames.device)
+    offsets = jpeg_encode_into(frames, stream, **kw)[0].cpu()
+    if int(offsets[-1]) > capacity:  # what status[0] flags on the device
+        stream = torch.empty(jpeg_stream_bound(F, H, W, subsampling, restart_rows), dtype=torch.uint8, device=frames.device)
+        offsets = jpeg_encode_into(frames, stream, **kw)[0].cpu()
+        if int(offsets[-1]) > stream.numel():
+            raise AmavError(f"jpeg_encode: {int(offsets[-1])} bytes exceed the worst-case bound {stream.numel()}")
+    return stream[:int(offsets[-1])], offsets
+
+
 # ------------------------------------------------------------------------------------------------------------ LBS
 def body_tables_struct(tables: dict) -> BodyTables:
     """dict of device tensors prepared by body_model.BodyModel.device_tables() -> amav_body_tables."""

@@ -1255,6 +1255,53 @@ typedef struct amav_mesh_overlay_args {
 size_t amav_mesh_overlay_workspace_bytes(int num_frames, int num_verts, int num_faces, int height, int width);
 int amav_mesh_overlay(const amav_mesh_overlay_args *args, void *stream);
 
+/* Motion-JPEG output (csrc/jpeg.hip): a batch of frames [F,H,W] -> baseline sequential JPEG (SOF0, 8 bit, YCbCr, JFIF),
+ * one complete file per frame (SOI, APP0, DQT x 2, SOF0, DHT x 4, DRI, SOS, entropy-coded data with RSTn, EOI), packed
+ * back to back.  frames_dev: fp32 RGBA [F,H,W,4] (frames_are_rgba_f32 = 1, 16-byte aligned; quantised first as
+ * amav_frames_to_rgb8 does: clamp, x 255, truncate) or uint8 RGB [F,H,W,3] (0); both give the same bytes for the same
+ * image.  1 <= H, W <= 65535.
+ * Arithmetic, all fp32: Y = 0.299 R + 0.587 G + 0.114 B, Cb = -0.168736 R - 0.331264 G + 0.5 B + 128,
+ * Cr = 0.5 R - 0.418688 G - 0.081312 B + 128, not rounded; AMAV_JPEG_420 (MCU 16x16, blocks Y Y Y Y Cb Cr, chroma = mean
+ * of each 2x2) or AMAV_JPEG_444 (MCU 8x8, blocks Y Cb Cr); a partial MCU replicates the last column / row; level shift
+ * -128; separable orthonormal 8x8 DCT-II; level = nearest integer of coefficient / table entry; tables = T.81 Annex K
+ * scaled by quality 1..100 with libjpeg's rule (s = 5000 / q below 50, else 200 - 2 q; (base s + 50) / 100 in 1..255);
+ * the Annex K Huffman tables.
+ * restart_rows: MCU rows per restart interval (DRI + RST0..RST7 cycling; the DC predictors reset, every interval is
+ * byte aligned); 0 = no restarts.  restart_rows x MCUs per row must fit DRI's 16 bits.
+ * tile_hint_dev (optional, int32 [F * ceil(H/16) * ceil(W/16)], as amav_frames_pack_tiles takes it): zero = the caller
+ * knows that 16x16 tile holds nothing but background_host3 (rgb in [0,1], quantised like the frames); such an MCU takes
+ * the levels of a constant block, computed once by the same code, without its pixels being read.
+ *
+ * amav_jpeg_num_blocks: 8x8 blocks of the batch (0 = rejected sizes).
+ * amav_jpeg_coefficients: the transform stage alone: int16 levels [F, blocks in MCU-interleaved scan order, 64 zigzag]
+ *   into levels_dev (16-byte aligned, levels_bytes >= 128 x blocks).  workspace: AMAV_JPEG_HINT_WORKSPACE bytes, needed
+ *   with a tile hint only.
+ * amav_jpeg_stream_bound: bytes the stream can need at worst (0 = rejected sizes); amav_jpeg_workspace_bytes: the
+ *   workspace of amav_jpeg_encode (levels + per-interval sizes and offsets; 0 = rejected sizes).
+ * amav_jpeg_encode: stream_out_dev [capacity] receives the frames; frame f is bytes frame_offsets[f] ..
+ *   frame_offsets[f + 1] (int64 [F + 1], device).  Nothing is written at or beyond `capacity`; when the stream needs more,
+ *   status[0] |= 1 (int32, device, zeroed by the caller) and frame_offsets[F] still holds the size that was needed: the
+ *   convention of the wire format and of the rasterizer's instance capacity.  Transform, entropy pass that sizes every
+ *   interval, scan, entropy pass that writes: no host synchronisation, no float atomics, the same bytes on every run.
+ * Refused with an error code before any launch: quality outside 1..100, an unknown subsampling, sizes outside
+ * 1..65535 or F <= 0, more than 2^31 - 1 blocks, a negative restart_rows or an interval beyond 65535 MCUs, a NULL
+ * required pointer, a hint without background, a misaligned buffer, a negative capacity, and a levels buffer or
+ * workspace that is NULL or too small (AMAV_ERR_WORKSPACE). */
+#define AMAV_JPEG_420 420
+#define AMAV_JPEG_444 444
+#define AMAV_JPEG_HINT_WORKSPACE 384
+int64_t amav_jpeg_num_blocks(int num_frames, int height, int width, int subsampling);
+size_t amav_jpeg_stream_bound(int num_frames, int height, int width, int subsampling, int restart_rows);
+size_t amav_jpeg_workspace_bytes(int num_frames, int height, int width, int subsampling, int restart_rows);
+int amav_jpeg_coefficients(int num_frames, int height, int width, const void *frames_dev, int frames_are_rgba_f32,
+                           int quality, int subsampling, const int32_t *tile_hint_dev, const float *background_host3,
+                           void *levels_dev, size_t levels_bytes, void *workspace_dev, size_t workspace_bytes,
+                           void *stream);
+int amav_jpeg_encode(int num_frames, int height, int width, const void *frames_dev, int frames_are_rgba_f32, int quality,
+                     int subsampling, int restart_rows, const int32_t *tile_hint_dev, const float *background_host3,
+                     uint8_t *stream_out_dev, int64_t capacity, int64_t *frame_offsets_dev, int32_t *status_dev,
+                     void *workspace_dev, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
