@@ -20,6 +20,8 @@
 #include <cstring>
 
 #include "amav_common.h"
+#include "split_bf16.h"
+#include "split_f16.h"
 
 namespace amav {
 namespace attn {
@@ -202,7 +204,6 @@ __global__ __launch_bounds__(256, 3) void selfattn_kernel(const float *__restric
 // h1 + h2: exactly what split_operand_f16_kernel makes of the fp32 result, without the pass over it).  kLse: the row's
 // log-sum-exp also goes to lse [B, H, S] (natural units; the partial states are selfattn_f16_kernel's, whose sums carry
 // the 2^14 of its probabilities: amav_selfattn_forward_lse).
-typedef _Float16 c_f16x4 __attribute__((ext_vector_type(4)));
 constexpr float kLn2 = 0.69314718055994531f;
 // combine_kernel's lse argument: an empty struct when kLse is off, so that the kernel the inference path runs keeps its
 // argument layout (its implicit arguments, read for blockDim, would move 8 bytes behind a pointer) and its code
@@ -239,7 +240,7 @@ __global__ __launch_bounds__(256) void combine_kernel(const float *__restrict__ 
     }
     if (kSplitOut) {
         const float v[4] = {o0 * inv, o1 * inv, o2 * inv, o3 * inv};
-        c_f16x4 p1, p2;
+        f16x4 p1, p2;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const float x = v[j] * prescale;
@@ -248,9 +249,9 @@ __global__ __launch_bounds__(256) void combine_kernel(const float *__restrict__ 
         }
         const size_t K = (size_t)H * kD;
         _Float16 *dst = out_split + ((size_t)b * S + qi) * 3 * K + head * kD + 4 * d4;
-        *reinterpret_cast<c_f16x4 *>(dst) = p2;
-        *reinterpret_cast<c_f16x4 *>(dst + K) = p1;
-        *reinterpret_cast<c_f16x4 *>(dst + 2 * K) = p1;
+        *reinterpret_cast<f16x4 *>(dst) = p2;
+        *reinterpret_cast<f16x4 *>(dst + K) = p1;
+        *reinterpret_cast<f16x4 *>(dst + 2 * K) = p1;
         return;
     }
     float *orow = out + ((size_t)b * S + qi) * out_row_stride + head * kD + 4 * d4;
@@ -271,28 +272,8 @@ __global__ __launch_bounds__(256) void combine_kernel(const float *__restrict__ 
 //     a row-major LDS tile (16 B per lane), P^T split in registers and used as the B operand of O^T = sum V_i^T P_j^T
 //     (accumulator-as-operand: its k order inside a step is key 16 s + 8 (j >> 2) + 4 h + (j & 3), which is how the V^T
 //     fragments are gathered).
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kLdK = kD + 8;   // bf16 per K row in LDS (144 B: 16-byte reads of 8 consecutive lanes cover all banks)
 constexpr int kLdV = kBN + 4;  // bf16 per V^T row in LDS (136 B: 8-byte reads of 16 consecutive lanes cover all banks)
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
-// Two-way fp16 split: x = h1 + h2 to 22 bits when the residual stays out of fp16's subnormals, which the callers arrange
-// by pre-scaling x with a power of two (exact) so that the tensor's bound sits just under fp16's maximum.
-__device__ __forceinline__ void split2(float x, _Float16 &a, _Float16 &b) {
-    a = (_Float16)x;
-    b = (_Float16)__builtin_fmaf((float)a, -1.0f, x);  // x - a, exact; written as an fma so it can be one mixed-precision op
-}
-
-__device__ __forceinline__ void split3(float x, __bf16 &a, __bf16 &b, __bf16 &c) {
-    a = (__bf16)x;
-    const float r1 = x - (float)a;
-    b = (__bf16)r1;
-    c = (__bf16)(r1 - (float)b);
-}
 
 // grid (key tiles of 64, H, B), 256 threads: a [64 keys][64 d] tile of K and of V of one head
 __global__ __launch_bounds__(256) void split_kv_kernel(const float *__restrict__ k, const float *__restrict__ v, int S,
@@ -570,15 +551,6 @@ struct Magnitudes {  // upper bounds of |q|, |k|, |v| handed over by the caller 
     float q, k, v;
 };
 
-__device__ __forceinline__ int fp16_scale_exp(float amax) {
-    if (!(amax > 0.f)) return 0;
-    return max(-100, min(100, 14 - ilogbf(amax)));
-}
-
-__device__ __forceinline__ float absmax4(float m, const float4 a) {
-    return fmaxf(m, fmaxf(fmaxf(fabsf(a.x), fabsf(a.y)), fmaxf(fabsf(a.z), fabsf(a.w))));
-}
-
 // kCross (cross-attention): q has its own row count and row stride (q_rows, q_row_stride) and is swept on its own;
 // `rows` and `row_stride` are then those of k and v.  Self-attention reads the three tensors in one sweep.
 template <bool kCross>
@@ -627,8 +599,8 @@ __global__ __launch_bounds__(256) void split_kv_f16_kernel(const float *__restri
     const int tid = threadIdx.x, head = blockIdx.y, b = blockIdx.z, H = gridDim.y, B = gridDim.z;
     const int key0 = blockIdx.x * kBN;
     const size_t bh = (size_t)b * H + head, part_k = (size_t)B * H * S * kD, part_v = (size_t)B * H * kD * Spad;
-    const float sk = ldexpf(1.0f, fp16_scale_exp(hdr ? __uint_as_float(hdr[1]) : given.k));
-    const float sv = ldexpf(1.0f, fp16_scale_exp(hdr ? __uint_as_float(hdr[2]) : given.v));
+    const float sk = ldexpf(1.0f, f16_scale_exp(hdr ? __uint_as_float(hdr[1]) : given.k));
+    const float sv = ldexpf(1.0f, f16_scale_exp(hdr ? __uint_as_float(hdr[2]) : given.v));
     const int key = tid >> 2, d0 = (tid & 3) * 16;
     const bool live = key0 + key < S;
     const size_t src = ((size_t)b * S + min(key0 + key, S - 1)) * row_stride + head * kD + d0;
@@ -726,9 +698,9 @@ __global__ __launch_bounds__(256, 3) void selfattn_f16_kernel(const float *__res
     const int split = slice % nsplit, head = (slice / nsplit) % H, b = slice / (nsplit * H);
     const int q0 = (j % q_tiles) * kBM + wave * 32;
     const size_t bh = (size_t)b * H + head, part_k = (size_t)B * H * S * kD, part_v = (size_t)B * H * kD * Spad;
-    const int eq = fp16_scale_exp((hdr ? __uint_as_float(hdr[0]) : given.q) * scale_log2e);
-    const int ek = fp16_scale_exp(hdr ? __uint_as_float(hdr[1]) : given.k);
-    const int ev = fp16_scale_exp(hdr ? __uint_as_float(hdr[2]) : given.v);
+    const int eq = f16_scale_exp((hdr ? __uint_as_float(hdr[0]) : given.q) * scale_log2e);
+    const int ek = f16_scale_exp(hdr ? __uint_as_float(hdr[1]) : given.k);
+    const int ev = f16_scale_exp(hdr ? __uint_as_float(hdr[2]) : given.v);
     const float qs = scale_log2e * ldexpf(1.0f, eq);  // Q pre-scale (softmax scale and log2 e folded in)
     const float cs = ldexpf(1.0f, -(eq + ek));        // raw accumulator -> log2-domain score
 
@@ -951,46 +923,155 @@ static int attn_variant() {  // 0: fp32 MFMA, 1: bf16 x 3, 2: fp16 x 2
     }();
     return v;
 }
-static bool attn_use_split() { return attn_variant() != 0; }
-constexpr size_t kAttnHeaderBytes = 256;  // fp16 variant: max |q|, |k|, |v| of the call
+static size_t attn_parts() { return attn_variant() == 0 ? 0 : attn_variant() == 1 ? 3 : 2; }  // split parts per operand
 
-static size_t attn_partial_bytes(int B, int S, int H, int ns) {
-    return ns > 1 ? align_up((size_t)ns * B * H * S * (attn::kD + 2) * sizeof(float), 256) : 256;
+// The forward workspace of one call, Sq queries over Sk keys: [partial states of `ns` key slices | header | K parts |
+// V^T parts], the last three for the split kernels only (parts > 0).  With a null base it only measures (`bytes`).
+struct ForwardWorkspace {
+    float *partial;            // [ns][B H][Sq][64 + 2]: un-normalised O, running max and sum (ns = 1: one unused block)
+    unsigned *hdr = nullptr;   // fp16 x 2: max |q|, |k|, |v| of the call
+    void *kp = nullptr;        // K parts [parts][B H][Sk][64], 2-byte elements
+    void *vt = nullptr;        // V^T parts [parts][B H][64][Spad], 2-byte elements
+    int Spad;                  // Sk rounded up to whole key tiles
+    size_t bytes;
+    ForwardWorkspace(void *base, int B, int Sq, int Sk, int H, int ns, size_t parts)
+        : Spad((Sk + attn::kBN - 1) / attn::kBN * attn::kBN) {
+        Carver c(base);
+        partial = c.take<float>(ns > 1 ? (size_t)ns * B * H * Sq * (attn::kD + 2) : 64);  // ns = 1: 256 bytes
+        if (parts) {
+            hdr = c.take<unsigned>(64);  // 256 bytes, three words used
+            kp = c.take<uint16_t>(parts * B * H * Sk * attn::kD);
+            vt = c.take<uint16_t>(parts * B * H * attn::kD * Spad);
+        }
+        bytes = c.total();
+    }
+};
+
+// Grid of the split kernels: the (batch, head, key-slice) slices go out in rounds of 8 (one per XCD), q_tiles workgroups each
+static unsigned xcd_grid(int B, int H, int ns, int q_tiles) {
+    return (unsigned)(((long long)ns * H * B + 7) / 8 * 8 * q_tiles);
 }
-static size_t attn_spad(int S) { return ((size_t)S + attn::kBN - 1) / attn::kBN * attn::kBN; }
-// [header] + K parts [parts][B H][S][64] + V^T parts [parts][B H][64][S_pad], 2-byte elements (S: the keys)
-static size_t attn_split_bytes(int B, int S, int H, size_t parts) {
-    return kAttnHeaderBytes + align_up(parts * B * H * S * attn::kD * 2, 256) +
-           align_up(parts * B * H * attn::kD * attn_spad(S) * 2, 256);
+
+// The fp16 x 2 kernels of one call, Sq queries over Sk keys: the magnitude pre-pass (unless the caller proved bounds:
+// `given` > 0), the K / V split and the attention kernel.  kCross: q has its own row count and stride.  The caller merges
+// the slices (launch_combine) when ns > 1.  false: the header could not be cleared.
+template <bool kCross>
+static bool launch_f16(int B, int Sq, int Sk, int H, const float *q, int64_t q_row_stride, const float *k, const float *v,
+                       int64_t kv_row_stride, float *out, int64_t out_row_stride, float sl2, attn::Magnitudes given,
+                       float *lse, int ns, const ForwardWorkspace &w, hipStream_t stream) {
+    const unsigned *hdr = nullptr;  // the kernels scale from `given`
+    if (!(given.q > 0.f)) {         // measure max |q|, |k|, |v|
+        if (zero_async(w.hdr, 16, stream) != hipSuccess) return false;
+        hdr = w.hdr;
+        const int row4 = H * attn::kD / 4;
+        const long long rows = (long long)B * Sk, q_rows = (long long)B * Sq;
+        const long long quads = std::max(rows, q_rows) * row4;
+        const unsigned blocks = (unsigned)std::min<long long>((quads + 255) / 256, 512);
+        if (kCross)
+            attn::absmax_kernel<true><<<blocks, 256, 0, stream>>>(q, k, v, rows, row4, kv_row_stride, w.hdr, q_rows, q_row_stride);
+        else
+            attn::absmax_kernel<false><<<blocks, 256, 0, stream>>>(q, k, v, rows, row4, kv_row_stride, w.hdr);
+    }
+    _Float16 *kp = static_cast<_Float16 *>(w.kp), *vt = static_cast<_Float16 *>(w.vt);
+    attn::split_kv_f16_kernel<<<dim3((unsigned)(w.Spad / attn::kBN), H, B), 256, 0, stream>>>(k, v, Sk, w.Spad, kv_row_stride,
+                                                                                             hdr, given, kp, vt);
+    const int q_tiles = (Sq + attn::kBM - 1) / attn::kBM;
+    const unsigned grid = xcd_grid(B, H, ns, q_tiles);
+    if (lse)
+        attn::selfattn_f16_kernel<true><<<grid, 256, 0, stream>>>(q, kp, vt, out, Sq, Sk, w.Spad, q_row_stride, out_row_stride,
+                                                                 sl2, ns, w.partial, hdr, given, H, B, q_tiles, lse);
+    else
+        attn::selfattn_f16_kernel<false><<<grid, 256, 0, stream>>>(q, kp, vt, out, Sq, Sk, w.Spad, q_row_stride, out_row_stride,
+                                                                  sl2, ns, w.partial, hdr, given, H, B, q_tiles);
+    return true;
+}
+
+// Merge the partial states of ns > 1 key slices into out [B, Sq, .]: straight into the next projection's fp16 x 2
+// operand (out_split), with the row log-sum-exp (lse), or plain
+static void launch_combine(const float *part, float *out, int B, int H, int Sq, int ns, int64_t out_row_stride, void *out_split,
+                           int split_scale_exp, float *lse, hipStream_t stream) {
+    const unsigned blocks = blocks_for((long long)B * H * Sq * 16);
+    if (out_split)
+        attn::combine_kernel<true><<<blocks, 256, 0, stream>>>(part, out, B, H, Sq, ns, out_row_stride,
+                                                              static_cast<_Float16 *>(out_split),
+                                                              std::ldexp(1.0f, split_scale_exp));
+    else if (lse)
+        attn::combine_kernel<false, true><<<blocks, 256, 0, stream>>>(part, out, B, H, Sq, ns, out_row_stride, nullptr, 1.0f,
+                                                                     attn::LseOut<true>{lse});
+    else
+        attn::combine_kernel<false><<<blocks, 256, 0, stream>>>(part, out, B, H, Sq, ns, out_row_stride, nullptr, 1.0f);
 }
 
 extern "C" size_t amav_selfattn_workspace_bytes(int B, int S, int H, int D) {
     if (B <= 0 || S <= 0 || H <= 0 || D != attn::kD) return 0;
+    return ForwardWorkspace(nullptr, B, S, S, H, attn::choose_split(B, S, S, H, attn_num_cus()), attn_parts()).bytes;
+}
+
+// Every self-attention forward: bounds all 0 = measured magnitudes; out_split / lse as the entry points below say
+static int selfattn_forward_impl(int B, int S, int H, int D, const float *q, const float *k, const float *v,
+                                 int64_t row_stride, float *out, int64_t out_row_stride, float scale, float q_bound,
+                                 float k_bound, float v_bound, void *out_split, int split_scale_exp, float *lse,
+                                 void *workspace, size_t workspace_bytes, void *stream_) {
+    AMAV_REQUIRE(out_split == nullptr || ((reinterpret_cast<uintptr_t>(out_split) & 15) == 0 && split_scale_exp >= -126 &&
+                                          split_scale_exp <= 126 && out_row_stride == (int64_t)H * D),
+                 "amav_selfattn_forward_split_out: out_split must be 16-byte aligned, |scale_exp| <= 126, out rows dense");
+    const bool bounded = q_bound > 0.f && k_bound > 0.f && v_bound > 0.f;
+    AMAV_REQUIRE(bounded || (q_bound == 0.f && k_bound == 0.f && v_bound == 0.f),
+                 "amav_selfattn_forward_bounded: give all three bounds (> 0, finite) or none (0)");
+    AMAV_REQUIRE(std::isfinite(q_bound) && std::isfinite(k_bound) && std::isfinite(v_bound),
+                 "amav_selfattn_forward_bounded: bounds must be finite");
+    AMAV_REQUIRE(B > 0 && S > 0 && H > 0, "amav_selfattn_forward: bad sizes B=%d S=%d H=%d", B, S, H);
+    AMAV_REQUIRE(D == attn::kD, "amav_selfattn_forward: head_dim %d (only %d is built)", D, attn::kD);
+    AMAV_REQUIRE(q && k && v && out, "amav_selfattn_forward: NULL pointer");
+    AMAV_REQUIRE(row_stride >= (int64_t)H * D && out_row_stride >= (int64_t)H * D && row_stride % 4 == 0 &&
+                     out_row_stride % 4 == 0,
+                 "amav_selfattn_forward: row strides must be multiples of 4 floats and >= H*D");
+    AMAV_REQUIRE(aligned16(q, k, v, out), "amav_selfattn_forward: q/k/v/out must be 16-byte aligned");
+    AMAV_REQUIRE(H <= 65535 && B <= 65535, "amav_selfattn_forward: grid too large");
     const int ns = attn::choose_split(B, S, S, H, attn_num_cus());
-    size_t need = attn_partial_bytes(B, S, H, ns);
-    if (attn_use_split()) need += attn_split_bytes(B, S, H, attn_variant() == 2 ? 2 : 3);
-    return need;
+    const size_t parts = attn_parts();
+    const ForwardWorkspace w(workspace, B, S, S, H, ns, parts);
+    if ((parts || ns > 1) && (workspace == nullptr || workspace_bytes < w.bytes))
+        return fail(AMAV_ERR_WORKSPACE, "amav_selfattn_forward: workspace %zu < required %zu", workspace_bytes, w.bytes);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const float sl2 = scale * 1.4426950408889634f;
+    if (parts == 2) {
+        if (!launch_f16<false>(B, S, S, H, q, row_stride, k, v, row_stride, out, out_row_stride, sl2,
+                               {q_bound, k_bound, v_bound}, lse, ns, w, stream))
+            return fail(AMAV_ERR_INVALID_ARG, "amav_selfattn_forward: header clear failed");
+    } else if (parts == 3) {
+        const int q_tiles = (S + attn::kBM - 1) / attn::kBM;
+        __bf16 *kp = static_cast<__bf16 *>(w.kp), *vt = static_cast<__bf16 *>(w.vt);
+        attn::split_kv_kernel<<<dim3((unsigned)(w.Spad / attn::kBN), H, B), 256, 0, stream>>>(k, v, S, w.Spad, row_stride, kp, vt);
+        attn::selfattn_split_kernel<<<xcd_grid(B, H, ns, q_tiles), 256, 0, stream>>>(
+            q, kp, vt, out, S, w.Spad, row_stride, out_row_stride, sl2, ns, w.partial, H, B, q_tiles);
+    } else {
+        const dim3 grid((unsigned)((S + attn::kBM - 1) / attn::kBM) * ns, H, B);
+        attn::selfattn_kernel<<<grid, 256, 0, stream>>>(q, k, v, out, S, row_stride, out_row_stride, sl2, ns, w.partial);
+    }
+    if (ns > 1) {
+        launch_combine(w.partial, out, B, H, S, ns, out_row_stride, out_split, split_scale_exp, lse, stream);
+    } else if (out_split) {  // one key slice: the kernel wrote `out`; split it as amav_split_operand would
+        if (int rc = check_launch("amav_selfattn_forward")) return rc;
+        return amav_split_operand((int64_t)B * S, H * D, out, out_row_stride, 0, AMAV_SPLIT_FP16X2, split_scale_exp, out_split, stream_);
+    }
+    return check_launch("amav_selfattn_forward");
 }
 
 extern "C" int amav_selfattn_forward(int B, int S, int H, int D, const float *q, const float *k, const float *v,
                                      int64_t row_stride, float *out, int64_t out_row_stride, float scale,
                                      void *workspace, size_t workspace_bytes, void *stream_) {
-    return amav_selfattn_forward_bounded(B, S, H, D, q, k, v, row_stride, out, out_row_stride, scale, 0.f, 0.f, 0.f,
-                                         workspace, workspace_bytes, stream_);
+    return selfattn_forward_impl(B, S, H, D, q, k, v, row_stride, out, out_row_stride, scale, 0.f, 0.f, 0.f, nullptr, 0,
+                                 nullptr, workspace, workspace_bytes, stream_);
 }
 
 extern "C" int amav_selfattn_forward_bounded(int B, int S, int H, int D, const float *q, const float *k, const float *v,
                                              int64_t row_stride, float *out, int64_t out_row_stride, float scale,
                                              float q_bound, float k_bound, float v_bound, void *workspace,
                                              size_t workspace_bytes, void *stream_) {
-    return amav_selfattn_forward_split_out(B, S, H, D, q, k, v, row_stride, out, out_row_stride, scale, q_bound, k_bound, v_bound,
-                                           nullptr, 0, workspace, workspace_bytes, stream_);
+    return selfattn_forward_impl(B, S, H, D, q, k, v, row_stride, out, out_row_stride, scale, q_bound, k_bound, v_bound,
+                                 nullptr, 0, nullptr, workspace, workspace_bytes, stream_);
 }
-
-static int selfattn_forward_impl(int B, int S, int H, int D, const float *q, const float *k, const float *v,
-                                 int64_t row_stride, float *out, int64_t out_row_stride, float scale, float q_bound,
-                                 float k_bound, float v_bound, void *out_split, int split_scale_exp, float *lse,
-                                 void *workspace, size_t workspace_bytes, void *stream_);
 
 extern "C" int amav_selfattn_forward_split_out(int B, int S, int H, int D, const float *q, const float *k, const float *v,
                                                int64_t row_stride, float *out, int64_t out_row_stride, float scale,
@@ -1013,126 +1094,6 @@ extern "C" int amav_selfattn_forward_lse(int B, int S, int H, int D, const float
                                  lse, workspace, workspace_bytes, stream_);
 }
 
-// The fp16 x 2 kernels of one call, Sq queries over Sk keys, on a workspace laid out as [partial states of `ns` key
-// slices | header | K parts | V^T parts]: the magnitude pre-pass (unless the caller proved bounds: `proven`), the K / V
-// split and the attention kernel.  kCross: q has its own row count and stride.  The caller merges the slices
-// (combine_kernel) when ns > 1.  false: the header could not be cleared.
-template <bool kCross>
-static bool launch_f16(int B, int Sq, int Sk, int H, const float *q, int64_t q_row_stride, const float *k, const float *v,
-                       int64_t kv_row_stride, float *out, int64_t out_row_stride, float sl2, const attn::Magnitudes *proven,
-                       float *lse, int ns, char *ws, hipStream_t stream) {
-    const int Spad = (int)attn_spad(Sk);
-    unsigned *hdr = reinterpret_cast<unsigned *>(ws + attn_partial_bytes(B, Sq, H, ns));
-    char *kp = reinterpret_cast<char *>(hdr) + kAttnHeaderBytes;
-    char *vt = kp + align_up((size_t)2 * B * H * Sk * attn::kD * 2, 256);
-    const dim3 kv_grid((unsigned)(Spad / attn::kBN), H, B);
-    const int q_tiles = (Sq + attn::kBM - 1) / attn::kBM;
-    const long long rounds = ((long long)ns * H * B + 7) / 8;  // 8 slices (one per XCD) per round
-    const unsigned main_grid = (unsigned)(rounds * 8 * q_tiles);
-    attn::Magnitudes given = {0.f, 0.f, 0.f};
-    if (proven) {
-        given = *proven;
-        hdr = nullptr;  // the kernels scale from `given`
-    } else {            // measure max |q|, |k|, |v|
-        if (zero_async(hdr, 16, stream) != hipSuccess) return false;
-        const int row4 = H * attn::kD / 4;
-        const long long rows = (long long)B * Sk, q_rows = (long long)B * Sq;
-        const long long quads = std::max(rows, q_rows) * row4;
-        const unsigned blocks = (unsigned)std::min<long long>((quads + 255) / 256, 512);
-        if (kCross)
-            attn::absmax_kernel<true><<<blocks, 256, 0, stream>>>(q, k, v, rows, row4, kv_row_stride, hdr, q_rows, q_row_stride);
-        else
-            attn::absmax_kernel<false><<<blocks, 256, 0, stream>>>(q, k, v, rows, row4, kv_row_stride, hdr);
-    }
-    attn::split_kv_f16_kernel<<<kv_grid, 256, 0, stream>>>(k, v, Sk, Spad, kv_row_stride, hdr, given,
-                                                          reinterpret_cast<_Float16 *>(kp), reinterpret_cast<_Float16 *>(vt));
-    if (lse)
-        attn::selfattn_f16_kernel<true><<<main_grid, 256, 0, stream>>>(
-            q, reinterpret_cast<const _Float16 *>(kp), reinterpret_cast<const _Float16 *>(vt), out, Sq, Sk, Spad,
-            q_row_stride, out_row_stride, sl2, ns, reinterpret_cast<float *>(ws), hdr, given, H, B, q_tiles, lse);
-    else
-        attn::selfattn_f16_kernel<false><<<main_grid, 256, 0, stream>>>(
-            q, reinterpret_cast<const _Float16 *>(kp), reinterpret_cast<const _Float16 *>(vt), out, Sq, Sk, Spad,
-            q_row_stride, out_row_stride, sl2, ns, reinterpret_cast<float *>(ws), hdr, given, H, B, q_tiles);
-    return true;
-}
-
-static int selfattn_forward_impl(int B, int S, int H, int D, const float *q, const float *k, const float *v,
-                                 int64_t row_stride, float *out, int64_t out_row_stride, float scale, float q_bound,
-                                 float k_bound, float v_bound, void *out_split, int split_scale_exp, float *lse,
-                                 void *workspace, size_t workspace_bytes, void *stream_) {
-    AMAV_REQUIRE(out_split == nullptr || ((reinterpret_cast<uintptr_t>(out_split) & 15) == 0 && split_scale_exp >= -126 &&
-                                          split_scale_exp <= 126 && out_row_stride == (int64_t)H * D),
-                 "amav_selfattn_forward_split_out: out_split must be 16-byte aligned, |scale_exp| <= 126, out rows dense");
-    const bool bounded = q_bound > 0.f && k_bound > 0.f && v_bound > 0.f;
-    AMAV_REQUIRE(bounded || (q_bound == 0.f && k_bound == 0.f && v_bound == 0.f),
-                 "amav_selfattn_forward_bounded: give all three bounds (> 0, finite) or none (0)");
-    AMAV_REQUIRE(std::isfinite(q_bound) && std::isfinite(k_bound) && std::isfinite(v_bound),
-                 "amav_selfattn_forward_bounded: bounds must be finite");
-    AMAV_REQUIRE(B > 0 && S > 0 && H > 0, "amav_selfattn_forward: bad sizes B=%d S=%d H=%d", B, S, H);
-    AMAV_REQUIRE(D == attn::kD, "amav_selfattn_forward: head_dim %d (only %d is built)", D, attn::kD);
-    AMAV_REQUIRE(q && k && v && out, "amav_selfattn_forward: NULL pointer");
-    AMAV_REQUIRE(row_stride >= (int64_t)H * D && out_row_stride >= (int64_t)H * D && row_stride % 4 == 0 &&
-                     out_row_stride % 4 == 0,
-                 "amav_selfattn_forward: row strides must be multiples of 4 floats and >= H*D");
-    AMAV_REQUIRE(((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) |
-                   reinterpret_cast<uintptr_t>(out)) & 15) == 0,
-                 "amav_selfattn_forward: q/k/v/out must be 16-byte aligned");
-    AMAV_REQUIRE(H <= 65535 && B <= 65535, "amav_selfattn_forward: grid too large");
-    const int ns = attn::choose_split(B, S, S, H, attn_num_cus());
-    const bool split = attn_use_split();
-    const size_t need = split || ns > 1 ? amav_selfattn_workspace_bytes(B, S, H, D) : 0;
-    if (need && (workspace == nullptr || workspace_bytes < need))
-        return fail(AMAV_ERR_WORKSPACE, "amav_selfattn_forward: workspace %zu < required %zu", workspace_bytes, need);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const dim3 grid((unsigned)((S + attn::kBM - 1) / attn::kBM) * ns, H, B);
-    if (split) {
-        char *ws = static_cast<char *>(workspace);
-        const int Spad = (int)attn_spad(S);
-        const size_t parts = attn_variant() == 2 ? 2 : 3;
-        unsigned *hdr = reinterpret_cast<unsigned *>(ws + attn_partial_bytes(B, S, H, ns));
-        char *kp = reinterpret_cast<char *>(hdr) + kAttnHeaderBytes;
-        char *vt = kp + align_up(parts * B * H * S * attn::kD * 2, 256);
-        const dim3 kv_grid((unsigned)(Spad / attn::kBN), H, B);
-        const int q_tiles = (S + attn::kBM - 1) / attn::kBM;
-        const long long rounds = ((long long)ns * H * B + 7) / 8;  // 8 slices (one per XCD) per round
-        const unsigned main_grid = (unsigned)(rounds * 8 * q_tiles);
-        const float sl2 = scale * 1.4426950408889634f;
-        if (attn_variant() == 2) {
-            const attn::Magnitudes given = {q_bound, k_bound, v_bound};
-            if (!launch_f16<false>(B, S, S, H, q, row_stride, k, v, row_stride, out, out_row_stride, sl2, bounded ? &given : nullptr,
-                                   lse, ns, ws, stream))
-                return fail(AMAV_ERR_INVALID_ARG, "amav_selfattn_forward: header clear failed");
-        } else {
-            attn::split_kv_kernel<<<kv_grid, 256, 0, stream>>>(k, v, S, Spad, row_stride, reinterpret_cast<__bf16 *>(kp),
-                                                              reinterpret_cast<__bf16 *>(vt));
-            attn::selfattn_split_kernel<<<main_grid, 256, 0, stream>>>(
-                q, reinterpret_cast<const __bf16 *>(kp), reinterpret_cast<const __bf16 *>(vt), out, S, Spad, row_stride,
-                out_row_stride, sl2, ns, static_cast<float *>(workspace), H, B, q_tiles);
-        }
-    } else
-        attn::selfattn_kernel<<<grid, 256, 0, stream>>>(q, k, v, out, S, row_stride, out_row_stride,
-                                                        scale * 1.4426950408889634f, ns, static_cast<float *>(workspace));
-    if (ns > 1) {
-        const long long threads = (long long)B * H * S * 16;
-        if (out_split)  // the partial states are merged straight into the next projection's fp16 x 2 operand
-            attn::combine_kernel<true><<<(unsigned)((threads + 255) / 256), 256, 0, stream>>>(
-                static_cast<const float *>(workspace), out, B, H, S, ns, out_row_stride, static_cast<_Float16 *>(out_split),
-                std::ldexp(1.0f, split_scale_exp));
-        else if (lse)
-            attn::combine_kernel<false, true><<<(unsigned)((threads + 255) / 256), 256, 0, stream>>>(
-                static_cast<const float *>(workspace), out, B, H, S, ns, out_row_stride, nullptr, 1.0f,
-                attn::LseOut<true>{lse});
-        else
-            attn::combine_kernel<false><<<(unsigned)((threads + 255) / 256), 256, 0, stream>>>(
-                static_cast<const float *>(workspace), out, B, H, S, ns, out_row_stride, nullptr, 1.0f);
-    } else if (out_split) {  // one key slice: the kernel wrote `out`; split it as amav_split_operand would
-        if (int rc = check_launch("amav_selfattn_forward")) return rc;
-        return amav_split_operand((int64_t)B * S, H * D, out, out_row_stride, 0, AMAV_SPLIT_FP16X2, split_scale_exp, out_split, stream_);
-    }
-    return check_launch("amav_selfattn_forward");
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // Cross-attention of the stage-1 encoder (fusion network: 3152 queries, SMPL-X predictor: 80 queries, over the 4096
 // Sapiens tokens; 8 heads x 64): the fp16 x 2 kernels above with Sq != Sk, whatever the attn option selects -- the
@@ -1144,7 +1105,7 @@ extern "C" int amav_crossattn_key_split(int B, int Sq, int Sk, int H) {
 
 extern "C" size_t amav_crossattn_workspace_bytes(int B, int Sq, int Sk, int H, int D) {
     if (B <= 0 || Sq <= 0 || Sk <= 0 || H <= 0 || D != attn::kD) return 0;
-    return attn_partial_bytes(B, Sq, H, amav_crossattn_key_split(B, Sq, Sk, H)) + attn_split_bytes(B, Sk, H, 2);
+    return ForwardWorkspace(nullptr, B, Sq, Sk, H, amav_crossattn_key_split(B, Sq, Sk, H), 2).bytes;
 }
 
 extern "C" int amav_crossattn_forward(int B, int Sq, int Sk, int H, int D, const float *q, int64_t q_row_stride,
@@ -1163,454 +1124,15 @@ extern "C" int amav_crossattn_forward(int B, int Sq, int Sk, int H, int D, const
     AMAV_REQUIRE(std::isfinite(scale), "amav_crossattn_forward: scale must be finite");
     AMAV_REQUIRE(H <= 65535 && B <= 65535, "amav_crossattn_forward: grid too large");
     const int ns = amav_crossattn_key_split(B, Sq, Sk, H);
-    const size_t need = amav_crossattn_workspace_bytes(B, Sq, Sk, H, D);
-    if (workspace == nullptr || workspace_bytes < need)
-        return fail(AMAV_ERR_WORKSPACE, "amav_crossattn_forward: workspace %zu < required %zu", workspace_bytes, need);
+    const ForwardWorkspace w(workspace, B, Sq, Sk, H, ns, 2);
+    if (workspace == nullptr || workspace_bytes < w.bytes)
+        return fail(AMAV_ERR_WORKSPACE, "amav_crossattn_forward: workspace %zu < required %zu", workspace_bytes, w.bytes);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (!launch_f16<true>(B, Sq, Sk, H, q, q_row_stride, k, v, kv_row_stride, out, out_row_stride,
-                          scale * 1.4426950408889634f, nullptr, lse, ns, static_cast<char *>(workspace), stream))
+                          scale * 1.4426950408889634f, {0.f, 0.f, 0.f}, lse, ns, w, stream))
         return fail(AMAV_ERR_INVALID_ARG, "amav_crossattn_forward: header clear failed");
-    if (ns > 1) {
-        const unsigned blocks = blocks_for((long long)B * H * Sq * 16);
-        if (lse)
-            attn::combine_kernel<false, true><<<blocks, 256, 0, stream>>>(static_cast<const float *>(workspace), out, B, H, Sq,
-                                                                         ns, out_row_stride, nullptr, 1.0f,
-                                                                         attn::LseOut<true>{lse});
-        else
-            attn::combine_kernel<false><<<blocks, 256, 0, stream>>>(static_cast<const float *>(workspace), out, B, H, Sq, ns,
-                                                                   out_row_stride, nullptr, 1.0f);
-    }
+    if (ns > 1) launch_combine(w.partial, out, B, H, Sq, ns, out_row_stride, nullptr, 0, lse, stream);
     return check_launch("amav_crossattn_forward");
-}
-
-
-// ---------------------------------------------------------------------------------------------------------------
-// Split operands of an fp32-equivalent GEMM on the bf16 matrix pipe (the same three-way split as the attention
-// kernel above): x = x1 + x2 + x3 with every part a bf16, and x W^T is the sum of the six partial products x_i W_j^T
-// with i + j <= 4 (the dropped ones are below 2^-24 of the result).  The six products are ONE bf16 GEMM with fp32
-// accumulation over operands concatenated along K, small terms first:
-//     activations  A' = [x3 | x2 | x1 | x2 | x1 | x1]      weights  B' = [w1 | w2 | w3 | w1 | w2 | w1]      (K' = 6 K)
-// which the matrix pipe runs at 16x the fp32 MFMA rate, i.e. 2.7x faster than the fp32 GEMM for the same result
-// (measured 1.9e-6 max abs against fp64 on the 512 -> 4096 projection, 6.0e-6 for the library's fp32 GEMM).
-namespace amav {
-namespace attn {
-template <bool kWeights>
-__global__ __launch_bounds__(256) void split_operand_kernel(long long octs, int k8, const float *__restrict__ x,
-                                                            long long row_stride, __bf16 *__restrict__ out) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= octs) return;
-    const long long row = i / k8;
-    const int c = (int)(i - row * k8) * 8;
-    const float *src = x + row * row_stride + c;
-    const float4 lo = *reinterpret_cast<const float4 *>(src), hi = *reinterpret_cast<const float4 *>(src + 4);
-    const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    bf16x8 p1, p2, p3;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        __bf16 a, b, cc;
-        split3(v[j], a, b, cc);
-        p1[j] = a, p2[j] = b, p3[j] = cc;
-    }
-    const long long K = (long long)k8 * 8;
-    __bf16 *dst = out + row * 6 * K + c;
-    auto put = [&](int block, const bf16x8 &p) { *reinterpret_cast<bf16x8 *>(dst + block * K) = p; };
-    if (kWeights) {
-        put(0, p1), put(1, p2), put(2, p3), put(3, p1), put(4, p2), put(5, p1);
-    } else {
-        put(0, p3), put(1, p2), put(2, p1), put(3, p2), put(4, p1), put(5, p1);
-    }
-}
-
-// fp16 x 2 format: (x * prescale) = h1 + h2; activations [h2 | h1 | h1], weights [g1 | g2 | g1] (K' = 3 K), so that
-// A' B'^T = h2 g1 + h1 g2 + h1 g1 -- the product to 2^-22, at half the MFMA work of the bf16 x 3 format.
-template <bool kWeights>
-__global__ __launch_bounds__(256) void split_operand_f16_kernel(long long octs, int k8, const float *__restrict__ x,
-                                                                long long row_stride, float prescale,
-                                                                _Float16 *__restrict__ out) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= octs) return;
-    const long long row = i / k8;
-    const int c = (int)(i - row * k8) * 8;
-    const float *src = x + row * row_stride + c;
-    const float4 lo = *reinterpret_cast<const float4 *>(src), hi = *reinterpret_cast<const float4 *>(src + 4);
-    const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    f16x8 p1, p2;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        _Float16 a, b;
-        split2(v[j] * prescale, a, b);
-        p1[j] = a, p2[j] = b;
-    }
-    const long long K = (long long)k8 * 8;
-    _Float16 *dst = out + row * 3 * K + c;
-    auto put = [&](int block, const f16x8 &p) { *reinterpret_cast<f16x8 *>(dst + block * K) = p; };
-    if (kWeights) {
-        put(0, p1), put(1, p2), put(2, p1);
-    } else {
-        put(0, p2), put(1, p1), put(2, p1);
-    }
-}
-// The bf16 x 3 operand of x^T (and, with out_rows, split_operand_kernel<false>'s operand of x from the same read): what
-// the two backward products of a linear layer contract over is the ROW dimension of their fp32 tensors (dW = g^T x over the
-// rows of both, dx = g W over the rows of W), and the library GEMM wants the contraction dimension innermost.
-// grid (row tiles, column tiles), 256 threads, one 64 x 64 fp32 tile: thread (pair = tid / 8, oct = tid % 8) reads rows
-// 2 pair, 2 pair + 1 x columns 8 oct .. 8 oct + 7 (four float4; rows past the end read as +0, whose parts are +0: the zero
-// tail of out_t), splits them in registers, writes the row-major operand with 16-byte stores, and stages each part in LDS
-// transposed: stage[part][column][dword d] = rows (2 d, 2 d + 1) of the tile.  A column's 32 dwords are eight 16-byte
-// slots, stored at slot ^ (column / 8):
-//   * writes (4 bytes; bank = dword % 32 over half a wave = 8 octs x 4 pairs of one slot): slot ^ oct takes 8 values, the
-//     pair's low bits the 4 dwords of a slot -- 32 banks, each once (unswizzled, all 8 octs would share 4 banks);
-//   * reads (16 bytes; bank = dword % 64 over the read's 16-lane groups): a wave reads the 8 columns of one column / 8, so
-//     the XOR permutes the slots of every column alike and keeps a 4-lane block on one half of a column; the groups' four
-//     blocks then sit on (even column, low half), (odd, high), (even, high), (odd, low) or the mirror image: 64 banks, each
-//     once.  A pad cannot serve both sides: 16-byte reads need a column stride that is a multiple of 4 dwords, and with any
-//     such stride the 8 octs of a write land on 4 banks.
-// out_t is written with 16-byte stores of 8 consecutive source rows, 8 lanes per column (128 contiguous bytes).
-template <bool kWeights>
-__global__ __launch_bounds__(256) void split_operand_transposed_kernel(long long rows, long long rows_padded, int k,
-                                                                       const float *__restrict__ x, long long row_stride,
-                                                                       __bf16 *__restrict__ out_rows,
-                                                                       __bf16 *__restrict__ out_t) {
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    __shared__ uint4 stage[3][64][8];
-    const int tid = threadIdx.x;
-    const long long row0 = (long long)blockIdx.x * 64;
-    const int col0 = blockIdx.y * 64;
-    {
-        const int pair = tid >> 3, oct = tid & 7;
-        const int col = col0 + 8 * oct;
-        float v[2][8];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const long long row = row0 + 2 * pair + h;
-            if (row < rows && col < k) {
-                const float *src = x + row * row_stride + col;
-                const float4 lo = *reinterpret_cast<const float4 *>(src), hi = *reinterpret_cast<const float4 *>(src + 4);
-                v[h][0] = lo.x, v[h][1] = lo.y, v[h][2] = lo.z, v[h][3] = lo.w;
-                v[h][4] = hi.x, v[h][5] = hi.y, v[h][6] = hi.z, v[h][7] = hi.w;
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) v[h][j] = 0.0f;
-            }
-        }
-        bf16x8 p[2][3];
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                __bf16 a, b, cc;
-                split3(v[h][j], a, b, cc);
-                p[h][0][j] = a, p[h][1][j] = b, p[h][2][j] = cc;
-            }
-        if (out_rows && col < k) {  // activation order, as split_operand_kernel<false>
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const long long row = row0 + 2 * pair + h;
-                if (row >= rows) continue;
-                __bf16 *dst = out_rows + row * 6 * k + col;
-                auto put = [&](int block, const bf16x8 &q) { *reinterpret_cast<bf16x8 *>(dst + (long long)block * k) = q; };
-                put(0, p[h][2]), put(1, p[h][1]), put(2, p[h][0]), put(3, p[h][1]), put(4, p[h][0]), put(5, p[h][0]);
-            }
-        }
-        unsigned *words = reinterpret_cast<unsigned *>(&stage[0][0][0]);
-        const int dword = (((pair >> 2) ^ oct) << 2) | (pair & 3);
-#pragma unroll
-        for (int part = 0; part < 3; ++part)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                bf16x2 two;
-                two[0] = p[0][part][j], two[1] = p[1][part][j];
-                words[(part * 64 + 8 * oct + j) * 32 + dword] = __builtin_bit_cast(unsigned, two);
-            }
-    }
-    __syncthreads();
-    const int slot = tid & 7;
-    const long long row = row0 + 8 * slot;  // the first of this lane's 8 source rows
-    if (row >= rows_padded) return;
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        const int c = 32 * half + (tid >> 3);
-        if (col0 + c >= k) continue;
-        const uint4 p1 = stage[0][c][slot ^ (c >> 3)], p2 = stage[1][c][slot ^ (c >> 3)], p3 = stage[2][c][slot ^ (c >> 3)];
-        __bf16 *dst = out_t + (long long)(col0 + c) * 6 * rows_padded + row;
-        auto put = [&](int block, const uint4 &q) { *reinterpret_cast<uint4 *>(dst + block * rows_padded) = q; };
-        if (kWeights) {
-            put(0, p1), put(1, p2), put(2, p3), put(3, p1), put(4, p2), put(5, p1);
-        } else {
-            put(0, p3), put(1, p2), put(2, p1), put(3, p2), put(4, p1), put(5, p1);
-        }
-    }
-}
-}  // namespace attn
-}  // namespace amav
-
-static bool split_format_ok(int format, int scale_exp) {
-    return format == AMAV_SPLIT_BF16X3 || (format == AMAV_SPLIT_FP16X2 && scale_exp >= -126 && scale_exp <= 126);
-}
-
-extern "C" int amav_split_operand(int64_t rows, int k, const float *x, int64_t x_row_stride, int weights, int format,
-                                  int scale_exp, void *out, void *stream_) {
-    AMAV_REQUIRE(rows > 0 && k > 0 && k % 8 == 0, "amav_split_operand: rows=%lld k=%d (k must be a multiple of 8)",
-                 (long long)rows, k);
-    AMAV_REQUIRE(x && out, "amav_split_operand: NULL pointer");
-    AMAV_REQUIRE(x_row_stride >= k && x_row_stride % 4 == 0, "amav_split_operand: bad row stride");
-    AMAV_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15) == 0,
-                 "amav_split_operand: buffers must be 16-byte aligned");
-    AMAV_REQUIRE(split_format_ok(format, scale_exp), "amav_split_operand: format %d / scale exponent %d", format, scale_exp);
-    const long long octs = rows * (k / 8);
-    const unsigned grid = (unsigned)((octs + 255) / 256);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (format == AMAV_SPLIT_FP16X2) {
-        const float prescale = ldexpf(1.0f, scale_exp);
-        _Float16 *o = static_cast<_Float16 *>(out);
-        if (weights)
-            amav::attn::split_operand_f16_kernel<true><<<grid, 256, 0, stream>>>(octs, k / 8, x, x_row_stride, prescale, o);
-        else
-            amav::attn::split_operand_f16_kernel<false><<<grid, 256, 0, stream>>>(octs, k / 8, x, x_row_stride, prescale, o);
-    } else if (weights) {
-        amav::attn::split_operand_kernel<true><<<grid, 256, 0, stream>>>(octs, k / 8, x, x_row_stride,
-                                                                       static_cast<__bf16 *>(out));
-    } else {
-        amav::attn::split_operand_kernel<false><<<grid, 256, 0, stream>>>(octs, k / 8, x, x_row_stride,
-                                                                        static_cast<__bf16 *>(out));
-    }
-    return check_launch("amav_split_operand");
-}
-
-extern "C" int64_t amav_split_transposed_rows(int64_t rows) { return rows > 0 ? (rows + 7) / 8 * 8 : 0; }
-
-extern "C" int amav_split_operand_transposed(int64_t rows, int k, const float *x, int64_t x_row_stride, int weights,
-                                             void *out_rows, void *out_t, void *stream_) {
-    AMAV_REQUIRE(rows > 0 && k > 0 && k % 8 == 0,
-                 "amav_split_operand_transposed: rows=%lld k=%d (k must be a multiple of 8)", (long long)rows, k);
-    AMAV_REQUIRE(x && out_t, "amav_split_operand_transposed: NULL pointer");
-    AMAV_REQUIRE(x_row_stride >= k && x_row_stride % 4 == 0, "amav_split_operand_transposed: bad row stride");
-    AMAV_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out_rows) |
-                   reinterpret_cast<uintptr_t>(out_t)) & 15) == 0,
-                 "amav_split_operand_transposed: buffers must be 16-byte aligned");
-    const long long row_tiles = (rows + 63) / 64, col_tiles = (k + 63) / 64;
-    AMAV_REQUIRE(row_tiles <= 0x7fffffffLL && col_tiles <= 65535,
-                 "amav_split_operand_transposed: rows=%lld k=%d exceed the launch grid", (long long)rows, k);
-    const dim3 grid((unsigned)row_tiles, (unsigned)col_tiles);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const long long rows_padded = amav_split_transposed_rows(rows);
-    __bf16 *o_rows = static_cast<__bf16 *>(out_rows), *o_t = static_cast<__bf16 *>(out_t);
-    if (weights)
-        amav::attn::split_operand_transposed_kernel<true><<<grid, 256, 0, stream>>>(rows, rows_padded, k, x, x_row_stride,
-                                                                                  o_rows, o_t);
-    else
-        amav::attn::split_operand_transposed_kernel<false><<<grid, 256, 0, stream>>>(rows, rows_padded, k, x, x_row_stride,
-                                                                                   o_rows, o_t);
-    return check_launch("amav_split_operand_transposed");
-}
-
-
-// ---------------------------------------------------------------------------------------------------------------
-// GEGLU gate of the feed-forward (src/models/transformers.py:484-508: hidden, gate = proj(x).chunk(2); hidden *
-// gelu(gate), exact-erf GELU): one pass over the projection's [rows, 2 * inner] output instead of torch's two
-// elementwise kernels (gelu, then mul), i.e. 1.5 instead of 2.5 tensor sweeps.
-namespace amav {
-namespace attn {
-__global__ __launch_bounds__(256) void geglu_kernel(long long quads, int inner4, const float4 *__restrict__ in,
-                                                    long long in_row4, const float4 *__restrict__ bias,
-                                                    float4 *__restrict__ out, _Float16 *__restrict__ out_split,
-                                                    float prescale) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= quads) return;
-    const long long row = i / inner4;
-    const int col = (int)(i - row * inner4);
-    float4 h = in[row * in_row4 + col], g = in[row * in_row4 + inner4 + col];
-    if (bias) {  // the projection's bias, when its GEMM ran without one
-        const float4 bh = bias[col], bg = bias[inner4 + col];
-        h = make_float4(h.x + bh.x, h.y + bh.y, h.z + bh.z, h.w + bh.w);
-        g = make_float4(g.x + bg.x, g.y + bg.y, g.z + bg.z, g.w + bg.w);
-    }
-    auto gelu = [](float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); };
-    const float4 y = make_float4(h.x * gelu(g.x), h.y * gelu(g.y), h.z * gelu(g.z), h.w * gelu(g.w));
-    if (out_split) {  // the fp16 x 2 activation operand of the output projection (split_operand_f16_kernel's layout)
-        const float yv[4] = {y.x, y.y, y.z, y.w};
-        f16x4 p1, p2;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            // split2 with + 0 on the fp32 residual: an exactly-zero residual is +0, as x - x is (one that only underflows
-            // fp16 keeps its sign).  Where y = -0 (a saturated gate) the compiler re-forms `a` for the subtraction as
-            // fma(y, prescale, +0) = +0 and the residual came out as -0 - 0 = -0, unlike split_operand_f16_kernel's.
-            const float ys = yv[j] * prescale;
-            const _Float16 a = (_Float16)ys;
-            p1[j] = a, p2[j] = (_Float16)(__builtin_fmaf((float)a, -1.0f, ys) + 0.0f);
-        }
-        const long long K = 4LL * inner4;
-        _Float16 *dst = out_split + row * 3 * K + 4 * col;
-        *reinterpret_cast<f16x4 *>(dst) = p2;
-        *reinterpret_cast<f16x4 *>(dst + K) = p1;
-        *reinterpret_cast<f16x4 *>(dst + 2 * K) = p1;
-    } else {
-        out[i] = y;
-    }
-}
-}  // namespace attn
-}  // namespace amav
-
-extern "C" int amav_geglu(int64_t rows, int inner, const float *proj, int64_t proj_row_stride, const float *bias,
-                          float *out, void *out_split, int split_scale_exp, void *stream) {
-    AMAV_REQUIRE(rows > 0 && inner > 0 && inner % 4 == 0, "amav_geglu: bad sizes rows=%lld inner=%d", (long long)rows, inner);
-    AMAV_REQUIRE(proj && ((out != nullptr) != (out_split != nullptr)),
-                 "amav_geglu: NULL projection, or not exactly one of out (fp32) and out_split (fp16 x 2 operand)");
-    AMAV_REQUIRE(split_scale_exp >= -126 && split_scale_exp <= 126, "amav_geglu: scale exponent %d", split_scale_exp);
-    AMAV_REQUIRE(proj_row_stride >= 2LL * inner && proj_row_stride % 4 == 0, "amav_geglu: bad row stride");
-    AMAV_REQUIRE(((reinterpret_cast<uintptr_t>(proj) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(bias) |
-                   reinterpret_cast<uintptr_t>(out_split)) & 15) == 0,
-                 "amav_geglu: buffers must be 16-byte aligned");
-    const long long quads = rows * (inner / 4);
-    amav::attn::geglu_kernel<<<(unsigned)((quads + 255) / 256), 256, 0, static_cast<hipStream_t>(stream)>>>(
-        quads, inner / 4, reinterpret_cast<const float4 *>(proj), proj_row_stride / 4,
-        reinterpret_cast<const float4 *>(bias), reinterpret_cast<float4 *>(out), static_cast<_Float16 *>(out_split),
-        ldexpf(1.0f, split_scale_exp));
-    return check_launch("amav_geglu");
-}
-
-
-// ---------------------------------------------------------------------------------------------------------------
-// Residual adds + LayerNorm of BasicTransformerBlock (src/models/transformers.py:292-399) in one pass:
-//   h = ((a + a_bias) + h);  h = (row_b + h);  n = LayerNorm(h) * w + b
-// i.e. `attn1(...) + h`, then `attn2(...) + h` whose value is ONE row per batch item (single audio key), then norm3.
-// torch runs two adds and two LayerNorms for this (norm2's result is never used on this path: the cross-attention
-// output does not depend on its queries).  One wave per row, row in registers, two-pass mean / variance.
-// a_bias is the bias of the projection that produced `a` when its GEMM ran without one; with kSplit the normalised row
-// is written as the activation operand of the next projection's split GEMM (split_operand_kernel's layout) instead of
-// fp32 -- the row never makes the round trip through HBM in between.
-namespace amav {
-namespace attn {
-template <int kVec, int kSplit>  // float4 per lane: dim = 256 * kVec; kSplit 0: fp32 rows, 1: bf16 x 3, 2: fp16 x 2
-__global__ __launch_bounds__(256) void add_layernorm_kernel(long long rows, long long rows_per_batch,
-                                                            const float4 *__restrict__ a, const float4 *__restrict__ a_bias,
-                                                            const float4 *__restrict__ brow,
-                                                            const float4 *__restrict__ h, float4 *__restrict__ h_out,
-                                                            const float4 *__restrict__ w,
-                                                            const float4 *__restrict__ b, float eps,
-                                                            float4 *__restrict__ out, void *__restrict__ out_split,
-                                                            float prescale) {
-    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (row >= rows) return;
-    constexpr int kRow4 = 64 * kVec;
-    const float4 *br = brow ? brow + (row / rows_per_batch) * kRow4 : nullptr;
-    float4 x[kVec];
-    float sum = 0.f;
-#pragma unroll
-    for (int v = 0; v < kVec; ++v) {
-        const int c = lane + 64 * v;
-        float4 t = h[row * kRow4 + c];
-        if (a) {
-            float4 av = a[row * kRow4 + c];
-            if (a_bias) {
-                const float4 ab = a_bias[c];
-                av = make_float4(av.x + ab.x, av.y + ab.y, av.z + ab.z, av.w + ab.w);
-            }
-            t = make_float4(av.x + t.x, av.y + t.y, av.z + t.z, av.w + t.w);
-        }
-        if (br) {
-            const float4 rv = br[c];
-            t = make_float4(rv.x + t.x, rv.y + t.y, rv.z + t.z, rv.w + t.w);
-        }
-        x[v] = t;
-        h_out[row * kRow4 + c] = t;
-        sum += (t.x + t.y) + (t.z + t.w);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-    const float mean = sum * (1.0f / (256.0f * kVec));
-    float var = 0.f;
-#pragma unroll
-    for (int v = 0; v < kVec; ++v) {
-        const float dx = x[v].x - mean, dy = x[v].y - mean, dz = x[v].z - mean, dw = x[v].w - mean;
-        var += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) var += __shfl_xor(var, o, 64);
-    const float rstd = 1.0f / sqrtf(var * (1.0f / (256.0f * kVec)) + eps);
-#pragma unroll
-    for (int v = 0; v < kVec; ++v) {
-        const int c = lane + 64 * v;
-        const float4 wv = w[c], bv = b[c];
-        const float4 n = make_float4((x[v].x - mean) * rstd * wv.x + bv.x, (x[v].y - mean) * rstd * wv.y + bv.y,
-                                     (x[v].z - mean) * rstd * wv.z + bv.z, (x[v].w - mean) * rstd * wv.w + bv.w);
-        if (kSplit == 2) {
-            constexpr int K = 256 * kVec;
-            const float nv[4] = {n.x, n.y, n.z, n.w};
-            f16x4 p1, p2;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                _Float16 s1, s2;
-                split2(nv[j] * prescale, s1, s2);
-                p1[j] = s1, p2[j] = s2;
-            }
-            _Float16 *dst = static_cast<_Float16 *>(out_split) + row * 3 * K + 4 * c;
-            *reinterpret_cast<f16x4 *>(dst) = p2;
-            *reinterpret_cast<f16x4 *>(dst + K) = p1;
-            *reinterpret_cast<f16x4 *>(dst + 2 * K) = p1;
-        } else if (kSplit == 1) {
-            constexpr int K = 256 * kVec;
-            const float nv[4] = {n.x, n.y, n.z, n.w};
-            bf16x4 p1, p2, p3;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                __bf16 s1, s2, s3;
-                split3(nv[j], s1, s2, s3);
-                p1[j] = s1, p2[j] = s2, p3[j] = s3;
-            }
-            __bf16 *dst = static_cast<__bf16 *>(out_split) + row * 6 * K + 4 * c;
-            auto put = [&](int block, const bf16x4 &p) { *reinterpret_cast<bf16x4 *>(dst + block * K) = p; };
-            put(0, p3), put(1, p2), put(2, p1), put(3, p2), put(4, p1), put(5, p1);
-        } else {
-            out[row * kRow4 + c] = n;
-        }
-    }
-}
-}  // namespace attn
-}  // namespace amav
-
-extern "C" int amav_add_layernorm(int64_t rows, int dim, int64_t rows_per_batch, const float *add, const float *add_bias,
-                                  const float *batch_row, const float *hidden, float *hidden_out, const float *weight,
-                                  const float *bias, float eps, float *out_norm, void *out_norm_split, int split_format,
-                                  int split_scale_exp, void *stream_) {
-    AMAV_REQUIRE(rows > 0 && rows_per_batch > 0 && (dim == 256 || dim == 512 || dim == 768 || dim == 1024),
-                 "amav_add_layernorm: rows=%lld dim=%d (dim must be 256, 512, 768 or 1024)", (long long)rows, dim);
-    AMAV_REQUIRE(hidden && hidden_out && weight && bias, "amav_add_layernorm: NULL pointer");
-    AMAV_REQUIRE((out_norm != nullptr) != (out_norm_split != nullptr),
-                 "amav_add_layernorm: give exactly one of out_norm (fp32) and out_norm_split (bf16 split operand)");
-    AMAV_REQUIRE(add || !add_bias, "amav_add_layernorm: add_bias without add");
-    AMAV_REQUIRE(!out_norm_split || split_format_ok(split_format, split_scale_exp),
-                 "amav_add_layernorm: split format %d / scale exponent %d", split_format, split_scale_exp);
-    AMAV_REQUIRE(((reinterpret_cast<uintptr_t>(hidden) | reinterpret_cast<uintptr_t>(hidden_out) |
-                   reinterpret_cast<uintptr_t>(out_norm) | reinterpret_cast<uintptr_t>(out_norm_split) |
-                   reinterpret_cast<uintptr_t>(add) | reinterpret_cast<uintptr_t>(add_bias) |
-                   reinterpret_cast<uintptr_t>(batch_row) |
-                   reinterpret_cast<uintptr_t>(weight) | reinterpret_cast<uintptr_t>(bias)) & 15) == 0,
-                 "amav_add_layernorm: buffers must be 16-byte aligned");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const unsigned grid = (unsigned)((rows + 3) / 4);
-    auto p4 = [](const float *p) { return reinterpret_cast<const float4 *>(p); };
-    float4 *h4 = reinterpret_cast<float4 *>(hidden_out), *o4 = reinterpret_cast<float4 *>(out_norm);
-    const float prescale = ldexpf(1.0f, out_norm_split && split_format == AMAV_SPLIT_FP16X2 ? split_scale_exp : 0);
-#define AMAV_LN_ARGS rows, rows_per_batch, p4(add), p4(add_bias), p4(batch_row), p4(hidden), h4, p4(weight), p4(bias), eps, \
-                     o4, out_norm_split, prescale
-#define AMAV_LN_LAUNCH(V)                                                                                   \
-    do {                                                                                                    \
-        if (!out_norm_split)                                                                                \
-            amav::attn::add_layernorm_kernel<V, 0><<<grid, 256, 0, stream>>>(AMAV_LN_ARGS);                 \
-        else if (split_format == AMAV_SPLIT_FP16X2)                                                         \
-            amav::attn::add_layernorm_kernel<V, 2><<<grid, 256, 0, stream>>>(AMAV_LN_ARGS);                 \
-        else                                                                                                \
-            amav::attn::add_layernorm_kernel<V, 1><<<grid, 256, 0, stream>>>(AMAV_LN_ARGS);                 \
-    } while (0)
-    if (dim == 256) AMAV_LN_LAUNCH(1);
-    else if (dim == 512) AMAV_LN_LAUNCH(2);
-    else if (dim == 768) AMAV_LN_LAUNCH(3);
-    else AMAV_LN_LAUNCH(4);
-#undef AMAV_LN_LAUNCH
-#undef AMAV_LN_ARGS
-    return check_launch("amav_add_layernorm");
 }
 
 #ifdef AMAV_ATTN_STAMPS

@@ -17,9 +17,7 @@
 // of an accumulator takes registers 8 u .. 8 u + 7 as the B operand of k-step u: lane half hh then holds rows
 // 16 u + {0..3, 8..11} + 4 hh, so the transposed [d][row] tiles in LDS store every group of 16 rows in that order
 // (tile_pos: bits 2 and 3 of the row index swapped) and the A operand is one 16-byte read.
-#include <cmath>
-
-#include "amav_common.h"
+#include "attention_dense_rows.h"
 #include "split_f16.h"
 
 namespace amav {
@@ -34,31 +32,7 @@ constexpr float kLog2e = 1.4426950408889634f;
 constexpr size_t kHeaderBytes = 256;  // six words: max |q|, |k|, |v|, |dO|, Ng, Nv
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
-// The addressing of attention_backward.hip's DenseRows: Sq query rows (q, out, dout, lse, delta, dq) and Sk key rows
-// (k, v, dk, dv) per batch item, each tensor behind its own row stride.
-struct Rows {
-    const float *q;
-    long long q_rs;
-    const float *k, *v;
-    long long kv_rs;
-    const float *out, *dout;
-    long long out_rs, dout_rs;
-    const float *lse;
-    float *delta;  // [B, H, Sq]
-    float *dq;
-    long long dq_rs;
-    float *dk, *dv;
-    long long dkv_rs;
-    int B, Sq, Sk, H;
-
-    __device__ void bind(int head, int b) {
-        const size_t qrow = (size_t)b * Sq, krow = (size_t)b * Sk, bh = ((size_t)b * H + head) * Sq;
-        q += qrow * q_rs + head * kD, k += krow * kv_rs + head * kD, v += krow * kv_rs + head * kD;
-        dout += qrow * dout_rs + head * kD;
-        lse += bh, delta += bh;
-        dq += qrow * dq_rs + head * kD, dk += krow * dkv_rs + head * kD, dv += krow * dkv_rs + head * kD;
-    }
-};
+using attn_bwd::DenseRows;  // the split kernels use its fields and bind only
 
 struct Scales {
     int eq, ek, ev, eg, es;  // exponents of the unfolded operands and of dS
@@ -76,14 +50,11 @@ __device__ __forceinline__ Scales read_scales(const unsigned *__restrict__ hdr) 
 __device__ __forceinline__ int tile_pos(int row) {  // column of a row in a transposed tile
     return (row & 0x13) | ((row & 4) << 1) | ((row & 8) >> 1);
 }
-__device__ __forceinline__ float absmax4(float m, const float4 a) {
-    return fmaxf(m, fmaxf(fmaxf(fabsf(a.x), fabsf(a.y)), fmaxf(fabsf(a.z), fabsf(a.w))));
-}
 __device__ __forceinline__ float sumsq4(const float4 a) { return (a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w); }
 
 // 16 threads per (row, head) pair, 4 consecutive d each: delta_i as delta_kernel of the fp32 core computes it, and the
 // six maxima of the header.  A thread serves query pair r and key pair r where they exist.
-__global__ __launch_bounds__(256) void prepass_kernel(Rows rows, unsigned *__restrict__ hdr) {
+__global__ __launch_bounds__(256) void prepass_kernel(DenseRows rows, unsigned *__restrict__ hdr) {
     constexpr int G = kD / 4;
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long r = gid / G;
@@ -243,7 +214,7 @@ __device__ __forceinline__ void store_row(float *__restrict__ row, const f32x16 
 // grid (key blocks of 128, H, B), 256 threads.  Wave w owns keys blockIdx.x * 128 + 32 w + (lane & 31): K' (softmax
 // scale and log2 e folded in) and V' stay in registers as B operands, and the wave sweeps every query tile, recomputing
 // P and dS and accumulating dV^T and dK^T -- no cross-workgroup sum.
-__global__ __launch_bounds__(256, 2) void dkdv_kernel(Rows rows, float scale, const unsigned *__restrict__ hdr) {
+__global__ __launch_bounds__(256, 2) void dkdv_kernel(DenseRows rows, float scale, const unsigned *__restrict__ hdr) {
     __shared__ __attribute__((aligned(16))) _Float16 Qr[2][kBT * kLdR], Gr[2][kBT * kLdR];  // [part][query][d]
     __shared__ __attribute__((aligned(16))) _Float16 Qt[2][kD * kLdT], Gt[2][kD * kLdT];    // [part][d][tile_pos(query)]
     __shared__ __attribute__((aligned(16))) float Ls[kBT], Ds[kBT];
@@ -335,7 +306,7 @@ __global__ __launch_bounds__(256, 2) void dkdv_kernel(Rows rows, float scale, co
 // grid (query blocks of 128, H, B), 256 threads.  Wave w owns queries blockIdx.x * 128 + 32 w + (lane & 31): Q' (scale
 // and log2 e folded in) and dO' stay in registers, and the wave sweeps every key tile, recomputing S^T and dP^T and
 // accumulating dQ^T.
-__global__ __launch_bounds__(256, 2) void dq_kernel(Rows rows, float scale, const unsigned *__restrict__ hdr) {
+__global__ __launch_bounds__(256, 2) void dq_kernel(DenseRows rows, float scale, const unsigned *__restrict__ hdr) {
     __shared__ __attribute__((aligned(16))) _Float16 Kr[2][kBT * kLdR], Vr[2][kBT * kLdR];  // [part][key][d]
     __shared__ __attribute__((aligned(16))) _Float16 Kt[2][kD * kLdT];                      // [part][d][tile_pos(key)]
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -413,7 +384,7 @@ static size_t workspace_bytes(int B, int Sq, int H) {
 }
 
 // `rows.delta` is set here; three kernels and the header's zero fill, no host synchronisation
-static int launch(Rows rows, float scale, void *workspace, hipStream_t stream, const char *what) {
+static int launch(DenseRows rows, float scale, void *workspace, hipStream_t stream, const char *what) {
     unsigned *hdr = static_cast<unsigned *>(workspace);
     rows.delta = reinterpret_cast<float *>(static_cast<char *>(workspace) + kHeaderBytes);
     if (zero_async(hdr, 32, stream) != hipSuccess) return check_launch(what);
@@ -441,26 +412,17 @@ extern "C" int amav_selfattn_backward_split(int B, int S, int H, int D, const fl
                                             const float *lse, const float *dout, int64_t dout_row_stride, float *dqkv,
                                             int64_t dqkv_row_stride, float scale, void *workspace,
                                             size_t workspace_bytes, void *stream_) {
-    AMAV_REQUIRE(B > 0 && S > 0 && H > 0, "amav_selfattn_backward_split: bad sizes B=%d S=%d H=%d", B, S, H);
-    AMAV_REQUIRE(D == attn_bwd_split::kD, "amav_selfattn_backward_split: head_dim %d (only %d is built)", D,
-                 attn_bwd_split::kD);
-    AMAV_REQUIRE(q && k && v && out && lse && dout && dqkv, "amav_selfattn_backward_split: NULL pointer");
-    const int64_t hd = (int64_t)H * D;
-    AMAV_REQUIRE(row_stride >= hd && out_row_stride >= hd && dout_row_stride >= hd && row_stride % 4 == 0 &&
-                     out_row_stride % 4 == 0 && dout_row_stride % 4 == 0,
-                 "amav_selfattn_backward_split: q/k/v, out and dout row strides must be multiples of 4 floats and >= H*D");
+    const char *what = "amav_selfattn_backward_split";
+    const int64_t hd = (int64_t)H * attn_bwd_split::kD;  // D itself is checked with the rest
     AMAV_REQUIRE(dqkv_row_stride >= 3 * hd && dqkv_row_stride % 4 == 0,
-                 "amav_selfattn_backward_split: dqkv row stride must be a multiple of 4 floats and >= 3*H*D");
-    AMAV_REQUIRE(aligned16(q, k, v, out, dout, dqkv) && (reinterpret_cast<uintptr_t>(lse) & 3) == 0,
-                 "amav_selfattn_backward_split: q/k/v/out/dout/dqkv must be 16-byte aligned, lse 4-byte aligned");
-    AMAV_REQUIRE(std::isfinite(scale), "amav_selfattn_backward_split: scale must be finite");
-    AMAV_REQUIRE(H <= 65535 && B <= 65535, "amav_selfattn_backward_split: grid too large");
-    const size_t need = amav_selfattn_backward_split_workspace_bytes(B, S, H, D);
-    if (workspace == nullptr || workspace_bytes < need)
-        return fail(AMAV_ERR_WORKSPACE, "amav_selfattn_backward_split: workspace %zu < required %zu", workspace_bytes, need);
-    const attn_bwd_split::Rows rows = {q, row_stride, k, v, row_stride, out, dout, out_row_stride, dout_row_stride, lse,
-                                       nullptr, dqkv, dqkv_row_stride, dqkv + hd, dqkv + 2 * hd, dqkv_row_stride, B, S, S, H};
-    return attn_bwd_split::launch(rows, scale, workspace, static_cast<hipStream_t>(stream_), "amav_selfattn_backward_split");
+                 "%s: dqkv row stride must be a multiple of 4 floats and >= 3*H*D", what);
+    attn_bwd::DenseRows rows = {q, row_stride, k, v, row_stride, out, dout, out_row_stride, dout_row_stride, lse, nullptr,
+                                dqkv, dqkv_row_stride, dqkv, nullptr, dqkv_row_stride, B, S, S, H};
+    if (int rc = attn_bwd::check_dense_backward(what, rows, D, scale, amav_selfattn_backward_split_workspace_bytes(B, S, H, D),
+                                                workspace, workspace_bytes))
+        return rc;
+    rows.dk = dqkv + hd, rows.dv = dqkv + 2 * hd;
+    return attn_bwd_split::launch(rows, scale, workspace, static_cast<hipStream_t>(stream_), what);
 }
 
 extern "C" size_t amav_crossattn_backward_split_workspace_bytes(int B, int Sq, int H, int D) {
@@ -474,26 +436,15 @@ extern "C" int amav_crossattn_backward_split(int B, int Sq, int Sk, int H, int D
                                              int64_t dout_row_stride, float *dq, int64_t dq_row_stride, float *dkv,
                                              int64_t dkv_row_stride, float scale, void *workspace,
                                              size_t workspace_bytes, void *stream_) {
-    AMAV_REQUIRE(B > 0 && Sq > 0 && Sk > 0 && H > 0, "amav_crossattn_backward_split: bad sizes B=%d Sq=%d Sk=%d H=%d", B,
-                 Sq, Sk, H);
-    AMAV_REQUIRE(D == attn_bwd_split::kD, "amav_crossattn_backward_split: head_dim %d (only %d is built)", D,
-                 attn_bwd_split::kD);
-    AMAV_REQUIRE(q && k && v && out && lse && dout && dq && dkv, "amav_crossattn_backward_split: NULL pointer");
-    const int64_t hd = (int64_t)H * D;
-    AMAV_REQUIRE(q_row_stride >= hd && kv_row_stride >= hd && out_row_stride >= hd && dout_row_stride >= hd &&
-                     dq_row_stride >= hd && q_row_stride % 4 == 0 && kv_row_stride % 4 == 0 && out_row_stride % 4 == 0 &&
-                     dout_row_stride % 4 == 0 && dq_row_stride % 4 == 0,
-                 "amav_crossattn_backward_split: q, k/v, out, dout and dq row strides must be multiples of 4 floats and >= H*D");
+    const char *what = "amav_crossattn_backward_split";
+    const int64_t hd = (int64_t)H * attn_bwd_split::kD;  // D itself is checked with the rest
     AMAV_REQUIRE(dkv_row_stride >= 2 * hd && dkv_row_stride % 4 == 0,
-                 "amav_crossattn_backward_split: dkv row stride must be a multiple of 4 floats and >= 2*H*D");
-    AMAV_REQUIRE(aligned16(q, k, v, out, dout, dq, dkv) && (reinterpret_cast<uintptr_t>(lse) & 3) == 0,
-                 "amav_crossattn_backward_split: q/k/v/out/dout/dq/dkv must be 16-byte aligned, lse 4-byte aligned");
-    AMAV_REQUIRE(std::isfinite(scale), "amav_crossattn_backward_split: scale must be finite");
-    AMAV_REQUIRE(H <= 65535 && B <= 65535, "amav_crossattn_backward_split: grid too large");
-    const size_t need = amav_crossattn_backward_split_workspace_bytes(B, Sq, H, D);
-    if (workspace == nullptr || workspace_bytes < need)
-        return fail(AMAV_ERR_WORKSPACE, "amav_crossattn_backward_split: workspace %zu < required %zu", workspace_bytes, need);
-    const attn_bwd_split::Rows rows = {q, q_row_stride, k, v, kv_row_stride, out, dout, out_row_stride, dout_row_stride, lse,
-                                       nullptr, dq, dq_row_stride, dkv, dkv + hd, dkv_row_stride, B, Sq, Sk, H};
-    return attn_bwd_split::launch(rows, scale, workspace, static_cast<hipStream_t>(stream_), "amav_crossattn_backward_split");
+                 "%s: dkv row stride must be a multiple of 4 floats and >= 2*H*D", what);
+    attn_bwd::DenseRows rows = {q, q_row_stride, k, v, kv_row_stride, out, dout, out_row_stride, dout_row_stride, lse, nullptr,
+                                dq, dq_row_stride, dkv, nullptr, dkv_row_stride, B, Sq, Sk, H};
+    if (int rc = attn_bwd::check_dense_backward(what, rows, D, scale, amav_crossattn_backward_split_workspace_bytes(B, Sq, H, D),
+                                                workspace, workspace_bytes))
+        return rc;
+    rows.dv = dkv + hd;
+    return attn_bwd_split::launch(rows, scale, workspace, static_cast<hipStream_t>(stream_), what);
 }

@@ -1,4 +1,4 @@
-// Backwards of the transformer step's row kernels (csrc/attention.hip: geglu_kernel, add_layernorm_kernel) and the
+// Backwards of the transformer step's row kernels (csrc/attention_rows.hip: geglu_kernel, add_layernorm_kernel) and the
 // column sum their bias-like gradients need.  Memory-bound passes: float4 accesses, 64-bit row
 // offsets, no atomics, no hidden allocation or synchronisation, kernel launches only (capturable).
 //

@@ -37,7 +37,7 @@ constexpr int kLds = kHaloPix * 64 + 64 * kTaps;  // floats: halo | weights of t
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
-// The splits of amav_split_operand (csrc/attention.hip), part for part.
+// The splits of amav_split_operand (csrc/attention_rows.hip), part for part.
 __device__ __forceinline__ void split2(float x, _Float16 &a, _Float16 &b) {
     a = (_Float16)x;
     b = (_Float16)(__builtin_fmaf((float)a, -1.0f, x) + 0.0f);  // + 0: an exactly-zero residual is +0 (geglu_kernel's note)

@@ -1500,20 +1500,36 @@ def points_project_differentiable(points, w2c, intrinsics, features, radius_px):
 ATTN_PROFILE_EVENTS = None
 
 
+def _rows(t, name, B=None, S=None, min_width=None, width=None):
+    """[B,S,C] fp32 device tensor with unit inner stride and dense batch stride, of the given sizes where given."""
+    _need(t, name)
+    if (t.dim() != 3 or t.stride(2) != 1 or t.stride(0) != t.shape[1] * t.stride(1)
+            or (B is not None and t.shape[0] != B) or (S is not None and t.shape[1] != S)
+            or (width is not None and t.shape[2] != width) or (min_width is not None and t.shape[2] < min_width)):
+        want = width if width is not None else f">={min_width}" if min_width is not None else "C"
+        raise AmavError(f"{name}: need [B,S,C] = [{B or 'B'},{S or 'S'},{want}] with unit inner stride and dense batch "
+                        f"stride, got {tuple(t.shape)} strides {tuple(t.stride())}")
+    return t
+
+
+def _launchable(t):
+    """t, or a contiguous copy where its layout is not one the attention entry points read in place."""
+    if t.stride(2) != 1 or t.stride(0) != t.shape[1] * t.stride(1) or t.stride(1) % 4 or t.data_ptr() % 16:
+        return t.contiguous()
+    return t
+
+
 def selfattn(q, k, v, heads, scale=None, bounds=None, split_out_exp=None):
     """softmax(q k^T * scale) v for [B,S,H*D] fp32 tensors (row stride may exceed H*D), D = 64.  bounds: (|q|, |k|, |v|)
     upper bounds the caller can prove, which spare the kernel its magnitude pre-pass (include/amav.h,
     amav_selfattn_forward_bounded); None: measured.  split_out_exp: return instead the fp16 x 2 activation operand
     [B*S, 3*H*D] of the projection that follows (split_operand(out, fmt=SPLIT_FP16X2, scale_exp=split_out_exp), written
     by the kernel's own last pass: amav_selfattn_forward_split_out)."""
-    for name, t in (("q", q), ("k", k), ("v", v)):
-        _need(t, name)
-        if t.dim() != 3 or t.stride(2) != 1 or t.stride(0) != t.shape[1] * t.stride(1):
-            raise AmavError(f"{name}: need [B,S,H*D] with unit inner stride and dense batch stride")
-    B, S, HD = q.shape
+    B, S, HD = _rows(q, "q").shape
+    _rows(k, "k", B, S, width=HD), _rows(v, "v", B, S, width=HD)
     D = HD // heads
-    if k.shape != q.shape or v.shape != q.shape or not (q.stride(1) == k.stride(1) == v.stride(1)):
-        raise AmavError("selfattn: q, k, v must share shape and row stride")
+    if not (q.stride(1) == k.stride(1) == v.stride(1)):
+        raise AmavError("selfattn: q, k, v must share their row stride")
     out = torch.empty(B, S, HD, device=q.device)
     ws = _scratch("amav_selfattn_workspace_bytes", q.device, B, S, heads, D, rejected=f"B={B} S={S} H={heads} D={D}")
     ev = ATTN_PROFILE_EVENTS.pop(0) if ATTN_PROFILE_EVENTS else None
@@ -1531,10 +1547,9 @@ def selfattn(q, k, v, heads, scale=None, bounds=None, split_out_exp=None):
 
 def _qkv_views(qkv, heads):
     """[B,S,3*H*D] fused projection output (unit inner stride, dense batch stride) -> (B, S, H*D, D)."""
-    _need(qkv, "qkv")
-    if qkv.dim() != 3 or qkv.stride(2) != 1 or qkv.stride(0) != qkv.shape[1] * qkv.stride(1) or qkv.shape[2] % (3 * heads):
-        raise AmavError(f"qkv: need [B,S,3*H*D] with unit inner stride and dense batch stride, got {tuple(qkv.shape)}")
-    B, S, C = qkv.shape
+    B, S, C = _rows(qkv, "qkv").shape
+    if C % (3 * heads):
+        raise AmavError(f"qkv: need [B,S,3*H*D], got {tuple(qkv.shape)} for {heads} heads")
     return B, S, C // 3, C // (3 * heads)
 
 
@@ -1563,30 +1578,27 @@ def _attn_backward_split(arithmetic):
     raise AmavError(f"attention backward: {where} must be 'f32' or 'split', got {chosen!r}")
 
 
+def _attn_backward_entry(kind, arithmetic):
+    """(size query, entry point) of the dense backward of kind "self" | "cross" in `arithmetic` (_attn_backward_split)."""
+    entry = f"amav_{kind}attn_backward" + ("_split" if _attn_backward_split(arithmetic) else "")
+    return entry + "_workspace_bytes", entry
+
+
 def selfattn_backward(qkv, out, lse, grad_out, heads, scale=None, grad_qkv=None, arithmetic=None):
     """amav_selfattn_backward: the gradient [B,S,3*H*D] (dq | dk | dv) of a fused qkv given the forward's out and lse
     (selfattn_lse) and grad_out = dLoss/d out.  out / grad_out: [B,S,H*D] with unit inner stride and dense batch stride;
     grad_qkv: optional [B,S,>=3*H*D] destination view (its first 3*H*D columns are written).  arithmetic: "f32" (exact
     fp32 products) or "split" (amav_selfattn_backward_split: fp16 x 2 split products); None follows AMAV_ATTN_BACKWARD."""
-    sizer, entry = (("amav_selfattn_backward_split_workspace_bytes", "amav_selfattn_backward_split")
-                    if _attn_backward_split(arithmetic) else
-                    ("amav_selfattn_backward_workspace_bytes", "amav_selfattn_backward"))
+    sizer, entry = _attn_backward_entry("self", arithmetic)
     B, S, HD, D = _qkv_views(qkv, heads)
-    for name, t in (("out", out), ("grad_out", grad_out)):
-        _need(t, name)
-        if tuple(t.shape) != (B, S, HD) or t.stride(2) != 1 or t.stride(0) != S * t.stride(1):
-            raise AmavError(f"{name}: need [B,S,H*D] = {(B, S, HD)} with unit inner stride, got {tuple(t.shape)}")
+    _rows(out, "out", B, S, width=HD), _rows(grad_out, "grad_out", B, S, width=HD)
     lse = _contig(lse, "lse")
     if tuple(lse.shape) != (B, heads, S):
         raise AmavError(f"lse: need [B,H,S] = {(B, heads, S)}, got {tuple(lse.shape)}")
     if grad_qkv is None:
         grad_qkv = torch.empty(B, S, 3 * HD, device=qkv.device)
-    _need(grad_qkv, "grad_qkv")
-    if (grad_qkv.dim() != 3 or tuple(grad_qkv.shape[:2]) != (B, S) or grad_qkv.shape[2] < 3 * HD
-            or grad_qkv.stride(2) != 1 or grad_qkv.stride(0) != S * grad_qkv.stride(1)):
-        raise AmavError(f"grad_qkv: need [B,S,>=3*H*D] with unit inner stride, got {tuple(grad_qkv.shape)}")
-    ws = _scratch(sizer, qkv.device, B, S, heads, D,
-                  rejected=f"B={B} S={S} H={heads} D={D}")
+    _rows(grad_qkv, "grad_qkv", B, S, min_width=3 * HD)
+    ws = _scratch(sizer, qkv.device, B, S, heads, D, rejected=f"B={B} S={S} H={heads} D={D}")
     p = qkv.data_ptr()
     _call(entry, B, S, heads, D, p, p + 4 * HD, p + 8 * HD, qkv.stride(1), out.data_ptr(),
           out.stride(1), lse.data_ptr(), grad_out.data_ptr(), grad_out.stride(1), grad_qkv.data_ptr(),
@@ -1608,32 +1620,14 @@ class _SelfAttn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         qkv, out, lse = ctx.saved_tensors
-        grad_out = grad_out.float()
-        if grad_out.stride(2) != 1 or grad_out.stride(0) != grad_out.shape[1] * grad_out.stride(1) or \
-                grad_out.stride(1) % 4 or grad_out.data_ptr() % 16:
-            grad_out = grad_out.contiguous()
-        return selfattn_backward(qkv, out, lse, grad_out, ctx.heads, ctx.scale), None, None
+        return selfattn_backward(qkv, out, lse, _launchable(grad_out.float()), ctx.heads, ctx.scale), None, None
 
 
 def selfattn_differentiable(qkv, heads, scale=None):
     """softmax(q k^T * scale) v as a torch.autograd.Function over a fused [B,S,3*H*D] qkv (q | k | v along the last axis,
     D = 64) -> [B,S,H*D]; the backward returns d qkv in the same fused layout (amav_selfattn_backward), so the gradient
     of a fused q/k/v weight is one GEMM.  Needs the default fp16 x 2 forward (set_option("attn", ...) = fp16)."""
-    if qkv.stride(2) != 1 or qkv.stride(0) != qkv.shape[1] * qkv.stride(1) or qkv.stride(1) % 4 or qkv.data_ptr() % 16:
-        qkv = qkv.contiguous()
-    return _SelfAttn.apply(qkv, int(heads), scale)
-
-
-def _rows(t, name, B=None, S=None, min_width=None, width=None):
-    """[B,S,C] fp32 device tensor with unit inner stride and dense batch stride, of the given sizes where given."""
-    _need(t, name)
-    if (t.dim() != 3 or t.stride(2) != 1 or t.stride(0) != t.shape[1] * t.stride(1)
-            or (B is not None and t.shape[0] != B) or (S is not None and t.shape[1] != S)
-            or (width is not None and t.shape[2] != width) or (min_width is not None and t.shape[2] < min_width)):
-        want = width if width is not None else f">={min_width}" if min_width is not None else "C"
-        raise AmavError(f"{name}: need [B,S,C] = [{B or 'B'},{S or 'S'},{want}] with unit inner stride and dense batch "
-                        f"stride, got {tuple(t.shape)} strides {tuple(t.stride())}")
-    return t
+    return _SelfAttn.apply(_launchable(qkv), int(heads), scale)
 
 
 def _kv_views(kv, heads):
@@ -1681,9 +1675,7 @@ def crossattn_backward(q, kv, out, lse, grad_out, heads, scale=None, grad_q=None
     (crossattn_lse) and grad_out = dLoss/d out.  grad_q / grad_kv: optional [B,Sq,>=H*D] / [B,Sk,>=2*H*D] destination
     views (their first H*D / 2*H*D columns are written).  arithmetic: as selfattn_backward's
     (amav_crossattn_backward_split)."""
-    sizer, entry = (("amav_crossattn_backward_split_workspace_bytes", "amav_crossattn_backward_split")
-                    if _attn_backward_split(arithmetic) else
-                    ("amav_crossattn_backward_workspace_bytes", "amav_crossattn_backward"))
+    sizer, entry = _attn_backward_entry("cross", arithmetic)
     k, v = _kv_views(kv, heads)
     B, Sk, HD = k.shape
     Sq = _rows(q, "q", B=B, width=HD).shape[1]
@@ -1704,13 +1696,6 @@ def crossattn_backward(q, kv, out, lse, grad_out, heads, scale=None, grad_q=None
           grad_q.data_ptr(), grad_q.stride(1), grad_kv.data_ptr(), grad_kv.stride(1),
           float(scale if scale is not None else D ** -0.5), ws.data_ptr(), ws.numel())
     return grad_q, grad_kv
-
-
-def _launchable(t):
-    """t, or a contiguous copy where its layout is not one the attention entry points read in place."""
-    if t.stride(2) != 1 or t.stride(0) != t.shape[1] * t.stride(1) or t.stride(1) % 4 or t.data_ptr() % 16:
-        return t.contiguous()
-    return t
 
 
 class _CrossAttn(torch.autograd.Function):

@@ -19,7 +19,7 @@ What runs where:
     biases) and AMAV_CROSS_ATTN=library (read per call) stay on the library's fused attention;
   * the four big projections of a block (q/k/v, to_out, both feed-forward layers) at inference: fp32-equivalent
     products on the low-precision matrix pipe -- both operands split into parts whose partial products are ONE library
-    GEMM with fp32 accumulation over the parts concatenated along K (csrc/attention.hip, split_operand kernels):
+    GEMM with fp32 accumulation over the parts concatenated along K (csrc/attention_rows.hip, split_operand kernels):
       - inside a block (forward_fused) two fp16 parts, three partial products, K' = 3 K.  fp16 has 5 exponent bits, so
         every operand is pre-scaled by a power of two (exact) taken from a PROVEN bound on its magnitude -- LayerNorm
         rows are bounded by sqrt(dim) max|w| + max|b|, projections of them by Cauchy-Schwarz, softmax averages by their
@@ -306,7 +306,7 @@ class GEGLU(nn.Module):
     def forward(self, hidden_states):
         proj = linear(hidden_states, self.proj.weight, self.proj.bias)
         if proj.is_cuda and proj.dtype == torch.float32 and not torch.is_grad_enabled() and proj.shape[-1] % 8 == 0:
-            return ops.geglu(proj.contiguous())  # one fused pass (csrc/attention.hip)
+            return ops.geglu(proj.contiguous())  # one fused pass (csrc/attention_rows.hip)
         hidden_states, gate = proj.chunk(2, dim=-1)  # CPU construction / autograd
         return hidden_states * F.gelu(gate)
 

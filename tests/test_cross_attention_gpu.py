@@ -12,7 +12,7 @@ import torch
 import torch.nn.functional as F
 
 import cross_attention_cases as cc
-import test_attention_backward_gpu as sb   # BOUND, make_qkv and the self-attention run the cross path must equal
+import test_attention_backward_gpu as sb   # BOUND and make_qkv
 
 pytestmark = pytest.mark.gpu
 
@@ -90,17 +90,21 @@ def test_v_zero_gives_zero():
 
 # ------------------------------------------------------------------------------------- equals self-attention, Sq = Sk
 @pytest.mark.parametrize("S", [65, 1025])
-def test_equals_self_attention_bitwise(S):
+@pytest.mark.parametrize("arithmetic", ["f32", "split"])
+def test_equals_self_attention_bitwise(arithmetic, S):
+    """Self-attention is cross-attention with Sq = Sk over the thirds of one fused row: the forward, and the backward in
+    either arithmetic, run the same kernels on the same rows."""
     ops, B, H = _ops(), 2, 3
     HD = H * D
     qkv = sb.make_qkv(B, S, H, seed=S, pad=12)
     dout = torch.randn(B, S, HD, generator=torch.Generator().manual_seed(S + 1)).cuda()
-    out_s, lse_s, dqkv = sb.run(qkv, dout, H)
+    out_s, lse_s = ops.selfattn_lse(qkv, H)
+    dqkv = ops.selfattn_backward(qkv, out_s, lse_s, dout, H, arithmetic=arithmetic)
     q, kv = qkv[..., :HD], qkv[..., HD:]
     out, lse = ops.crossattn_lse(q, kv, H)
     assert torch.equal(out, out_s) and torch.equal(lse, lse_s)
     assert torch.equal(ops.crossattn(q, kv[..., :HD], kv[..., HD:], H), out_s)
-    dq, dkv = ops.crossattn_backward(q, kv, out, lse, dout, H)
+    dq, dkv = ops.crossattn_backward(q, kv, out, lse, dout, H, arithmetic=arithmetic)
     assert torch.equal(dq, dqkv[..., :HD])
     assert torch.equal(dkv[..., :HD], dqkv[..., HD:2 * HD]) and torch.equal(dkv[..., HD:], dqkv[..., 2 * HD:])
 

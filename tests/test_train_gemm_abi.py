@@ -1,4 +1,4 @@
-"""Host-side checks of the transposing operand split (csrc/attention.hip, amav_split_operand_transposed; DESIGN.md section
+"""Host-side checks of the transposing operand split (csrc/attention_rows.hip, amav_split_operand_transposed; DESIGN.md section
 4.19) and of the names the training GEMMs add.  No kernel is launched: every call below is refused before it reaches the
 device."""
 import ctypes

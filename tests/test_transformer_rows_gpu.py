@@ -1,4 +1,4 @@
-"""The row kernels of the transformer step (csrc/attention.hip: add_layernorm_kernel at its 4 widths x 3 output
+"""The row kernels of the transformer step (csrc/attention_rows.hip: add_layernorm_kernel at its 4 widths x 3 output
 formats, geglu_kernel, the split_operand kernels) one by one through their ops wrappers, against the CPU statements of
 tests/split_model.py: fp64 for the arithmetic, bit for bit for the operand formats.  Shapes are the edges of each
 kernel's launch geometry (fewer rows than a block holds, dead rows and idle lanes in the last block, a batch boundary
