@@ -588,6 +588,84 @@ def jpeg_encode(frames, quality=90, subsampling="420", restart_rows=1, tile_hint
     return stream[:int(offsets[-1])], offsets
 
 
+JPEG_SAMPLING = dict(JPEG_SUBSAMPLING, gray=_lib.DEFINES["AMAV_JPEG_GRAY"])  # what the decoder takes
+JPEG_LAYOUTS = {"hwc_u8": _lib.DEFINES["AMAV_JPEG_HWC_U8"], "chw_f32": _lib.DEFINES["AMAV_JPEG_CHW_F32"]}
+JPEG_STATUS_MARKERS, JPEG_STATUS_ENTROPY = _lib.DEFINES["AMAV_JPEG_STATUS_MARKERS"], _lib.DEFINES["AMAV_JPEG_STATUS_ENTROPY"]
+JpegFrame = _lib.STRUCTS["amav_jpeg_frame"]
+
+
+class JpegRecords:
+    """The per-frame records of one decode call: `table`, a uint8 tensor holding F amav_jpeg_frame records back to back
+    (on the host until .to(device)), and the geometry the frames share.  mjpeg.frame_records() builds one from parsed
+    headers."""
+
+    def __init__(self, table, height, width, sampling):
+        if str(sampling) not in JPEG_SAMPLING:
+            raise AmavError(f"JpegRecords: unknown sampling {sampling!r} (420, 444 or gray)")
+        if table.dtype != torch.uint8 or table.dim() != 1 or table.numel() == 0 or table.numel() % ctypes.sizeof(JpegFrame):
+            raise AmavError(f"JpegRecords: the table must be a uint8 tensor of whole {ctypes.sizeof(JpegFrame)}-byte records")
+        self.table, self.height, self.width, self.sampling = table, int(height), int(width), str(sampling)
+
+    @property
+    def num_frames(self):
+        return self.table.numel() // ctypes.sizeof(JpegFrame)
+
+    def to(self, device):
+        return JpegRecords(self.table.to(device), self.height, self.width, self.sampling)
+
+
+def _jpeg_decode_args(stream, records, status, who):
+    if not isinstance(records, JpegRecords):
+        raise AmavError(f"{who}: records must be an ops.JpegRecords")
+    if not isinstance(stream, torch.Tensor) or not stream.is_cuda or stream.dtype != torch.uint8 or stream.dim() != 1 or \
+            stream.stride(0) != 1:
+        raise AmavError(f"{who}: stream must be a uint8 vector on the HIP device")
+    table = records.table
+    if table.device != stream.device or not table.is_contiguous():
+        raise AmavError(f"{who}: the record table must be contiguous on the stream's device (records.to(device))")
+    F = records.num_frames
+    if status is None:
+        status = torch.empty(F, dtype=torch.int32, device=stream.device)
+    elif not isinstance(status, torch.Tensor) or status.dtype != torch.int32 or status.device != stream.device or \
+            not status.is_contiguous() or status.numel() != F:
+        raise AmavError(f"{who}: status must be a contiguous int32 [F] tensor on the stream's device")
+    return F, records.height, records.width, JPEG_SAMPLING[records.sampling], status
+
+
+def jpeg_decode_levels(stream, records, status=None):
+    """The decoder's marker search and entropy decode alone: (int16 levels [F, blocks per frame, 64] in the layout of
+    jpeg_coefficients, status int32 [F]), both on the device; no host synchronisation."""
+    F, H, W, sampling, status = _jpeg_decode_args(stream, records, status, "jpeg_decode_levels")
+    ws = _scratch("amav_jpeg_decode_workspace_bytes", stream.device, F, H, W, sampling, 1, rejected=f"F={F} H={H} W={W}")
+    mcu = 16 if records.sampling == "420" else 8
+    blocks = -(-H // mcu) * -(-W // mcu) * {"420": 6, "444": 3, "gray": 1}[records.sampling]
+    levels = torch.empty(F, blocks, 64, dtype=torch.int16, device=stream.device)
+    _call("amav_jpeg_decode_levels", F, H, W, sampling, stream.data_ptr(), stream.numel(), records.table.data_ptr(),
+          levels.data_ptr(), levels.numel() * 2, status.data_ptr(), ws.data_ptr(), ws.numel())
+    return levels, status
+
+
+def jpeg_decode(stream, records, layout="chw_f32", out=None, status=None):
+    """Baseline JPEG frames lying in the device byte vector `stream` -> (frames, status), both on the device, without a
+    host synchronisation.  layout "hwc_u8": uint8 RGB [F,H,W,3]; "chw_f32": fp32 [F,3,H,W] holding exactly uint8 / 255
+    (include/amav.h has the arithmetic).  status int32 [F]: 0, or JPEG_STATUS_MARKERS | JPEG_STATUS_ENTROPY for a
+    damaged frame, whose undecodable blocks are zero levels; the other frames are not affected."""
+    F, H, W, sampling, status = _jpeg_decode_args(stream, records, status, "jpeg_decode")
+    if layout not in JPEG_LAYOUTS:
+        raise AmavError(f"jpeg_decode: unknown layout {layout!r} (hwc_u8 or chw_f32)")
+    shape, dtype = ((F, H, W, 3), torch.uint8) if layout == "hwc_u8" else ((F, 3, H, W), torch.float32)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=stream.device)
+    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or \
+            out.device != stream.device:
+        raise AmavError(f"jpeg_decode: out must be a contiguous {dtype} {shape} tensor on the stream's device")
+    ws = _scratch("amav_jpeg_decode_workspace_bytes", stream.device, F, H, W, sampling, 0, rejected=f"F={F} H={H} W={W}")
+    _call("amav_jpeg_decode", F, H, W, sampling, stream.data_ptr(), stream.numel(), records.table.data_ptr(),
+          JPEG_LAYOUTS[layout], out.data_ptr(), out.numel() * out.element_size(), status.data_ptr(), ws.data_ptr(),
+          ws.numel())
+    return out, status
+
+
 # ------------------------------------------------------------------------------------------------------------ LBS
 def body_tables_struct(tables: dict) -> BodyTables:
     """dict of device tensors prepared by body_model.BodyModel.device_tables() -> amav_body_tables."""

@@ -1302,6 +1302,64 @@ int amav_jpeg_encode(int num_frames, int height, int width, const void *frames_d
                      uint8_t *stream_out_dev, int64_t capacity, int64_t *frame_offsets_dev, int32_t *status_dev,
                      void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* Motion-JPEG input (csrc/jpeg_decode.hip): the inverse of the above.  One call decodes num_frames baseline JPEG frames
+ * (SOF0, 8 bit, one interleaved sequential scan) that share height, width and sampling: AMAV_JPEG_444 (3 components,
+ * MCU 8x8, blocks Y Cb Cr), AMAV_JPEG_420 (3 components, MCU 16x16, blocks Y Y Y Y Cb Cr) or AMAV_JPEG_GRAY (1 component,
+ * MCU 8x8).  The frames lie anywhere (unaligned) in stream_dev [stream_bytes]; the host has parsed their headers into
+ * one amav_jpeg_frame record per frame (records_dev: the records back to back on the device, 8-byte aligned), so
+ * quantisation tables, Huffman tables and the restart interval are per frame.  A record's scan range is clamped to the
+ * stream buffer on the device, table indices are masked: no record makes a kernel read or write out of bounds.
+ *   markers  one wave per frame searches [scan_begin, scan_end) byte-parallel for FF D0..D7 (RSTn) and FF D9 (EOI) up to
+ *            the first EOI.  In entropy-coded data an FF is followed by 00 (a stuffed byte) or belongs to a marker or to
+ *            the fill bytes FF FF.. before one, so a marker code preceded by FF is a marker.  Interval k starts after
+ *            marker k - 1 and ends at marker k; the offsets are written in stream order (ballot + prefix count, no
+ *            atomics).  status[f] = AMAV_JPEG_STATUS_MARKERS unless EOI was found, the markers number
+ *            ceil(MCUs / restart_interval) (1 without DRI) and RSTn counts 0..7 cyclically; else 0.
+ *   entropy  one lane per restart interval (a frame without DRI is one lane's work: correct, and slow).  The frame's
+ *            DHT pairs are expanded per workgroup into 9-bit lookup tables in LDS (longer codes: the canonical
+ *            first-code / count comparison per length).  Per interval: DC predictors = 0; per block DC category +
+ *            extend, then AC run / size with ZRL and EOB.  Reads stay inside the interval's byte range, writes inside
+ *            its own blocks.  An invalid code, a run past coefficient 63 or data that ends inside a symbol zeroes that
+ *            block and the interval's remaining blocks and sets AMAV_JPEG_STATUS_ENTROPY in status[f]; an interval
+ *            whose start the marker search did not find is zero levels.  Other intervals and frames are unaffected.
+ *            Levels: int16 [F, blocks, 64], MCU-interleaved scan order, zigzag: the layout of amav_jpeg_coefficients.
+ *   pixels   coefficient = level x table entry; separable orthonormal 8x8 inverse DCT in fp32; + 128; clamp to
+ *            [0, 255], not rounded, per component sample.  4:2:0 chroma is upsampled on its ceil(H/2) x ceil(W/2) plane
+ *            with the triangle filter: 3/4 of the nearer sample and 1/4 of the farther one, vertically then
+ *            horizontally, neighbours clamped at the plane's edge, nothing rounded in between.  R = Y + 1.402 Cr',
+ *            G = Y - 0.344136 Cb' - 0.714136 Cr', B = Y + 1.772 Cb' with Cb' = Cb - 128, Cr' = Cr - 128; rounded to
+ *            nearest, clamped to 0..255.  One component: R = G = B = Y.  AMAV_JPEG_HWC_U8: uint8 [F,H,W,3];
+ *            AMAV_JPEG_CHW_F32: fp32 [F,3,H,W] holding exactly uint8 / 255.0f.
+ * amav_jpeg_decode_levels runs the first two stages (levels_dev 16-byte aligned, levels_bytes >= 128 x blocks);
+ * amav_jpeg_decode all three.  status_dev: int32 [F], written by the call (no need to zero it).  Workspace:
+ * amav_jpeg_decode_workspace_bytes (levels_only != 0 for amav_jpeg_decode_levels); 0 = rejected sizes.  No allocation,
+ * no host synchronisation, no memset, no float atomics; the same bytes on every run, and a frame does not depend on the
+ * others of the batch.  Refused with an error code before any launch: F outside 1..65535, H or W outside 1..65535, more
+ * than 2^31 - 1 blocks, an unknown sampling or layout, a NULL or misaligned pointer, a negative stream_bytes, and an
+ * output, levels buffer or workspace that is too small (AMAV_ERR_WORKSPACE). */
+#define AMAV_JPEG_GRAY 400
+#define AMAV_JPEG_HWC_U8 0
+#define AMAV_JPEG_CHW_F32 1
+#define AMAV_JPEG_STATUS_MARKERS 1
+#define AMAV_JPEG_STATUS_ENTROPY 2
+typedef struct amav_jpeg_frame {
+    int64_t scan_begin, scan_end; /* bytes of stream_dev: first byte after SOS .. end of the frame (EOI included) */
+    int32_t restart_interval;     /* MCUs per interval (DRI); 0 = none */
+    int32_t reserved;
+    uint8_t quant[192];           /* [component][zigzag position]: the component's DQT entries as the file has them */
+    uint8_t dc_counts[48];        /* [component][length - 1]: codes of length 1..16 of the component's DC table */
+    uint8_t dc_values[48];        /* [component][16] */
+    uint8_t ac_counts[48];
+    uint8_t ac_values[768];       /* [component][256] */
+} amav_jpeg_frame;
+size_t amav_jpeg_decode_workspace_bytes(int num_frames, int height, int width, int sampling, int levels_only);
+int amav_jpeg_decode_levels(int num_frames, int height, int width, int sampling, const uint8_t *stream_dev,
+                            int64_t stream_bytes, const void *records_dev, void *levels_dev, size_t levels_bytes,
+                            int32_t *status_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+int amav_jpeg_decode(int num_frames, int height, int width, int sampling, const uint8_t *stream_dev, int64_t stream_bytes,
+                     const void *records_dev, int layout, void *out_dev, size_t out_bytes, int32_t *status_dev,
+                     void *workspace_dev, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
