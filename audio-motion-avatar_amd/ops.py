@@ -666,6 +666,80 @@ def jpeg_decode(stream, records, layout="chw_f32", out=None, status=None):
     return out, status
 
 
+def padded_size(height, width, pad_ratio):
+    """pad_image's geometry (src/datasets/dataset_speech_vid.py:319-327), in Python doubles as there:
+    (Hp, Wp, offset_y, offset_x)."""
+    hp, wp = int(height * (1 + pad_ratio)), int(width * (1 + pad_ratio))
+    return hp, wp, (hp - height) // 2, (wp - width) // 2
+
+
+def _frame_view(t, name, channels):
+    """Element strides (f, [c,] y, x) of a decoder-layout tensor or a view of one: uint8 [F,H,W(,3)] or fp32 [F(,3),H,W]."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in (torch.uint8, torch.float32):
+        raise AmavError(f"{name}: expected a uint8 or float32 tensor on the HIP device")
+    if t.dim() != 3 + channels:
+        raise AmavError(f"{name}: expected {3 + channels} dimensions, got {tuple(t.shape)}")
+    if not channels:
+        return tuple(t.shape), t.stride()
+    if t.dtype == torch.uint8:
+        t = t.permute(0, 3, 1, 2)  # [F,H,W,3] read as [F,3,H,W]
+    if t.shape[1] != 3:
+        raise AmavError(f"{name}: expected uint8 [F,H,W,3] or float32 [F,3,H,W], got {tuple(t.shape)}")
+    return (t.shape[0], t.shape[2], t.shape[3]), t.stride()
+
+
+def prepare_frames(frames, masks=None, pad_ratio=0.0, crop_size=1024, normalize=None, images=True, cropped=True,
+                   out_images=None, out_cropped=None):
+    """The image half of the reference dataset's __getitem__ (src/datasets/dataset_speech_vid.py:184-252) for a whole clip
+    in one amav_frames_prepare call, without a host synchronisation: (images, cropped, boxes).
+
+    frames: uint8 [F,H,W,3] or fp32 [F,3,H,W] (jpeg_decode's two layouts) or a view of one; masks: uint8 or fp32 [F,H,W]
+    or a view (channel 0 of a decoded grey clip: clip[..., 0]); None = all ones.
+    images  fp32 [F,3,Hp,Wp], Hp = int(H * (1 + pad_ratio)): the frame over white, padded with ones  (`images`)
+    cropped fp32 [F,3,crop_size,crop_size]: the mask's box grown by 20 %, squared, cropped from the padded image, padded
+            to a square with ones and resized bilinearly with align_corners=True  (`cropped_images`); with
+            normalize=(mean[3], std[3]) it holds (x - mean) / std, SapiensWrapper._preprocess_image's normalize
+    boxes   int32 [F,5]: y_min, y_max, x_min, x_max (inclusive) and max_size
+    images=False / cropped=False skip that output (None is returned in its place); out_images / out_cropped are written
+    instead of fresh tensors.  Where the crop's side already equals crop_size the reference skips its resize and hands
+    back the crop before squaring; this returns the square image."""
+    _no_autograd("prepare_frames", frames, masks)
+    (F, H, W), fs = _frame_view(frames, "frames", 1)
+    ms = (0, 0, 0)
+    if masks is not None:
+        shape, ms = _frame_view(masks, "masks", 0)
+        if shape != (F, H, W) or masks.device != frames.device:
+            raise AmavError(f"prepare_frames: masks {shape} on {masks.device} do not match frames {(F, H, W)} on {frames.device}")
+    Hp, Wp, oy, ox = padded_size(H, W, pad_ratio)
+    S, dev = int(crop_size), frames.device
+
+    def output(wanted, given, shape, name):
+        if not wanted:
+            return None  # a buffer given for it stays untouched
+        if given is None:
+            return torch.empty(shape, device=dev)
+        if not isinstance(given, torch.Tensor) or given.dtype != torch.float32 or given.device != dev or \
+                not given.is_contiguous() or tuple(given.shape) != shape:
+            raise AmavError(f"prepare_frames: {name} must be a contiguous float32 {shape} tensor on the frames' device")
+        return given
+
+    if Hp < H or Wp < W or S < 1:
+        raise AmavError(f"prepare_frames: pad_ratio {pad_ratio} or crop_size {crop_size} out of range")
+    out_i = output(images, out_images, (F, 3, Hp, Wp), "out_images")
+    out_c = output(cropped, out_cropped, (F, 3, S, S), "out_cropped")
+    boxes = torch.empty(F, 5, dtype=torch.int32, device=dev)
+    mean3 = std3 = None
+    if normalize is not None:
+        mean3, std3 = ((ctypes.c_float * 3)(*[float(v) for v in part]) for part in normalize)
+    ws = _scratch("amav_frames_prepare_workspace_bytes", dev, F, rejected=f"F={F}")
+    nbytes = lambda t: 0 if t is None else t.numel() * t.element_size()  # noqa: E731
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    _call("amav_frames_prepare", F, H, W, frames.data_ptr(), int(frames.dtype == torch.float32), *fs, ptr(masks),
+          int(masks is not None and masks.dtype == torch.float32), *ms, Hp, Wp, oy, ox, S, mean3, std3, ptr(out_i),
+          nbytes(out_i), ptr(out_c), nbytes(out_c), boxes.data_ptr(), nbytes(boxes), ws.data_ptr(), ws.numel())
+    return out_i, out_c, boxes
+
+
 # ------------------------------------------------------------------------------------------------------------ LBS
 def body_tables_struct(tables: dict) -> BodyTables:
     """dict of device tensors prepared by body_model.BodyModel.device_tables() -> amav_body_tables."""

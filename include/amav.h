@@ -1360,6 +1360,46 @@ int amav_jpeg_decode(int num_frames, int height, int width, int sampling, const 
                      const void *records_dev, int layout, void *out_dev, size_t out_bytes, int32_t *status_dev,
                      void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* Training-clip frame preparation (csrc/frame_prep.hip): what the reference's dataset does to every frame on the CPU
+ * (src/datasets/dataset_speech_vid.py:170-252, pad_image :319-331), for num_frames frames of one size H x W per call.
+ *   frames_dev  uint8 (frames_are_f32 = 0; the value is byte / 255.0f) or fp32, read in place at element
+ *               f frame_stride_f + c frame_stride_c + y frame_stride_y + x frame_stride_x (strides in elements): the
+ *               decoder's [F,H,W,3] and [F,3,H,W], or any view of them.  The strides inside a frame (c, y, x) are not
+ *               negative and one frame's view spans fewer than 2^31 elements; the frame stride is free.
+ *   masks_dev   uint8 (byte / 255.0f) or fp32 in [0,1] at f mask_stride_f + y mask_stride_y + x mask_stride_x; NULL =
+ *               all ones.
+ *   images_dev  fp32 [F,3,Hp,Wp]: ones, and at (offset_y, offset_x) the frame composited over white,
+ *               image * mask + (1 - mask), each operator rounded to fp32 on its own (:184, pad_image).
+ *   boxes_dev   int32 [F,5]: y_min, y_max, x_min, x_max (inclusive, as finally used) and max_size.  The bounding box of
+ *               mask != 0 grows by extent / 5 (= int(extent * 0.2)), is clamped to H - 1, W - 1, made square around its
+ *               centre with crop_size // 2 and clamped again (:195-216).  It is found in frame coordinates and applied to
+ *               the padded image as it is, as the reference does.  An empty mask: the whole padded image.
+ *               max_size = max(y_max - y_min, x_max - x_min) + 1.
+ *   cropped_dev fp32 [F,3,S,S], S = crop_side: the crop, centred in a square of ones of side max_size ((max_size - w) / 2
+ *               columns on the left, (max_size - h) / 2 rows on top, :227-244), resized with torch's bilinear,
+ *               align_corners=True: scale = float(max_size - 1) / float(S - 1) (0 for S = 1), src = scale * dst,
+ *               i0 = (int)src, i1 = min(i0 + 1, max_size - 1), w1 = src - i0, w0 = 1 - w1,
+ *               value = h0 (w0 p00 + w1 p01) + h1 (w0 p10 + w1 p11), fp32, nothing contracted.  The taps are composited
+ *               on the fly, so images_dev is not read.  max_size == S takes the same path with scale 1 (the square image
+ *               itself; the reference skips its resize there and returns the crop before squaring).  With mean_host3 /
+ *               std_host3 (both or neither) the stored value is (value - mean[c]) / std[c], an IEEE division.
+ * Each output is optional (NULL = not produced, its buffer is not touched).  At most three launches on `stream` (images
+ * + box table initialisation, box reduction with integer atomicMin / atomicMax, cropped); no allocation, no memset, no
+ * float atomics, no host synchronisation; the same bits on every run.  workspace: amav_frames_prepare_workspace_bytes
+ * (0 = rejected F), needed when cropped_dev or boxes_dev is given.  Refused with an error code before any launch: NULL
+ * frames, F outside 1..16384, H, W, Hp, Wp or crop_side outside 1..65535, Hp < H or Wp < W, offsets that put the frame
+ * outside the padded image, a flag other than 0 / 1, a negative or too large stride inside a frame, mean without std,
+ * a std of zero, a misaligned buffer (images, cropped, workspace: 16 bytes), and an output buffer or workspace that is
+ * too small (AMAV_ERR_WORKSPACE). */
+size_t amav_frames_prepare_workspace_bytes(int num_frames);
+int amav_frames_prepare(int num_frames, int height, int width, const void *frames_dev, int frames_are_f32,
+                        int64_t frame_stride_f, int64_t frame_stride_c, int64_t frame_stride_y, int64_t frame_stride_x,
+                        const void *masks_dev, int masks_are_f32, int64_t mask_stride_f, int64_t mask_stride_y,
+                        int64_t mask_stride_x, int padded_height, int padded_width, int offset_y, int offset_x,
+                        int crop_side, const float *mean_host3, const float *std_host3, float *images_dev,
+                        size_t images_bytes, float *cropped_dev, size_t cropped_bytes, int32_t *boxes_dev,
+                        size_t boxes_bytes, void *workspace_dev, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
