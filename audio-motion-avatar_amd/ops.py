@@ -666,6 +666,111 @@ def jpeg_decode(stream, records, layout="chw_f32", out=None, status=None):
     return out, status
 
 
+# ------------------------------------------------------------------------------------------------------------ PNG
+PNG_MODES = {"rgb": _lib.DEFINES["AMAV_PNG_RGB"], "l": _lib.DEFINES["AMAV_PNG_L"]}
+PNG_STATUS_INFLATE, PNG_STATUS_SIZE, PNG_STATUS_FILTER = (_lib.DEFINES["AMAV_PNG_STATUS_" + n] for n in ("INFLATE", "SIZE", "FILTER"))
+InflateStream = _lib.STRUCTS["amav_inflate_stream"]
+PngFrame = _lib.STRUCTS["amav_png_frame"]
+
+
+class PngRecords:
+    """The per-frame records of one PNG decode call: `table`, a uint8 tensor holding F amav_png_frame records back to
+    back (on the host until .to(device)), and the height and width the frames share.  png.frame_records() builds one."""
+
+    def __init__(self, table, height, width):
+        if not isinstance(table, torch.Tensor) or table.dtype != torch.uint8 or table.dim() != 1 or table.numel() == 0 or \
+                table.numel() % ctypes.sizeof(PngFrame):
+            raise AmavError(f"PngRecords: the table must be a uint8 tensor of whole {ctypes.sizeof(PngFrame)}-byte records")
+        self.table, self.height, self.width = table, int(height), int(width)
+
+    @property
+    def num_frames(self):
+        return self.table.numel() // ctypes.sizeof(PngFrame)
+
+    def to(self, device):
+        return PngRecords(self.table.to(device), self.height, self.width)
+
+
+def _byte_stream(stream, who):
+    if not isinstance(stream, torch.Tensor) or not stream.is_cuda or stream.dtype != torch.uint8 or stream.dim() != 1 or \
+            stream.stride(0) != 1:
+        raise AmavError(f"{who}: stream must be a uint8 vector on the HIP device")
+    return stream
+
+
+def _status_words(status, n, device, who):
+    if status is None:
+        return torch.empty(n, dtype=torch.int32, device=device)
+    if not isinstance(status, torch.Tensor) or status.dtype != torch.int32 or status.device != device or \
+            not status.is_contiguous() or status.numel() != n:
+        raise AmavError(f"{who}: status must be a contiguous int32 [{n}] tensor on the stream's device")
+    return status
+
+
+def inflate(stream, records, out=None, status=None):
+    """DEFLATE streams lying in the device byte vector `stream` -> (out, produced, status), all on the device.  With
+    records on the host there is no host synchronisation (the table goes up in one copy); records given on the device
+    are read back first, which is one.  records: int64 [N,5], one row per stream: in_begin, in_end (bytes
+    of `stream`), out_begin, out_capacity (bytes of `out`), wrapper (0 raw, 1 zlib; the Adler-32 is not verified).
+    out: the uint8 vector written into (default: a fresh one that just holds every row's range; the bytes between the
+    ranges are not touched).  produced int64 [N]: bytes written per stream; status int32 [N]: 0, or PNG_STATUS_INFLATE /
+    PNG_STATUS_SIZE (include/amav.h has the rules)."""
+    _byte_stream(stream, "inflate")
+    if not isinstance(records, torch.Tensor) or records.dtype != torch.int64 or records.dim() != 2 or records.shape[1] != 5 or \
+            records.shape[0] == 0:
+        raise AmavError("inflate: records must be an int64 [N,5] tensor (in_begin, in_end, out_begin, out_capacity, wrapper)")
+    host = records.cpu() if records.is_cuda else records
+    N = host.shape[0]
+    if out is None:
+        out = torch.empty(max(1, int((host[:, 2] + host[:, 3]).max())), dtype=torch.uint8, device=stream.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.dim() != 1 or out.stride(0) != 1 or \
+            out.device != stream.device:
+        raise AmavError("inflate: out must be a uint8 vector on the stream's device")
+    table = torch.zeros(N, ctypes.sizeof(InflateStream) // 8, dtype=torch.int64)
+    table[:, :4] = host[:, :4]
+    table[:, 4] = host[:, 4] & 0xFFFFFFFF  # wrapper (int32) + reserved
+    table = table.to(stream.device)
+    status = _status_words(status, N, stream.device, "inflate")
+    produced = torch.empty(N, dtype=torch.int64, device=stream.device)
+    ws = _scratch("amav_inflate_workspace_bytes", stream.device, N, rejected=f"{N} streams")
+    _call("amav_inflate", N, stream.data_ptr(), stream.numel(), table.data_ptr(), out.data_ptr(), out.numel(),
+          produced.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel())
+    return out, produced, status
+
+
+def png_decode(stream, records, mode="rgb", layout="hwc_u8", out=None, status=None):
+    """PNG frames whose joined IDAT streams (and palettes) lie in the device byte vector `stream` -> (frames, status),
+    both on the device, without a host synchronisation.  mode "rgb" / "l": PIL's convert("RGB") / convert("L"), bit for
+    bit.  layout "hwc_u8": uint8 [F,H,W,3] / [F,H,W]; "chw_f32": fp32 [F,3,H,W] / [F,1,H,W] holding exactly uint8 / 255.
+    status int32 [F]: 0, or PNG_STATUS_INFLATE | PNG_STATUS_SIZE | PNG_STATUS_FILTER for a damaged frame (its pixels
+    are 0 unless FILTER is the only bit); the other frames are not affected."""
+    if not isinstance(records, PngRecords):
+        raise AmavError("png_decode: records must be an ops.PngRecords")
+    _byte_stream(stream, "png_decode")
+    table = records.table
+    if table.device != stream.device or not table.is_contiguous():
+        raise AmavError("png_decode: the record table must be contiguous on the stream's device (records.to(device))")
+    if mode not in PNG_MODES:
+        raise AmavError(f"png_decode: unknown mode {mode!r} (rgb or l)")
+    if layout not in JPEG_LAYOUTS:
+        raise AmavError(f"png_decode: unknown layout {layout!r} (hwc_u8 or chw_f32)")
+    F, H, W = records.num_frames, records.height, records.width
+    status = _status_words(status, F, stream.device, "png_decode")
+    if layout == "hwc_u8":
+        shape, dtype = ((F, H, W, 3) if mode == "rgb" else (F, H, W)), torch.uint8
+    else:
+        shape, dtype = (F, 3 if mode == "rgb" else 1, H, W), torch.float32
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=stream.device)
+    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or \
+            out.device != stream.device:
+        raise AmavError(f"png_decode: out must be a contiguous {dtype} {shape} tensor on the stream's device")
+    ws = _scratch("amav_png_decode_workspace_bytes", stream.device, F, H, W, rejected=f"F={F} H={H} W={W}")
+    _call("amav_png_decode", F, H, W, stream.data_ptr(), stream.numel(), table.data_ptr(), PNG_MODES[mode],
+          JPEG_LAYOUTS[layout], out.data_ptr(), out.numel() * out.element_size(), status.data_ptr(), ws.data_ptr(), ws.numel())
+    return out, status
+
+
 def padded_size(height, width, pad_ratio):
     """pad_image's geometry (src/datasets/dataset_speech_vid.py:319-327), in Python doubles as there:
     (Hp, Wp, offset_y, offset_x)."""

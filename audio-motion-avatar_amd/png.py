@@ -1,0 +1,224 @@
+"""PNG clip input: the host side.  Chunk parsing only (struct + zlib.crc32; no Pillow, nothing is inflated here): the
+frames of the reference's dataset (imgs_png/%05d.png, samurai_seg/%05d.png) are parsed, each frame's IDAT payloads are
+joined into one zlib stream, and records, palettes and streams go up in one copy to one ops.png_decode call.
+
+Not covered: interlaced (Adam7) and 16-bit files, which parse_png refuses; the Adler-32 of the zlib stream, which the
+device does not verify (a chunk's CRC is checked here)."""
+import os
+import struct
+import zlib
+
+SIGNATURE = b"\x89PNG\r\n\x1a\n"
+MAX_SIDE = 16384
+ALLOWED_DEPTHS = {0: (1, 2, 4, 8, 16), 2: (8, 16), 3: (1, 2, 4, 8), 4: (8, 16), 6: (8, 16)}  # the standard's pairs
+PNG_RECORD_BYTES = 40  # sizeof(amav_png_frame), include/amav.h
+
+
+class PngError(ValueError):
+    """The file is not a PNG this decoder takes (or the device flagged its stream)."""
+
+
+class PngHeader:
+    """What the decoder needs of one file: geometry, the PLTE bytes and where the IDAT payloads lie (byte ranges of the
+    file, in file order)."""
+
+    def __init__(self, height, width, color_type, bit_depth, palette, idat):
+        self.height, self.width, self.color_type, self.bit_depth = height, width, color_type, bit_depth
+        self.palette, self.idat = palette, idat
+
+    @property
+    def palette_entries(self):
+        return len(self.palette) // 3
+
+
+def parse_png(data):
+    """bytes of one PNG file -> PngHeader.  Ancillary chunks (gAMA, tRNS, tEXt, unknown ones) are skipped, as PIL's
+    convert("RGB") / convert("L") ignore them.  Raises PngError for what the module docstring and README list."""
+    data = bytes(data) if not isinstance(data, (bytes, bytearray, memoryview)) else data
+    if bytes(data[:8]) != SIGNATURE:
+        raise PngError("bad PNG signature")
+    at, header, palette, idat, idat_closed, ended = 8, None, b"", [], False, False
+    while at < len(data):
+        if at + 12 > len(data):
+            raise PngError(f"truncated chunk at byte {at}")
+        n, kind = struct.unpack(">I4s", data[at:at + 8])
+        if at + 12 + n > len(data):
+            raise PngError(f"chunk {kind!r} at byte {at} runs past the end of the file")
+        body = data[at + 8:at + 8 + n]
+        if zlib.crc32(data[at + 4:at + 8 + n]) != struct.unpack(">I", data[at + 8 + n:at + 12 + n])[0]:
+            raise PngError(f"chunk {kind!r} at byte {at}: CRC mismatch")
+        if header is None and kind != b"IHDR":
+            raise PngError(f"{kind!r} before IHDR")
+        if kind == b"IHDR":
+            if header is not None or n != 13:
+                raise PngError("misplaced or malformed IHDR")
+            width, height, depth, color_type, compression, filter_method, interlace = struct.unpack(">IIBBBBB", body)
+            if color_type not in ALLOWED_DEPTHS or depth not in ALLOWED_DEPTHS[color_type]:
+                raise PngError(f"colour type {color_type} with bit depth {depth} is not a PNG combination")
+            if depth == 16:
+                raise PngError("bit depth 16 is not covered")
+            if compression != 0 or filter_method != 0:
+                raise PngError(f"compression method {compression} / filter method {filter_method} (only 0 / 0 exist)")
+            if interlace != 0:
+                raise PngError("interlaced (Adam7) files are not covered" if interlace == 1 else f"interlace method {interlace}")
+            if not (1 <= width <= MAX_SIDE and 1 <= height <= MAX_SIDE):
+                raise PngError(f"size {width}x{height} outside 1..{MAX_SIDE}")
+            header = (height, width, color_type, depth)
+        elif kind == b"PLTE":
+            if idat or palette or n % 3 or not 3 <= n <= 768:
+                raise PngError("misplaced or malformed PLTE")
+            palette = bytes(body)
+        elif kind == b"IDAT":
+            if idat_closed:
+                raise PngError("IDAT chunks are not consecutive")
+            idat.append((at + 8, at + 8 + n))
+        elif kind == b"IEND":
+            ended = True
+            break
+        elif not kind[0] & 0x20:
+            raise PngError(f"unknown critical chunk {kind!r}")
+        if idat and kind != b"IDAT":
+            idat_closed = True
+        at += 12 + n
+    if header is None:
+        raise PngError("no IHDR")
+    if not idat:
+        raise PngError("no IDAT")
+    if not ended:
+        raise PngError("no IEND")
+    if header[2] == 3 and not palette:
+        raise PngError("colour type 3 without PLTE")
+    return PngHeader(*header, palette if header[2] == 3 else b"", idat)  # elsewhere PLTE is a suggestion, not the pixels
+
+
+def zlib_stream(data, header):
+    """The file's IDAT payloads joined: one zlib stream."""
+    return b"".join(bytes(data[a:b]) for a, b in header.idat)
+
+
+class PngDirReader:
+    """A directory of per-frame PNG files.  With the dataset's all-digit stems (00000.png ...) in the order of
+    int(stem), otherwise every *.png in name order.  Same shape as mjpeg.DirReader."""
+
+    fps = None
+
+    def __init__(self, path):
+        names = sorted(n for n in os.listdir(path) if n.lower().endswith(".png"))
+        if not names:
+            raise ValueError(f"{path}: no PNG files")
+        if all(os.path.splitext(n)[0].isdigit() for n in names):
+            names.sort(key=lambda n: int(os.path.splitext(n)[0]))
+        self._frames = [os.path.join(path, n) for n in names]
+        self.height = self.width = None
+
+    def __len__(self):
+        return len(self._frames)
+
+    def frame_bytes(self, i):
+        with open(self._frames[i], "rb") as fh:
+            return fh.read()
+
+    def close(self):
+        pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def pack_clip(blobs):
+    """PNG files (bytes; None = an absent frame, all 255) -> (host uint8 tensor, table_bytes, height, width): the
+    amav_png_frame records first, then the palettes, then each frame's IDAT payloads joined into one zlib stream; a
+    record's offsets count from the end of the table (the `stream` of ops.png_decode is buffer[table_bytes:])."""
+    import torch
+
+    headers = []
+    for i, blob in enumerate(blobs):
+        try:
+            headers.append(None if blob is None else parse_png(blob))
+        except PngError as e:
+            raise PngError(f"frame {i}: {e}") from None
+    present = [h for h in headers if h is not None]
+    if not present:
+        raise PngError("pack_clip: at least one frame must be present")
+    H, W = present[0].height, present[0].width
+    for i, h in enumerate(headers):
+        if h is not None and (h.height, h.width) != (H, W):
+            raise PngError(f"frames of unequal size in one call: frame {i} is {h.width}x{h.height}, the first is {W}x{H}")
+    parts, at, table = [], 0, bytearray()
+    palette_at = []
+    for h in headers:
+        palette_at.append(at)
+        if h is not None and h.palette:
+            parts.append(h.palette)
+            at += len(h.palette)
+    for h, blob, pal in zip(headers, blobs, palette_at):
+        if h is None:
+            table += struct.pack("<qqqiiii", 0, 0, 0, 0, 8, 0, 1)
+            continue
+        begin = at
+        for a, b in h.idat:
+            parts.append(bytes(blob[a:b]))
+            at += b - a
+        table += struct.pack("<qqqiiii", begin, at, pal, h.color_type, h.bit_depth, h.palette_entries, 0)
+    assert len(table) == PNG_RECORD_BYTES * len(headers)
+    host = torch.frombuffer(bytearray(bytes(table) + b"".join(parts)) or bytearray(1), dtype=torch.uint8)
+    return host, len(table), H, W
+
+
+def frame_records(blobs):
+    """PNG files -> (ops.PngRecords on the host, the stream bytes as a host uint8 tensor)."""
+    from .ops import PngRecords
+
+    host, table_bytes, H, W = pack_clip(blobs)
+    return PngRecords(host[:table_bytes], H, W), host[table_bytes:]
+
+
+def status_text(s):
+    from . import ops
+
+    names = [(ops.PNG_STATUS_INFLATE, "inflate"), (ops.PNG_STATUS_SIZE, "size"), (ops.PNG_STATUS_FILTER, "filter")]
+    return "+".join(name for bit, name in names if s & bit)
+
+
+def load_clip(path, frames=None, mode="rgb", device="cuda", layout="chw_f32", check=True):
+    """A directory of PNG files (or an open reader, or a list of file contents in which None is an absent frame) ->
+    device tensor: mode "rgb": fp32 [F,3,H,W] in [0, 1] (layout "chw_f32") or uint8 [F,H,W,3] ("hwc_u8"); mode "l":
+    fp32 [F,1,H,W] or uint8 [F,H,W].  `frames`: indices (default: all).  The files are parsed on the host, one buffer
+    goes up in one copy and one ops.png_decode call decodes it.  check=True reads the status words back once and raises
+    PngError naming the frames the decoder flagged; check=False returns (tensor, status on the device) without
+    synchronising."""
+    from . import ops
+
+    if isinstance(path, (list, tuple)):
+        count = len(path)
+        picked = list(range(count)) if frames is None else [int(i) for i in frames]
+        blobs = [path[i] for i in picked]
+    else:
+        reader = path if hasattr(path, "frame_bytes") else PngDirReader(os.fspath(path))
+        try:
+            count = len(reader)
+            picked = list(range(count)) if frames is None else [int(i) for i in frames]
+            for i in picked:
+                if not -count <= i < count:
+                    raise IndexError(f"load_clip: frame {i} of a clip of {count}")
+            blobs = [reader.frame_bytes(i) for i in picked]
+        finally:
+            if reader is not path:
+                reader.close()
+    if not blobs:
+        raise ValueError("load_clip: no frames selected")
+    try:
+        host, table_bytes, H, W = pack_clip(blobs)
+    except PngError as e:
+        raise PngError(f"load_clip: {e}") from None
+    dev = host.to(device)  # the one upload: records first (8-byte aligned), then palettes and streams
+    out, status = ops.png_decode(dev[table_bytes:], ops.PngRecords(dev[:table_bytes], H, W), mode=mode, layout=layout)
+    if not check:
+        return out, status
+    bad = [(i, s) for i, s in zip(picked, status.cpu().tolist()) if s]
+    if bad:
+        raise PngError("load_clip: damaged frames " + ", ".join(f"{i} ({status_text(s)})" for i, s in bad))
+    return out

@@ -1400,6 +1400,82 @@ int amav_frames_prepare(int num_frames, int height, int width, const void *frame
                         size_t images_bytes, float *cropped_dev, size_t cropped_bytes, int32_t *boxes_dev,
                         size_t boxes_bytes, void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* PNG input (csrc/png_decode.hip, csrc/png_inflate_core.h): the reference's dataset stores its frames and masks as PNG
+ * (imgs_png/%05d.png, samurai_seg/%05d.png); they are inflated, unfiltered and converted on the device, bit for bit what
+ * PIL's Image.open(...).convert("RGB") / .convert("L") give.
+ *
+ * amav_inflate decodes num_streams DEFLATE streams (RFC 1951), one wave each.  Stream n lies at bytes [in_begin, in_end)
+ * of stream_dev [stream_bytes], unaligned; its output goes to out_dev [out_bytes] at out_begin, at most out_capacity
+ * bytes (unaligned as well; nothing is written outside [out_begin, out_begin + out_capacity), and both ranges are clamped
+ * to their buffers on the device, so no record makes the kernel read or write out of bounds).  wrapper 0: raw DEFLATE;
+ * 1: zlib (RFC 1950): CMF / FLG are checked (method 8, window <= 32 KiB, the mod-31 check), a preset dictionary (FDICT)
+ * is refused by status, and the 4 Adler-32 bytes after the last block are neither read nor VERIFIED.  Bytes after the
+ * final block are ignored.  produced_dev: int64 [N], bytes written; status_dev: int32 [N], written by the call:
+ *   AMAV_PNG_STATUS_INFLATE  a reserved block type (3); a stored block whose LEN is not ~NLEN; HLIT above 286 or HDIST
+ *                            above 30; over-subscribed code lengths (an incomplete set is accepted, its unused codes are
+ *                            "not in the set"); a repeat code 16 with nothing before it, or a repeat that runs past
+ *                            HLIT + HDIST (it may cross from one into the other); a code not in the set; literal/length
+ *                            symbol 286 / 287 or distance symbol 30 / 31; a distance that reaches before the start of
+ *                            the output; input that ends before the final block's end-of-block (or inside a stored
+ *                            block); a bad zlib header or FDICT.  Decoding stops there; produced = the bytes so far.
+ *   AMAV_PNG_STATUS_SIZE     the stream would produce more than out_capacity bytes: decoding stops before the symbol
+ *                            that would pass it.
+ * workspace: amav_inflate_workspace_bytes (0 = rejected count; one 256-byte granule, the kernel keeps its state in LDS).
+ * This entry point stands on its own so that the entropy stage can be held to an independent decoder on any stream.
+ *
+ * amav_png_decode decodes num_frames frames of one height and width; colour type and bit depth are per frame
+ * (amav_png_frame, records_dev: back to back, 8-byte aligned).  The host has joined a frame's IDAT payloads into one zlib
+ * stream at [zlib_begin, zlib_end) of stream_dev and put its PLTE bytes (3 x palette_entries) at palette_at.
+ *   inflate   into workspace, H x (1 + rowbytes) bytes per frame, rowbytes = ceil(W x channels x depth / 8), channels
+ *             1, 3, 1, 2, 4 for colour types 0, 2, 3, 4, 6; the workspace is sized for 4 bytes per pixel
+ *             (amav_png_decode_workspace_bytes; 0 = rejected sizes).  AMAV_PNG_STATUS_INFLATE as above;
+ *             AMAV_PNG_STATUS_SIZE also when the stream ends with fewer bytes than the frame needs.
+ *   unfilter  per row by its filter byte, on bytes, with bpp = max(1, channels x depth / 8): 0 None; 1 Sub, + the byte bpp
+ *             to the left; 2 Up, + the byte above; 3 Average, + floor((left + above) / 2); 4 Paeth, + whichever of left,
+ *             above, above-left is nearest to left + above - above-left (ties in that order); all mod 256, bytes outside
+ *             the image are 0.  A filter byte above 4 sets AMAV_PNG_STATUS_FILTER and the row is taken as filter 0.
+ *   convert   pixels of fewer than 8 bits are unpacked after the filter, most significant bits first.  AMAV_PNG_RGB:
+ *             colour type 2 as it is; 6: alpha dropped; 0 / 4: R = G = B = grey, a grey of depth d < 8 scaled by
+ *             255 / (2^d - 1); 3: the PLTE entry.  AMAV_PNG_L: 0 / 4: grey; 2 / 6 / 3:
+ *             (19595 R + 38470 G + 7471 B + 0x8000) >> 16.  tRNS, gAMA and the like never reach the device.  A palette
+ *             index at or beyond palette_entries is (0, 0, 0) and is not flagged.  absent != 0: no stream; the frame is
+ *             all 255 (a missing mask file).  A record whose colour type / depth pair the standard does not allow, or
+ *             depth 16, is flagged INFLATE | SIZE and not decoded.
+ *   out_dev   AMAV_JPEG_HWC_U8: uint8 [F,H,W,3] (RGB) / [F,H,W] (L); AMAV_JPEG_CHW_F32: fp32 [F,3,H,W] / [F,1,H,W] holding
+ *             exactly uint8 / 255.0f.
+ * A frame flagged INFLATE or SIZE is not unfiltered and its pixels are 0; a frame flagged FILTER alone is decoded with
+ * filter 0 on the offending rows.  Either way only that frame's output is written; the other frames are not affected.  Two launches, no allocation, no memset, no float atomics, no host synchronisation; the same bytes on every
+ * run.  Interlaced and 16-bit files are not decoded (png.parse_png refuses them).
+ * Refused with an error code before any launch: amav_inflate: num_streams outside 1..65535, a NULL pointer, a negative
+ * stream_bytes or out_bytes, misaligned records, produced (8) or status (4), a NULL, misaligned (16) or short workspace
+ * (AMAV_ERR_WORKSPACE).  amav_png_decode: F outside 1..65535, H or W outside 1..16384, an unknown mode or layout, NULL
+ * stream, records, status or out, a negative stream_bytes, misaligned records (8), status (4) or fp32 out (4), and an
+ * output buffer or workspace that is too small, NULL or not 16-byte aligned (AMAV_ERR_WORKSPACE). */
+#define AMAV_PNG_RGB 0
+#define AMAV_PNG_L 1
+#define AMAV_PNG_STATUS_INFLATE 1
+#define AMAV_PNG_STATUS_SIZE 2
+#define AMAV_PNG_STATUS_FILTER 4
+typedef struct amav_inflate_stream {
+    int64_t in_begin, in_end;        /* bytes of stream_dev */
+    int64_t out_begin, out_capacity; /* bytes of out_dev */
+    int32_t wrapper;                 /* 0 raw, 1 zlib */
+    int32_t reserved;
+} amav_inflate_stream;
+typedef struct amav_png_frame {
+    int64_t zlib_begin, zlib_end; /* bytes of stream_dev: the frame's IDAT payloads, joined */
+    int64_t palette_at;           /* byte of stream_dev where the PLTE entries lie (colour type 3) */
+    int32_t color_type, bit_depth, palette_entries, absent;
+} amav_png_frame;
+size_t amav_inflate_workspace_bytes(int num_streams);
+int amav_inflate(int num_streams, const uint8_t *stream_dev, int64_t stream_bytes, const void *records_dev, uint8_t *out_dev,
+                 int64_t out_bytes, int64_t *produced_dev, int32_t *status_dev, void *workspace_dev, size_t workspace_bytes,
+                 void *stream);
+size_t amav_png_decode_workspace_bytes(int num_frames, int height, int width);
+int amav_png_decode(int num_frames, int height, int width, const uint8_t *stream_dev, int64_t stream_bytes,
+                    const void *records_dev, int mode, int layout, void *out_dev, size_t out_bytes, int32_t *status_dev,
+                    void *workspace_dev, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
