@@ -14,7 +14,11 @@
 //   amav_points_project  nearest-point-per-pixel z-buffer over discs of `radius_px`, then every point that is the
 //                     nearest one somewhere takes the feature of the LAST such pixel in (y, x) order (what a sequential
 //                     index_put does), all other points get zeros.
+//   amav_points_project_grid  the same selection, but the features are RGB [B,3,H,W] plus a channels-last grid
+//                     [B,Gh,Gw,Cg] that the reference resizes bilinearly to the image first: the resize is evaluated at
+//                     the claimed pixel only (grid_bilinear.h), so the image-sized feature tensor never exists.
 #include "amav_common.h"
+#include "grid_bilinear.h"
 
 namespace amav {
 namespace splat {
@@ -120,6 +124,41 @@ __global__ __launch_bounds__(256) void project_fetch_kernel(int N, int C, int H,
     for (int c = lane; c < C; c += 64) o[c] = px >= 0 ? f[(size_t)c * H * W] : 0.0f;
 }
 
+// pass 3 of amav_points_project_grid: one wave per point, lanes along the 3 + Cg output channels.  Channels 0..2 copy
+// rgb [B,3,H,W] at the claimed pixel, the others evaluate the bilinear resize of grid [B,Gh,Gw,Cg] there: the four node
+// rows are contiguous in the channel, so every load is one coalesced row.
+__global__ __launch_bounds__(256) void project_grid_fetch_kernel(int N, int H, int W, int Gh, int Gw, int Cg,
+                                                                 const float *__restrict__ rgb,
+                                                                 const float *__restrict__ grid,
+                                                                 const int *__restrict__ pixel_of,
+                                                                 float *__restrict__ out) {
+#pragma clang fp contract(off)  // the value's operations in source order (include/amav.h states it)
+    const int b = blockIdx.y;
+    const int n = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (n >= N) return;
+    const int px = pixel_of[(size_t)b * N + n];
+    const int C = 3 + Cg;
+    float *o = out + ((size_t)b * N + n) * C;
+    if (px < 0) {
+        for (int c = lane; c < C; c += 64) o[c] = 0.0f;
+        return;
+    }
+    const int y = px / W, x = px - y * W;
+    const GridAxis ay = grid_axis(y, H, Gh), ax = grid_axis(x, W, Gw);
+    const float *gb = grid + (size_t)b * Gh * Gw * Cg;
+    const float *g00 = gb + ((size_t)ay.i0 * Gw + ax.i0) * Cg, *g01 = gb + ((size_t)ay.i0 * Gw + ax.i1) * Cg;
+    const float *g10 = gb + ((size_t)ay.i1 * Gw + ax.i0) * Cg, *g11 = gb + ((size_t)ay.i1 * Gw + ax.i1) * Cg;
+    const float *rb = rgb + (size_t)b * 3 * H * W + px;
+    for (int c = lane; c < C; c += 64) {
+        if (c < 3) {
+            o[c] = rb[(size_t)c * H * W];
+        } else {
+            const int k = c - 3;
+            o[c] = ay.h * (ax.h * g00[k] + ax.l * g01[k]) + ay.l * (ax.h * g10[k] + ax.l * g11[k]);
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void fill_u64_kernel(size_t n, unsigned long long v, unsigned long long *p) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;
@@ -127,6 +166,22 @@ __global__ __launch_bounds__(256) void fill_u64_kernel(size_t n, unsigned long l
 __global__ __launch_bounds__(256) void fill_i32_kernel(size_t n, int v, int *p) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;
+}
+
+// passes 1 and 2 into a workspace of amav_points_project_workspace_bytes: z-buffer keys first, then pixel_of (returned)
+static int *select_pixels(int B, int N, int H, int W, const float *points, const float *w2c, const float *intrinsics,
+                          float radius_px, void *workspace, hipStream_t stream) {
+    Carver c(workspace);
+    unsigned long long *zbuf = c.take<unsigned long long>((size_t)B * H * W);
+    int *pixel_of = c.take<int>((size_t)B * N);
+    const size_t npix = (size_t)B * H * W, npts = (size_t)B * N;
+    fill_u64_kernel<<<(unsigned)((npix + 255) / 256), 256, 0, stream>>>(npix, ~0ull, zbuf);
+    fill_i32_kernel<<<(unsigned)((npts + 255) / 256), 256, 0, stream>>>(npts, -1, pixel_of);
+    project_zbuffer_kernel<<<dim3((unsigned)((N + 255) / 256), (unsigned)B), 256, 0, stream>>>(N, H, W, points, w2c,
+                                                                                              intrinsics, radius_px, zbuf);
+    project_claim_kernel<<<dim3((unsigned)(((size_t)H * W + 255) / 256), (unsigned)B), 256, 0, stream>>>(N, H, W, zbuf,
+                                                                                                         pixel_of);
+    return pixel_of;
 }
 
 }  // namespace splat
@@ -178,17 +233,28 @@ extern "C" int amav_points_project(int B, int N, int C, int H, int W, const floa
     if (workspace_bytes < need)
         return fail(AMAV_ERR_WORKSPACE, "amav_points_project: workspace %zu < required %zu", workspace_bytes, need);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    Carver c(workspace);
-    unsigned long long *zbuf = c.take<unsigned long long>((size_t)B * H * W);
-    int *pixel_of = c.take<int>((size_t)B * N);
-    const size_t npix = (size_t)B * H * W, npts = (size_t)B * N;
-    fill_u64_kernel<<<(unsigned)((npix + 255) / 256), 256, 0, stream>>>(npix, ~0ull, zbuf);
-    fill_i32_kernel<<<(unsigned)((npts + 255) / 256), 256, 0, stream>>>(npts, -1, pixel_of);
-    project_zbuffer_kernel<<<dim3((unsigned)((N + 255) / 256), (unsigned)B), 256, 0, stream>>>(N, H, W, points, w2c,
-                                                                                              intrinsics, radius_px, zbuf);
-    project_claim_kernel<<<dim3((unsigned)(((size_t)H * W + 255) / 256), (unsigned)B), 256, 0, stream>>>(N, H, W, zbuf,
-                                                                                                         pixel_of);
+    const int *pixel_of = select_pixels(B, N, H, W, points, w2c, intrinsics, radius_px, workspace, stream);
     project_fetch_kernel<<<dim3((unsigned)((N + 3) / 4), (unsigned)B), 256, 0, stream>>>(N, C, H, W, features, pixel_of,
                                                                                         out);
     return check_launch("amav_points_project");
+}
+
+extern "C" int amav_points_project_grid(int B, int N, int H, int W, int Gh, int Gw, int Cg, const float *points,
+                                        const float *w2c, const float *intrinsics, const float *rgb, const float *grid,
+                                        float radius_px, float *out, void *workspace, size_t workspace_bytes,
+                                        void *stream_) {
+    AMAV_REQUIRE(B > 0 && N > 0 && H > 0 && W > 0 && Gh > 0 && Gw > 0 && Cg > 0 && B <= 65535 && radius_px > 0.0f,
+                 "amav_points_project_grid: bad sizes");
+    AMAV_REQUIRE((long long)H * W < (1ll << 31), "amav_points_project_grid: image too large");
+    AMAV_REQUIRE((long long)Gh * Gw < (1ll << 31), "amav_points_project_grid: grid too large");
+    AMAV_REQUIRE(points && w2c && intrinsics && rgb && grid && out && workspace,
+                 "amav_points_project_grid: NULL pointer");
+    const size_t need = amav_points_project_workspace_bytes(B, N, H, W);
+    if (workspace_bytes < need)
+        return fail(AMAV_ERR_WORKSPACE, "amav_points_project_grid: workspace %zu < required %zu", workspace_bytes, need);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const int *pixel_of = select_pixels(B, N, H, W, points, w2c, intrinsics, radius_px, workspace, stream);
+    project_grid_fetch_kernel<<<dim3((unsigned)((N + 3) / 4), (unsigned)B), 256, 0, stream>>>(N, H, W, Gh, Gw, Cg, rgb,
+                                                                                             grid, pixel_of, out);
+    return check_launch("amav_points_project_grid");
 }

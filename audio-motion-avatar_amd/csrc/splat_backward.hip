@@ -12,10 +12,18 @@
 //   amav_points_project_backward  points_projection's index_put, w.r.t. the features: every pixel a point wins takes
 //                            that point's output row, dfeat[c][y][x] = dout[winner(y, x)][c], 0 where no point won
 //                            (the forward keeps only the last won pixel, but index_put's backward credits them all)
+//   amav_points_project_grid_backward  the same credit carried on through the bilinear resize into the grid, without
+//                            the image-sized gradient: dgrid[j][i][c] = sum over the won pixels that have node (j, i) as
+//                            a corner of weight * dout[winner][3 + c], in ascending pixel index, corners 00 01 10 11
 #include "amav_common.h"
+#include "grid_bilinear.h"
 
 namespace amav {
 namespace splat_bwd {
+
+using splat::grid_axis;
+using splat::grid_axis_first_pixel;
+using splat::GridAxis;
 
 // pool_local, pass 1: one block per (cell, plane, b); thread = channel (strided).  Walks the cell's run of `order` once:
 // arg = first point of the maximum (strict >), S = sum of dout over the run in ascending point id.  Tables [B,3,cells,C].
@@ -90,8 +98,9 @@ __global__ __launch_bounds__(256) void cell_mean_backward_kernel(int N, int C, i
     }
 }
 
-// points_projection: one thread per (pixel, b): the pixel's winner is the low 32 bits of the forward's z-buffer key
-__global__ __launch_bounds__(256) void project_backward_kernel(int N, int C, int H, int W,
+// points_projection: one thread per (pixel, b): the pixel's winner is the low 32 bits of the forward's z-buffer key.
+// dout rows are `row` floats apart, of which the first C are taken (row > C: the RGB columns of the grid form's rows).
+__global__ __launch_bounds__(256) void project_backward_kernel(int N, int C, int row, int H, int W,
                                                                const unsigned long long *__restrict__ zbuf,
                                                                const float *__restrict__ dout, float *__restrict__ dfeat) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
@@ -100,9 +109,68 @@ __global__ __launch_bounds__(256) void project_backward_kernel(int N, int C, int
     const unsigned long long key = zbuf[b * HW + i];
     const unsigned id = (unsigned)key;
     const bool won = key != ~0ull && id < (unsigned)N;
-    const float *g = dout + ((size_t)b * N + (won ? id : 0)) * C;
+    const float *g = dout + ((size_t)b * N + (won ? id : 0)) * row;
     float *o = dfeat + (size_t)b * C * HW + i;
     for (int c = 0; c < C; ++c) o[c * HW] = won ? g[c] : 0.0f;
+}
+
+// amav_points_project_grid, w.r.t. the grid: a gather, one wave per (node, b), lanes along channels (two accumulators
+// per lane: 128 channels per sweep).  The node (j, i) is a corner of the pixels whose i0 is j - 1 or j (rows) and i - 1
+// or i (columns): a rectangle, found by bisection over grid_axis itself.  The wave walks the rectangle in row-major
+// order (= ascending pixel index y * W + x) 64 pixels at a time: every lane reads one z-buffer key, a ballot finds the
+// won pixels, and the set bits are taken in ascending order; within a pixel the corners 00, 01, 10, 11 that are this
+// node each add one term w * g (in the clamped half-cells i0 == i1: two separate terms).
+__global__ __launch_bounds__(256) void project_grid_backward_kernel(int N, int H, int W, int Gh, int Gw, int Cg,
+                                                                    const unsigned long long *__restrict__ zbuf,
+                                                                    const float *__restrict__ dout,
+                                                                    float *__restrict__ dgrid) {
+#pragma clang fp contract(off)  // w = wy * wx, then acc += w * g: three roundings per term, in that order
+    const int b = blockIdx.y;
+    const int node = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (node >= Gh * Gw) return;
+    const int j = node / Gw, i = node - j * Gw;
+    const int ylo = grid_axis_first_pixel(j - 1, H, Gh), yhi = grid_axis_first_pixel(j + 1, H, Gh);
+    const int xlo = grid_axis_first_pixel(i - 1, W, Gw), xhi = grid_axis_first_pixel(i + 1, W, Gw);
+    const int fw = xhi - xlo, count = fw * (yhi - ylo);  // at most H * W < 2^31
+    const unsigned long long *zb = zbuf + (size_t)b * H * W;
+    const int row = 3 + Cg;
+    const float *gb = dout + (size_t)b * N * row + 3;
+    float *o = dgrid + (((size_t)b * Gh + j) * Gw + i) * Cg;
+    for (int c0 = 0; c0 < Cg; c0 += 128) {
+        const int ca = c0 + lane, cb = c0 + 64 + lane;
+        float acc_a = 0.0f, acc_b = 0.0f;
+        for (int k0 = 0; k0 < count; k0 += 64) {
+            const int k = k0 + lane;
+            unsigned id = 0;
+            bool won = false;
+            if (k < count) {
+                const int y = ylo + k / fw, x = xlo + k % fw;
+                const unsigned long long key = zb[(size_t)y * W + x];
+                id = (unsigned)key;
+                won = key != ~0ull && id < (unsigned)N;
+            }
+            unsigned long long mask = __ballot(won);
+            while (mask) {
+                const int bit = __ffsll((long long)mask) - 1;
+                mask &= mask - 1;
+                const int kk = k0 + bit;
+                const int y = ylo + kk / fw, x = xlo + kk % fw;
+                const unsigned n = (unsigned)__shfl((int)id, bit);
+                const GridAxis ay = grid_axis(y, H, Gh), ax = grid_axis(x, W, Gw);
+                const float *g = gb + (size_t)n * row;
+                const float ga = ca < Cg ? g[ca] : 0.0f, gc = cb < Cg ? g[cb] : 0.0f;
+                for (int corner = 0; corner < 4; ++corner) {
+                    const int cy = corner >> 1 ? ay.i1 : ay.i0, cx = corner & 1 ? ax.i1 : ax.i0;
+                    if (cy != j || cx != i) continue;
+                    const float w = (corner >> 1 ? ay.l : ay.h) * (corner & 1 ? ax.l : ax.h);
+                    acc_a = acc_a + w * ga;
+                    acc_b = acc_b + w * gc;
+                }
+            }
+        }
+        if (ca < Cg) o[ca] = acc_a;
+        if (cb < Cg) o[cb] = acc_b;
+    }
 }
 
 inline unsigned channel_threads(int C) { return (unsigned)min(256, (C + kWave - 1) / kWave * kWave); }
@@ -163,6 +231,28 @@ extern "C" int amav_points_project_backward(int B, int N, int C, int H, int W, c
     // the z-buffer is the first carve of amav_points_project's workspace (splat.hip)
     const unsigned long long *zbuf = static_cast<const unsigned long long *>(workspace);
     project_backward_kernel<<<dim3((unsigned)(((size_t)H * W + 255) / 256), (unsigned)B), 256, 0,
-                              static_cast<hipStream_t>(stream)>>>(N, C, H, W, zbuf, grad_out, grad_features);
+                              static_cast<hipStream_t>(stream)>>>(N, C, C, H, W, zbuf, grad_out, grad_features);
     return check_launch("amav_points_project_backward");
+}
+
+extern "C" int amav_points_project_grid_backward(int B, int N, int H, int W, int Gh, int Gw, int Cg,
+                                                 const float *grad_out, const void *workspace, size_t workspace_bytes,
+                                                 float *grad_grid, float *grad_rgb, void *stream_) {
+    AMAV_REQUIRE(B > 0 && N > 0 && H > 0 && W > 0 && Gh > 0 && Gw > 0 && Cg > 0 && B <= 65535,
+                 "amav_points_project_grid_backward: bad sizes");
+    AMAV_REQUIRE((long long)H * W < (1ll << 31), "amav_points_project_grid_backward: image too large");
+    AMAV_REQUIRE((long long)Gh * Gw < (1ll << 31), "amav_points_project_grid_backward: grid too large");
+    AMAV_REQUIRE(grad_out && grad_grid, "amav_points_project_grid_backward: NULL pointer");
+    const size_t need = amav_points_project_workspace_bytes(B, N, H, W);
+    if (!workspace || workspace_bytes < need)
+        return fail(AMAV_ERR_WORKSPACE, "amav_points_project_grid_backward: workspace %zu < required %zu",
+                    workspace ? workspace_bytes : 0, need);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const unsigned long long *zbuf = static_cast<const unsigned long long *>(workspace);  // the first carve (splat.hip)
+    project_grid_backward_kernel<<<dim3((unsigned)(((size_t)Gh * Gw + 3) / 4), (unsigned)B), 256, 0, stream>>>(
+        N, H, W, Gh, Gw, Cg, zbuf, grad_out, grad_grid);
+    if (grad_rgb)  // the first three columns of every winner's row, as amav_points_project_backward routes them
+        project_backward_kernel<<<dim3((unsigned)(((size_t)H * W + 255) / 256), (unsigned)B), 256, 0, stream>>>(
+            N, 3, 3 + Cg, H, W, zbuf, grad_out, grad_rgb);
+    return check_launch("amav_points_project_grid_backward");
 }

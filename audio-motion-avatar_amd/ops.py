@@ -1636,6 +1636,50 @@ def _points_project(points, w2c, intrinsics, features, radius_px):
     return out, ws
 
 
+def points_project_grid(points, w2c, intrinsics, rgb, grid, radius_px):
+    """points_project on torch.cat([rgb, bilinear resize of grid]) without that tensor: points [B,N,3], w2c [B,4,4],
+    intrinsics [B,3,3], rgb [B,3,H,W], grid [B,Gh,Gw,Cg] channels-last -> [B,N,3+Cg]; the resize is evaluated at the
+    claimed pixels only (include/amav.h, amav_points_project_grid)."""
+    return _points_project_grid(points, w2c, intrinsics, rgb, grid, radius_px)[0]
+
+
+def _points_project_grid(points, w2c, intrinsics, rgb, grid, radius_px):
+    """points_project_grid -> (out, workspace): the workspace holds the z-buffer the backward reads."""
+    points, w2c, intrinsics = _contig(points, "points"), _contig(w2c, "w2c"), _contig(intrinsics, "intrinsics")
+    rgb, grid = _contig(rgb, "rgb"), _contig(grid, "grid")
+    if points.dim() != 3 or rgb.dim() != 4 or grid.dim() != 4:
+        raise AmavError("points_project_grid: need points [B,N,3], rgb [B,3,H,W] and grid [B,Gh,Gw,Cg]")
+    B, N, _ = points.shape
+    H, W = rgb.shape[2:]
+    _, Gh, Gw, Cg = grid.shape
+    if (points.shape[2] != 3 or tuple(rgb.shape[:2]) != (B, 3) or grid.shape[0] != B or tuple(w2c.shape) != (B, 4, 4)
+            or tuple(intrinsics.shape) != (B, 3, 3)):
+        raise AmavError("points_project_grid: batch sizes / matrix shapes do not match")
+    ws = _scratch("amav_points_project_workspace_bytes", points.device, B, N, H, W, rejected=f"B={B} N={N} H={H} W={W}")
+    out = torch.empty(B, N, 3 + Cg, device=points.device)
+    _call("amav_points_project_grid", B, N, H, W, Gh, Gw, Cg, points.data_ptr(), w2c.data_ptr(), intrinsics.data_ptr(),
+          rgb.data_ptr(), grid.data_ptr(), float(radius_px), out.data_ptr(), ws.data_ptr(), ws.numel())
+    return out, ws
+
+
+def points_project_grid_backward(grad_out, workspace, grid_shape, height, width, want_rgb=False):
+    """Gradients of points_project_grid given grad_out [B,N,3+Cg] and the forward's workspace -> (grad_grid
+    [B,Gh,Gw,Cg], grad_rgb [B,3,H,W] or None without want_rgb): every pixel a point wins passes that point's gradient
+    row through its four bilinear weights into the grid, summed per node in a fixed order
+    (amav_points_project_grid_backward)."""
+    grad_out = _contig(grad_out, "grad_out")
+    B, N, C = grad_out.shape
+    Gh, Gw, Cg = (int(v) for v in tuple(grid_shape)[-3:])
+    if C != 3 + Cg or (len(grid_shape) == 4 and grid_shape[0] != B):
+        raise AmavError(f"points_project_grid_backward: grad_out {tuple(grad_out.shape)} does not match a grid of "
+                        f"{tuple(grid_shape)}")
+    grad_grid = torch.empty(B, Gh, Gw, Cg, device=grad_out.device)
+    grad_rgb = torch.empty(B, 3, int(height), int(width), device=grad_out.device) if want_rgb else None
+    _call("amav_points_project_grid_backward", B, N, int(height), int(width), Gh, Gw, Cg, grad_out.data_ptr(),
+          workspace.data_ptr(), workspace.numel(), grad_grid.data_ptr(), grad_rgb.data_ptr() if want_rgb else None)
+    return grad_grid, grad_rgb
+
+
 def cell_pool_max_backward(feat, cell_of, cells, segments, grad_out):
     """Gradient of cell_pool_max(feat, cell_of, cells, segments) w.r.t. feat, given grad_out [B,N,C]
     (amav_cell_max_backward): per plane, the cell's summed gradient goes to the one point that holds the maximum, the
@@ -1726,6 +1770,23 @@ class _PointsProject(torch.autograd.Function):
         return None, None, None, grad, None
 
 
+class _PointsProjectGrid(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points, w2c, intrinsics, rgb, grid, radius_px):
+        out, ws = _points_project_grid(points, w2c, intrinsics, rgb, grid, radius_px)
+        ctx.size, ctx.grid_shape, ctx.ws = tuple(rgb.shape[2:]), tuple(grid.shape), ws  # the z-buffer the backward reads
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        if not (ctx.needs_input_grad[3] or ctx.needs_input_grad[4]):
+            return None, None, None, None, None, None
+        grad_grid, grad_rgb = points_project_grid_backward(grad_out.float(), ctx.ws, ctx.grid_shape, *ctx.size,
+                                                           want_rgb=ctx.needs_input_grad[3])
+        return None, None, None, grad_rgb, grad_grid if ctx.needs_input_grad[4] else None, None
+
+
 def _segments(cell_of, cells, segments):
     order, seg = segments if segments is not None else cell_segments(cell_of, cells)
     return _contig(order, "order", torch.int32), _contig(seg, "seg", torch.int32)
@@ -1750,6 +1811,13 @@ def points_project_differentiable(points, w2c, intrinsics, features, radius_px):
     (amav_points_project_backward: index_put's backward, every pixel a point wins takes that point's gradient row).
     points, w2c and intrinsics get no gradient: the selection is piecewise constant."""
     return _PointsProject.apply(points, w2c, intrinsics, features, float(radius_px))
+
+
+def points_project_grid_differentiable(points, w2c, intrinsics, rgb, grid, radius_px):
+    """points_project_grid as a torch.autograd.Function: the same values bit for bit, differentiable in grid and, when
+    it requires grad, in rgb (amav_points_project_grid_backward: the gradient of the dense path, index_put's credit to
+    every won pixel carried through the bilinear weights).  points, w2c and intrinsics get no gradient."""
+    return _PointsProjectGrid.apply(points, w2c, intrinsics, rgb, grid, float(radius_px))
 
 
 # ------------------------------------------------------------------------------------------------------ attention

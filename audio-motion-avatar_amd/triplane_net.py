@@ -14,7 +14,8 @@ correctness and determinism, on library kernels except where the reference's own
     points stably sorted by cell (csrc/splat.hip), with HIP backwards for stage-1 training (csrc/splat_backward.hip);
   * `points_projection` (pytorch3d point rasterizer + an index_put with duplicate indices: which pixel a point
     receives is undefined) -> z-buffer kernel with a fixed rule: the last pixel in (y, x) order that the point wins
-    (what a sequential index_put does);
+    (what a sequential index_put does); with AMAV_STAGE1_SAMPLE=grid the image features are sampled from the 64 x 64
+    token grid at those pixels only (ops.points_project_grid), without the [B*T,128,H,W] tensor of `ImageFeature`;
   * cross-attention to the 4096 image tokens and self-attention -> the fp16 x 2 MFMA kernels of csrc/attention.hip,
     forward and backward (transformer.py; AMAV_CROSS_ATTN=library keeps the library's fused attention for the former);
   * with cfg.upsample_triplane -- what the reference runs: renderer.yaml's `upsample_triplane: true` overrides
@@ -90,6 +91,13 @@ class ImageFeature(nn.Module):
         super().__init__()
         self.feature_reducer = nn.Linear(image_feature_dim, 128 - 3)
 
+    def reduce(self, feature):
+        """feature [B,Nv,Nt,C] -> the reduced token grid [B*Nv, side, side, 125], channels-last as the Linear writes it
+        (no permute, no resize): what ops.points_project_grid samples under the vertices (GridImageFeatures)."""
+        B, Nv, Nt, C = feature.shape
+        side = int(round(Nt ** 0.5))
+        return self.feature_reducer(feature.reshape(B * Nv * Nt, C)).reshape(B * Nv, side, side, -1)
+
     def forward(self, rgb, feature):
         B, Nv, Nt, C = feature.shape
         H, W = rgb.shape[-2:]
@@ -97,6 +105,15 @@ class ImageFeature(nn.Module):
         f = self.feature_reducer(feature.reshape(B * Nv * Nt, C)).reshape(B * Nv, side, side, -1).permute(0, 3, 1, 2)
         f = F.interpolate(f.contiguous(), size=(H, W), mode="bilinear", align_corners=False)
         return torch.cat([rgb.reshape(B * Nv, *rgb.shape[2:]), f], dim=1).reshape(B, Nv, -1, H, W)
+
+
+class GridImageFeatures:
+    """The image features of ImageFeature.forward before the resize: rgb [B,T,3,H,W] and the reduced token grid
+    [B*T,Gh,Gw,125] (ImageFeature.reduce).  SMPLXTriplaneEncoder.forward takes it in place of the dense
+    [B,T,128,H,W] tensor and samples the grid at the projected vertices' pixels only."""
+
+    def __init__(self, rgb, grid):
+        self.rgb, self.grid = rgb, grid
 
 
 class ConvNeXtBlock(nn.Module):
@@ -299,7 +316,11 @@ class SMPLXTriplaneEncoder(nn.Module):
         autograd Functions (ops.*_differentiable: the same values bit for bit, csrc/splat_backward.hip), so the point
         network, vertex_emb and the image features (with sample_feature) receive gradients; with predicted SMPL-X
         parameters the vertices carry them on to the predictor through BodyModel's LBS backward.  Neither the cell
-        indices nor the projection's pixel selection carry a gradient."""
+        indices nor the projection's pixel selection carry a gradient.
+
+        img: the dense image features [B,T,128,H,W] of ImageFeature.forward, or a GridImageFeatures (RGB + the reduced
+        token grid), from which ops.points_project_grid samples the same 128 channels at the claimed pixels without the
+        image-sized tensor or its gradient."""
         B, T, S, C = img_tokens.shape
         pred_smpl_params = smpl_tokens = None
         if self.cfg.predict_smplx_params:
@@ -307,18 +328,25 @@ class SMPLXTriplaneEncoder(nn.Module):
         smpl_params = smpl_params_gt if smpl_params_gt is not None else pred_smpl_params
         if smpl_params is None:
             raise AmavError("SMPLXTriplaneEncoder: no SMPL-X parameters (predict_smplx_params off, no smpl_params_gt)")
-        grad = self._wants_grad(img_tokens, img, smpl_params=smpl_params)
+        from_grid = isinstance(img, GridImageFeatures)
+        grad = self._wants_grad(img_tokens, *((img.rgb, img.grid) if from_grid else (img,)), smpl_params=smpl_params)
         project = ops.points_project_differentiable if grad else ops.points_project
         pool = ops.cell_pool_max_differentiable if grad else ops.cell_pool_max
         splat = ops.cell_splat_mean_differentiable if grad else ops.cell_splat_mean
         verts = self.get_smplx_verts(smpl_params)                                    # [BT, N, 3]
         verts_emb = self.vertex_emb.weight.unsqueeze(0).expand(verts.shape[0], -1, -1)
         if self.cfg.sample_feature:                                                  # :139-157
-            Himg, Wimg = img.shape[-2:]
+            rgb = img.rgb if from_grid else img
+            Himg, Wimg = rgb.shape[-2:]
             pts = verts + smpl_params["transl"].reshape(B * T, 1, 3)
-            sampled = project(pts.contiguous(), cam_params["extrinsic"].reshape(B * T, 4, 4).float(),
-                              cam_params["intrinsic"].reshape(B * T, 3, 3).float(),
-                              img.reshape(B * T, *img.shape[2:]).float(), POINT_RADIUS_NDC * min(Himg, Wimg) / 2.0)
+            camera = (pts.contiguous(), cam_params["extrinsic"].reshape(B * T, 4, 4).float(),
+                      cam_params["intrinsic"].reshape(B * T, 3, 3).float())
+            radius_px = POINT_RADIUS_NDC * min(Himg, Wimg) / 2.0
+            if from_grid:  # channels as torch.cat([rgb, feature]): the resize is evaluated under the vertices only
+                project = ops.points_project_grid_differentiable if grad else ops.points_project_grid
+                sampled = project(*camera, rgb.reshape(B * T, *rgb.shape[2:]).float(), img.grid.float(), radius_px)
+            else:
+                sampled = project(*camera, img.reshape(B * T, *img.shape[2:]).float(), radius_px)
             verts_feat = torch.cat([verts_emb, sampled], dim=-1)
         else:
             verts_feat = verts_emb
@@ -370,6 +398,9 @@ class FeatureFusionNetwork(nn.Module):
         return tokens.reshape(B, T, *tokens.shape[1:]), smpl_out.reshape(B, T, *smpl_out.shape[1:])
 
 
+STAGE1_SAMPLE_DEFAULT = "dense"  # `grid` becomes the default with measured numbers (tools/bench_stage1_sample.py)
+
+
 class TriplaneGaussianAvatar(nn.Module):
     """lightning_model_wrapper.py:25-53.  `cfg`: the flattened model config (config.RendererConfig + the stage-1
     fields below, or any object with those attributes).  The Sapiens encoder is external: pass its tokens."""
@@ -387,7 +418,15 @@ class TriplaneGaussianAvatar(nn.Module):
 
     def forward(self, img, smpl_params_gt, cam_params, image_tokens=None):
         """img [B,T,3,H,W], smpl_params_gt dict of [B,T,...] (or None), cam_params dict -> the reference's 7-tuple
-        (rendered_images, gaussians, fused_triplane_tokens, image_tokens, pred_smpl_1, pred_smpl_2, smpl_tokens)."""
+        (rendered_images, gaussians, fused_triplane_tokens, image_tokens, pred_smpl_1, pred_smpl_2, smpl_tokens).
+
+        AMAV_STAGE1_SAMPLE, read per call: `dense` (the default) builds the reference's [B,T,128,H,W] image features
+        (ImageFeature.forward) for the encoder to look up; `grid` hands it RGB and the reduced token grid
+        (GridImageFeatures) and never evaluates ImageFeature.forward -- with cfg.sample_feature off it reduces and
+        samples nothing at all."""
+        mode = os.environ.get("AMAV_STAGE1_SAMPLE", STAGE1_SAMPLE_DEFAULT)
+        if mode not in ("dense", "grid"):
+            raise AmavError(f"AMAV_STAGE1_SAMPLE={mode!r}: expected `dense` or `grid`")
         B, T = img.shape[:2]
         if image_tokens is None:
             if self.sapiens_encoder is None:
@@ -396,7 +435,12 @@ class TriplaneGaussianAvatar(nn.Module):
                                 "[B,T,4096,image_feature_dim]")
             image_tokens = self.sapiens_encoder(img.reshape(B * T, *img.shape[2:]))
         image_tokens = image_tokens.reshape(B, T, -1, image_tokens.shape[-1])
-        image_features = self.image_feature(img, image_tokens)
+        if mode == "dense":
+            image_features = self.image_feature(img, image_tokens)
+        elif self.cfg.sample_feature:
+            image_features = GridImageFeatures(img, self.image_feature.reduce(image_tokens))
+        else:
+            image_features = None
         smplx_triplane, smpl_tokens, pred_smpl_1 = self.smplx_triplane_encoder(cam_params, image_tokens, smpl_params_gt,
                                                                               image_features)
         fused_tokens, smpl_tokens = self.fusion_network(smplx_triplane, image_tokens, smpl_tokens)

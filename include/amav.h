@@ -666,6 +666,41 @@ int amav_points_project_backward(int batch, int num_points, int channels, int he
                                  const float *grad_out_dev, const void *forward_workspace, size_t workspace_bytes,
                                  float *grad_features_dev, void *stream);
 
+/* Stage-1 image features sampled from the token grid.  ImageFeature resizes a [Gh,Gw,Cg] grid
+ * bilinearly to the image, concatenates RGB and lets amav_points_project look up one pixel per visible point; these two
+ * entry points evaluate the resize at those pixels only and gather the gradient straight back into the grid, so neither
+ * the [B,3+Cg,H,W] tensor nor its gradient exists.
+ * amav_points_project_grid: points, w2c, intrinsics, radius_px and the selection exactly as amav_points_project (the
+ *   same two kernels; the same workspace, amav_points_project_workspace_bytes: z-buffer keys first, then pixel_of);
+ *   rgb [B,3,H,W]; grid [B,Gh,Gw,Cg] channels-last (the layout of the reducing Linear's output) -> out [B,N,3+Cg].  For a
+ *   point that claims pixel (y, x): channels 0..2 = rgb[b,:,y,x] copied, channel 3 + c = the grid resized as
+ *   F.interpolate(mode="bilinear", align_corners=False) defines it, at (y, x).  A point that claims nothing: zeros.
+ *   Per axis (pixel i of `size`, G nodes), all in fp32, in this order, no contraction:
+ *     scale = (float)G / (float)size;  s = scale * ((float)i + 0.5f) - 0.5f;  s = s < 0 ? 0 : s;
+ *     i0 = min((int)s, G - 1);  i1 = i0 + (i0 < G - 1);  l = s - (float)i0;  h = 1 - l
+ *   value = hy * (hx * g00 + lx * g01) + ly * (hx * g10 + lx * g11), g_yx = grid[b, iy_y, ix_x, c].
+ * amav_points_project_grid_backward: given grad_out [B,N,3+Cg] and the forward's WORKSPACE, unchanged since that call,
+ *   grad_grid [B,Gh,Gw,Cg] (every element overwritten) and, unless grad_rgb is NULL, grad_rgb [B,3,H,W] (overwritten).
+ *   The gradient of the dense path: index_put's backward credits every pixel a point WINS (not only the claimed one), so
+ *     grad_grid[b,j,i,c] = sum over the pixels p whose z-buffer winner n is valid, and over those of p's corners 00, 01,
+ *                          10, 11 that are node (j, i), of w_corner(p) * grad_out[b,n,3+c]
+ *   with w_00 = hy * hx, w_01 = hy * lx, w_10 = ly * hx, w_11 = ly * lx (one fp32 product), each term one fp32 product
+ *   w * g added to the running fp32 sum, starting from 0, in ascending pixel index y * W + x and, within a pixel, corners
+ *   in the order 00, 01, 10, 11.  In the clamped first and last half-cell of an axis i0 == i1 and both weights reach the
+ *   same node as two separate terms.  A node no won pixel reaches (also: every node of a down-sampled axis that no
+ *   pixel maps to) is exactly 0.  grad_rgb[b,:,y,x] = grad_out[b,winner(y,x),0:3], 0 where no point won.  No float
+ *   atomics; the order depends on neither B nor the launch geometry: bitwise reproducible, and B frames equal B calls.
+ * Both refuse, before any launch: sizes <= 0, B > 65535, H * W >= 2^31, Gh * Gw >= 2^31 (AMAV_ERR_INVALID_ARG), NULL
+ * pointers (grad_rgb excepted), and a workspace that is NULL or smaller than amav_points_project_workspace_bytes
+ * (AMAV_ERR_WORKSPACE; the forward reports a NULL workspace as a NULL pointer, as amav_points_project does). */
+int amav_points_project_grid(int batch, int num_points, int height, int width, int grid_height, int grid_width,
+                             int grid_channels, const float *points_dev, const float *w2c_dev,
+                             const float *intrinsics_dev, const float *rgb_dev, const float *grid_dev, float radius_px,
+                             float *out_dev, void *workspace, size_t workspace_bytes, void *stream);
+int amav_points_project_grid_backward(int batch, int num_points, int height, int width, int grid_height, int grid_width,
+                                      int grid_channels, const float *grad_out_dev, const void *forward_workspace,
+                                      size_t workspace_bytes, float *grad_grid_dev, float *grad_rgb_dev, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Self-attention of the audio transformer (diffusers Attention -> F.scaled_dot_product_attention as reached from
  * src/models/transformers.py:329-336): softmax(Q K^T * scale) V, fp32 in/out, no mask.  q,k,v,out: [B, S, H*D] with
