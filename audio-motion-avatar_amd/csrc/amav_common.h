@@ -36,6 +36,8 @@ inline int check_launch(const char *what) {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+__device__ __forceinline__ long long clampll(long long v, long long lo, long long hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
 inline unsigned blocks_for(long long threads) { return (unsigned)((threads + 255) / 256); }  // of 256 threads
 
 template <typename... P>

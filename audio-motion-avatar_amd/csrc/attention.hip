@@ -22,6 +22,7 @@
 #include "amav_common.h"
 #include "split_bf16.h"
 #include "split_f16.h"
+#include "wave_ops.h"
 
 namespace amav {
 namespace attn {
@@ -574,18 +575,8 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float *__restrict__ q
         mk = absmax4(mk, *reinterpret_cast<const float4 *>(k + off));
         mv = absmax4(mv, *reinterpret_cast<const float4 *>(v + off));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        mq = fmaxf(mq, __shfl_xor(mq, o, 64)), mk = fmaxf(mk, __shfl_xor(mk, o, 64)), mv = fmaxf(mv, __shfl_xor(mv, o, 64));
-    }
-    __shared__ float wave_max[4][3];
-    if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6][0] = mq, wave_max[threadIdx.x >> 6][1] = mk, wave_max[threadIdx.x >> 6][2] = mv;
-    __syncthreads();
-    if (threadIdx.x < 3) {  // one atomic per block and tensor (same-address atomics serialise in L2: ~10 ns each);
-        const float m = fmaxf(fmaxf(wave_max[0][threadIdx.x], wave_max[1][threadIdx.x]),
-                              fmaxf(wave_max[2][threadIdx.x], wave_max[3][threadIdx.x]));
-        atomicMax(hdr + threadIdx.x, __float_as_uint(m));  // non-negative floats order like their bit patterns
-    }
+    const float m[3] = {mq, mk, mv};
+    block_absmax_publish(m, hdr);  // one atomic per block and tensor
 }
 
 // grid (key tiles of 64, H, B), 256 threads: as split_kv_kernel, two fp16 parts of K 2^ek and V 2^ev.  V^T rows store

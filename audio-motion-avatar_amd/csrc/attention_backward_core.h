@@ -77,6 +77,8 @@ __global__ __launch_bounds__(256) void delta_kernel(Rows rows) {
         const float4 g = *reinterpret_cast<const float4 *>(gp + 4 * d4);
         acc = (o.x * g.x + o.y * g.y) + (o.z * g.z + o.w * g.w);
     }
+    // written out, not group_sum<G> (wave_ops.h): with the call the compiler fuses one of the products above into an
+    // fma, which changes the low bits of delta and with them of every gradient
 #pragma unroll
     for (int o = G / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o, G);
     if (live && d4 == 0) *dst = acc;

@@ -19,6 +19,7 @@
 // (tile_pos: bits 2 and 3 of the row index swapped) and the A operand is one 16-byte read.
 #include "attention_dense_rows.h"
 #include "split_f16.h"
+#include "wave_ops.h"
 
 namespace amav {
 namespace attn_bwd_split {
@@ -82,28 +83,10 @@ __global__ __launch_bounds__(256) void prepass_kernel(DenseRows rows, unsigned *
         vv = sumsq4(vx);
         m[1] = absmax4(0.f, kx), m[2] = absmax4(0.f, vx);
     }
-#pragma unroll
-    for (int o = G / 2; o > 0; o >>= 1) {
-        acc += __shfl_xor(acc, o, G), gg += __shfl_xor(gg, o, G), vv += __shfl_xor(vv, o, G);
-    }
+    acc = group_sum<G>(acc), gg = group_sum<G>(gg), vv = group_sum<G>(vv);
     if (dst && d4 == 0) *dst = acc;
     m[4] = sqrtf(gg), m[5] = sqrtf(vv);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int x = 0; x < 6; ++x) m[x] = fmaxf(m[x], __shfl_xor(m[x], o, 64));
-    }
-    __shared__ float wave_max[4][6];
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int x = 0; x < 6; ++x) wave_max[threadIdx.x >> 6][x] = m[x];
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {  // one atomic per block and word; non-negative floats order like their bit patterns
-        const float w = fmaxf(fmaxf(wave_max[0][threadIdx.x], wave_max[1][threadIdx.x]),
-                              fmaxf(wave_max[2][threadIdx.x], wave_max[3][threadIdx.x]));
-        atomicMax(hdr + threadIdx.x, __float_as_uint(w));
-    }
+    block_absmax_publish(m, hdr);  // one atomic per block and word
 }
 
 // One thread's share of a 32-row tile: rows 2 pi and 2 pi + 1, 4 consecutive d at d4, scaled by `mul`, split, and

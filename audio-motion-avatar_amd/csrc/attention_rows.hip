@@ -4,8 +4,10 @@
 #include <cmath>
 
 #include "amav_common.h"
+#include "gelu.h"
 #include "split_bf16.h"
 #include "split_f16.h"
+#include "wave_ops.h"
 
 using namespace amav;
 
@@ -250,7 +252,6 @@ __global__ __launch_bounds__(256) void geglu_kernel(long long quads, int inner4,
         h = make_float4(h.x + bh.x, h.y + bh.y, h.z + bh.z, h.w + bh.w);
         g = make_float4(g.x + bg.x, g.y + bg.y, g.z + bg.z, g.w + bg.w);
     }
-    auto gelu = [](float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); };
     const float4 y = make_float4(h.x * gelu(g.x), h.y * gelu(g.y), h.z * gelu(g.z), h.w * gelu(g.w));
     if (out_split) {  // the fp16 x 2 activation operand of the output projection (split_operand_f16_kernel's layout)
         const float yv[4] = {y.x, y.y, y.z, y.w};
@@ -342,18 +343,14 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(long long rows, long
         h_out[row * kRow4 + c] = t;
         sum += (t.x + t.y) + (t.z + t.w);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-    const float mean = sum * (1.0f / (256.0f * kVec));
+    const float mean = wave_sum(sum) * (1.0f / (256.0f * kVec));
     float var = 0.f;
 #pragma unroll
     for (int v = 0; v < kVec; ++v) {
         const float dx = x[v].x - mean, dy = x[v].y - mean, dz = x[v].z - mean, dw = x[v].w - mean;
         var += (dx * dx + dy * dy) + (dz * dz + dw * dw);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) var += __shfl_xor(var, o, 64);
-    const float rstd = 1.0f / sqrtf(var * (1.0f / (256.0f * kVec)) + eps);
+    const float rstd = 1.0f / sqrtf(wave_sum(var) * (1.0f / (256.0f * kVec)) + eps);
 #pragma unroll
     for (int v = 0; v < kVec; ++v) {
         const int c = lane + 64 * v;

@@ -12,6 +12,7 @@
 #include <cmath>
 
 #include "amav_common.h"
+#include "wave_ops.h"
 
 namespace amav {
 namespace rows_bwd {
@@ -142,18 +143,14 @@ __global__ __launch_bounds__(256) void add_layernorm_backward_kernel(long long r
             up[v] = dh_out ? dh_out[at] : make_float4(0.f, 0.f, 0.f, 0.f);
             sum += (x[v].x + x[v].y) + (x[v].z + x[v].w);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-        const float mean = sum * kInv;
+        const float mean = wave_sum(sum) * kInv;
         float var = 0.f;
 #pragma unroll
         for (int v = 0; v < kVec; ++v) {
             const float dx = x[v].x - mean, dy = x[v].y - mean, dz = x[v].z - mean, dw_ = x[v].w - mean;
             var += (dx * dx + dy * dy) + (dz * dz + dw_ * dw_);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) var += __shfl_xor(var, o, 64);
-        const float rstd = 1.0f / sqrtf(var * kInv + eps);
+        const float rstd = 1.0f / sqrtf(wave_sum(var) * kInv + eps);
         if (!dnorm) {  // wave-uniform: the LayerNorm part is zero, dweight / dbias partials stay +0
 #pragma unroll
             for (int v = 0; v < kVec; ++v) dh[row * kRow4 + lane + 64 * v] = up[v];
@@ -172,12 +169,7 @@ __global__ __launch_bounds__(256) void add_layernorm_backward_kernel(long long r
                                 dw[v].w + dn[v].w * x[v].w);
             db[v] = add4(db[v], dn[v]);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            s1 += __shfl_xor(s1, o, 64);
-            s2 += __shfl_xor(s2, o, 64);
-        }
-        const float m1 = s1 * kInv, m2 = s2 * kInv;
+        const float m1 = wave_sum(s1) * kInv, m2 = wave_sum(s2) * kInv;
 #pragma unroll
         for (int v = 0; v < kVec; ++v) {
             dh[row * kRow4 + lane + 64 * v] =

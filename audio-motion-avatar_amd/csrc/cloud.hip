@@ -26,30 +26,17 @@
 #include <cmath>
 
 #include "amav_common.h"
+#include "gelu.h"
 #include "split_f16.h"
+#include "wave_ops.h"
 
 namespace amav {
 namespace cloud {
-
-
-
-__device__ __forceinline__ float gelu(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 
 // ---- voxelize -----------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void bounds_init_kernel(int clouds, int *__restrict__ bounds) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < clouds * 6) bounds[i] = (i % 6) < 3 ? INT_MAX : INT_MIN;
-}
-
-__device__ __forceinline__ int wave_min(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
 }
 
 __global__ __launch_bounds__(256) void bounds_kernel(long long n, const float *__restrict__ points,
@@ -290,15 +277,9 @@ using amav::kSplitHeader;
 __global__ __launch_bounds__(256) void absmax_kernel(const float4 *__restrict__ x4, long long n4, unsigned *__restrict__ out) {
     float m = 0.f;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-        const float4 v = x4[i];
-        m = fmaxf(m, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
+        m = absmax4(m, x4[i]);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    __shared__ float wm[4];
-    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicMax(out, __float_as_uint(fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]))));
+    block_absmax_publish(m, out);
 }
 
 // weights [taps][cin][cout] fp32 -> [tap][cout / 32][cin / 16][part][lane half hh][column c][8 k] fp16: the B fragment of
@@ -686,23 +667,18 @@ __global__ __launch_bounds__(256) void rows_norm_kernel(long long rows, const fl
     const long long row = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * (64 / G) + lane / G;
     const bool live = row < rows;
     const long long r = live ? row : rows - 1;
-    auto group_sum = [](float v) {
-#pragma unroll
-        for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        return v;
-    };
     auto normalise = [&](float4 (&t)[V], const float4 *w, const float4 *b) {
         float sum = 0.f;
 #pragma unroll
         for (int v = 0; v < V; ++v) sum += (t[v].x + t[v].y) + (t[v].z + t[v].w);
-        const float mean = group_sum(sum) * kInvC;
+        const float mean = group_sum<G>(sum) * kInvC;
         float var = 0.f;
 #pragma unroll
         for (int v = 0; v < V; ++v) {
             const float dx = t[v].x - mean, dy = t[v].y - mean, dz = t[v].z - mean, dw = t[v].w - mean;
             var += (dx * dx + dy * dy) + (dz * dz + dw * dw);
         }
-        const float rstd = 1.0f / sqrtf(group_sum(var) * kInvC + eps);
+        const float rstd = 1.0f / sqrtf(group_sum<G>(var) * kInvC + eps);
 #pragma unroll
         for (int v = 0; v < V; ++v) {
             const float4 wv = w[sub + G * v], bv = b[sub + G * v];

@@ -22,6 +22,7 @@
 #include <cmath>
 
 #include "attention_backward_core.h"
+#include "gelu.h"
 
 namespace amav {
 namespace cloud_bwd {
@@ -184,10 +185,6 @@ __global__ __launch_bounds__(256) void pa_borrow_add_kernel(long long threads, i
 }
 
 // ---- segment kernels --------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float gelu_grad(float z) {
-    return 0.5f * (1.0f + erff(z * 0.70710678118654752440f)) + z * 0.39894228040143267794f * expf(-0.5f * z * z);
-}
-
 // one wave per cluster, as cluster_max_kernel: recompute the maximum and the first member (in segment order) that attains
 // it, dz = dout * gelu'(max * scale + shift); dx = dz * scale on that member's row and zero on the others
 __global__ __launch_bounds__(256) void cluster_max_backward_kernel(long long clusters, int C4, const float4 *__restrict__ x,

@@ -28,6 +28,7 @@
 #include <cmath>
 
 #include "amav_common.h"
+#include "gelu.h"
 
 namespace amav {
 namespace cloud_norm {
@@ -42,9 +43,6 @@ __device__ __forceinline__ float4 shfl_xor4(const float4 &a, int o) {
 }
 __device__ __forceinline__ float4 shfl_down4(const float4 &a, int o) {
     return make_float4(__shfl_down(a.x, o, 64), __shfl_down(a.y, o, 64), __shfl_down(a.z, o, 64), __shfl_down(a.w, o, 64));
-}
-__device__ __forceinline__ float gelu_grad(float z) {
-    return 0.5f * (1.0f + erff(z * 0.70710678118654752440f)) + z * 0.39894228040143267794f * expf(-0.5f * z * z);
 }
 
 // The wave's place in the layout above.  `live` is false for lanes past the last channel quad of a column pass; they

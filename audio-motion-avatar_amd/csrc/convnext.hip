@@ -22,6 +22,10 @@
 #include <cmath>
 
 #include "amav_common.h"
+#include "gelu.h"
+#include "split_bf16.h"
+#include "split_f16.h"
+#include "wave_ops.h"
 
 namespace amav {
 namespace convnext {
@@ -34,19 +38,11 @@ constexpr int kTilePart = kTaps + 1;         // per-tile partials: 49 weight tap
 constexpr int kRowChunk = 16;                // rows per first-stage partial of LayerNorm's dweight / dbias
 constexpr int kLds = kHaloPix * 64 + 64 * kTaps;  // floats: halo | weights of the chunk (>= 4 * kTilePart * 64)
 
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
-// The splits of amav_split_operand (csrc/attention_rows.hip), part for part.
-__device__ __forceinline__ void split2(float x, _Float16 &a, _Float16 &b) {
+// The splits of amav_split_operand (csrc/attention_rows.hip), part for part: split3 of split_bf16.h, and split2 with
+// + 0 on the residual (not split_f16.h's split2).
+__device__ __forceinline__ void split2_plus0(float x, _Float16 &a, _Float16 &b) {
     a = (_Float16)x;
     b = (_Float16)(__builtin_fmaf((float)a, -1.0f, x) + 0.0f);  // + 0: an exactly-zero residual is +0 (geglu_kernel's note)
-}
-__device__ __forceinline__ void split3(float x, __bf16 &a, __bf16 &b, __bf16 &c) {
-    a = (__bf16)x;
-    const float r1 = x - (float)a;
-    b = (__bf16)r1;
-    c = (__bf16)(r1 - (float)b);
 }
 
 // One value of row `row`, column `col` of a [rows, K] result: fp32 (kind 0), or the activation operand of
@@ -62,7 +58,7 @@ __device__ __forceinline__ void store1(int kind, float *out, void *out_split, fl
         dst[0] = p3, dst[K] = p2, dst[2 * K] = p1, dst[3 * K] = p2, dst[4 * K] = p1, dst[5 * (long long)K] = p1;
     } else {
         _Float16 h1, h2;
-        split2(v * prescale, h1, h2);
+        split2_plus0(v * prescale, h1, h2);
         _Float16 *dst = static_cast<_Float16 *>(out_split) + row * 3 * K + col;
         dst[0] = h2, dst[K] = h1, dst[2 * K] = h1;
     }
@@ -92,7 +88,7 @@ __device__ __forceinline__ void store4(int kind, float *out, void *out_split, fl
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             _Float16 a, b;
-            split2(x[j] * prescale, a, b);
+            split2_plus0(x[j] * prescale, a, b);
             p1[j] = a, p2[j] = b;
         }
         _Float16 *dst = static_cast<_Float16 *>(out_split) + row * 3 * K + col;
@@ -100,12 +96,6 @@ __device__ __forceinline__ void store4(int kind, float *out, void *out_split, fl
         *reinterpret_cast<f16x4 *>(dst + K) = p1;
         *reinterpret_cast<f16x4 *>(dst + 2 * (long long)K) = p1;
     }
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // The 14 x 14 halo of the tile at (ty0, tx0) of one plane, channels [c0, c0 + 64), and the 64 x 49 depthwise weights of
@@ -373,8 +363,6 @@ __global__ __launch_bounds__(64) void sum_parts_kernel(long long count, int cols
     }
 }
 
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
-
 // out[row, :] = gelu(proj[row, :] + bias), one thread per column quad (geglu_kernel's expression for gelu)
 __global__ __launch_bounds__(256) void gelu_bias_kernel(long long quads, int inner4, const float4 *__restrict__ in,
                                                         long long in_row4, const float4 *__restrict__ bias,
@@ -390,7 +378,7 @@ __global__ __launch_bounds__(256) void gelu_bias_kernel(long long quads, int inn
         g = make_float4(g.x + b.x, g.y + b.y, g.z + b.z, g.w + b.w);
     }
     store4(kind, out, out_split, prescale, row, 4 * inner4, 4 * col,
-           make_float4(gelu_erf(g.x), gelu_erf(g.y), gelu_erf(g.z), gelu_erf(g.w)));
+           make_float4(gelu(g.x), gelu(g.y), gelu(g.z), gelu(g.w)));
 }
 
 // dproj = dout (Phi(g) + g phi(g)) with g = proj + bias recomputed (geglu_backward_kernel's expressions)

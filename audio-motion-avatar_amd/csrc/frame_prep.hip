@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "amav_common.h"
+#include "wave_ops.h"
 
 #pragma clang fp contract(off)
 
@@ -164,13 +165,7 @@ __global__ void __launch_bounds__(kBoxThreads) prep_box_kernel(PrepSrc s, int32_
             x_max = max(x_max, x0 + 31 - __clz(hit));
         }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        y_min = min(y_min, __shfl_xor(y_min, d));
-        y_max = max(y_max, __shfl_xor(y_max, d));
-        x_min = min(x_min, __shfl_xor(x_min, d));
-        x_max = max(x_max, __shfl_xor(x_max, d));
-    }
+    y_min = wave_min(y_min), y_max = wave_max(y_max), x_min = wave_min(x_min), x_max = wave_max(x_max);
     constexpr int kWaves = kBoxThreads / kWave;
     __shared__ int part[kWaves][4];
     const int wave = threadIdx.x >> 6;

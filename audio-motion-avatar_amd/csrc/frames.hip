@@ -5,6 +5,7 @@
 #include <cmath>
 
 #include "amav_common.h"
+#include "wave_ops.h"
 
 namespace amav {
 
@@ -109,8 +110,7 @@ __global__ __launch_bounds__(256) void frame_count_kernel(int T, const int *__re
     const int f = blockIdx.x;
     int c = 0;
     for (int t = threadIdx.x; t < T; t += 256) c += flags[(size_t)f * T + t];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    c = wave_sum(c);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) frame_counts[f] = part[0] + part[1] + part[2] + part[3];
@@ -126,8 +126,7 @@ __global__ __launch_bounds__(1024) void tile_scan_kernel(int F, int T, int cap, 
     const int f = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int mine = 0;
     for (int g = threadIdx.x; g < f; g += 1024) mine += frame_counts[g];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+    mine = wave_sum(mine);
     if (lane == 0) wave_tot[wave] = mine;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -140,12 +139,7 @@ __global__ __launch_bounds__(1024) void tile_scan_kernel(int F, int T, int cap, 
     for (int base = 0; base < T; base += 1024) {
         const int i = base + threadIdx.x;
         const int fl = i < T ? off[i] : 0;
-        int incl = fl;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int up = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += up;
-        }
+        const int incl = wave_inclusive_sum(fl, lane);
         __syncthreads();  // wave_tot / carry of the previous round have been read
         if (lane == 63) wave_tot[wave] = incl;
         __syncthreads();

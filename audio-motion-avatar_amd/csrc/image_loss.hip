@@ -219,7 +219,7 @@ __global__ __launch_bounds__(kWave) void finalize_kernel(int N, int tiles, const
         ssim_sum += p[2 * s + 1];
     }
 #pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) {
+    for (int off = kWave / 2; off > 0; off >>= 1) {  // wave_sum's order (wave_ops.h); two calls cost two more VGPRs
         l1_sum += __shfl_xor(l1_sum, off, kWave);
         ssim_sum += __shfl_xor(ssim_sum, off, kWave);
     }

@@ -19,6 +19,7 @@
 
 #include "amav_common.h"
 #include "jpeg_tables.h"
+#include "wave_ops.h"
 
 namespace amav {
 namespace jpeg {
@@ -43,12 +44,6 @@ __device__ const CodeTable d_dc_codes[2] = {make_code_table(kDcBits[0], kDcVals)
 __device__ const CodeTable d_ac_codes[2] = {make_code_table(kAcBits[0], kAcVals[0]),
                                             make_code_table(kAcBits[1], kAcVals[1])};
 __device__ const ZigzagPos d_zigzag_pos = make_zigzag_pos();  // natural index -> position in the scan
-
-__device__ __forceinline__ void wave_sync() {  // orders this wave's LDS traffic (every LDS array here is per wave)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // ------------------------------------------------------------------------------------------------------ transform
 __device__ __forceinline__ float quant8f(float v) { return (float)(unsigned char)(fminf(fmaxf(v, 0.f), 1.f) * 255.0f); }
@@ -236,15 +231,6 @@ __device__ __forceinline__ int code_block(const short *__restrict__ lv, int dc_d
     return nbits;
 }
 
-__device__ __forceinline__ int wave_inclusive(int v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int up = __shfl_up(v, o, 64);
-        if (lane >= o) v += up;
-    }
-    return v;
-}
-
 // One wave (= one workgroup) per restart interval.  kWrite = 0: sizes[interval] = bytes of its entropy-coded segment
 // (stuffing included); kWrite = 1: the frame header (first interval) or the RSTn marker, the segment, and EOI after the
 // frame's last interval, at offsets[interval] of the stream; nothing is stored at or beyond `cap`.
@@ -304,7 +290,7 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(Geom g, const short *_
             table = g.s444 ? (i % 3 != 0) : (k >= 4);
             nbits = code_block<false>(mine, dc_diff, dc_tab[table], ac_tab[table], cur);
         }
-        const int incl = wave_inclusive(nbits, lane);
+        const int incl = wave_inclusive_sum(nbits, lane);
         int total = carry_bits + __shfl(incl, 63, 64);
         if (active) {
             cur.pos = carry_bits + incl - nbits;
@@ -328,7 +314,7 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(Geom g, const short *_
 #pragma unroll
             for (int t = 0; t < 4; ++t) ff += (w * 4 + t < nbytes) && ((word >> (24 - 8 * t)) & 255u) == 255u;
             if (kWrite) {
-                const int incl_ff = wave_inclusive(ff, lane);
+                const int incl_ff = wave_inclusive_sum(ff, lane);
                 long long p = at + (long long)w * 4 + stuffed + (incl_ff - ff);
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
@@ -356,9 +342,7 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(Geom g, const short *_
     if (kWrite) {
         if (iv == g.I - 1 && lane < 2 && at + lane < cap) stream[at + lane] = lane == 0 ? 0xff : 0xd9;
     } else {
-        long long all = stuffed;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) all += __shfl_xor(all, o, 64);
+        const long long all = wave_sum(stuffed);
         if (lane == 0) sizes[blockIdx.x] = plain + all;
     }
 }
@@ -381,12 +365,7 @@ __global__ __launch_bounds__(1024) void jpeg_scan_kernel(int F, int I, int heade
         const int iv = (int)(i % I);
         long long span = 0;
         if (i < n) span = sizes[i] + (iv == 0 ? header_bytes : 2) + (iv == I - 1 ? 2 : 0);
-        long long incl = span;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const long long up = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += up;
-        }
+        const long long incl = wave_inclusive_sum(span, lane);
         if (lane == 63) wave_tot[wave] = incl;
         __syncthreads();
         long long before = carry;

@@ -17,6 +17,7 @@
 
 #include "amav_common.h"
 #include "jpeg_tables.h"
+#include "wave_ops.h"
 
 // include/amav.h states the pixel arithmetic product by product; where a product is fused with an addition it is an
 // explicit fmaf, nothing else contracts
@@ -38,14 +39,6 @@ struct Geom {
 };
 
 __device__ const ZigzagPos d_zigzag_pos = make_zigzag_pos();  // natural index -> position in the scan
-
-__device__ __forceinline__ void wave_sync() {  // orders this wave's LDS traffic
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ long long clampll(long long v, long long lo, long long hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // MCUs per restart interval and intervals per frame of a record
 __device__ __forceinline__ int interval_mcus(const Geom &g, int ri) { return (ri <= 0 || ri >= g.mcus) ? g.mcus : ri; }

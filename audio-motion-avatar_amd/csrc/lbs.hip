@@ -26,6 +26,8 @@
 #include <cstring>
 
 #include "lbs_common.h"
+#include "split_f16.h"
+#include "wave_ops.h"
 
 #ifndef AMAV_LBS_ABLATE
 #define AMAV_LBS_ABLATE 0  /* diagnostic builds only (tools/ablate_lbs.sh) */
@@ -34,18 +36,8 @@
 namespace amav {
 namespace lbs {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 constexpr size_t kSplitHeaderBytes = 256;  // [0]: float, largest |table entry|; [1]: int, the table's scale exponent
 
-__device__ __forceinline__ int f16_scale_exp(float amax) {
-    if (!(amax > 0.f)) return 0;
-    return max(-100, min(100, 14 - ilogbf(amax)));
-}
-__device__ __forceinline__ void split2(float x, _Float16 &a, _Float16 &b) {
-    a = (_Float16)x;
-    b = (_Float16)__builtin_fmaf((float)a, -1.0f, x);
-}
 static inline int k16_of(int KB) { return (KB + 31) / 32 * 32; }  // table rows padded to whole 32-row chunks
 
 // One 64-lane block per frame (kSplit: per padded frame).  kSplit = the feature row of the frame goes straight into the
@@ -182,9 +174,7 @@ __global__ __launch_bounds__(64) void joint_chain_kernel(Tables t, int F, int Fp
         const int KB = t.KB;
         float m = 0.f;
         for (int k = j; k < KB; k += 64) m = fmaxf(m, live ? fabsf(feat_s[k]) : 0.f);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-        const int e = f16_scale_exp(m);
+        const int e = f16_scale_exp(wave_max(m));
         const float scale = ldexpf(1.0f, e);
         if (j == 0) fscale[f] = ldexpf(1.0f, -(e + reinterpret_cast<const int *>(hdr)[1]));
         const size_t part = (size_t)(K16 / 8) * Fpad * 8;
@@ -425,15 +415,9 @@ __global__ __launch_bounds__(256) void table_absmax_kernel(const float4 *__restr
                                                            unsigned *__restrict__ hdr) {
     float m = 0.f;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-        const float4 v = blend4[i];
-        m = fmaxf(m, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
+        m = absmax4(m, blend4[i]);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    __shared__ float wm[4];
-    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicMax(hdr, __float_as_uint(fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]))));
+    block_absmax_publish(m, hdr);
 }
 
 // blend [tile][KB][3][32] fp32 -> split [tile][k-step of 16][part][comp][lane half hh][vertex c][8 k] fp16: the B operand

@@ -28,6 +28,7 @@
 #include <cmath>
 
 #include "lbs_common.h"
+#include "wave_ops.h"
 
 namespace amav {
 namespace lbs {
@@ -228,9 +229,7 @@ __global__ __launch_bounds__(64) void joint_grad_kernel(int V, int J, const int 
         }
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-        for (int e = 0; e < 12; ++e) acc[e] += __shfl_xor(acc[e], o, 64);
+    for (int e = 0; e < 12; ++e) acc[e] = wave_sum(acc[e]);
     if (lane == 0) {
         float *dst = dA + ((size_t)f * J + j) * 12;
 #pragma unroll

@@ -17,8 +17,6 @@
 namespace amav {
 namespace png {
 
-__device__ __forceinline__ long long clampll(long long v, long long lo, long long hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 struct InflateRecord {  // amav_inflate's record, 40 bytes
     long long in_begin, in_end, out_begin, out_capacity;
     int wrapper, reserved;

@@ -37,6 +37,7 @@
 #include "decode_quad.h"
 #include "raster_project.h"
 #include "raster_workspace.h"
+#include "wave_ops.h"
 
 namespace amav {
 namespace raster {
@@ -170,13 +171,6 @@ __device__ __forceinline__ unsigned zero_now() {
     unsigned z;
     asm volatile("v_mov_b32 %0, 0" : "=v"(z));
     return z;
-}
-
-__device__ __forceinline__ void wave_sync() {
-    // LDS operations of one wave execute in order; this only stops the compiler from moving them.
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // ---------------------------------------------------------------------------------------------------- preprocess
@@ -333,12 +327,7 @@ __device__ __forceinline__ uint4 preprocess_one(const Params &p, const GaussRec 
 // Block-wide exclusive scan helper (blockDim.x = 1024 = 16 waves).
 __device__ __forceinline__ int block_exclusive_scan(int v, int *lds_wave, int *total) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-    }
+    const int incl = wave_inclusive_sum(v, lane);
     if (lane == 63) lds_wave[wave] = incl;
     __syncthreads();
     int wave_prefix = 0, tot = 0;
@@ -374,8 +363,7 @@ __global__ __launch_bounds__(256) void preprocess_kernel(Params p) {
     }
     // upstream's instance count (3-sigma rectangles), summed per block
     __shared__ int part[4];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) up += __shfl_xor(up, o, 64);
+    up = wave_sum(up);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = up;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -785,46 +773,8 @@ __global__ __launch_bounds__(1024) void slice_scatter_kernel(Params p) {
     }
 }
 
-// Wave-wide min / max / inclusive sum WITHOUT ds_bpermute: __shfl_xor / __shfl_up keep one address register per
-// distance alive (the compiler hoists (lane ^ o) << 2 out of the tile loop: thirteen registers), and what did not fit
-// was spilled -- reloaded per tile as scratch loads, i.e. vector-memory operations whose s_waitcnt vmcnt(0) also drains
-// every background store issued before them.  DPP permutes inside rows of 16 lanes need no address; the four rows are
-// combined on the scalar unit (the results are wave-uniform anyway).
-template <int kCtrl>
-__device__ __forceinline__ unsigned dpp_permute(unsigned v) {  // every lane has a source for these controls
-    return (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, kCtrl, 0xf, 0xf, false);
-}
-__device__ __forceinline__ unsigned wave_min_u32(unsigned v) {  // all 64 lanes active
-    v = min(v, dpp_permute<0xB1>(v));   // quad_perm [1,0,3,2]
-    v = min(v, dpp_permute<0x4E>(v));   // quad_perm [2,3,0,1]
-    v = min(v, dpp_permute<0x141>(v));  // row_half_mirror
-    v = min(v, dpp_permute<0x140>(v));  // row_mirror: every lane of a row holds the row's minimum
-    const unsigned a = __builtin_amdgcn_readlane((int)v, 0), b = __builtin_amdgcn_readlane((int)v, 16);
-    const unsigned c = __builtin_amdgcn_readlane((int)v, 32), d = __builtin_amdgcn_readlane((int)v, 48);
-    return min(min(a, b), min(c, d));
-}
-__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
-    v = max(v, dpp_permute<0xB1>(v));
-    v = max(v, dpp_permute<0x4E>(v));
-    v = max(v, dpp_permute<0x141>(v));
-    v = max(v, dpp_permute<0x140>(v));
-    const unsigned a = __builtin_amdgcn_readlane((int)v, 0), b = __builtin_amdgcn_readlane((int)v, 16);
-    const unsigned c = __builtin_amdgcn_readlane((int)v, 32), d = __builtin_amdgcn_readlane((int)v, 48);
-    return max(max(a, b), max(c, d));
-}
-template <int kShift>
-__device__ __forceinline__ unsigned dpp_row_shr(unsigned v) {  // lane i of a row <- lane i - kShift, 0 at the row's start
-    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x110 + kShift, 0xf, 0xf, false);
-}
-__device__ __forceinline__ unsigned wave_inclusive_sum_u32(unsigned v, int lane) {  // all 64 lanes active
-    v += dpp_row_shr<1>(v);
-    v += dpp_row_shr<2>(v);
-    v += dpp_row_shr<4>(v);
-    v += dpp_row_shr<8>(v);  // inclusive sums inside every row of 16
-    const unsigned r0 = __builtin_amdgcn_readlane((int)v, 15), r1 = __builtin_amdgcn_readlane((int)v, 31);
-    const unsigned r2 = __builtin_amdgcn_readlane((int)v, 47);
-    return v + (lane >= 16 ? r0 : 0u) + (lane >= 32 ? r1 : 0u) + (lane >= 48 ? r2 : 0u);
-}
+// wave_min_u32 / wave_max_u32 / wave_inclusive_sum_u32: the DPP forms of wave_ops.h, for the reason given there: nothing
+// inside the tile loops may use __shfl_*.
 
 // ----------------------------------------------------------------------------------------------------------- sort
 // Normalised bitonic network: every comparator orders (lo, hi) ascending, so a tail of "+inf" needs no storage:
@@ -1538,12 +1488,8 @@ __global__ __launch_bounds__(64, kRenderWavesPerSimd) void render_kernel(Params 
     // The queue's bucket table, read ONCE: lane b holds where bucket b starts and ends among the queue's positions.
     // (Looked up in memory per tile, the walk was a chain of up to 17 dependent loads of the status block -- which the
     // kernel also updates atomically, so nothing could be kept in registers -- each queued behind the wave's stores.)
-    int bucket_end = (lane < kBuckets && !st->overflow) ? st->qcount[q][lane] : 0;
-#pragma unroll
-    for (int d = 1; d < 32; d <<= 1) {  // kBuckets <= 32 lanes carry the table
-        const int o = __shfl_up(bucket_end, d, 64);
-        if (lane >= d) bucket_end += o;
-    }
+    // kBuckets <= 32 lanes carry the table
+    const int bucket_end = wave_inclusive_sum((lane < kBuckets && !st->overflow) ? st->qcount[q][lane] : 0, lane);
     const int total = __builtin_amdgcn_readlane(bucket_end, kBuckets - 1);
     // the table lives in LDS from here on (in a register it was spilled: see lane_now())
     if (lane < 32) L.bucket_end[lane] = bucket_end;

@@ -29,6 +29,7 @@
 #include "amav_common.h"
 #include "raster_project.h"
 #include "raster_workspace.h"
+#include "wave_ops.h"
 
 namespace amav {
 namespace raster_bwd {
@@ -82,12 +83,7 @@ __global__ __launch_bounds__(1024) void seg_kernel(Params p) {
     for (int base = 0; base < p.N; base += 1024) {  // block-uniform trip count
         const int i = base + threadIdx.x;
         const int a = i < p.N ? rect_area(p.ws.rectd[(size_t)f * p.N + i]) : 0;
-        int incl = a;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int o = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += o;
-        }
+        const int incl = wave_inclusive_sum(a, lane);
         if (lane == 63) wave_tot[wave] = incl;
         __syncthreads();
         int before = carry_s;
@@ -104,29 +100,6 @@ __global__ __launch_bounds__(1024) void seg_kernel(Params p) {
 }
 
 // ------------------------------------------------------------------------------------------------------ tile pass
-// wave sum in a fixed order (all 64 lanes active): DPP inside each row of 16, then the four row totals
-__device__ __forceinline__ float row_shr_add(float v, int k) {
-    int s;
-    switch (k) {
-        case 1: s = __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111, 0xf, 0xf, false); break;
-        case 2: s = __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x112, 0xf, 0xf, false); break;
-        case 4: s = __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x114, 0xf, 0xf, false); break;
-        default: s = __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x118, 0xf, 0xf, false); break;
-    }
-    return v + __int_as_float(s);
-}
-__device__ __forceinline__ float wave_sum(float v) {
-    v = row_shr_add(v, 1);
-    v = row_shr_add(v, 2);
-    v = row_shr_add(v, 4);
-    v = row_shr_add(v, 8);  // lane 15 of every row holds the row's sum
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 15));
-    const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 31));
-    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 47));
-    const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-    return (r0 + r1) + (r2 + r3);
-}
-
 struct TileLds {
     union {
         unsigned long long keys[kLocalSort];  // the list while it is sorted
@@ -314,7 +287,7 @@ __global__ __launch_bounds__(256) void tile_grad_kernel(Params p) {
             if (__any(hit)) {  // wave-uniform
 #pragma unroll
                 for (int k = 0; k < kComp; ++k) {
-                    const float s = wave_sum(c[k]);
+                    const float s = wave_sum_rows(c[k]);
                     if (lane == 0) L.part[wave][k][j] = s;
                 }
             } else if (lane == 0) {

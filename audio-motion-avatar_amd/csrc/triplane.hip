@@ -23,6 +23,7 @@
 #include "decode_quad.h"
 #include "sample_taps.h"
 #include "triplane_region.h"
+#include "wave_ops.h"
 
 namespace amav {
 namespace triplane {
@@ -289,14 +290,8 @@ __global__ __launch_bounds__(1024) void bbox_kernel(int N, const float *__restri
         }
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            lo[d] = fminf(lo[d], __shfl_xor(lo[d], o, 64));
-            hi[d] = fmaxf(hi[d], __shfl_xor(hi[d], o, 64));
-        }
-        bad = fmaxf(bad, __shfl_xor(bad, o, 64));
-    }
+    for (int d = 0; d < 3; ++d) lo[d] = wave_min(lo[d]), hi[d] = wave_max(hi[d]);
+    bad = wave_max(bad);
     const int wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll

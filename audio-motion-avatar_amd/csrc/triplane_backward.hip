@@ -31,6 +31,7 @@
 #include "amav_common.h"
 #include "decode_quad.h"
 #include "triplane_region.h"
+#include "wave_ops.h"
 
 namespace amav {
 namespace triplane_bwd {
@@ -58,12 +59,6 @@ __device__ __forceinline__ triplane::TexelRect backward_rect(const float *__rest
         r.x0 &= ~3, r.x1 |= 3;  // the projection walks whole quads of a row
     }
     return r;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // grid: F * ceil(N / 256) blocks of 256 threads, block b = frame b / bpf.

@@ -30,6 +30,7 @@
 
 #include "amav_common.h"
 #include "sample_taps.h"
+#include "wave_ops.h"
 
 namespace amav {
 namespace sample_bwd {
@@ -89,12 +90,7 @@ __global__ __launch_bounds__(kBinWaves * 64) void bin_kernel(int N, int R, const
         int run = 0;
         for (int c0 = 0; c0 < cells; c0 += 64) {
             const int c = c0 + lane, v = c < cells ? tot[c] : 0;
-            int incl = v;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int t = __shfl_up(incl, o, 64);
-                if (lane >= o) incl += t;
-            }
+            const int incl = wave_inclusive_sum(v, lane);
             if (c < cells) tot[c] = run + incl - v;
             run += __shfl(incl, 63, 64);
         }

@@ -30,6 +30,7 @@
 #include "amav_common.h"
 #include "split_f16.h"
 #include "upsample_conv_stage.h"
+#include "wave_ops.h"
 
 namespace amav {
 namespace upconv {
@@ -51,14 +52,9 @@ __global__ __launch_bounds__(256) void operand_absmax_kernel(const float4 *__res
             const float4 s = scale4[c], b = shift4[c];
             v = make_float4(prologue(v.x, s.x, b.x), prologue(v.y, s.y, b.y), prologue(v.z, s.z, b.z), prologue(v.w, s.w, b.w));
         }
-        m = fmaxf(m, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
+        m = absmax4(m, v);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    __shared__ float wm[4];
-    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicMax(out, __float_as_uint(fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]))));
+    block_absmax_publish(m, out);
 }
 
 // largest |w[co][ci][tap] * scale[co]| -> hdr[0]
@@ -67,12 +63,7 @@ __global__ __launch_bounds__(256) void weights_absmax_kernel(const float *__rest
     float m = 0.f;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
         m = fmaxf(m, fabsf(scale ? w[i] * scale[i / per_cout] : w[i]));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    __shared__ float wm[4];
-    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicMax(hdr, __float_as_uint(fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]))));
+    block_absmax_publish(m, hdr);
 }
 
 // w [cout][cin][3][3] (x scale[cout]) -> [tap][cout / 32][cin / 16][part][lane half hh][column c][8 k] fp16, as
