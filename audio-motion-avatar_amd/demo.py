@@ -25,7 +25,8 @@ side-car with width / height / fps) or any writable binary stream works everywhe
 An `.avi` target needs no encoder process: the frames are JPEG-encoded on the device (ops.jpeg_encode; fp32 RGBA frames
 never become rgb24) and only the streams cross to the host, into a Motion-JPEG AVI with the clip's audio as 16-bit PCM
 (mjpeg.AviWriter).  `.mjpeg` is the bare concatenation of the JPEGs, and `--frames-dir` the reference's per-frame
-image dump (main2.py:231-236) as frame_000.jpg ... from the same streams.
+image dump (main2.py:231-236) as frame_000.jpg ... from the same streams, or, with `--frames-format png`, as lossless
+frame_000.png ... from the device's PNG encoder (ops.png_encode, the reference's own format for that dump).
 """
 import argparse
 import json
@@ -45,10 +46,11 @@ JPEG_CHUNK = 64  # frames per ops.jpeg_encode call: bounds the encoder's workspa
 class FrameWriter:
     """Sink of rendered frames: `write(frames)` takes fp32 [..., H, W, 3|4] in [0, 1] on the HIP device (or uint8 RGB
     on any device) and appends them; `close()` finishes the file (and waits for ffmpeg).  `.avi` / `.mjpeg` targets
-    and `frames_dir` take the frames through the device's JPEG encoder (`jpeg_quality`, `jpeg_subsampling`)."""
+    and `frames_dir` take the frames through the device's JPEG encoder (`jpeg_quality`, `jpeg_subsampling`); with
+    `frames_format="png"` the `frames_dir` files are lossless PNGs from the device's PNG encoder instead."""
 
     def __init__(self, target, height, width, fps=24.0, audio_path=None, ffmpeg="ffmpeg", jpeg_quality=90,
-                 jpeg_subsampling="420", frames_dir=None, device="cuda"):
+                 jpeg_subsampling="420", frames_dir=None, device="cuda", frames_format="jpg"):
         self.height, self.width, self.fps = int(height), int(width), float(fps)
         self.frames = 0
         self.proc = None
@@ -56,7 +58,9 @@ class FrameWriter:
         self.avi = None
         self._close_stream = False
         self.jpeg_quality, self.jpeg_subsampling, self.device = int(jpeg_quality), str(jpeg_subsampling), device
-        self.frames_dir = frames_dir
+        if frames_format not in ("jpg", "png"):
+            raise ValueError(f"frames_format {frames_format!r}: jpg or png")
+        self.frames_dir, self.frames_format = frames_dir, frames_format
         if frames_dir is not None:
             os.makedirs(frames_dir, exist_ok=True)
         suffix = "" if hasattr(target, "write") else os.path.splitext(str(target))[1].lower()
@@ -101,9 +105,21 @@ class FrameWriter:
                     self.avi.write_frame(jpeg)
                 elif self.bare_jpeg:
                     self.stream.write(jpeg)
-                if self.frames_dir is not None:
+                if self.frames_dir is not None and self.frames_format == "jpg":
                     with open(os.path.join(self.frames_dir, f"frame_{self.frames + at + i:03d}.jpg"), "wb") as fh:
                         fh.write(jpeg)
+
+    def _write_png(self, frames):
+        """The lossless frame dump: PNG-encode on the device (save_image's rounding), one file per frame."""
+        frames = frames.reshape(-1, self.height, self.width, frames.shape[-1])
+        if not frames.is_cuda:
+            frames = frames.to(self.device)
+        for at in range(0, frames.shape[0], JPEG_CHUNK):
+            stream, offsets = ops.png_encode(frames[at:at + JPEG_CHUNK].contiguous(), rounding="nearest")
+            data, offsets = stream.cpu().numpy().tobytes(), offsets.tolist()
+            for i in range(len(offsets) - 1):
+                with open(os.path.join(self.frames_dir, f"frame_{self.frames + at + i:03d}.png"), "wb") as fh:
+                    fh.write(data[offsets[i]:offsets[i + 1]])
 
     def write(self, frames):
         if frames.dtype != torch.uint8 and frames.shape[-1] == 3:
@@ -111,8 +127,11 @@ class FrameWriter:
             frames = torch.cat([frames, torch.ones_like(frames[..., :1])], dim=-1)
         count = frames.numel() // (self.height * self.width * frames.shape[-1])
         jpeg = self.avi is not None or self.bare_jpeg
-        if jpeg or self.frames_dir is not None:
+        png = self.frames_dir is not None and self.frames_format == "png"
+        if jpeg or (self.frames_dir is not None and not png):
             self._write_jpeg(frames)
+        if png:
+            self._write_png(frames)
         if not jpeg:
             if frames.dtype != torch.uint8:
                 frames = ops.frames_to_rgb8(frames.contiguous())
@@ -185,7 +204,10 @@ def main(argv=None):
                                         "SMPL-X mesh drawn over it (height 2H; same suffix rules and audio as --out)")
     ap.add_argument("--jpeg-quality", type=int, default=90, help="quality 1..100 of .avi / .mjpeg / --frames-dir output")
     ap.add_argument("--jpeg-subsampling", choices=("420", "444"), default="420")
-    ap.add_argument("--frames-dir", help="also write every frame of --out there as frame_000.jpg ... (main2.py:231-236)")
+    ap.add_argument("--frames-dir", help="also write every frame of --out there as frame_000.jpg ... (main2.py:231-236), or as "
+                                          "frame_000.png ... with --frames-format png")
+    ap.add_argument("--frames-format", choices=("jpg", "png"), default="jpg",
+                    help="--frames-dir files: jpg (through the JPEG encoder) or png (lossless, frame_000.png ...)")
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--seed", type=int, default=42)
     args = ap.parse_args(argv)
@@ -216,7 +238,8 @@ def main(argv=None):
     target = sys.stdout.buffer if args.out == "-" else args.out
     want_mesh = args.smplx_out is not None
     jpeg = dict(jpeg_quality=args.jpeg_quality, jpeg_subsampling=args.jpeg_subsampling, device=args.device)
-    with FrameWriter(target, H, W, fps=args.fps, audio_path=args.audio, frames_dir=args.frames_dir, **jpeg) as writer:
+    with FrameWriter(target, H, W, fps=args.fps, audio_path=args.audio, frames_dir=args.frames_dir,
+                     frames_format=args.frames_format, **jpeg) as writer:
         if args.interleave:
             if len(seeds) < 2:
                 raise SystemExit("--interleave needs two token pairs (even and odd chain)")

@@ -771,6 +771,129 @@ def png_decode(stream, records, mode="rgb", layout="hwc_u8", out=None, status=No
     return out, status
 
 
+PNG_STATUS_TABLE = _lib.DEFINES["AMAV_PNG_STATUS_TABLE"]
+DEFLATE_PIECE = _lib.DEFINES["AMAV_DEFLATE_PIECE"]
+DeflateStream = _lib.STRUCTS["amav_deflate_stream"]
+PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": _lib.DEFINES["AMAV_PNG_FILTER_ADAPTIVE"]}
+PNG_ROUNDINGS = {"nearest": _lib.DEFINES["AMAV_PNG_ROUND_NEAREST"], "truncate": _lib.DEFINES["AMAV_PNG_ROUND_TRUNCATE"]}
+
+
+def deflate_bound(nbytes, wrapper=True):
+    """The most bytes deflate() makes of `nbytes` input bytes: every piece stored."""
+    return int(nbytes) + 5 * max(1, -(-int(nbytes) // DEFLATE_PIECE)) + (6 if wrapper else 0)
+
+
+def deflate(data, records, out=None, status=None):
+    """Byte ranges of the device byte vector `data` -> DEFLATE streams: (out, produced, status), all on the device; the
+    mirror of inflate().  With records on the host there is no host synchronisation; records given on the device are
+    read back first, which is one.  records: int64 [N,5], one row per stream: in_begin, in_end (bytes of `data`),
+    out_begin, out_capacity (bytes of `out`), wrapper (0 raw, 1 zlib).  out: the uint8 vector written into (default: a
+    fresh one that just holds every row's range).  produced int64 [N]: the bytes each stream needs; status int32 [N]: 0,
+    PNG_STATUS_SIZE (produced > out_capacity; the part that fits was written) or PNG_STATUS_TABLE (ranges that overlap
+    beyond the piece table; include/amav.h has the rules)."""
+    _byte_stream(data, "deflate")
+    if not isinstance(records, torch.Tensor) or records.dtype != torch.int64 or records.dim() != 2 or records.shape[1] != 5 or \
+            records.shape[0] == 0:
+        raise AmavError("deflate: records must be an int64 [N,5] tensor (in_begin, in_end, out_begin, out_capacity, wrapper)")
+    host = records.cpu() if records.is_cuda else records
+    N = host.shape[0]
+    if out is None:
+        out = torch.empty(max(1, int((host[:, 2] + host[:, 3]).max())), dtype=torch.uint8, device=data.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.dim() != 1 or out.stride(0) != 1 or \
+            out.device != data.device:
+        raise AmavError("deflate: out must be a uint8 vector on the data's device")
+    table = torch.zeros(N, ctypes.sizeof(DeflateStream) // 8, dtype=torch.int64)
+    table[:, :4] = host[:, :4]
+    table[:, 4] = host[:, 4] & 0xFFFFFFFF  # wrapper (int32) + reserved
+    table = table.to(data.device)
+    status = _status_words(status, N, data.device, "deflate")
+    produced = torch.empty(N, dtype=torch.int64, device=data.device)
+    ws = _scratch("amav_deflate_workspace_bytes", data.device, N, data.numel(), rejected=f"{N} streams")
+    _call("amav_deflate", N, data.data_ptr(), data.numel(), table.data_ptr(), out.data_ptr(), out.numel(),
+          produced.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel())
+    return out, produced, status
+
+
+def _png_frames(frames, who):
+    """(frames, F, H, W, layout code) of a PNG encode call: fp32 RGBA [F,H,W,4], fp32 [F,3,H,W], uint8 RGB [F,H,W,3],
+    or uint8 / fp32 grey [F,H,W]; contiguous, on the device.  An fp32 [F,3,H,4] tensor is taken as RGBA."""
+    if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
+        raise AmavError(f"{who}: frames must be a tensor on the HIP device")
+    d = _lib.DEFINES
+    layout = None
+    if frames.is_contiguous() and frames.dtype == torch.float32:
+        if frames.dim() == 4 and frames.shape[-1] == 4:
+            layout, (F, H, W) = d["AMAV_PNG_IN_RGBA_F32"], frames.shape[:3]
+        elif frames.dim() == 4 and frames.shape[1] == 3:
+            layout, (F, H, W) = d["AMAV_PNG_IN_CHW_F32"], (frames.shape[0], frames.shape[2], frames.shape[3])
+        elif frames.dim() == 3:
+            layout, (F, H, W) = d["AMAV_PNG_IN_GREY_F32"], frames.shape
+    elif frames.is_contiguous() and frames.dtype == torch.uint8:
+        if frames.dim() == 4 and frames.shape[-1] == 3:
+            layout, (F, H, W) = d["AMAV_PNG_IN_RGB_U8"], frames.shape[:3]
+        elif frames.dim() == 3:
+            layout, (F, H, W) = d["AMAV_PNG_IN_GREY_U8"], frames.shape
+    if layout is None:
+        raise AmavError(f"{who}: need contiguous fp32 RGBA [F,H,W,4], fp32 [F,3,H,W], uint8 RGB [F,H,W,3] or uint8 / fp32 "
+                        f"grey [F,H,W] frames, got {frames.dtype} {tuple(frames.shape)}")
+    return frames, int(F), int(H), int(W), layout
+
+
+def png_stream_bound(F, H, W, channels=3):
+    layout = _lib.DEFINES["AMAV_PNG_IN_RGB_U8" if channels == 3 else "AMAV_PNG_IN_GREY_U8"]
+    n = _lib.lib().amav_png_stream_bound(int(F), int(H), int(W), layout)
+    if n == 0:
+        raise AmavError(f"png_stream_bound: bad sizes F={F} H={H} W={W}")
+    return int(n)
+
+
+def png_encode_into(frames, stream, filter="adaptive", rounding="nearest", capacity=None, frame_offsets=None, status=None):
+    """One amav_png_encode call into the caller's uint8 `stream` buffer (its first `capacity` bytes; default: all of it).
+    Returns (frame_offsets int64 [F+1], status int32 [F]) on the device; no host synchronisation.  status[f] != 0: frame
+    f ends behind the capacity (frame_offsets still holds the sizes needed), and nothing at or beyond the capacity was
+    written."""
+    frames, F, H, W, layout = _png_frames(frames, "png_encode")
+    if filter not in PNG_FILTERS:
+        raise AmavError(f"png_encode: unknown filter {filter!r} ({', '.join(PNG_FILTERS)})")
+    if rounding not in PNG_ROUNDINGS:
+        raise AmavError(f"png_encode: unknown rounding {rounding!r} (nearest or truncate)")
+    if not isinstance(stream, torch.Tensor) or stream.dtype != torch.uint8 or not stream.is_contiguous() or \
+            stream.device != frames.device:
+        raise AmavError("png_encode: stream must be a contiguous uint8 tensor on the frames' device")
+    capacity = stream.numel() if capacity is None else int(capacity)
+    if not 0 <= capacity <= stream.numel():
+        raise AmavError(f"png_encode: capacity {capacity} outside the {stream.numel()}-byte stream buffer")
+    if frame_offsets is None:
+        frame_offsets = torch.empty(F + 1, dtype=torch.int64, device=frames.device)
+    status = _status_words(status, F, frames.device, "png_encode")
+    ws = _scratch("amav_png_encode_workspace_bytes", frames.device, F, H, W, layout, rejected=f"F={F} H={H} W={W}")
+    _call("amav_png_encode", F, H, W, frames.data_ptr(), layout, PNG_FILTERS[filter], PNG_ROUNDINGS[rounding],
+          stream.data_ptr(), capacity, frame_offsets.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel())
+    return frame_offsets, status
+
+
+def png_encode(frames, filter="adaptive", rounding="nearest", capacity=None):
+    """Frames (fp32 RGBA [F,H,W,4] as the rasterizer leaves them, fp32 [F,3,H,W], uint8 RGB [F,H,W,3], or uint8 / fp32
+    grey [F,H,W]) -> PNG, one complete file per frame, packed back to back: (stream uint8 [bytes] on the device,
+    frame_offsets int64 [F+1] on the host); frame f is stream[frame_offsets[f]:frame_offsets[f + 1]].  `rounding`
+    "nearest" is torchvision's save_image (x * 255 + 0.5, clamped, truncated), "truncate" frames_to_rgb8's rule.
+
+    `capacity` (default: half the raw size, at least 4 KiB) is the buffer the first attempt encodes into; when the
+    stream does not fit, the call is repeated once at amav_png_stream_bound.  Reading frame_offsets (the size) back is
+    the call's single host synchronisation; png_encode_into() is the form without any."""
+    frames, F, H, W, layout = _png_frames(frames, "png_encode")
+    channels = 1 if frames.dim() == 3 else 3
+    capacity = max(4096, F * H * W * channels // 2) if capacity is None else int(capacity)
+    stream = torch.empty(max(1, capacity), dtype=torch.uint8, device=frames.device)
+    offsets = png_encode_into(frames, stream, filter, rounding, capacity=capacity)[0].cpu()
+    if int(offsets[-1]) > capacity:  # what status flags on the device
+        stream = torch.empty(png_stream_bound(F, H, W, channels), dtype=torch.uint8, device=frames.device)
+        offsets = png_encode_into(frames, stream, filter, rounding)[0].cpu()
+        if int(offsets[-1]) > stream.numel():
+            raise AmavError(f"png_encode: {int(offsets[-1])} bytes exceed the worst-case bound {stream.numel()}")
+    return stream[:int(offsets[-1])], offsets
+
+
 def padded_size(height, width, pad_ratio):
     """pad_image's geometry (src/datasets/dataset_speech_vid.py:319-327), in Python doubles as there:
     (Hp, Wp, offset_y, offset_x)."""

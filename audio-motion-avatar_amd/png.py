@@ -3,7 +3,10 @@ frames of the reference's dataset (imgs_png/%05d.png, samurai_seg/%05d.png) are 
 joined into one zlib stream, and records, palettes and streams go up in one copy to one ops.png_decode call.
 
 Not covered: interlaced (Adam7) and 16-bit files, which parse_png refuses; the Adler-32 of the zlib stream, which the
-device does not verify (a chunk's CRC is checked here)."""
+device does not verify (a chunk's CRC is checked here).
+
+PNG clip output (below): save_clip, save_image, save_comparison and write_dataset_clip hand device tensors to
+ops.png_encode and write the files it returns; conversion, filtering, deflate and the CRCs happen on the device."""
 import os
 import struct
 import zlib
@@ -222,3 +225,91 @@ def load_clip(path, frames=None, mode="rgb", device="cuda", layout="chw_f32", ch
     if bad:
         raise PngError("load_clip: damaged frames " + ", ".join(f"{i} ({status_text(s)})" for i, s in bad))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------- output
+SAVE_CHUNK = 64  # frames per ops.png_encode call: bounds the encoder's workspace for long clips
+
+
+def save_clip(directory, frames, pattern="%05d.png", start=0, filter="adaptive", rounding="nearest"):
+    """Frames on the device (any layout ops.png_encode takes) -> one PNG file per frame, directory/pattern % (start + i).
+    One encode call per SAVE_CHUNK frames, one download of its stream (not of the frames), one file write per frame.
+    Returns the paths."""
+    from . import ops
+
+    os.makedirs(directory, exist_ok=True)
+    paths = []
+    for at in range(0, frames.shape[0], SAVE_CHUNK):
+        stream, offsets = ops.png_encode(frames[at:at + SAVE_CHUNK].contiguous(), filter=filter, rounding=rounding)
+        data, offsets = stream.cpu().numpy().tobytes(), offsets.tolist()
+        for i in range(len(offsets) - 1):
+            paths.append(os.path.join(directory, pattern % (start + at + i)))
+            with open(paths[-1], "wb") as fh:
+                fh.write(data[offsets[i]:offsets[i + 1]])
+    return paths
+
+
+def normalize_range(tensor):
+    """torchvision.utils.make_grid(normalize=True) for one image: clamp to its own (min, max), then
+    (x - min) / max(max - min, 1e-5).  Everything stays on the tensor's device."""
+    import torch
+
+    x = tensor.to(torch.float32)
+    low, high = x.min(), x.max()
+    return (x.clamp(min=low, max=high) - low) / (high - low).clamp(min=1e-5)
+
+
+def _one_image(tensor, who):
+    """[H,W], [1,H,W] -> grey [1,H,W]; [3,H,W] -> [1,3,H,W] (what save_image makes of a single image)."""
+    if tensor.dim() == 4 and tensor.shape[0] == 1:
+        tensor = tensor[0]
+    if tensor.dim() == 2:
+        tensor = tensor[None]
+    if tensor.dim() != 3 or tensor.shape[0] not in (1, 3):
+        raise ValueError(f"{who}: need one image [3,H,W], [1,H,W] or [H,W], got {tuple(tensor.shape)}")
+    return tensor if tensor.shape[0] == 1 else tensor[None]
+
+
+def save_image(tensor, path, normalize=False):
+    """torchvision.utils.save_image(tensor, path, normalize=normalize) for a single fp32 image on the device: the
+    optional min / max normalisation (on the device), then x * 255 + 0.5 clamped and truncated (the encoder's `nearest`
+    rule), written as one PNG.  A one-channel image is written as greyscale (torchvision repeats it to RGB; the pixels
+    read back with convert("RGB") are the same)."""
+    import torch
+
+    from . import ops
+
+    image = _one_image(tensor, "save_image")
+    if normalize:
+        image = normalize_range(image)
+    stream, _ = ops.png_encode(image.to(torch.float32).contiguous(), rounding="nearest")
+    with open(path, "wb") as fh:
+        fh.write(stream.cpu().numpy().tobytes())
+
+
+def comparison_sheet(rendered, real):
+    """The sheet of lightning_model_wrapper.py:536-570 / :610-638: rendered [T,H,W,3] and real [T,3,H,W] -> [3, T H, 2 W]:
+    row t is rendered_t | real_t, the rows stacked downwards."""
+    import torch
+
+    rendered = rendered.permute(0, 3, 1, 2).to(torch.float32)
+    rows = torch.cat([rendered, real.to(torch.float32)], dim=3)           # [T,3,H,2W]
+    return rows.permute(1, 0, 2, 3).reshape(3, rows.shape[0] * rows.shape[2], rows.shape[3])
+
+
+def save_comparison(path, rendered, real, normalize=True):
+    """Write the rendered | real comparison sheet as one PNG: composed on the device with torch operators, normalised as
+    save_image(..., normalize=True) does, encoded as one frame."""
+    save_image(comparison_sheet(rendered, real), path, normalize=normalize)
+
+
+def write_dataset_clip(root_dir, frames, masks=None, start=0):
+    """Fill root_dir/imgs_png/%05d.png (frames: uint8 [F,H,W,3] or fp32 in any layout ops.png_encode takes) and
+    root_dir/samurai_seg/%05d.png (masks: uint8 / fp32 [F,H,W], optional) from frame id `start`, the layout
+    clip_data.load_dataset_clip and PngDirReader read back."""
+    paths = save_clip(os.path.join(root_dir, "imgs_png"), frames, start=start)
+    if masks is not None:
+        if masks.dim() == 4 and masks.shape[1] == 1:
+            masks = masks[:, 0]
+        paths += save_clip(os.path.join(root_dir, "samurai_seg"), masks, start=start)
+    return paths

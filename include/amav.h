@@ -1511,6 +1511,99 @@ int amav_png_decode(int num_frames, int height, int width, const uint8_t *stream
                     const void *records_dev, int mode, int layout, void *out_dev, size_t out_bytes, int32_t *status_dev,
                     void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* PNG output (csrc/png_encode.hip, csrc/png_deflate_core.h): everything the reference writes to disk as a picture is a PNG
+ * (vutils.save_image sheets, plt.imsave frame dumps, the dataset's imgs_png / samurai_seg); the frames are converted,
+ * filtered, deflated and framed on the device.
+ *
+ * amav_deflate is the counterpart of amav_inflate: num_streams byte ranges [in_begin, in_end) of in_dev [in_bytes] become
+ * num_streams DEFLATE streams (RFC 1951), raw (wrapper 0) or zlib-wrapped (1: 78 01 in front, the Adler-32 behind), each
+ * written to out_dev [out_bytes] from out_begin, never at or past out_begin + out_capacity.  Both ranges are clamped to
+ * their buffers on the device.  produced_dev: int64 [N], the bytes the stream needs; status_dev: int32 [N], written by
+ * the call: 0, or AMAV_PNG_STATUS_SIZE when the stream needs more than out_capacity (what fits, the stream's start, is
+ * written; produced says how much room to come back with), or AMAV_PNG_STATUS_TABLE (below).
+ *   pieces    a stream is cut into pieces of AMAV_DEFLATE_PIECE input bytes, one wave each, so a frame is compressed by
+ *             as many waves as it has pieces.  A piece is coded with no reference across its start.  It ends on a byte
+ *             boundary: a stored piece by itself, a Huffman piece with an empty stored block (00 00 00 ff ff); the last
+ *             piece carries BFINAL instead.  The pieces back to back are one stream for any decoder.  An empty range is
+ *             one empty piece.
+ *   matches   LDS hash of 3-byte prefixes (4096 entries), 64 consecutive positions a step.  A position is compared with
+ *             the newest position of an EARLIER step that has its hash and with the byte before it (runs); the longer
+ *             match wins, the nearer on a tie; a 3-byte match farther than 4096 is dropped.  Positions of one step that
+ *             share a hash leave the largest position in the table (an integer max), so the bytes do not depend on lane
+ *             timing.  The parse is greedy and walked wave-uniformly: a match is taken wherever one starts.
+ *   coding    literal/length and distance histograms in LDS; code lengths of at most 15 bits (7 for the code-length
+ *             code): the lanes rank the symbols by frequency, one lane runs the linear in-place minimum-redundancy
+ *             construction on the sorted list and moves codes up until the Kraft sum is one; the header is run-length
+ *             coded with 16 / 17 / 18.  A piece without a match sends one unused distance code of one bit, a piece with
+ *             one used distance code sends it with one bit.  The piece is then sized exactly as stored (5 + n bytes),
+ *             fixed and dynamic, each with the empty stored block it needs, and the smallest is kept (stored, then fixed,
+ *             on ties; a piece with fewer than two literal/length symbols is never dynamic).  So a stream never exceeds
+ *             input + 5 bytes per piece + 6 for the wrapper.
+ *   two runs  the pieces are run twice, as amav_jpeg_encode runs its entropy stage: once for sizes and Adler-32 sums
+ *             (sum of bytes; sum of (n - i) x byte i), then one thread per stream lays them back to back and joins the
+ *             sums (b += n a + s2, a += s1 mod 65521), then once more to write.  A piece's bytes are put together in LDS
+ *             (integer OR of each token's bits at its prefix-summed bit offset) and leave in one pass.
+ * workspace: amav_deflate_workspace_bytes(num_streams, in_bytes) holds the tables of in_bytes / AMAV_DEFLATE_PIECE +
+ * num_streams pieces, which covers any ranges that do not overlap; a stream whose pieces no longer fit the table (ranges
+ * that overlap) is not coded: AMAV_PNG_STATUS_TABLE, produced 0.  No allocation, no memset, no float atomics, no host
+ * synchronisation; the same bytes on every run, and the bytes of csrc/png_deflate_core.h compiled for the host
+ * (tools/png_deflate_host.cpp).
+ *
+ * amav_png_encode writes num_frames frames of one height and width as num_frames complete PNG files (8 bit, not
+ * interlaced; no alpha, palette or 16-bit output), back to back in stream_out_dev [capacity]: frame f is bytes
+ * [frame_offsets_dev[f], frame_offsets_dev[f + 1]) (int64 [F + 1]).  frames_dev is read in place:
+ *   AMAV_PNG_IN_RGBA_F32  fp32 [F,H,W,4], alpha dropped      colour type 2
+ *   AMAV_PNG_IN_CHW_F32   fp32 [F,3,H,W]                     colour type 2
+ *   AMAV_PNG_IN_RGB_U8    uint8 [F,H,W,3]                    colour type 2
+ *   AMAV_PNG_IN_GREY_U8   uint8 [F,H,W]                      colour type 0
+ *   AMAV_PNG_IN_GREY_F32  fp32 [F,H,W]                       colour type 0
+ * fp32 -> level: AMAV_PNG_ROUND_NEAREST is torchvision's save_image, x.mul(255).add_(0.5).clamp_(0, 255) truncated: the
+ * product and the sum are rounded to fp32 separately (no fused multiply-add), so the level equals the torch expression
+ * bit for bit; AMAV_PNG_ROUND_TRUNCATE is amav_frames_to_rgb8's clamp to [0, 1], x 255, truncated.  NaN -> 0.
+ *   filter    one wave per scanline writes filter byte + filtered row into the workspace.  filter 0..4 (None, Sub, Up,
+ *             Average, Paeth) for every row, or AMAV_PNG_FILTER_ADAPTIVE: all five per row, the smallest sum of the
+ *             residuals' absolute values as signed bytes wins, the lowest filter number on ties.  The previous row is
+ *             converted from the image again, so rows and pieces stay independent.
+ *   deflate   as above over each frame's H x (1 + W x channels) filtered bytes, zlib-wrapped.
+ *   container signature, IHDR, ONE IDAT CHUNK PER PIECE (the first holds the zlib header, the last the Adler-32), IEND.
+ *             Each wave computes its chunk's CRC-32 over the staged bytes in parallel: every lane runs the register over
+ *             its run of the chunk, lane 0 joins the 64 registers (register x x^(8 len) + next, modulo the polynomial).
+ * status_dev: int32 [F]: 0, or AMAV_PNG_STATUS_SIZE for a frame that ends behind the capacity; frame_offsets_dev holds the
+ * needed sizes either way, and nothing is written at or past the capacity.  amav_png_stream_bound: a capacity that always
+ * suffices (every piece stored); amav_png_encode_workspace_bytes: filtered bytes + piece tables; both 0 for rejected
+ * sizes or layout.  Six launches, no allocation, no memset, no float atomics, no host synchronisation; the same bytes on
+ * every run.
+ * Refused with an error code before any launch: amav_deflate: num_streams outside 1..65535, a NULL pointer, a negative
+ * in_bytes or out_bytes, misaligned records, produced (8) or status (4), a NULL, misaligned (16) or short workspace
+ * (AMAV_ERR_WORKSPACE).  amav_png_encode: F outside 1..65535, H or W outside 1..16384, an unknown layout, filter or
+ * rounding, NULL frames, stream, frame_offsets or status, a negative capacity, misaligned fp32 frames (4), frame_offsets
+ * (8) or status (4), and a workspace that is too small, NULL or not 16-byte aligned (AMAV_ERR_WORKSPACE). */
+#define AMAV_DEFLATE_PIECE 8192
+#define AMAV_PNG_STATUS_TABLE 8
+#define AMAV_PNG_IN_RGBA_F32 0
+#define AMAV_PNG_IN_CHW_F32 1
+#define AMAV_PNG_IN_RGB_U8 2
+#define AMAV_PNG_IN_GREY_U8 3
+#define AMAV_PNG_IN_GREY_F32 4
+#define AMAV_PNG_FILTER_ADAPTIVE 5
+#define AMAV_PNG_ROUND_NEAREST 0
+#define AMAV_PNG_ROUND_TRUNCATE 1
+typedef struct amav_deflate_stream {
+    int64_t in_begin, in_end;        /* bytes of in_dev */
+    int64_t out_begin, out_capacity; /* bytes of out_dev */
+    int32_t wrapper;                 /* 0 raw, 1 zlib */
+    int32_t reserved;
+} amav_deflate_stream;
+size_t amav_deflate_workspace_bytes(int num_streams, int64_t in_bytes);
+int amav_deflate(int num_streams, const uint8_t *in_dev, int64_t in_bytes, const void *records_dev, uint8_t *out_dev,
+                 int64_t out_bytes, int64_t *produced_dev, int32_t *status_dev, void *workspace_dev, size_t workspace_bytes,
+                 void *stream);
+int64_t amav_png_stream_bound(int num_frames, int height, int width, int layout);
+size_t amav_png_encode_workspace_bytes(int num_frames, int height, int width, int layout);
+int amav_png_encode(int num_frames, int height, int width, const void *frames_dev, int layout, int filter, int rounding,
+                    uint8_t *stream_out_dev, int64_t capacity, int64_t *frame_offsets_dev, int32_t *status_dev,
+                    void *workspace_dev, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
