@@ -124,6 +124,7 @@ STRUCTS, SIGNATURES, DEFINES = _load_header()
 Attr = STRUCTS["amav_attr"]  # element (f, i) at ptr[f * frame_stride + i * elem_stride] (strides in floats)
 RasterArgs = STRUCTS["amav_raster_args"]
 RasterBackwardArgs = STRUCTS["amav_raster_backward_args"]
+ShArgs = STRUCTS["amav_sh_args"]
 TriplaneDecodeBackwardArgs = STRUCTS["amav_triplane_decode_backward_args"]
 TriplaneSampleBackwardArgs = STRUCTS["amav_triplane_sample_backward_args"]
 DecodeSource = STRUCTS["amav_decode_source"]

@@ -392,6 +392,98 @@ def rasterize_differentiable(means3d, rotations, scales, opacities, colors, view
                 workspace=None)
 
 
+# ------------------------------------------------------------------------------------- spherical-harmonic colours
+SH_MAX_DEGREE = 4
+
+
+def _sh_args(means3d, sh, campos, degree, who):
+    """means3d [F,N,3], sh [F,N,3*K] or [F,N,K,3] (any frame / element strides, unit stride on the last axis; frame
+    stride 0 = one set for every frame), campos [F,3] -> (amav_sh_args, the tensors it points into, F, N, K)."""
+    degree = int(degree)
+    if not 0 <= degree <= SH_MAX_DEGREE:
+        raise AmavError(f"{who}: degree {degree} outside 0..{SH_MAX_DEGREE}")
+    _need(sh, f"{who}: sh")
+    if sh.dim() == 4:
+        if sh.shape[3] != 3:
+            raise AmavError(f"{who}: sh {tuple(sh.shape)}; expected [F,N,K,3] or [F,N,3*K]")
+        if sh.stride(3) != 1 or sh.stride(2) != 3:
+            sh = sh.contiguous()
+        sh = sh.as_strided((sh.shape[0], sh.shape[1], sh.shape[2] * 3), (sh.stride(0), sh.stride(1), 1))
+    if sh.dim() != 3 or sh.shape[2] % 3 != 0 or sh.shape[2] == 0:
+        raise AmavError(f"{who}: sh {tuple(sh.shape)}; expected [F,N,K,3] or [F,N,3*K]")
+    K = sh.shape[2] // 3
+    if K < (degree + 1) ** 2:
+        raise AmavError(f"{who}: {K} coefficients per channel; degree {degree} needs (degree+1)^2 = {(degree + 1) ** 2}")
+    args = _lib.ShArgs()
+    args.sh, sh = _attr(sh, f"{who}: sh", 3 * K)
+    args.means3d, means3d = _attr(means3d, f"{who}: means3d", 3)
+    F, N = means3d.shape[0], means3d.shape[1]
+    if sh.shape[0] != F or sh.shape[1] != N:
+        raise AmavError(f"{who}: sh {tuple(sh.shape)} does not match means3d [F={F},N={N},3]")
+    campos = _contig(campos, f"{who}: campos")
+    if campos.numel() != F * 3:
+        raise AmavError(f"{who}: campos {tuple(campos.shape)}, expected [F={F},3]")
+    args.campos = campos.data_ptr()
+    args.num_frames, args.num_gaussians, args.degree, args.num_coeffs = F, N, degree, K
+    return args, (means3d, sh, campos), F, N, K
+
+
+def sh_colors(means3d, sh, campos, degree):
+    """View-dependent colours [F,N,3] = clamp_min(eval_sh(degree, sh, dir) + 0.5, 0), dir = (p - campos) / |p - campos|:
+    the SH branch of render_one (src/models/renderer.py:540-545) for all frames in one launch (amav_sh_colors).
+    means3d [F,N,3]; sh [F,N,K,3] or [F,N,3*K] with K >= (degree+1)^2 (coefficient-major, read in place; frame stride 0
+    shares one set among the frames); campos [F,3] (camera_from_intrinsics).  No clamp at 1, no host sync."""
+    args, keep, F, N, _ = _sh_args(means3d, sh, campos, degree, "sh_colors")
+    colors = torch.empty(F, N, 3, device=keep[0].device)
+    _call("amav_sh_colors", ctypes.byref(args), colors.data_ptr())
+    return colors
+
+
+def sh_colors_backward(means3d, sh, campos, degree, grad_colors, want_means3d=True, grad_sh=None):
+    """Gradients of sh_colors (amav_sh_colors_backward) for grad_colors = dL/d colours [F,N,3]: (grad_sh [F,N,3*K],
+    grad_means3d [F,N,3] | None), dense rows per frame (a frame-stride-0 input gets one row per frame; the caller sums
+    them).  Coefficients beyond (degree+1)^2 get exact zeros; campos gets no gradient.  One launch, deterministic.
+    `grad_sh`: a contiguous [F,N,3*K] buffer to write into (every element is written; it needs no initialisation)."""
+    args, keep, F, N, K = _sh_args(means3d, sh, campos, degree, "sh_colors_backward")
+    grad_colors = _contig(grad_colors, "sh_colors_backward: grad_colors")
+    if tuple(grad_colors.shape) != (F, N, 3):
+        raise AmavError(f"sh_colors_backward: grad_colors {tuple(grad_colors.shape)}, expected {(F, N, 3)}")
+    dev = keep[0].device
+    if grad_sh is None:
+        grad_sh = torch.empty(F, N, 3 * K, device=dev)
+    else:
+        _need(grad_sh, "sh_colors_backward: grad_sh")
+        if tuple(grad_sh.shape) != (F, N, 3 * K) or not grad_sh.is_contiguous():
+            raise AmavError(f"sh_colors_backward: grad_sh must be contiguous [F,N,3*K] = {(F, N, 3 * K)}")
+    grad_means3d = torch.empty(F, N, 3, device=dev) if want_means3d else None
+    _call("amav_sh_colors_backward", ctypes.byref(args), grad_colors.data_ptr(), grad_sh.data_ptr(),
+          grad_means3d.data_ptr() if want_means3d else None)
+    return grad_sh, grad_means3d
+
+
+class _ShColors(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, means3d, sh, campos, degree):
+        ctx.save_for_backward(means3d, sh, campos)
+        ctx.degree = degree
+        return sh_colors(means3d, sh, campos, degree)
+
+    @staticmethod
+    def backward(ctx, grad_colors):
+        means3d, sh, campos = ctx.saved_tensors
+        grad_sh, grad_means3d = sh_colors_backward(means3d, sh, campos, ctx.degree, grad_colors.float(),
+                                                   want_means3d=ctx.needs_input_grad[0])
+        return grad_means3d, (grad_sh.view(sh.shape) if ctx.needs_input_grad[1] else None), None, None
+
+
+def sh_colors_differentiable(means3d, sh, campos, degree):
+    """sh_colors() as a torch.autograd.Function, differentiable in sh and means3d (campos gets no gradient).  Expanded
+    (frame-stride-0) views are taken as they are: the Function returns one gradient row per frame and autograd's own
+    expand backward sums them over the frames."""
+    _sh_args(means3d, sh, campos, degree, "sh_colors_differentiable")
+    return _ShColors.apply(means3d, sh, campos, int(degree))
+
+
 def frames_to_rgb8(rgba, out=None):
     """fp32 RGBA [...,4] (contiguous) -> uint8 RGB [...,3], truncating like src/main2.py:351."""
     rgba = _need(rgba, "rgba")

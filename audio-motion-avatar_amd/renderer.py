@@ -58,6 +58,11 @@ class _WindowTooSmall(Exception):
 
 
 class Renderer(nn.Module):
+    """The stage-2 renderer.  Its colour head and the fused decode write 3 colour channels per Gaussian, as in the
+    reference, so Renderer itself always renders RGB colours; view-dependent (spherical-harmonic) colours are for callers
+    that bring the coefficients themselves to render_batch / render_one / render_multi_view (args.rgb=False) or to
+    GaussianRasterizer (shs=)."""
+
     def __init__(self, cfg=None, smpl_decoder=None):
         super().__init__()
         self.cfg = cfg
@@ -937,6 +942,19 @@ class TriplaneUpsampler(nn.Module):
 ### Gaussian Splatting Renderer ###
 
 
+SH_C0 = 0.28209479177387814  # 1 / (2 sqrt(pi)): the degree-0 basis function (graphic_utils.py:676)
+
+
+def RGB2SH(rgb):
+    """graphic_utils.py:764-765: the degree-0 coefficient whose colour is `rgb`."""
+    return (rgb - 0.5) / SH_C0
+
+
+def SH2RGB(sh):
+    """graphic_utils.py:767-768: the colour of a degree-0 coefficient."""
+    return sh * SH_C0 + 0.5
+
+
 def _flat(t, width):
     return t.reshape(-1, t.shape[-2], width).float()
 
@@ -973,29 +991,64 @@ def render_batch(gaussians, K, E, args, bg_color=None, debug=False, return_alpha
     `decode` and `return_workspace` are refused then.
     `decode`, `fuse_decode`: ops.decode_source whose `out` the Gaussians view, decoded as part of the rasterizer's launch
     sequence (ops.rasterize).
+    `args.rgb=False`: the reference's SH branch (renderer.py:540-545).  gaussians["color"] holds 3*K spherical-harmonic
+    coefficients per Gaussian ([..., N, 3*K], coefficient-major, K >= (args.sh_degree+1)^2) and the colours are
+    clamp_min(eval_sh + 0.5, 0) for each camera's centre (ops.sh_colors, not clamped at 1); the scale and opacity
+    activations are then torch ops, since the rasterizer's own activation switch would clamp the colours at 1.  A
+    caller's `camera=` must be the 4-tuple of ops.camera_from_intrinsics (with campos); `decode` is refused, because the
+    decode writes 3 colour channels.  Under grad the colours carry ops.sh_colors_differentiable's backward.
     """
-    if not getattr(args, "rgb", True):
-        raise NotImplementedError("args.rgb=False selects the reference's SH branch (renderer.py:540-545), which "
-                                  "cannot run with 3-channel colours (SURVEY.md Appendix C.4)")
+    sh_branch = not getattr(args, "rgb", True)
     B, T = E.shape[0], E.shape[1]
     H, W = int(args.image_size[0]), int(args.image_size[1])
+    if sh_branch and (decode is not None or fuse_decode):
+        raise AmavError("render_batch: decode= / fuse_decode= write 3 colour channels and cannot be combined with "
+                        "args.rgb=False (spherical-harmonic colours)")
+    campos = None
     if camera is None:
-        view, proj, tanfov, _ = ops.camera_from_intrinsics(K.reshape(-1, 3, 3).float(), E.reshape(-1, 4, 4).float(), H, W)
+        view, proj, tanfov, campos = ops.camera_from_intrinsics(K.reshape(-1, 3, 3).float(), E.reshape(-1, 4, 4).float(),
+                                                                H, W)
+    elif sh_branch:
+        if len(camera) != 4:
+            raise AmavError("render_batch: args.rgb=False needs camera=(viewmatrix, projmatrix, tanfov, campos), the "
+                            "4-tuple of ops.camera_from_intrinsics; the colours depend on the camera centre")
+        view, proj, tanfov, campos = camera
     else:  # (viewmatrix, projmatrix, tanfov) already built from these K / E
         view, proj, tanfov = camera
     xyz, rot = _flat(gaussians["xyz"], 3), _flat(gaussians["rot"], 4)
-    scale, opacity, color = _flat(gaussians["scale"], 3), _flat(gaussians["opacity"], 1), _flat(gaussians["color"], 3)
+    scale, opacity = _flat(gaussians["scale"], 3), _flat(gaussians["opacity"], 1)
     if xyz.shape[0] != B * T:
         raise AmavError(f"render_batch: {xyz.shape[0]} Gaussian sets for B*T = {B * T} cameras")
     bg = [1.0, 1.0, 1.0] if bg_color is None else [float(c) for c in bg_color]
     activate = True
     if debug and decode is not None:
         raise AmavError("render_batch: debug replaces the attributes; decode the Gaussians first")
-    if debug:  # renderer.py:535-537
-        scale = torch.full_like(scale, 0.01)
-        opacity = torch.full_like(opacity, 0.1)
-        color = color.clamp(0.0, 1.0)
+    if sh_branch:
+        degree, width = int(getattr(args, "sh_degree", 3)), gaussians["color"].shape[-1]
+        need = (degree + 1) ** 2
+        if width % 3 != 0 or width // 3 < need:
+            raise AmavError(f"render_batch: args.rgb=False with sh_degree={degree} needs gaussians['color'] of 3 * K "
+                            f"channels with K >= (sh_degree+1)^2 = {need} (eval_sh, graphic_utils.py:721-722); "
+                            f"got {width} channels")
+        sh = _flat(gaussians["color"], width)
+        # renderer.py:532-537: the activations as torch ops (differentiable by autograd where a gradient is asked for)
+        if debug:
+            scale, opacity = torch.full_like(scale, 0.01), torch.full_like(opacity, 0.1)
+        else:
+            scale = torch.clamp_max(torch.exp(scale - ops.SCALE_BIAS), ops.SCALE_MAX)
+            opacity = torch.sigmoid(opacity - ops.OPACITY_BIAS)
         activate = False
+        if _needs_grad(xyz, rot, scale, opacity, sh):
+            color = ops.sh_colors_differentiable(xyz, sh, campos, degree)
+        else:
+            color = ops.sh_colors(xyz, sh, campos, degree)
+    else:
+        color = _flat(gaussians["color"], 3)
+        if debug:  # renderer.py:535-537
+            scale = torch.full_like(scale, 0.01)
+            opacity = torch.full_like(opacity, 0.1)
+            color = color.clamp(0.0, 1.0)
+            activate = False
     if _needs_grad(xyz, rot, scale, opacity, color):
         # differentiable path (ops.rasterize_differentiable): same images, owns its workspace
         refused = [n for n, v in (("workspace", workspace), ("out_rgba", out_rgba), ("wire", wire), ("decode", decode))
@@ -1047,9 +1100,12 @@ class GaussianRasterizer(nn.Module):
     """`GaussianRasterizer(raster_settings)(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
     cov3D_precomp)` -> (color [3,H,W], radii [N] int32, inv_depth [1,H,W]); inputs already activated.
 
-    Differentiable in means3D, rotations, scales, opacities and colors_precomp when grad mode is on and one of them
-    requires grad (ops.rasterize_differentiable).  inv_depth and radii carry no gradient, and means2D is not used:
-    its .grad stays None (no screen-space densification statistics)."""
+    The colours are either `colors_precomp` [N,3] or `shs` [N,K,3] (K >= (sh_degree+1)^2): spherical-harmonic
+    coefficients evaluated at raster_settings.sh_degree from raster_settings.campos (ops.sh_colors); passing both or
+    neither raises NotImplementedError.
+    Differentiable in means3D, rotations, scales, opacities and colors_precomp / shs when grad mode is on and one of them
+    requires grad (ops.rasterize_differentiable, ops.sh_colors_differentiable).  inv_depth and radii carry no gradient,
+    and means2D is not used: its .grad stays None (no screen-space densification statistics)."""
 
     def __init__(self, raster_settings):
         super().__init__()
@@ -1058,12 +1114,23 @@ class GaussianRasterizer(nn.Module):
     def forward(self, means3D, means2D=None, shs=None, colors_precomp=None, opacities=None, scales=None,
                 rotations=None, cov3D_precomp=None):
         s = self.raster_settings
-        if colors_precomp is None or shs is not None:
-            raise NotImplementedError("only colors_precomp is supported (the reference never passes shs, "
-                                      "renderer.py:561-562)")
+        if (colors_precomp is None) == (shs is None):
+            raise NotImplementedError("pass either colors_precomp or shs, not both and not neither (as "
+                                      "diff_gaussian_rasterization requires)")
         if cov3D_precomp is not None or scales is None or rotations is None:
             raise NotImplementedError("cov3D_precomp is not supported (the reference passes None, renderer.py:566)")
         dev = means3D.device
+        if shs is not None:  # upstream's SH path: colours from shs [N,K,3] at settings.sh_degree, seen from settings.campos
+            if s.campos is None:
+                raise AmavError("GaussianRasterizer: shs= needs raster_settings.campos (the camera centre)")
+            if shs.dim() != 3 or shs.shape[2] != 3:
+                raise AmavError(f"GaussianRasterizer: shs {tuple(shs.shape)}, expected [N,K,3]")
+            campos = s.campos.reshape(1, 3).float()
+            if _needs_grad(means3D, shs):
+                colors_precomp = ops.sh_colors_differentiable(means3D[None].float(), shs[None].float(), campos,
+                                                              int(s.sh_degree))[0]
+            else:
+                colors_precomp = ops.sh_colors(means3D[None].float(), shs[None].float(), campos, int(s.sh_degree))[0]
         if _needs_grad(means3D, rotations, scales, opacities, colors_precomp):
             if s.antialiasing:
                 raise NotImplementedError("the rasterizer has no backward for antialiasing=True")

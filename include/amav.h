@@ -89,7 +89,7 @@ typedef struct amav_raster_args {
     amav_attr rotations; /* 4 floats: unit quaternion (w,x,y,z); NOT normalised here (renderer.py:333 did it) */
     amav_attr scales;    /* 3 floats */
     amav_attr opacities; /* 1 float  */
-    amav_attr colors;    /* 3 floats (colors_precomp; the SH branch of the reference is dead code) */
+    amav_attr colors;    /* 3 floats (colors_precomp; colours from SH coefficients come from amav_sh_colors below) */
     const float *viewmatrix; /* device [F,16] */
     const float *projmatrix; /* device [F,16] */
     const float *tanfov;     /* device [F,2]  */
@@ -167,6 +167,33 @@ typedef struct amav_raster_backward_args {
 } amav_raster_backward_args;
 size_t amav_rasterize_backward_bytes(int num_frames, int num_gaussians, int64_t max_frame_instances);
 int amav_rasterize_backward(const amav_raster_args *fwd, const amav_raster_backward_args *bwd, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * View-dependent colours from spherical-harmonic coefficients: the SH branch of render_one (src/models/renderer.py:
+ * 540-545 with eval_sh, src/utils/graphic_utils.py:707-762), which the reference's own 3-channel colour head never
+ * reaches but a caller with 3 * (degree+1)^2 colour channels does.  For every frame f and Gaussian i
+ *     d = (p - campos[f]) / |p - campos[f]|,   colours[f,i,c] = max(sum_k B_k(d) * sh[k][c] + 0.5, 0)
+ * with the real SH basis of degree 0..4 in the reference's order and signs; there is no clamp at 1.  The result is what
+ * amav_raster_args.colors takes with apply_activations = 0.  A Gaussian exactly at the camera centre gives NaN, as in
+ * the reference (the rasterizer culls it at the near plane).
+ * amav_sh_colors_backward: grad_sh[f,i,k*3+c] = gate * grad_colors[f,i,c] * B_k(d) with gate = (the value before the
+ * clamp > 0), replayed with the forward's own arithmetic; coefficients k >= (degree+1)^2 are written as zeros, so the
+ * buffer needs no initialisation.  grad_means3d (may be NULL) goes through d(d)/d(p) = (I - d d^T) / |p - campos|.
+ * Both gradients are dense rows per frame: a frame-stride-0 input gets one row per frame and the caller sums them, as
+ * for amav_rasterize_backward.  campos gets no gradient.
+ * No workspace, no allocation, no host synchronisation, no atomics: bitwise the same results from run to run.
+ * Refused (AMAV_ERR_INVALID_ARG, before any launch): negative counts, degree outside 0..4, num_coeffs < (degree+1)^2, an
+ * element stride below the attribute's width, a NULL required pointer.  num_frames = 0 or num_gaussians = 0 return 0. */
+typedef struct amav_sh_args {
+    int32_t num_frames, num_gaussians, degree, num_coeffs; /* degree 0..4; num_coeffs stored per Gaussian >= (degree+1)^2 */
+    amav_attr means3d;   /* 3 floats */
+    amav_attr sh;        /* 3 * num_coeffs floats, coefficient-major: coefficient k, channel c at k * 3 + c (the layout of
+                            colors.reshape(N,-1,3) at renderer.py:541 and of upstream's shs [N,K,3]) */
+    const float *campos; /* device [F,3], from amav_camera_from_intrinsics */
+} amav_sh_args;
+int amav_sh_colors(const amav_sh_args *a, float *colors_dev, void *stream);
+int amav_sh_colors_backward(const amav_sh_args *a, const float *grad_colors_dev, float *grad_sh_dev,
+                            float *grad_means3d_dev, void *stream);
 
 /* amav_triplane_sample_decode_indexed + amav_rasterize_forward in one call: the packed Gaussian records are decoded
  * from the inputs below into the buffer the attributes of `args` view -- which must be the packed views
