@@ -14,7 +14,9 @@
 // staged once in LDS (50 176 B) and read by all 49 taps; coordinates outside the plane are written as zero, never loaded,
 // so planes cannot bleed into each other.
 //
-// Summation orders.  Convolution: bias, then the taps in (ky, kx) order, one fma each.  LayerNorm statistics: the lane's
+// Summation orders.  Convolution: the taps in (ky, kx) order from +0, one fma each, then the bias -- added last, as the
+// library does: with the bias first, a bias far above the tap sum costs every one of the 49 roundings the bias's ulp (found
+// at a bias of 8: 5.6e-7 of max |y| against the library's 1e-7).  LayerNorm statistics: the lane's
 // chunks ascending, then the xor butterfly (32, 16, .., 1) -- add_layernorm_kernel's two-pass form.  Parameter gradients:
 // two stages, amav_rows_colsum's scheme with another first-stage unit: LayerNorm's dweight / dbias over chunks of 16 rows
 // (ascending rows, then ascending chunks); the depthwise dweight / dbias over the 8 x 8 tiles (inside a tile: the wave's
@@ -164,7 +166,7 @@ __global__ __launch_bounds__(256) void dwconv7_layernorm_kernel(int H, int W, in
             const int row = 2 * wave + r;
             float a[kTile];
 #pragma unroll
-            for (int o = 0; o < kTile; ++o) a[o] = bias;
+            for (int o = 0; o < kTile; ++o) a[o] = 0.f;
 #pragma unroll
             for (int ky = 0; ky < 7; ++ky) {
                 float in[kHalo];
@@ -176,7 +178,7 @@ __global__ __launch_bounds__(256) void dwconv7_layernorm_kernel(int H, int W, in
                     for (int o = 0; o < kTile; ++o) a[o] = fmaf(wr[ky * 7 + kx], in[o + kx], a[o]);
             }
 #pragma unroll
-            for (int o = 0; o < kTile; ++o) acc[r][o][v] = a[o];
+            for (int o = 0; o < kTile; ++o) acc[r][o][v] = a[o] + bias;
         }
     }
     float lw[kVec], lb[kVec];

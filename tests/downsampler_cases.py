@@ -17,10 +17,10 @@ import torch.nn.functional as F
 ORDER_FACTOR = 4.0
 # kind -> the library's fp32 error against the fp64 restatement (relative to max |reference|), measured as described above
 LIBRARY_ERR = {         # library fp32: CPU / MI355X      HIP kernels on the MI355X
-    "conv": 3e-7,       # 2.8e-7 / 2.7e-7                 3.1e-7   depthwise 7x7 + bias
+    "conv": 3e-7,       # 2.8e-7 / 2.7e-7                 2.8e-7   depthwise 7x7 + bias
     "norm": 4e-7,       # 2.4e-7 / 3.5e-7                 2.7e-7   ... + LayerNorm
     "gelu": 2e-7,       # 1.0e-7 / 6.2e-8                 6.2e-8   gelu(proj + bias)
-    "block": 3e-6,      # 2.5e-6 / 8.6e-7                 7.4e-7   the downsampler after one / two blocks and after the
+    "block": 3e-6,      # 2.5e-6 / 8.6e-7                 8.6e-7   the downsampler after one / two blocks and after the
     #                                                              strided convolution, fp32 GEMMs (C = 64 fixture, C = 256)
     "dx": 3e-7,         # 2.1e-7 / 2.6e-7                 2.1e-7   d input of dwconv + LayerNorm
     "dparam": 5e-7,     # 4.9e-7 / 3.7e-7                 2.2e-7   d dwconv weight / bias, d LayerNorm weight / bias, d GELU bias
@@ -222,4 +222,115 @@ def measure_library(device="cpu"):
     got = module_grads(to(p, torch.float32, device), x, g)
     for k in want:
         up("dmodule", got[k], want[k])
+    return err
+
+
+# ---------------------------------------------------------------- every built width, off-square tile grids, magnitudes
+# The second case list of the stencil (tests/test_stage1_downsampler_widths_gpu.py; its conditions are asserted on the
+# CPU by tests/test_stage1_downsampler_cases.py).  A case is (group, (K, H, W, C), options of wide_case as sorted pairs).
+#   widths  every instantiation V = C / 64 = 1..8 on 19 x 27: a 3 x 4 tile grid, ragged on both axes, whose tiles (1, 1) and
+#           (1, 2) have their whole 14 x 14 halo inside the plane; 12 tiles = one unrolled-by-8 pass of sum_parts_kernel and
+#           a tail of three.  27 x 19 is the transpose.  17 x 17: 9 tiles (the unrolled body once, an empty tail) and 289
+#           rows (the last LayerNorm chunk of 16 holds one row); K = 3 of them: 27 tiles across planes.
+#   eps     var(y) ~ 1e-6 = eps: inputs x 1e-3, dwconv bias x 1e-4
+#   large   inputs x 1e3, dwconv bias x 1e2
+#   offset  dwconv bias 8 + 0.1 randn: |row mean| > 5 standard deviations, the cancellation of a one-pass variance
+MAGNITUDES = {
+    "eps": (("b_scale", 1e-4), ("eps", 1e-6), ("x_scale", 1e-3)),
+    "large": (("b_scale", 1e2), ("x_scale", 1e3)),
+    "offset": (("b_offset", 8.0),),
+}
+WIDE_GROUPS = ("widths", "eps", "large", "offset")
+WIDE_KINDS = ("conv", "norm", "dx", "dparam")
+WIDE_CASES = ([("widths", (1, 19, 27, C), ()) for C in range(64, 513, 64)]
+              + [("widths", (1, 27, 19, 192), ()), ("widths", (1, 17, 17, 64), ()), ("widths", (3, 17, 17, 128), ())]
+              + [(group, (1, 9, 13, C), MAGNITUDES[group]) for group in ("eps", "large", "offset") for C in (64, 192, 512)])
+
+# (group, kind) -> the library's fp32 error against the fp64 restatement over the group's cases, measured by
+# measure_library_wide() on the CPU and on the MI355X; the larger of the two, rounded up to one digit.  A test's bound is
+# the figure x ORDER_FACTOR (bound_wide).  None of it comes from the HIP kernels, whose errors stand beside for comparison.
+LIBRARY_ERR_WIDE = {                # library fp32: CPU / MI355X      HIP kernels on the MI355X
+    ("widths", "conv"): 4e-7,       # 2.8e-7 / 3.1e-7                   2.8e-7
+    ("widths", "norm"): 5e-7,       # 4.6e-7 / 3.2e-7                   3.2e-7
+    ("widths", "dx"): 4e-7,         # 3.3e-7 / 3.1e-7                   3.2e-7
+    ("widths", "dparam"): 1e-6,     # 9.0e-7 / 9.8e-7                   2.6e-7
+    ("eps", "conv"): 3e-7,          # 2.3e-7 / 2.4e-7                   2.3e-7
+    ("eps", "norm"): 3e-7,          # 2.8e-7 / 2.7e-7                   3.2e-7
+    ("eps", "dx"): 3e-7,            # 2.1e-7 / 2.5e-7                   2.3e-7
+    ("eps", "dparam"): 6e-7,        # 2.8e-7 / 5.2e-7                   2.0e-7
+    ("large", "conv"): 3e-7,        # 2.6e-7 / 2.1e-7                   2.6e-7
+    ("large", "norm"): 3e-7,        # 2.8e-7 / 2.7e-7                   2.8e-7
+    ("large", "dx"): 3e-7,          # 2.6e-7 / 2.3e-7                   2.5e-7
+    ("large", "dparam"): 6e-7,      # 3.2e-7 / 5.2e-7                   1.5e-7
+    ("offset", "conv"): 1e-7,       # 9.1e-8 / 9.9e-8                   9.1e-8   (5.6e-7 with the bias first)
+    ("offset", "norm"): 3e-6,       # 6.6e-7 / 2.6e-6                   6.8e-7   (the library on the MI355X: 4x the CPU's)
+    ("offset", "dx"): 7e-7,         # 3.2e-7 / 6.4e-7                   2.5e-7
+    ("offset", "dparam"): 6e-6,     # 7.3e-7 / 5.1e-6                   6.3e-7   (... 7x the CPU's)
+}
+# bias + GELU at the product's inner = 4 C = 1024 and at inner = 12 (no multiple of 8: fp32 output only).  The library's
+# fp32 error there is inside LIBRARY_ERR's gelu / dgelu / dparam entries, which therefore apply unchanged:
+#   gelu 8.8e-8 / 6.6e-8; 6.6e-8      dgelu 1.5e-7 / 8.6e-8; 8.6e-8      dparam (d bias) 1.3e-7 / 1.4e-7; 1.5e-7
+#   (library fp32 on the CPU / on the MI355X; the HIP kernels on the MI355X)
+GELU_WIDE = ((67, 1024), (5, 12))
+
+
+def bound_wide(group, kind):
+    return LIBRARY_ERR_WIDE[group, kind] * ORDER_FACTOR
+
+
+def case_id(case):
+    group, shape, _ = case
+    return group + "-" + "x".join(map(str, shape))
+
+
+@functools.lru_cache(maxsize=None)
+def wide_tensors(K, H, W, C, x_scale=1.0, b_scale=1.0, b_offset=0.0, eps=1e-6, seed=100):
+    x = randn(seed + 1, K, H, W, C, scale=x_scale)
+    dw_w = randn(seed + 2, C, 1, 7, 7, scale=1.0 / 7)
+    dw_b = b_offset + randn(seed + 3, C, scale=0.1 * b_scale)
+    ln_w, ln_b = 1.0 + randn(seed + 4, C, scale=0.1), randn(seed + 5, C, scale=0.1)
+    args = (x, dw_w, dw_b, ln_w, ln_b)
+    g = randn(seed + 6, K * H * W, C)
+    leaves = [t.double().requires_grad_(True) for t in args]
+    y, n = dwconv_norm(*leaves, eps=eps)
+    n = n.reshape(-1, C)
+    grads = torch.autograd.grad(n, leaves, g.double())
+    return args, eps, (y.detach(), n.detach()), g, tuple(t.detach() for t in grads)
+
+
+def wide_case(case):
+    """A case of WIDE_CASES -> (fp32 inputs (x, dw_w, dw_b, ln_w, ln_b), eps, fp64 (y, norm rows), grad_norm fp32, fp64
+    gradients (dx, d dw_w, d dw_b, d ln_w, d ln_b)), generated like dw_case / dw_backward_case -- computed once, shared,
+    never modified."""
+    _, shape, options = case
+    return wide_tensors(*shape, **dict(options))
+
+
+def library_wide(case, device="cpu"):
+    """The library's fp32 evaluation of a case: {kind: (results, fp64 references)}."""
+    args, eps, (y, n), g, want = wide_case(case)
+    leaves = [t.to(device).requires_grad_(True) for t in args]
+    ly, ln = dwconv_norm(*leaves, eps=eps)
+    ln = ln.reshape(n.shape)
+    grads = torch.autograd.grad(ln, leaves, g.to(device))
+    return {"conv": ([ly], [y]), "norm": ([ln], [n]), "dx": (grads[:1], want[:1]), "dparam": (grads[1:], want[1:])}
+
+
+def measure_library_wide(device="cpu"):
+    """{(group, kind): the library's fp32 error against the fp64 restatement, the largest over the group's cases} on
+    `device`, and under ("gelu", kind) the same for GELU_WIDE."""
+    err = {}
+    up = lambda key, got, want: err.__setitem__(key, max(err.get(key, 0.0), rel_err(got, want)))
+    for case in WIDE_CASES:
+        for kind, (got, want) in library_wide(case, device).items():
+            for a, b in zip(got, want):
+                up((case[0], kind), a, b)
+    for rows, inner in GELU_WIDE:
+        (proj, bias, g), (out, d_proj, d_bias) = gelu_case(rows, inner)
+        leaves = [proj.to(device).requires_grad_(True), bias.to(device).requires_grad_(True)]
+        lo = gelu_bias(*leaves)
+        lp, lb = torch.autograd.grad(lo, leaves, g.to(device))
+        up(("gelu", "gelu"), lo, out)
+        up(("gelu", "dgelu"), lp, d_proj)
+        up(("gelu", "dparam"), lb, d_bias)
     return err

@@ -7,7 +7,7 @@ F.layer_norm, F.gelu and their autograd; the larger of the CPU and the MI355X me
 the cases of this file (downsampler_cases.measure_library; every test prints its own figure):
 
     kind     library fp32, CPU   library fp32, MI355X   HIP kernels, MI355X   bound
-    conv         2.8e-7              2.7e-7                 3.1e-7             1.2e-6
+    conv         2.8e-7              2.7e-7                 2.8e-7             1.2e-6
     norm         2.4e-7              3.5e-7                 2.7e-7             1.6e-6
     gelu         1.0e-7              6.2e-8                 6.2e-8             8.0e-7
     dx           2.1e-7              2.6e-7                 2.1e-7             1.2e-6

@@ -5,8 +5,10 @@ resolution, and TriplaneGaussianAvatar.training_step through the downsampler's H
 Bounds.  With fp32 library GEMMs (AMAV_GEMM=f32) the `block` bound of tests/downsampler_cases.py: the library's fp32
 error against the fp64 restatement (forward: CPU 2.5e-6, MI355X 8.6e-7, bound 1.2e-5; gradients of the whole module at
 C = 256: CPU 1.7e-6, MI355X 1.8e-6, bound 8e-6) times 4 -- plus that error once more against a reference-run fp32 vector.
-Measured for the HIP path on the MI355X: 1.2e-6 against the fixture, 7.4e-7 at C = 256, gradients up to 1.9e-6 (pwconv2's
-weight, a library GEMM).  With the
+Measured for the HIP path on the MI355X: 1.3e-6 against the fixture, 8.6e-7 at C = 256, gradients up to 1.9e-6 (pwconv2's
+weight, a library GEMM).  The two module cases added for the pass split and for a width without kernels (C = 64, 27
+planes of 6 x 6; C = 32, 12 x 12) stay inside the same figures: the library measures 1.1e-6 / 7.2e-7 (forward) and 1.2e-6 /
+1.2e-6 (gradients) at the first and 1.2e-6 / 1.1e-6 at the second (CPU / MI355X); the HIP path 3.5e-7 and 1.0e-6.  With the
 products as bf16 x 3 split GEMMs (the inference default) the project's bound for that path, 2e-5 relative to the output
 scale (close() of tests/test_stage1_gpu.py, as for the encoder and the transformer stack there)."""
 from types import SimpleNamespace
@@ -231,3 +233,82 @@ def test_training_step_reaches_the_downsampler_and_is_deterministic():
     sd = model.state_dict()
     assert "smplx_triplane_encoder.triplane_downsampler.down.weight" in sd
     model.load_state_dict({k: v.clone() for k, v in sd.items()}, strict=True)
+
+
+def _grads(ds, leaf):
+    return dict([("input", leaf.grad)] + [(n, q.grad.clone()) for n, q in ds.named_parameters()])
+
+
+def test_more_than_one_pass_is_the_concatenation_of_its_passes(monkeypatch):
+    """C = 64, factor 3, nine frames of 6 x 6 planes: K = 27 planes, so forward_planes cuts at 3 * 8 = 24.  The output, and
+    under autograd the input gradient, equal the module applied to frames 0-7 and to frame 8 on their own bit for bit;
+    the parameter gradients (sums over both passes) meet the `dmodule` bound against fp64 autograd of the restatement."""
+    from audio_motion_avatar_amd import triplane_net
+
+    frames, cut = 9, 3 * triplane_net.DOWNSAMPLER_FRAMES_PER_PASS
+    p, x, want = dc.module_case(C=64, R=2, factor=3, frames=frames)
+    assert x.shape == (27, 6, 6, 64) and cut == 24 < x.shape[0]
+    ds = _module(dict(triplane_feature_dim=64, upsample_factor=3), {k: list(v.shape) for k, v in p.items()},
+                 "triplane_downsampler.")
+    monkeypatch.setenv("AMAV_GEMM", "f32")
+    xc = x.cuda()
+    passes, real = [], ds.blocks[0].forward_planes
+
+    def counted(part, *a, **k):
+        passes.append(part.shape[0])
+        return real(part, *a, **k)
+
+    monkeypatch.setattr(ds.blocks[0], "forward_planes", counted)
+    with torch.no_grad():
+        y = ds(xc)
+        assert passes == [24, 3]
+        parts = [ds(xc[:cut].contiguous()), ds(xc[cut:].contiguous())]
+    assert y.shape == (27, 2, 2, 64) and torch.equal(y, torch.cat(parts))
+    _check("block", y, want[2], "hip, two passes")
+    # the reference's layout splits at the same frame
+    with torch.no_grad():
+        x5 = xc.view(frames, 3, 6, 6, 64).permute(0, 1, 4, 2, 3)
+        assert torch.equal(dc.planes_of(ds(x5)), y)
+    g = dc.randn(42, *want[2].shape)
+    want_grads = dc.module_grads(dc.to(p, torch.float64), x, g)
+    gc = g.cuda()
+    leaf = xc.clone().requires_grad_(True)
+    ds.zero_grad(set_to_none=True)
+    del passes[:]
+    out = ds(leaf)
+    assert passes == [24, 3] and torch.equal(out.detach(), y)
+    out.backward(gc)
+    got = _grads(ds, leaf)
+    halves = []
+    for part, gpart in ((xc[:cut], gc[:cut]), (xc[cut:], gc[cut:])):
+        part_leaf = part.clone().requires_grad_(True)
+        ds.zero_grad(set_to_none=True)
+        ds(part_leaf).backward(gpart.contiguous())
+        halves.append(part_leaf.grad)
+    assert torch.equal(got["input"], torch.cat(halves))
+    assert set(got) == set(want_grads)
+    for k in want_grads:
+        _check("dmodule", got[k], want_grads[k], f"hip, two passes, d {k}")
+
+
+def test_a_width_the_kernels_are_not_built_for_takes_the_library(monkeypatch):
+    """C = 32: ops.dwconv7_channels_ok refuses it, the module evaluates the library's operators on the GPU and meets the
+    `block` bound; none of the downsampler's kernels is called."""
+    from audio_motion_avatar_amd import ops
+
+    p, x, want = dc.module_case(C=32, R=4, factor=3)
+    ds = _module(dict(triplane_feature_dim=32, upsample_factor=3), {k: list(v.shape) for k, v in p.items()},
+                 "triplane_downsampler.")
+    assert not ops.dwconv7_channels_ok(32) and not ds._hip(x.cuda())
+
+    def refuse(*a, **k):
+        raise AssertionError("a HIP kernel of the downsampler ran at C = 32")
+
+    for name in ("dwconv7_layernorm", "dwconv7_layernorm_differentiable", "gelu_bias", "gelu_bias_differentiable",
+                 "patch4_gather", "patch4_gather_differentiable"):
+        monkeypatch.setattr(ops, name, refuse)
+    monkeypatch.setenv("AMAV_GEMM", "f32")
+    with torch.no_grad():
+        y = ds(x.cuda())
+    assert y.shape == want[2].shape == (3, 4, 4, 32)
+    _check("block", y, want[2], "library path on the GPU, C = 32")
