@@ -45,6 +45,28 @@ inline bool aligned16(const P *...p) {
     return ((... | reinterpret_cast<uintptr_t>(p)) & 15) == 0;
 }
 
+// The caller's workspace holds `need` bytes and is 16-byte aligned (the codecs' common check and message).
+inline int check_workspace(const char *who, size_t need, const void *workspace, size_t workspace_bytes) {
+    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15))
+        return fail(AMAV_ERR_WORKSPACE, "%s: workspace %zu < %zu (or NULL / not 16-byte aligned)", who,
+                    workspace ? workspace_bytes : (size_t)0, need);
+    return AMAV_OK;
+}
+
+// What the decoders take next to their frames: a byte stream, 8-byte aligned records and 4-byte aligned status words.
+inline int check_stream_args(const char *who, const void *stream, int64_t stream_bytes, const void *records, const void *status) {
+    AMAV_REQUIRE(stream && records && status, "%s: NULL stream, records or status", who);
+    AMAV_REQUIRE(stream_bytes >= 0, "%s: negative stream_bytes", who);
+    AMAV_REQUIRE((reinterpret_cast<uintptr_t>(records) & 7) == 0 && (reinterpret_cast<uintptr_t>(status) & 3) == 0,
+                 "%s: misaligned records or status", who);
+    return AMAV_OK;
+}
+
+// The 8-bit level of a colour sample: clamp to [0, 1], x 255, truncate (the reference's `(frame * 255).astype(np.uint8)`).
+// Raw rgb24 frames, the tile wire format (packed here or emitted by the rasterizer), the JPEG encoder's input and PNG
+// rounding="truncate" all call this one function, which is why they agree bit for bit.
+__host__ __device__ __forceinline__ unsigned char quant8(float v) { return (unsigned char)(fminf(fmaxf(v, 0.f), 1.f) * 255.0f); }
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));  // a 32x32 MFMA accumulator
 
 // Tile-sparse wire format of the frame exchange (frames.hip has the description): shared with the rasterizer, which can

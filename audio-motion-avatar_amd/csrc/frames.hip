@@ -18,9 +18,9 @@ __global__ __launch_bounds__(256) void rgba_to_rgb8_kernel(size_t quads, const f
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const float4 p = rgba[q * 4 + k];
-        b[k * 3 + 0] = (unsigned char)(fminf(fmaxf(p.x, 0.f), 1.f) * 255.0f);
-        b[k * 3 + 1] = (unsigned char)(fminf(fmaxf(p.y, 0.f), 1.f) * 255.0f);
-        b[k * 3 + 2] = (unsigned char)(fminf(fmaxf(p.z, 0.f), 1.f) * 255.0f);
+        b[k * 3 + 0] = quant8(p.x);
+        b[k * 3 + 1] = quant8(p.y);
+        b[k * 3 + 2] = quant8(p.z);
     }
     uint3 w;
     w.x = b[0] | (b[1] << 8) | (b[2] << 16) | ((unsigned)b[3] << 24);
@@ -40,8 +40,6 @@ __global__ __launch_bounds__(256) void rgba_to_rgb8_kernel(size_t quads, const f
 //         `count` > `cap` tells every receiver (unpack raises its overflow flag; the caller re-packs with more room).
 // unpack: every tile of every gathered buffer is written back into dense [frames, H, W, 3] uint8.
 constexpr int kTileBytes = kWireTileBytes;  // header constants: amav_common.h
-
-__device__ __forceinline__ unsigned char quant8(float v) { return (unsigned char)(fminf(fmaxf(v, 0.f), 1.f) * 255.0f); }
 
 struct TileGeom {
     int f, x0, y, cq;  // frame, first pixel column of this lane's quad, pixel row, quad column inside the tile
@@ -354,10 +352,7 @@ extern "C" size_t amav_frames_wire_bytes(int F, int H, int W, int64_t cap_tiles)
     return (wire_payload_at(F, (int)tiles) + (size_t)cap_tiles * kTileBytes + 15) / 16 * 16;
 }
 
-static unsigned pack_bg(const float *bg) {
-    auto q = [](float v) { return (unsigned)(unsigned char)(std::fmin(std::fmax(v, 0.f), 1.f) * 255.0f); };
-    return q(bg[0]) | (q(bg[1]) << 8) | (q(bg[2]) << 16);
-}
+static unsigned pack_bg(const float *bg) { return quant8(bg[0]) | (quant8(bg[1]) << 8) | (quant8(bg[2]) << 16); }
 
 extern "C" int amav_frames_pack_tiles(int F, int H, int W, const float *rgba, const float *bg_host3,
                                       const int32_t *tile_hint, int64_t cap_tiles, void *wire, size_t wire_bytes,

@@ -43,10 +43,9 @@ struct HeaderBytes {
 __device__ const CodeTable d_dc_codes[2] = {make_code_table(kDcBits[0], kDcVals), make_code_table(kDcBits[1], kDcVals)};
 __device__ const CodeTable d_ac_codes[2] = {make_code_table(kAcBits[0], kAcVals[0]),
                                             make_code_table(kAcBits[1], kAcVals[1])};
-__device__ const ZigzagPos d_zigzag_pos = make_zigzag_pos();  // natural index -> position in the scan
 
 // ------------------------------------------------------------------------------------------------------ transform
-__device__ __forceinline__ float quant8f(float v) { return (float)(unsigned char)(fminf(fmaxf(v, 0.f), 1.f) * 255.0f); }
+__device__ __forceinline__ float quant8f(float v) { return (float)quant8(v); }
 
 // pixel (clamped to the image: a partial MCU replicates the last column / row) as 8-bit values in floats
 __device__ __forceinline__ void load_rgb(const float4 *__restrict__ px, size_t at, float &r, float &g, float &b) {
@@ -174,7 +173,6 @@ __global__ __launch_bounds__(256) void jpeg_transform_kernel(Geom g, const Px *_
 // -------------------------------------------------------------------------------------------------------- entropy
 constexpr int kRound = 64;                                          // blocks per round: one per lane
 constexpr int kBitWords = (kRound * kMaxBlockBits + 31) / 32 + 8;   // + the carried byte and the spill word
-constexpr int kLevelStride = 66;                                    // shorts per staged block: 33 words, conflict-free
 
 struct BitCursor {
     unsigned *bits;
@@ -453,8 +451,6 @@ static Workspace carve(const Geom &g, void *base) {
     return w;
 }
 
-static float quant8_host(float v) { return (float)(unsigned char)(std::fmin(std::fmax(v, 0.f), 1.f) * 255.0f); }
-
 // stage (a): levels of every block; const_levels (3 x 64 shorts, device) is needed with a hint only
 static void launch_transform(const Geom &g, const void *frames, int rgba_f32, const QuantTables &qt, const int32_t *hint,
                             const float *bg3, short *const_levels, short *levels, hipStream_t stream) {
@@ -462,7 +458,7 @@ static void launch_transform(const Geom &g, const void *frames, int rgba_f32, co
     const unsigned grid = (unsigned)((total + 31) / 32);
     float bg[3] = {255.f, 255.f, 255.f};
     if (hint) {
-        for (int c = 0; c < 3; ++c) bg[c] = quant8_host(bg3[c]);
+        for (int c = 0; c < 3; ++c) bg[c] = (float)quant8(bg3[c]);
         jpeg_transform_kernel<uint8_t, true><<<1, 256, 0, stream>>>(g, nullptr, qt, nullptr, bg[0], bg[1], bg[2], nullptr,
                                                                    const_levels, 3);
     }
@@ -549,9 +545,7 @@ extern "C" int amav_jpeg_encode(int F, int H, int W, const void *frames, int fra
     AMAV_REQUIRE((reinterpret_cast<uintptr_t>(frame_offsets) & 7) == 0 && (reinterpret_cast<uintptr_t>(status) & 3) == 0,
                  "amav_jpeg_encode: misaligned frame_offsets or status");
     const Workspace ws = carve(g, workspace);
-    if (!workspace || workspace_bytes < ws.bytes || (reinterpret_cast<uintptr_t>(workspace) & 15))
-        return fail(AMAV_ERR_WORKSPACE, "amav_jpeg_encode: workspace %zu < %zu (or NULL / not 16-byte aligned)",
-                    workspace ? workspace_bytes : (size_t)0, ws.bytes);
+    if (int rc = check_workspace("amav_jpeg_encode", ws.bytes, workspace, workspace_bytes)) return rc;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     QuantTables qt;
     scaled_tables(quality, qt);

@@ -26,8 +26,8 @@
 namespace amav {
 namespace jpeg_decode {
 
-using jpeg::make_zigzag_pos;
-using jpeg::ZigzagPos;
+using jpeg::d_zigzag_pos;
+using jpeg::kLevelStride;
 
 struct Geom {
     int F, H, W;
@@ -37,8 +37,6 @@ struct Geom {
     int cw, ch;                      // one chroma plane as stored (whole blocks); 0 for one component
     int ccw, cch;                    // 4:2:0: the chroma plane proper, ceil(W/2) x ceil(H/2)
 };
-
-__device__ const ZigzagPos d_zigzag_pos = make_zigzag_pos();  // natural index -> position in the scan
 
 // MCUs per restart interval and intervals per frame of a record
 __device__ __forceinline__ int interval_mcus(const Geom &g, int ri) { return (ri <= 0 || ri >= g.mcus) ? g.mcus : ri; }
@@ -105,7 +103,6 @@ __global__ __launch_bounds__(64) void jpeg_marker_kernel(Geom g, const uint8_t *
 
 // -------------------------------------------------------------------------------------------------------- entropy
 constexpr int kLookBits = 9;
-constexpr int kLevelStride = 66;  // shorts per staged block: 33 words, so the lanes' rows start in different banks
 
 struct HuffmanLds {
     unsigned short look[6][1 << kLookBits];  // [component * 2 + class][next 9 bits] = length << 8 | symbol, 0: longer
@@ -467,18 +464,7 @@ static int check_common(const char *who, int F, int H, int W, int sampling, cons
     AMAV_REQUIRE(F >= 1 && F <= 65535 && H >= 1 && H <= 65535 && W >= 1 && W <= 65535,
                  "%s: sizes outside 1..65535 (F=%d H=%d W=%d)", who, F, H, W);
     AMAV_REQUIRE(make_geom(F, H, W, sampling, g), "%s: %d frames of %dx%d exceed the decoder's limits", who, F, W, H);
-    AMAV_REQUIRE(stream && records && status, "%s: NULL stream, records or status", who);
-    AMAV_REQUIRE(stream_bytes >= 0, "%s: negative stream_bytes", who);
-    AMAV_REQUIRE((reinterpret_cast<uintptr_t>(records) & 7) == 0 && (reinterpret_cast<uintptr_t>(status) & 3) == 0,
-                 "%s: misaligned records or status", who);
-    return AMAV_OK;
-}
-
-static int check_workspace(const char *who, const Workspace &ws, const void *workspace, size_t workspace_bytes) {
-    if (!workspace || workspace_bytes < ws.bytes || (reinterpret_cast<uintptr_t>(workspace) & 15))
-        return fail(AMAV_ERR_WORKSPACE, "%s: workspace %zu < %zu (or NULL / not 16-byte aligned)", who,
-                    workspace ? workspace_bytes : (size_t)0, ws.bytes);
-    return AMAV_OK;
+    return check_stream_args(who, stream, stream_bytes, records, status);
 }
 
 static void launch_levels(const Geom &g, const uint8_t *bytes, int64_t stream_bytes, const void *records, const Workspace &ws,
@@ -514,7 +500,7 @@ extern "C" int amav_jpeg_decode_levels(int F, int H, int W, int sampling, const 
     const size_t need = (size_t)F * g.bpf * 64 * sizeof(short);
     if (levels_bytes < need) return fail(AMAV_ERR_WORKSPACE, "%s: levels buffer %zu < %zu", who, levels_bytes, need);
     const Workspace ws = carve(g, true, workspace);
-    if (int rc = check_workspace(who, ws, workspace, workspace_bytes)) return rc;
+    if (int rc = check_workspace(who, ws.bytes, workspace, workspace_bytes)) return rc;
     launch_levels(g, bytes, stream_bytes, records, ws, static_cast<short *>(levels), status, static_cast<hipStream_t>(stream_));
     return check_launch(who);
 }
@@ -531,7 +517,7 @@ extern "C" int amav_jpeg_decode(int F, int H, int W, int sampling, const uint8_t
     const size_t need = (size_t)F * H * W * 3 * (layout == AMAV_JPEG_CHW_F32 ? sizeof(float) : 1);
     if (out_bytes < need) return fail(AMAV_ERR_WORKSPACE, "%s: output buffer %zu < %zu", who, out_bytes, need);
     const Workspace ws = carve(g, false, workspace);
-    if (int rc = check_workspace(who, ws, workspace, workspace_bytes)) return rc;
+    if (int rc = check_workspace(who, ws.bytes, workspace, workspace_bytes)) return rc;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     launch_levels(g, bytes, stream_bytes, records, ws, ws.levels, status, stream);
     const long long total = (long long)F * g.bpf, pixels = (long long)F * H * W;

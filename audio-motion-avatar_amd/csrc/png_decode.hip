@@ -11,16 +11,11 @@
 //             of the next.  Sub-byte pixels are unpacked, colour converted and the output layout written in the same pass.
 // No float atomics (the status words take integer atomicOr), no host synchronisation, no memset: a frame's pixels are
 // written by its own wave only.
-#include "amav_common.h"
+#include "png_common.h"
 #include "png_inflate_core.h"
 
 namespace amav {
 namespace png {
-
-struct InflateRecord {  // amav_inflate's record, 40 bytes
-    long long in_begin, in_end, out_begin, out_capacity;
-    int wrapper, reserved;
-};
 
 // channels of a colour type the decoder takes at this depth, else 0
 __device__ __forceinline__ int channels_of(int color_type, int depth) {
@@ -31,7 +26,7 @@ __device__ __forceinline__ long long row_bytes(int W, int channels, int depth) {
 
 // grid: one wave per stream.  frames == nullptr: amav_inflate's records; else PNG frames, stream f -> workspace frame f.
 __global__ __launch_bounds__(64) void png_inflate_kernel(const uint8_t *__restrict__ stream, long long stream_bytes,
-                                                        const InflateRecord *__restrict__ records,
+                                                        const amav_inflate_stream *__restrict__ records,
                                                         const amav_png_frame *__restrict__ frames, int H, int W,
                                                         long long frame_stride, uint8_t *__restrict__ out, long long out_bytes,
                                                         long long *__restrict__ produced, int *__restrict__ status) {
@@ -53,7 +48,7 @@ __global__ __launch_bounds__(64) void png_inflate_kernel(const uint8_t *__restri
         in_begin = r.zlib_begin, in_end = r.zlib_end;
         out_begin = (long long)n * frame_stride, cap = H * (1 + row_bytes(W, ch, r.bit_depth));
     } else {
-        const InflateRecord r = records[n];
+        const amav_inflate_stream r = records[n];
         in_begin = r.in_begin, in_end = r.in_end, out_begin = r.out_begin, cap = r.out_capacity, wrapper = r.wrapper != 0;
     }
     // whatever the record says, reads stay inside the stream buffer and writes inside the output buffer
@@ -69,12 +64,6 @@ __global__ __launch_bounds__(64) void png_inflate_kernel(const uint8_t *__restri
 }
 
 // ------------------------------------------------------------------------------------------------------- unfilter
-__device__ __forceinline__ unsigned paeth(unsigned a, unsigned b, unsigned c) {
-    const int p = (int)a + (int)b - (int)c;
-    const int pa = abs(p - (int)a), pb = abs(p - (int)b), pc = abs(p - (int)c);
-    return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
-}
-
 template <bool kChwF32>
 __device__ __forceinline__ void store_pixel(void *out, int mode_l, size_t f, int y, int x, int H, int W, unsigned R, unsigned G,
                                             unsigned B, bool grey) {
@@ -171,7 +160,7 @@ __global__ __launch_bounds__(64) void png_unfilter_kernel(int H, int W, const ui
                 for (int c = 0; c < bpp; ++c) {
                     const unsigned v = (raw[u] >> (8 * c)) & 255u, a = (left >> (8 * c)) & 255u, b = (above >> (8 * c)) & 255u,
                                    cc = (upleft >> (8 * c)) & 255u;
-                    const unsigned p = ft == 1 ? a : ft == 2 ? b : ft == 3 ? (a + b) >> 1 : ft == 4 ? paeth(a, b, cc) : 0u;
+                    const unsigned p = ft == 1 ? a : ft == 2 ? b : ft == 3 ? (a + b) >> 1 : ft == 4 ? (unsigned)paeth((int)a, (int)b, (int)cc) : 0u;
                     cur |= ((v + p) & 255u) << (8 * c);
                 }
                 left = cur, upleft = above, mine = cur;
@@ -207,16 +196,8 @@ __global__ __launch_bounds__(64) void png_unfilter_kernel(int H, int W, const ui
 }
 
 // ----------------------------------------------------------------------------------------------------------- host
-static bool sizes_ok(int F, int H, int W) { return F >= 1 && F <= 65535 && H >= 1 && H <= 16384 && W >= 1 && W <= 16384; }
 // one frame's inflated bytes at 4 bytes per pixel, a multiple of 16 so that every frame starts 16-byte aligned
 static long long frame_stride_of(int H, int W) { return (long long)align_up((size_t)H * (1 + 4 * (size_t)W), 16); }
-
-static int check_workspace(const char *who, size_t need, const void *workspace, size_t workspace_bytes) {
-    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15))
-        return fail(AMAV_ERR_WORKSPACE, "%s: workspace %zu < %zu (or NULL / not 16-byte aligned)", who,
-                    workspace ? workspace_bytes : (size_t)0, need);
-    return AMAV_OK;
-}
 
 }  // namespace png
 }  // namespace amav
@@ -224,25 +205,23 @@ static int check_workspace(const char *who, size_t need, const void *workspace, 
 using namespace amav;
 using namespace amav::png;
 
-static_assert(sizeof(amav_inflate_stream) == 40 && sizeof(InflateRecord) == 40, "amav_inflate_stream is packed by the host as 40 bytes");
-static_assert(sizeof(amav_png_frame) == 40, "amav_png_frame is packed by the host as 40 bytes");
 static_assert(inflate::kStatusInflate == AMAV_PNG_STATUS_INFLATE && inflate::kStatusSize == AMAV_PNG_STATUS_SIZE, "status bits");
 
 extern "C" size_t amav_inflate_workspace_bytes(int num_streams) {
-    return num_streams >= 1 && num_streams <= 65535 ? 256 : 0;  // the kernel keeps its state in LDS; one granule, unused
+    return num_streams >= 1 && num_streams <= kMaxFrames ? 256 : 0;  // the kernel keeps its state in LDS; one granule, unused
 }
 
 extern "C" int amav_inflate(int N, const uint8_t *bytes, int64_t stream_bytes, const void *records, uint8_t *out, int64_t out_bytes,
                             int64_t *produced, int32_t *status, void *workspace, size_t workspace_bytes, void *stream_) {
     const char *who = "amav_inflate";
-    AMAV_REQUIRE(N >= 1 && N <= 65535, "%s: num_streams %d outside 1..65535", who, N);
+    AMAV_REQUIRE(N >= 1 && N <= kMaxFrames, "%s: num_streams %d outside 1..65535", who, N);
     AMAV_REQUIRE(bytes && records && out && produced && status, "%s: NULL stream, records, out, produced or status", who);
     AMAV_REQUIRE(stream_bytes >= 0 && out_bytes >= 0, "%s: negative stream_bytes or out_bytes", who);
     AMAV_REQUIRE((reinterpret_cast<uintptr_t>(records) & 7) == 0 && (reinterpret_cast<uintptr_t>(produced) & 7) == 0 &&
                      (reinterpret_cast<uintptr_t>(status) & 3) == 0,
                  "%s: misaligned records, produced or status", who);
     if (int rc = check_workspace(who, amav_inflate_workspace_bytes(N), workspace, workspace_bytes)) return rc;
-    png_inflate_kernel<<<N, 64, 0, static_cast<hipStream_t>(stream_)>>>(bytes, stream_bytes, static_cast<const InflateRecord *>(records),
+    png_inflate_kernel<<<N, 64, 0, static_cast<hipStream_t>(stream_)>>>(bytes, stream_bytes, static_cast<const amav_inflate_stream *>(records),
                                                                        nullptr, 0, 0, 0, out, out_bytes,
                                                                        reinterpret_cast<long long *>(produced), status);
     return check_launch(who);
@@ -257,14 +236,11 @@ extern "C" int amav_png_decode(int F, int H, int W, const uint8_t *bytes, int64_
                                int layout, void *out, size_t out_bytes, int32_t *status, void *workspace, size_t workspace_bytes,
                                void *stream_) {
     const char *who = "amav_png_decode";
-    AMAV_REQUIRE(F >= 1 && F <= 65535, "%s: num_frames %d outside 1..65535", who, F);
-    AMAV_REQUIRE(H >= 1 && H <= 16384 && W >= 1 && W <= 16384, "%s: height or width outside 1..16384 (H=%d W=%d)", who, H, W);
+    AMAV_REQUIRE(F >= 1 && F <= kMaxFrames, "%s: num_frames %d outside 1..65535", who, F);
+    AMAV_REQUIRE(H >= 1 && H <= kMaxSide && W >= 1 && W <= kMaxSide, "%s: height or width outside 1..16384 (H=%d W=%d)", who, H, W);
     AMAV_REQUIRE(mode == AMAV_PNG_RGB || mode == AMAV_PNG_L, "%s: unknown mode %d", who, mode);
     AMAV_REQUIRE(layout == AMAV_JPEG_HWC_U8 || layout == AMAV_JPEG_CHW_F32, "%s: unknown layout %d", who, layout);
-    AMAV_REQUIRE(bytes && records && status, "%s: NULL stream, records or status", who);
-    AMAV_REQUIRE(stream_bytes >= 0, "%s: negative stream_bytes", who);
-    AMAV_REQUIRE((reinterpret_cast<uintptr_t>(records) & 7) == 0 && (reinterpret_cast<uintptr_t>(status) & 3) == 0,
-                 "%s: misaligned records or status", who);
+    if (int rc = check_stream_args(who, bytes, stream_bytes, records, status)) return rc;
     AMAV_REQUIRE(out, "%s: NULL out", who);
     AMAV_REQUIRE(layout == AMAV_JPEG_HWC_U8 || (reinterpret_cast<uintptr_t>(out) & 3) == 0, "%s: misaligned out", who);
     const size_t need = (size_t)F * H * W * (mode == AMAV_PNG_L ? 1 : 3) * (layout == AMAV_JPEG_CHW_F32 ? sizeof(float) : 1);

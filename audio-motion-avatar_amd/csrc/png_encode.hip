@@ -10,7 +10,7 @@
 //   container signature, IHDR and IEND, one wave per frame.
 // No allocation, no memset, no float atomics (LDS integer max / add / or only, order-independent), no host
 // synchronisation; nothing is written at or past the capacity; the same bytes on every run.
-#include "amav_common.h"
+#include "png_common.h"
 
 // Diagnostic build (-DAMAV_PNG_STAMPS, tools/bench_png_encode.py): lane 0 of every deflate wave adds the wall-clock ticks
 // (100 MHz) of each phase of encode_piece, over both runs of the pieces, to amav_png_stamp_totals: [0] loading the piece,
@@ -31,16 +31,16 @@ __device__ unsigned long long amav_png_stamp_totals[4];
 namespace amav {
 namespace png_enc {
 
-struct Record {  // amav_deflate_stream, 40 bytes
-    long long in_begin, in_end, out_begin, out_capacity;
-    int wrapper, reserved;
-};
+using png::kMaxFrames;
+using png::kMaxSide;
+using png::paeth;
+using png::sizes_ok;
 
 // what the three deflate kernels share
 struct Job {
     const uint8_t *in;  // deflate: the caller's bytes; PNG: the filtered scanlines
     long long in_bytes;
-    const Record *records;  // nullptr: PNG frames
+    const amav_deflate_stream *records;  // nullptr: PNG frames
     int streams;            // N or F
     long long table;        // pieces the tables hold
     // PNG
@@ -65,7 +65,7 @@ struct Range {
 };
 // whatever the record says, reads stay inside the input buffer and writes inside the output buffer
 __device__ __forceinline__ Range range_of(const Job &j, int n) {
-    const Record r = j.records[n];
+    const amav_deflate_stream r = j.records[n];
     Range g;
     g.in_begin = clampll(r.in_begin, 0, j.in_bytes);
     g.in_len = clampll(r.in_end, g.in_begin, j.in_bytes) - g.in_begin;
@@ -197,7 +197,7 @@ __global__ __launch_bounds__(64) void png_container_kernel(Job j, int H, int W, 
 __device__ __forceinline__ unsigned to_level(float v, int rounding) {
     if (rounding == AMAV_PNG_ROUND_NEAREST)  // x 255, + 0.5, clamp, truncate: two roundings, never one fused operation
         return (unsigned)(int)fminf(fmaxf(__fadd_rn(__fmul_rn(v, 255.0f), 0.5f), 0.0f), 255.0f);  // fmaxf(NaN, 0) = 0
-    return (unsigned)(int)(fminf(fmaxf(v, 0.f), 1.f) * 255.0f);
+    return quant8(v);
 }
 
 // byte i (= pixel x channel) of row y of frame f, as the PNG stores it
@@ -217,11 +217,6 @@ __device__ __forceinline__ unsigned sample(const void *frames, int rounding, siz
     } else {
         return to_level(static_cast<const float *>(frames)[f * hw + (size_t)y * W + i], rounding);
     }
-}
-
-__device__ __forceinline__ int paeth(int a, int b, int c) {
-    const int p = a + b - c, pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
-    return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
 }
 
 // grid-stride over the F x H scanlines, one wave each (the launch takes at most 2^20 workgroups, so any accepted F and H
@@ -269,7 +264,6 @@ __global__ __launch_bounds__(64) void png_filter_kernel(const void *__restrict__
 }
 
 // ------------------------------------------------------------------------------------------------------------- host
-static bool sizes_ok(int F, int H, int W) { return F >= 1 && F <= 65535 && H >= 1 && H <= 16384 && W >= 1 && W <= 16384; }
 static int channels_of(int layout) { return layout == AMAV_PNG_IN_GREY_U8 || layout == AMAV_PNG_IN_GREY_F32 ? 1 : 3; }
 static bool layout_ok(int layout) { return layout >= AMAV_PNG_IN_RGBA_F32 && layout <= AMAV_PNG_IN_GREY_F32; }
 static long long frame_bytes_of(int H, int W, int C) { return (long long)H * (1 + (long long)W * C); }
@@ -285,13 +279,6 @@ static void carve_tables(Carver &c, Job &j, long long streams, long long table, 
     j.offset = c.take<long long>(table);
 }
 
-static int check_workspace(const char *who, size_t need, const void *workspace, size_t workspace_bytes) {
-    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15))
-        return fail(AMAV_ERR_WORKSPACE, "%s: workspace %zu < %zu (or NULL / not 16-byte aligned)", who,
-                    workspace ? workspace_bytes : (size_t)0, need);
-    return AMAV_OK;
-}
-
 static unsigned piece_grid(long long pieces) { return (unsigned)(pieces < 65536 ? (pieces > 0 ? pieces : 1) : 65536); }
 
 }  // namespace png_enc
@@ -300,12 +287,11 @@ static unsigned piece_grid(long long pieces) { return (unsigned)(pieces < 65536 
 using namespace amav;
 using namespace amav::png_enc;
 
-static_assert(sizeof(amav_deflate_stream) == 40 && sizeof(Record) == 40, "amav_deflate_stream is packed by the host as 40 bytes");
 static_assert(deflate::kPiece == AMAV_DEFLATE_PIECE && AMAV_DEFLATE_PIECE <= 32768, "the piece size named in amav.h");
 static_assert(sizeof(deflate::Lds) <= 160 * 1024 / 3 - 512, "three pieces' state fits a compute unit's LDS");
 
 extern "C" size_t amav_deflate_workspace_bytes(int N, int64_t in_bytes) {
-    if (N < 1 || N > 65535 || in_bytes < 0) return 0;
+    if (N < 1 || N > kMaxFrames || in_bytes < 0) return 0;
     Carver c(nullptr);
     Job j{};
     carve_tables(c, j, N, in_bytes / AMAV_DEFLATE_PIECE + N, true);
@@ -315,7 +301,7 @@ extern "C" size_t amav_deflate_workspace_bytes(int N, int64_t in_bytes) {
 extern "C" int amav_deflate(int N, const uint8_t *bytes, int64_t in_bytes, const void *records, uint8_t *out, int64_t out_bytes,
                             int64_t *produced, int32_t *status, void *workspace, size_t workspace_bytes, void *stream_) {
     const char *who = "amav_deflate";
-    AMAV_REQUIRE(N >= 1 && N <= 65535, "%s: num_streams %d outside 1..65535", who, N);
+    AMAV_REQUIRE(N >= 1 && N <= kMaxFrames, "%s: num_streams %d outside 1..65535", who, N);
     AMAV_REQUIRE(bytes && records && out && produced && status, "%s: NULL input, records, out, produced or status", who);
     AMAV_REQUIRE(in_bytes >= 0 && out_bytes >= 0, "%s: negative in_bytes or out_bytes", who);
     AMAV_REQUIRE((reinterpret_cast<uintptr_t>(records) & 7) == 0 && (reinterpret_cast<uintptr_t>(produced) & 7) == 0 &&
@@ -326,7 +312,7 @@ extern "C" int amav_deflate(int N, const uint8_t *bytes, int64_t in_bytes, const
     Job j{};
     Carver c(workspace);
     carve_tables(c, j, N, in_bytes / AMAV_DEFLATE_PIECE + N, true);
-    j.in = bytes, j.in_bytes = in_bytes, j.records = static_cast<const Record *>(records), j.streams = N;
+    j.in = bytes, j.in_bytes = in_bytes, j.records = static_cast<const amav_deflate_stream *>(records), j.streams = N;
     j.out = out, j.out_bytes = out_bytes, j.produced = reinterpret_cast<long long *>(produced), j.status = status;
     const unsigned grid = piece_grid(j.table);
     deflate_count_kernel<<<1, 64, 0, stream>>>(j);
@@ -356,8 +342,8 @@ extern "C" int amav_png_encode(int F, int H, int W, const void *frames, int layo
                                int64_t capacity, int64_t *frame_offsets, int32_t *status, void *workspace, size_t workspace_bytes,
                                void *stream_) {
     const char *who = "amav_png_encode";
-    AMAV_REQUIRE(F >= 1 && F <= 65535, "%s: num_frames %d outside 1..65535", who, F);
-    AMAV_REQUIRE(H >= 1 && H <= 16384 && W >= 1 && W <= 16384, "%s: height or width outside 1..16384 (H=%d W=%d)", who, H, W);
+    AMAV_REQUIRE(F >= 1 && F <= kMaxFrames, "%s: num_frames %d outside 1..65535", who, F);
+    AMAV_REQUIRE(H >= 1 && H <= kMaxSide && W >= 1 && W <= kMaxSide, "%s: height or width outside 1..16384 (H=%d W=%d)", who, H, W);
     AMAV_REQUIRE(layout_ok(layout), "%s: unknown layout %d", who, layout);
     AMAV_REQUIRE(filter >= 0 && filter <= AMAV_PNG_FILTER_ADAPTIVE, "%s: unknown filter %d", who, filter);
     AMAV_REQUIRE(rounding == AMAV_PNG_ROUND_NEAREST || rounding == AMAV_PNG_ROUND_TRUNCATE, "%s: unknown rounding %d", who, rounding);

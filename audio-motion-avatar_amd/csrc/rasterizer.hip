@@ -1800,9 +1800,9 @@ __global__ __launch_bounds__(64, kRenderWavesPerSimd) void render_kernel(Params 
                         unsigned cr = bgw & 255u, cg = (bgw >> 8) & 255u, cb = (bgw >> 16) & 255u;  // outside the image
                         if (X0 + tx16 < p.W && Y0 + ty16 < p.H) {
                             const float r = Rq[qd] + Tq[qd] * p.bg[0], g = Gq[qd] + Tq[qd] * p.bg[1], bl = Bq[qd] + Tq[qd] * p.bg[2];
-                            cr = (unsigned)(unsigned char)(fminf(fmaxf(r, 0.f), 1.f) * 255.0f);
-                            cg = (unsigned)(unsigned char)(fminf(fmaxf(g, 0.f), 1.f) * 255.0f);
-                            cb = (unsigned)(unsigned char)(fminf(fmaxf(bl, 0.f), 1.f) * 255.0f);
+                            cr = quant8(r);
+                            cg = quant8(g);
+                            cb = quant8(bl);
                         }
                         unsigned char *px3 = bytes + (ty16 * 16 + tx16) * 3;
                         px3[0] = (unsigned char)cr, px3[1] = (unsigned char)cg, px3[2] = (unsigned char)cb;
@@ -1937,8 +1937,7 @@ static int rasterize_forward(const amav_raster_args *a, const amav_decode_source
         p.wire_offsets = p.wire_frame_counts + F;
         p.wire_payload = static_cast<unsigned char *>(a->wire) + wire_payload_at(F, F * T);
         p.wire_cap = (int)a->wire_capacity_tiles;
-        auto q8 = [](float v) { return (unsigned)(unsigned char)(std::fmin(std::fmax(v, 0.f), 1.f) * 255.0f); };
-        p.wire_bg = q8(a->bg[0]) | (q8(a->bg[1]) << 8) | (q8(a->bg[2]) << 16);
+        p.wire_bg = quant8(a->bg[0]) | (quant8(a->bg[1]) << 8) | (quant8(a->bg[2]) << 16);
     }
 
     hipStream_t stream = static_cast<hipStream_t>(stream_);

@@ -18,10 +18,13 @@ The way back in: `parse_jpeg` reads a baseline JPEG's header segments into the r
 frame_*.jpg; `load_clip` turns any of them into a device tensor with one upload and one decode call.  All of it is host
 code on `struct` / `bytes`.
 """
+import ctypes
 import dataclasses
 import os
 import struct
 from fractions import Fraction
+
+from . import _lib, clip_io
 
 AVI_MAX_BYTES = (1 << 31) - 1
 AVIF_HASINDEX, AVIF_ISINTERLEAVED, AVIIF_KEYFRAME = 0x10, 0x100, 0x10
@@ -327,19 +330,26 @@ def parse_jpeg(data, pos=0):
     return header, end - pos
 
 
-JPEG_RECORD_BYTES = 1128  # sizeof(amav_jpeg_frame), include/amav.h
+JpegFrame = _lib.STRUCTS["amav_jpeg_frame"]
+JPEG_RECORD_BYTES = ctypes.sizeof(JpegFrame)
 
 
 def pack_record(header, offset=0):
     """amav_jpeg_frame of a frame whose SOI lies at byte `offset` of the stream buffer."""
-    def rows(items, n):  # three rows of n bytes, zero-padded: one per component
-        return b"".join(bytes(b) + bytes(n - len(b)) for b in items) + bytes(n * (3 - len(items)))
+    rec = JpegFrame(scan_begin=offset + header.scan_begin, scan_end=offset + header.scan_end,
+                    restart_interval=header.restart_interval)
 
-    rec =struct.pack("<qqii", offset + header.scan_begin, offset + header.scan_end, header.restart_interval, 0) + \
-        rows(header.quant, 64) + rows([c for c, _ in header.dc], 16) + rows([v[:16] for _, v in header.dc], 16) + \
-        rows([c for c, _ in header.ac], 16) + rows([v for _, v in header.ac], 256)
-    assert len(rec) == JPEG_RECORD_BYTES
-    return rec
+    def rows(field, items):  # three rows of equal length, one per component; what a table leaves free stays zero
+        n = len(field) // 3
+        for c, row in enumerate(items):
+            field[n * c:n * c + len(row)] = row
+
+    rows(rec.quant, header.quant)
+    rows(rec.dc_counts, [c for c, _ in header.dc])
+    rows(rec.dc_values, [v[:16] for _, v in header.dc])
+    rows(rec.ac_counts, [c for c, _ in header.ac])
+    rows(rec.ac_values, [v for _, v in header.ac])
+    return bytes(rec)
 
 
 def frame_records(headers, offsets):
@@ -361,26 +371,7 @@ def frame_records(headers, offsets):
 
 
 # ------------------------------------------------------------------------------------------------------------ readers
-class _Reader:
-    fps = None
-
-    def __len__(self):
-        return len(self._frames)
-
-    def frame_bytes(self, i):
-        raise NotImplementedError
-
-    def close(self):
-        pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-
-class AviReader(_Reader):
+class AviReader(clip_io.Reader):
     """Motion-JPEG AVI 1.0 -> frame bytes.  Walks the first RIFF 'AVI ' of the file: `hdrl` for the streams (fps from the
     video strh's rate / scale, size and 'MJPG' from its strf; PCM format from the audio strf), then `movi` chunk by
     chunk ('##dc' / '##db' of the video stream, '##wb' of the audio stream, even padding, LIST 'rec ' groups, JUNK).
@@ -486,7 +477,7 @@ class AviReader(_Reader):
             self.fh.close()
 
 
-class MjpegReader(_Reader):
+class MjpegReader(clip_io.Reader):
     """The bare concatenation of JPEG files (.mjpeg).  Frame boundaries are not stored anywhere, so the file is read
     once and every frame's header parsed to find its EOI."""
 
@@ -507,7 +498,7 @@ class MjpegReader(_Reader):
         return self._data[at:at + n]
 
 
-class DirReader(_Reader):
+class DirReader(clip_io.Reader):
     """A directory of per-frame JPEG files, frame_000.jpg ... in numeric order (what --frames-dir writes); without such
     names, every *.jpg / *.jpeg in name order."""
 
@@ -546,19 +537,7 @@ def load_clip(path, frames=None, device="cuda", layout="chw_f32", check=True):
 
     from . import ops
 
-    reader = path if hasattr(path, "frame_bytes") else open_clip(path)
-    try:
-        count = len(reader)
-        picked = list(range(count)) if frames is None else [int(i) for i in frames]
-        if not picked:
-            raise ValueError("load_clip: no frames selected")
-        for i in picked:
-            if not -count <= i < count:
-                raise IndexError(f"load_clip: frame {i} of a clip of {count}")
-        blobs = [reader.frame_bytes(i) for i in picked]
-    finally:
-        if reader is not path:
-            reader.close()
+    picked, blobs = clip_io.read_frames(path, frames, open_clip)
     headers, offsets, at = [], [], 0
     for i, blob in zip(picked, blobs):
         try:
@@ -572,15 +551,10 @@ def load_clip(path, frames=None, device="cuda", layout="chw_f32", check=True):
     host = torch.empty(table_bytes + at, dtype=torch.uint8)
     host[:table_bytes] = records.table
     host[table_bytes:] = torch.frombuffer(bytearray(b"".join(blobs)), dtype=torch.uint8)
-    dev = host.to(device)  # the one upload: records first (the table is 8-byte aligned), then the frames
-    out, status = ops.jpeg_decode(dev[table_bytes:], ops.JpegRecords(dev[:table_bytes], records.height, records.width,
-                                                                    records.sampling), layout=layout)
+    out, status = clip_io.decode_uploaded(host, table_bytes, device, lambda stream, table: ops.jpeg_decode(
+        stream, ops.JpegRecords(table, records.height, records.width, records.sampling), layout=layout))
     if not check:
         return out, status
-    flagged = status.cpu().tolist()
-    bad = [(i, s) for i, s in zip(picked, flagged) if s]
-    if bad:
-        raise JpegError("load_clip: damaged frames " + ", ".join(
-            f"{i} ({'markers' if s & ops.JPEG_STATUS_MARKERS else ''}{'+' if s == 3 else ''}"
-            f"{'entropy' if s & ops.JPEG_STATUS_ENTROPY else ''})" for i, s in bad))
+    names = [(ops.JPEG_STATUS_MARKERS, "markers"), (ops.JPEG_STATUS_ENTROPY, "entropy")]
+    clip_io.raise_damaged(JpegError, picked, status, lambda s: "+".join(name for bit, name in names if s & bit))
     return out

@@ -2,6 +2,7 @@
 
 Every function requires CUDA(HIP) float32 tensors and raises on anything else: there is no CPU path.
 """
+import copy
 import ctypes
 import math
 import os
@@ -686,42 +687,81 @@ JPEG_STATUS_MARKERS, JPEG_STATUS_ENTROPY = _lib.DEFINES["AMAV_JPEG_STATUS_MARKER
 JpegFrame = _lib.STRUCTS["amav_jpeg_frame"]
 
 
-class JpegRecords:
-    """The per-frame records of one decode call: `table`, a uint8 tensor holding F amav_jpeg_frame records back to back
-    (on the host until .to(device)), and the geometry the frames share.  mjpeg.frame_records() builds one from parsed
+class _FrameRecords:
+    """The per-frame records of one decode call: `table`, a uint8 tensor holding F records of the struct `Frame` back to
+    back (on the host until .to(device)), and the height and width the frames share."""
+    Frame = None
+
+    def __init__(self, table, height, width):
+        size = ctypes.sizeof(self.Frame)
+        if not isinstance(table, torch.Tensor) or table.dtype != torch.uint8 or table.dim() != 1 or table.numel() == 0 or \
+                table.numel() % size:
+            raise AmavError(f"{type(self).__name__}: the table must be a uint8 tensor of whole {size}-byte records")
+        self.table, self.height, self.width = table, int(height), int(width)
+
+    @property
+    def num_frames(self):
+        return self.table.numel() // ctypes.sizeof(self.Frame)
+
+    def to(self, device):
+        moved = copy.copy(self)
+        moved.table = self.table.to(device)
+        return moved
+
+
+class JpegRecords(_FrameRecords):
+    """F amav_jpeg_frame records and the geometry the frames share.  mjpeg.frame_records() builds one from parsed
     headers."""
+    Frame = JpegFrame
 
     def __init__(self, table, height, width, sampling):
         if str(sampling) not in JPEG_SAMPLING:
             raise AmavError(f"JpegRecords: unknown sampling {sampling!r} (420, 444 or gray)")
-        if table.dtype != torch.uint8 or table.dim() != 1 or table.numel() == 0 or table.numel() % ctypes.sizeof(JpegFrame):
-            raise AmavError(f"JpegRecords: the table must be a uint8 tensor of whole {ctypes.sizeof(JpegFrame)}-byte records")
-        self.table, self.height, self.width, self.sampling = table, int(height), int(width), str(sampling)
+        super().__init__(table, height, width)
+        self.sampling = str(sampling)
 
-    @property
-    def num_frames(self):
-        return self.table.numel() // ctypes.sizeof(JpegFrame)
 
-    def to(self, device):
-        return JpegRecords(self.table.to(device), self.height, self.width, self.sampling)
+def _byte_stream(stream, who):
+    if not isinstance(stream, torch.Tensor) or not stream.is_cuda or stream.dtype != torch.uint8 or stream.dim() != 1 or \
+            stream.stride(0) != 1:
+        raise AmavError(f"{who}: stream must be a uint8 vector on the HIP device")
+    return stream
+
+
+def _status_words(status, n, device, who):
+    if status is None:
+        return torch.empty(n, dtype=torch.int32, device=device)
+    if not isinstance(status, torch.Tensor) or status.dtype != torch.int32 or status.device != device or \
+            not status.is_contiguous() or status.numel() != n:
+        raise AmavError(f"{who}: status must be a contiguous int32 [{n}] tensor on the stream's device")
+    return status
+
+
+def _out_like(out, shape, dtype, device, who, source="stream"):
+    """`out` after its checks, or a fresh tensor in its place: contiguous, of `dtype` and `shape` (None: a vector of any
+    length, which the caller supplies) on `device`."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    ok = isinstance(out, torch.Tensor) and out.dtype == dtype and out.device == device
+    if ok and shape is None:
+        ok = out.dim() == 1 and out.stride(0) == 1
+    elif ok:
+        ok = tuple(out.shape) == shape and out.is_contiguous()
+    if not ok:
+        what = "a uint8 vector" if shape is None else f"a contiguous {dtype} {shape} tensor"
+        raise AmavError(f"{who}: out must be {what} on the {source}'s device")
+    return out
 
 
 def _jpeg_decode_args(stream, records, status, who):
     if not isinstance(records, JpegRecords):
         raise AmavError(f"{who}: records must be an ops.JpegRecords")
-    if not isinstance(stream, torch.Tensor) or not stream.is_cuda or stream.dtype != torch.uint8 or stream.dim() != 1 or \
-            stream.stride(0) != 1:
-        raise AmavError(f"{who}: stream must be a uint8 vector on the HIP device")
+    _byte_stream(stream, who)
     table = records.table
     if table.device != stream.device or not table.is_contiguous():
         raise AmavError(f"{who}: the record table must be contiguous on the stream's device (records.to(device))")
     F = records.num_frames
-    if status is None:
-        status = torch.empty(F, dtype=torch.int32, device=stream.device)
-    elif not isinstance(status, torch.Tensor) or status.dtype != torch.int32 or status.device != stream.device or \
-            not status.is_contiguous() or status.numel() != F:
-        raise AmavError(f"{who}: status must be a contiguous int32 [F] tensor on the stream's device")
-    return F, records.height, records.width, JPEG_SAMPLING[records.sampling], status
+    return F, records.height, records.width, JPEG_SAMPLING[records.sampling], _status_words(status, F, stream.device, who)
 
 
 def jpeg_decode_levels(stream, records, status=None):
@@ -746,11 +786,7 @@ def jpeg_decode(stream, records, layout="chw_f32", out=None, status=None):
     if layout not in JPEG_LAYOUTS:
         raise AmavError(f"jpeg_decode: unknown layout {layout!r} (hwc_u8 or chw_f32)")
     shape, dtype = ((F, H, W, 3), torch.uint8) if layout == "hwc_u8" else ((F, 3, H, W), torch.float32)
-    if out is None:
-        out = torch.empty(shape, dtype=dtype, device=stream.device)
-    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or \
-            out.device != stream.device:
-        raise AmavError(f"jpeg_decode: out must be a contiguous {dtype} {shape} tensor on the stream's device")
+    out = _out_like(out, shape, dtype, stream.device, "jpeg_decode")
     ws = _scratch("amav_jpeg_decode_workspace_bytes", stream.device, F, H, W, sampling, 0, rejected=f"F={F} H={H} W={W}")
     _call("amav_jpeg_decode", F, H, W, sampling, stream.data_ptr(), stream.numel(), records.table.data_ptr(),
           JPEG_LAYOUTS[layout], out.data_ptr(), out.numel() * out.element_size(), status.data_ptr(), ws.data_ptr(),
@@ -761,42 +797,36 @@ def jpeg_decode(stream, records, layout="chw_f32", out=None, status=None):
 # ------------------------------------------------------------------------------------------------------------ PNG
 PNG_MODES = {"rgb": _lib.DEFINES["AMAV_PNG_RGB"], "l": _lib.DEFINES["AMAV_PNG_L"]}
 PNG_STATUS_INFLATE, PNG_STATUS_SIZE, PNG_STATUS_FILTER = (_lib.DEFINES["AMAV_PNG_STATUS_" + n] for n in ("INFLATE", "SIZE", "FILTER"))
-InflateStream = _lib.STRUCTS["amav_inflate_stream"]
 PngFrame = _lib.STRUCTS["amav_png_frame"]
 
 
-class PngRecords:
-    """The per-frame records of one PNG decode call: `table`, a uint8 tensor holding F amav_png_frame records back to
-    back (on the host until .to(device)), and the height and width the frames share.  png.frame_records() builds one."""
-
-    def __init__(self, table, height, width):
-        if not isinstance(table, torch.Tensor) or table.dtype != torch.uint8 or table.dim() != 1 or table.numel() == 0 or \
-                table.numel() % ctypes.sizeof(PngFrame):
-            raise AmavError(f"PngRecords: the table must be a uint8 tensor of whole {ctypes.sizeof(PngFrame)}-byte records")
-        self.table, self.height, self.width = table, int(height), int(width)
-
-    @property
-    def num_frames(self):
-        return self.table.numel() // ctypes.sizeof(PngFrame)
-
-    def to(self, device):
-        return PngRecords(self.table.to(device), self.height, self.width)
+class PngRecords(_FrameRecords):
+    """F amav_png_frame records and the height and width the frames share.  png.frame_records() builds one."""
+    Frame = PngFrame
 
 
-def _byte_stream(stream, who):
-    if not isinstance(stream, torch.Tensor) or not stream.is_cuda or stream.dtype != torch.uint8 or stream.dim() != 1 or \
-            stream.stride(0) != 1:
-        raise AmavError(f"{who}: stream must be a uint8 vector on the HIP device")
-    return stream
-
-
-def _status_words(status, n, device, who):
-    if status is None:
-        return torch.empty(n, dtype=torch.int32, device=device)
-    if not isinstance(status, torch.Tensor) or status.dtype != torch.int32 or status.device != device or \
-            not status.is_contiguous() or status.numel() != n:
-        raise AmavError(f"{who}: status must be a contiguous int32 [{n}] tensor on the stream's device")
-    return status
+def _flate(entry, query, data, records, out, status, who, *query_sizes, source="stream"):
+    """What inflate() and deflate() share: the [N,5] rows become 40-byte records, go up in one copy, and one call of
+    `entry` runs over them with the scratch that `query`(N, *query_sizes) asks for."""
+    _byte_stream(data, who)
+    if not isinstance(records, torch.Tensor) or records.dtype != torch.int64 or records.dim() != 2 or records.shape[1] != 5 or \
+            records.shape[0] == 0:
+        raise AmavError(f"{who}: records must be an int64 [N,5] tensor (in_begin, in_end, out_begin, out_capacity, wrapper)")
+    host = records.cpu() if records.is_cuda else records
+    N = host.shape[0]
+    if out is None:
+        out = torch.empty(max(1, int((host[:, 2] + host[:, 3]).max())), dtype=torch.uint8, device=data.device)
+    out = _out_like(out, None, torch.uint8, data.device, who, source)
+    table = torch.zeros(N, ctypes.sizeof(_lib.STRUCTS[entry + "_stream"]) // 8, dtype=torch.int64)
+    table[:, :4] = host[:, :4]
+    table[:, 4] = host[:, 4] & 0xFFFFFFFF  # wrapper (int32) + reserved
+    table = table.to(data.device)
+    status = _status_words(status, N, data.device, who)
+    produced = torch.empty(N, dtype=torch.int64, device=data.device)
+    ws = _scratch(query, data.device, N, *query_sizes, rejected=f"{N} streams")
+    _call(entry, N, data.data_ptr(), data.numel(), table.data_ptr(), out.data_ptr(), out.numel(), produced.data_ptr(),
+          status.data_ptr(), ws.data_ptr(), ws.numel())
+    return out, produced, status
 
 
 def inflate(stream, records, out=None, status=None):
@@ -807,27 +837,7 @@ def inflate(stream, records, out=None, status=None):
     out: the uint8 vector written into (default: a fresh one that just holds every row's range; the bytes between the
     ranges are not touched).  produced int64 [N]: bytes written per stream; status int32 [N]: 0, or PNG_STATUS_INFLATE /
     PNG_STATUS_SIZE (include/amav.h has the rules)."""
-    _byte_stream(stream, "inflate")
-    if not isinstance(records, torch.Tensor) or records.dtype != torch.int64 or records.dim() != 2 or records.shape[1] != 5 or \
-            records.shape[0] == 0:
-        raise AmavError("inflate: records must be an int64 [N,5] tensor (in_begin, in_end, out_begin, out_capacity, wrapper)")
-    host = records.cpu() if records.is_cuda else records
-    N = host.shape[0]
-    if out is None:
-        out = torch.empty(max(1, int((host[:, 2] + host[:, 3]).max())), dtype=torch.uint8, device=stream.device)
-    elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.dim() != 1 or out.stride(0) != 1 or \
-            out.device != stream.device:
-        raise AmavError("inflate: out must be a uint8 vector on the stream's device")
-    table = torch.zeros(N, ctypes.sizeof(InflateStream) // 8, dtype=torch.int64)
-    table[:, :4] = host[:, :4]
-    table[:, 4] = host[:, 4] & 0xFFFFFFFF  # wrapper (int32) + reserved
-    table = table.to(stream.device)
-    status = _status_words(status, N, stream.device, "inflate")
-    produced = torch.empty(N, dtype=torch.int64, device=stream.device)
-    ws = _scratch("amav_inflate_workspace_bytes", stream.device, N, rejected=f"{N} streams")
-    _call("amav_inflate", N, stream.data_ptr(), stream.numel(), table.data_ptr(), out.data_ptr(), out.numel(),
-          produced.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel())
-    return out, produced, status
+    return _flate("amav_inflate", "amav_inflate_workspace_bytes", stream, records, out, status, "inflate")
 
 
 def png_decode(stream, records, mode="rgb", layout="hwc_u8", out=None, status=None):
@@ -852,11 +862,7 @@ def png_decode(stream, records, mode="rgb", layout="hwc_u8", out=None, status=No
         shape, dtype = ((F, H, W, 3) if mode == "rgb" else (F, H, W)), torch.uint8
     else:
         shape, dtype = (F, 3 if mode == "rgb" else 1, H, W), torch.float32
-    if out is None:
-        out = torch.empty(shape, dtype=dtype, device=stream.device)
-    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or \
-            out.device != stream.device:
-        raise AmavError(f"png_decode: out must be a contiguous {dtype} {shape} tensor on the stream's device")
+    out = _out_like(out, shape, dtype, stream.device, "png_decode")
     ws = _scratch("amav_png_decode_workspace_bytes", stream.device, F, H, W, rejected=f"F={F} H={H} W={W}")
     _call("amav_png_decode", F, H, W, stream.data_ptr(), stream.numel(), table.data_ptr(), PNG_MODES[mode],
           JPEG_LAYOUTS[layout], out.data_ptr(), out.numel() * out.element_size(), status.data_ptr(), ws.data_ptr(), ws.numel())
@@ -865,7 +871,6 @@ def png_decode(stream, records, mode="rgb", layout="hwc_u8", out=None, status=No
 
 PNG_STATUS_TABLE = _lib.DEFINES["AMAV_PNG_STATUS_TABLE"]
 DEFLATE_PIECE = _lib.DEFINES["AMAV_DEFLATE_PIECE"]
-DeflateStream = _lib.STRUCTS["amav_deflate_stream"]
 PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": _lib.DEFINES["AMAV_PNG_FILTER_ADAPTIVE"]}
 PNG_ROUNDINGS = {"nearest": _lib.DEFINES["AMAV_PNG_ROUND_NEAREST"], "truncate": _lib.DEFINES["AMAV_PNG_ROUND_TRUNCATE"]}
 
@@ -883,27 +888,8 @@ def deflate(data, records, out=None, status=None):
     fresh one that just holds every row's range).  produced int64 [N]: the bytes each stream needs; status int32 [N]: 0,
     PNG_STATUS_SIZE (produced > out_capacity; the part that fits was written) or PNG_STATUS_TABLE (ranges that overlap
     beyond the piece table; include/amav.h has the rules)."""
-    _byte_stream(data, "deflate")
-    if not isinstance(records, torch.Tensor) or records.dtype != torch.int64 or records.dim() != 2 or records.shape[1] != 5 or \
-            records.shape[0] == 0:
-        raise AmavError("deflate: records must be an int64 [N,5] tensor (in_begin, in_end, out_begin, out_capacity, wrapper)")
-    host = records.cpu() if records.is_cuda else records
-    N = host.shape[0]
-    if out is None:
-        out = torch.empty(max(1, int((host[:, 2] + host[:, 3]).max())), dtype=torch.uint8, device=data.device)
-    elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.dim() != 1 or out.stride(0) != 1 or \
-            out.device != data.device:
-        raise AmavError("deflate: out must be a uint8 vector on the data's device")
-    table = torch.zeros(N, ctypes.sizeof(DeflateStream) // 8, dtype=torch.int64)
-    table[:, :4] = host[:, :4]
-    table[:, 4] = host[:, 4] & 0xFFFFFFFF  # wrapper (int32) + reserved
-    table = table.to(data.device)
-    status = _status_words(status, N, data.device, "deflate")
-    produced = torch.empty(N, dtype=torch.int64, device=data.device)
-    ws = _scratch("amav_deflate_workspace_bytes", data.device, N, data.numel(), rejected=f"{N} streams")
-    _call("amav_deflate", N, data.data_ptr(), data.numel(), table.data_ptr(), out.data_ptr(), out.numel(),
-          produced.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel())
-    return out, produced, status
+    return _flate("amav_deflate", "amav_deflate_workspace_bytes", data, records, out, status, "deflate",
+                  _byte_stream(data, "deflate").numel(), source="data")
 
 
 def _png_frames(frames, who):

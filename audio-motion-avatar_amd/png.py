@@ -7,14 +7,18 @@ device does not verify (a chunk's CRC is checked here).
 
 PNG clip output (below): save_clip, save_image, save_comparison and write_dataset_clip hand device tensors to
 ops.png_encode and write the files it returns; conversion, filtering, deflate and the CRCs happen on the device."""
+import ctypes
 import os
 import struct
 import zlib
 
+from . import _lib, clip_io
+
 SIGNATURE = b"\x89PNG\r\n\x1a\n"
 MAX_SIDE = 16384
 ALLOWED_DEPTHS = {0: (1, 2, 4, 8, 16), 2: (8, 16), 3: (1, 2, 4, 8), 4: (8, 16), 6: (8, 16)}  # the standard's pairs
-PNG_RECORD_BYTES = 40  # sizeof(amav_png_frame), include/amav.h
+PngFrame = _lib.STRUCTS["amav_png_frame"]
+PNG_RECORD_BYTES = ctypes.sizeof(PngFrame)
 
 
 class PngError(ValueError):
@@ -99,11 +103,9 @@ def zlib_stream(data, header):
     return b"".join(bytes(data[a:b]) for a, b in header.idat)
 
 
-class PngDirReader:
+class PngDirReader(clip_io.Reader):
     """A directory of per-frame PNG files.  With the dataset's all-digit stems (00000.png ...) in the order of
     int(stem), otherwise every *.png in name order.  Same shape as mjpeg.DirReader."""
-
-    fps = None
 
     def __init__(self, path):
         names = sorted(n for n in os.listdir(path) if n.lower().endswith(".png"))
@@ -114,21 +116,19 @@ class PngDirReader:
         self._frames = [os.path.join(path, n) for n in names]
         self.height = self.width = None
 
-    def __len__(self):
-        return len(self._frames)
-
     def frame_bytes(self, i):
         with open(self._frames[i], "rb") as fh:
             return fh.read()
 
-    def close(self):
-        pass
 
-    def __enter__(self):
-        return self
+class _Blobs(clip_io.Reader):
+    """File contents the caller already holds (None = an absent frame), as a reader."""
 
-    def __exit__(self, *exc):
-        self.close()
+    def __init__(self, blobs):
+        self._frames = blobs
+
+    def frame_bytes(self, i):
+        return self._frames[i]
 
 
 def pack_clip(blobs):
@@ -159,14 +159,14 @@ def pack_clip(blobs):
             at += len(h.palette)
     for h, blob, pal in zip(headers, blobs, palette_at):
         if h is None:
-            table += struct.pack("<qqqiiii", 0, 0, 0, 0, 8, 0, 1)
+            table += bytes(PngFrame(bit_depth=8, absent=1))
             continue
         begin = at
         for a, b in h.idat:
             parts.append(bytes(blob[a:b]))
             at += b - a
-        table += struct.pack("<qqqiiii", begin, at, pal, h.color_type, h.bit_depth, h.palette_entries, 0)
-    assert len(table) == PNG_RECORD_BYTES * len(headers)
+        table += bytes(PngFrame(zlib_begin=begin, zlib_end=at, palette_at=pal, color_type=h.color_type, bit_depth=h.bit_depth,
+                                palette_entries=h.palette_entries))
     host = torch.frombuffer(bytearray(bytes(table) + b"".join(parts)) or bytearray(1), dtype=torch.uint8)
     return host, len(table), H, W
 
@@ -195,35 +195,16 @@ def load_clip(path, frames=None, mode="rgb", device="cuda", layout="chw_f32", ch
     synchronising."""
     from . import ops
 
-    if isinstance(path, (list, tuple)):
-        count = len(path)
-        picked = list(range(count)) if frames is None else [int(i) for i in frames]
-        blobs = [path[i] for i in picked]
-    else:
-        reader = path if hasattr(path, "frame_bytes") else PngDirReader(os.fspath(path))
-        try:
-            count = len(reader)
-            picked = list(range(count)) if frames is None else [int(i) for i in frames]
-            for i in picked:
-                if not -count <= i < count:
-                    raise IndexError(f"load_clip: frame {i} of a clip of {count}")
-            blobs = [reader.frame_bytes(i) for i in picked]
-        finally:
-            if reader is not path:
-                reader.close()
-    if not blobs:
-        raise ValueError("load_clip: no frames selected")
+    picked, blobs = clip_io.read_frames(_Blobs(path) if isinstance(path, (list, tuple)) else path, frames, PngDirReader)
     try:
         host, table_bytes, H, W = pack_clip(blobs)
     except PngError as e:
         raise PngError(f"load_clip: {e}") from None
-    dev = host.to(device)  # the one upload: records first (8-byte aligned), then palettes and streams
-    out, status = ops.png_decode(dev[table_bytes:], ops.PngRecords(dev[:table_bytes], H, W), mode=mode, layout=layout)
+    out, status = clip_io.decode_uploaded(host, table_bytes, device, lambda stream, table: ops.png_decode(
+        stream, ops.PngRecords(table, H, W), mode=mode, layout=layout))
     if not check:
         return out, status
-    bad = [(i, s) for i, s in zip(picked, status.cpu().tolist()) if s]
-    if bad:
-        raise PngError("load_clip: damaged frames " + ", ".join(f"{i} ({status_text(s)})" for i, s in bad))
+    clip_io.raise_damaged(PngError, picked, status, status_text)
     return out
 
 

@@ -150,3 +150,14 @@ def test_packed_record_is_the_headers_struct():
             assert bytes(r.dc_values[16 * c:16 * c + 16]).rstrip(b"\0") == bytes(h.dc[c][1]).rstrip(b"\0")
             assert bytes(r.ac_counts[16 * c:16 * c + 16]) == bytes(h.ac[c][0])
             assert bytes(r.ac_values[256 * c:256 * c + len(h.ac[c][1])]) == bytes(h.ac[c][1])
+            assert not any(r.ac_values[256 * c + len(h.ac[c][1]):256 * c + 256])
+        assert r.reserved == 0
+    # a grey frame fills the first component's rows; the other two stay zero
+    grey = parse_jpeg(pillow(jc.noise(1, 40, 24, seed=3)[0], "L", quality=60, restart_marker_rows=2))[0]
+    r = Frame.from_buffer_copy(bytes(frame_records([grey], [7]).table.numpy()))
+    assert (r.scan_begin, r.scan_end, r.restart_interval, r.reserved) == (7 + grey.scan_begin, 7 + grey.scan_end, 6, 0)
+    assert bytes(r.quant[:64]) == bytes(grey.quant[0]) and bytes(r.dc_counts[:16]) == bytes(grey.dc[0][0])
+    assert bytes(r.dc_values[:len(grey.dc[0][1])]) == bytes(grey.dc[0][1]) and bytes(r.ac_counts[:16]) == bytes(grey.ac[0][0])
+    assert bytes(r.ac_values[:len(grey.ac[0][1])]) == bytes(grey.ac[0][1])
+    for field, n in ((r.quant, 64), (r.dc_counts, 16), (r.dc_values, 16), (r.ac_counts, 16), (r.ac_values, 256)):
+        assert not any(field[n:])

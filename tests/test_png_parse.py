@@ -1,4 +1,5 @@
 """png.parse_png: what it accepts and every PngError it lists; PngDirReader's order; pack_clip's buffer layout."""
+import ctypes
 import struct
 import zlib
 
@@ -105,6 +106,22 @@ def test_pack_clip_layout():
     assert (ct, depth, entries) == (3, 8, 10) and body[pal:pal + 30] == bytes(range(30))
     assert len(zlib.decompress(body[z0:z1])) == 5 * 7  # the IDAT payloads, joined
     assert len(zlib.decompress(body[recs[2][0]:recs[2][1]])) == 5 * 19 and recs[2][3:6] == (2, 8, 0)
+    # the same bytes read back through the struct generated from include/amav.h: every field is the parsed header's
+    from audio_motion_avatar_amd import _lib
+
+    Frame = _lib.STRUCTS["amav_png_frame"]
+    assert ctypes.sizeof(Frame) == png.PNG_RECORD_BYTES
+    raw, at = bytes(host[:table_bytes].tolist()), 30  # the streams follow the one palette
+    for i, (blob, h) in enumerate([(a, png.parse_png(a)), (None, None), (b, png.parse_png(b))]):
+        r = Frame.from_buffer_copy(raw, i * png.PNG_RECORD_BYTES)
+        fields = (r.zlib_begin, r.zlib_end, r.palette_at, r.color_type, r.bit_depth, r.palette_entries, r.absent)
+        if h is None:
+            assert fields == (0, 0, 0, 0, 8, 0, 1)
+            continue
+        size = sum(e - s for s, e in h.idat)
+        assert fields == (at, at + size, 0 if i == 0 else 30, h.color_type, h.bit_depth, h.palette_entries, 0)
+        assert body[at:at + size] == png.zlib_stream(blob, h)
+        at += size
     with pytest.raises(png.PngError, match="unequal size"):
         png.pack_clip([a, pc.write_png(pc.random_samples(rng, 5, 7, 2, 8), 2, 8)])
     with pytest.raises(png.PngError, match="frame 1: bad PNG signature"):
