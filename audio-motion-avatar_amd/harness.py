@@ -118,15 +118,17 @@ class AudioDrivenAvatar(nn.Module):
         attention; .eval() makes the step deterministic.  .train() also switches on gradient checkpointing of the audio
         transformer's blocks (each keeps only its input and runs its forward again in the backward: a second forward
         for a fraction of the activation memory, the same gradients).  The image terms come from the fused HIP loss
-        (losses.image_losses); AMAV_IMAGE_LOSS=library, read per call, keeps the library's l1_loss and ssim."""
-        from .losses import smplx_param_loss, training_image_terms
+        (losses.image_losses); AMAV_IMAGE_LOSS=library, read per call, keeps the library's l1_loss and ssim.  The
+        parameter term is losses.training_smplx_term: smplx_param_loss, or with AMAV_SMPLX_PARAMS=hip (read per call)
+        the fused losses.smplx_param_losses, and then the SMPL-X decoder's rot6d conversion is the HIP one as well."""
+        from .losses import training_image_terms, training_smplx_term
 
         images, _, pred_smplx_future, _, _ = self.audio_triplane(audio_features, triplanes, None, cam_params,
                                                                  smplx_tokens)
         target = target_video.permute(0, 1, 3, 4, 2)
         parts = dict(zip(("l1_target", "ssim_target"), training_image_terms(images, target)))
         parts["loss_target"] = parts["l1_target"] + 0.1 * parts["ssim_target"]
-        parts["smpl_loss_future"] = smplx_param_loss(pred_smplx_future, target_smpl_params)[0]
+        parts["smpl_loss_future"] = training_smplx_term(pred_smplx_future, target_smpl_params)
         total = 10 * parts["loss_target"] + 0.05 * parts["smpl_loss_future"]
         return total, parts
 

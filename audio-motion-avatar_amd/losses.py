@@ -126,6 +126,98 @@ def smplx_param_loss(pred_params, gt_params, weights=None):
     return total, losses
 
 
+def _fused_smplx_terms(pred_params, gt_params):
+    """Whether ops.smplx_param_loss_differentiable can take these dicts as they are."""
+    keys = [k for k in ("betas",) + ROTATION_KEYS + ("expression", "transl") if k in pred_params and k in gt_params]
+    for k in keys:
+        p, g = pred_params[k], gt_params[k]
+        if not (isinstance(p, torch.Tensor) and isinstance(g, torch.Tensor) and p.is_cuda and g.is_cuda):
+            return False
+        if p.dtype != torch.float32 or g.dtype != torch.float32 or p.shape != g.shape or p.device != g.device:
+            return False
+        if g.requires_grad and torch.is_grad_enabled():
+            return False
+    return bool(keys)
+
+
+_smplx_weight_vectors = {}
+
+
+def _smplx_weight_vector(weights, present, device):
+    """[12] device tensor of the factors smplx_param_loss puts on its parts (0.01 on the two priors; 0 for a key that
+    is not present, whose weight smplx_param_loss never looks up), cached per set of weights; None when a weight is not
+    a plain number.  A present betas / expression / transl without a weight is smplx_param_loss's KeyError."""
+    named = {k: weights[k] if k in present else 0.0 for k in ("betas", "expression", "transl")}
+    values = [named["betas"], 0.01] + [weights.get(k, 1.0) for k in ROTATION_KEYS] + [named["expression"], 0.01,
+                                                                                      named["transl"]]
+    if not all(isinstance(v, (int, float)) for v in values):
+        return None
+    key = (tuple(float(v) for v in values), device)
+    if key not in _smplx_weight_vectors:
+        _smplx_weight_vectors[key] = torch.tensor(key[0], dtype=torch.float32, device=device)
+    return _smplx_weight_vectors[key]
+
+
+def smplx_param_losses(pred_params, gt_params, weights=None):
+    """smplx_param_loss from the fused HIP kernels (ops.smplx_param_loss_differentiable; csrc/smplx_params.hip): the
+    same (total, parts) -- the same part names, the same weights semantics, the same keys skipped when either dict
+    lacks them -- from one forward launch and, under autograd, one backward launch for all pred tensors.  The twelve
+    means come back as one [12] device tensor; the parts are views of it and total is its product with the weights,
+    in torch.  pred tensors are read in place (slices of the decoder's [F,55,3] included); gt gets no gradient.
+
+    It takes float32 device tensors with pred[k].shape == gt[k].shape.  A rotation key whose shapes differ raises the
+    AssertionError of rotation_geodesic_loss.  Everything else it cannot take is handed to smplx_param_loss itself:
+    CPU tensors, other dtypes, betas / expression / transl that broadcast, a gt that requires a gradient, weights that
+    are not plain numbers.  smplx_param_loss remains the fixture-pinned statement of the reference."""
+    from . import ops
+
+    for key in ROTATION_KEYS:
+        if key in pred_params and key in gt_params:
+            if pred_params[key].shape != gt_params[key].shape:
+                raise AssertionError(f"Shape mismatch: {pred_params[key].shape} vs {gt_params[key].shape}")
+            if pred_params[key].shape[-1] != 3:
+                raise AssertionError("the last dimension must be 3")
+    if not _fused_smplx_terms(pred_params, gt_params):
+        return smplx_param_loss(pred_params, gt_params, weights)
+    if weights is None:
+        weights = {k: 1.0 for k in ("betas",) + ROTATION_KEYS + ("expression", "transl")}
+    present = [k for k in ops.SMPLX_TERM_KEYS if k in pred_params and k in gt_params]
+    factors = _smplx_weight_vector(weights, present, pred_params[present[0]].device)
+    if factors is None:
+        return smplx_param_loss(pred_params, gt_params, weights)
+    parts = ops.smplx_param_loss_differentiable(pred_params, gt_params)
+    named = dict(zip(ops.SMPLX_PART_NAMES, parts.unbind(0)))
+    losses = {name: named[name] for name in ops.SMPLX_PART_NAMES if _part_key(name) in present}
+    return torch.dot(parts, factors), losses
+
+
+def _part_key(name):
+    """The parameter key a part of smplx_param_loss belongs to (`body_pose_geo` -> `body_pose`)."""
+    return name.rsplit("_", 1)[0]
+
+
+SMPLX_PARAMS_DEFAULT = "library"   # tools/bench_smplx_params.py has the numbers a later change of the default cites
+
+
+def smplx_params_path():
+    """AMAV_SMPLX_PARAMS, read per call like AMAV_IMAGE_LOSS: `library` (the torch statements of this module and of
+    smplx_decoder.py) or `hip` (csrc/smplx_params.hip)."""
+    import os
+
+    path = os.environ.get("AMAV_SMPLX_PARAMS", SMPLX_PARAMS_DEFAULT)
+    if path not in ("library", "hip"):
+        raise ValueError(f"AMAV_SMPLX_PARAMS={path!r}: expected `library` or `hip`")
+    return path
+
+
+def training_smplx_term(pred_params, gt_params):
+    """The SMPL-X parameter term of a training step, smplx_param_loss(pred, gt)[0]: the library statement, or with
+    AMAV_SMPLX_PARAMS=hip the fused smplx_param_losses."""
+    if smplx_params_path() == "hip":
+        return smplx_param_losses(pred_params, gt_params)[0]
+    return smplx_param_loss(pred_params, gt_params)[0]
+
+
 def image_losses(img1, img2, size_average=True):
     """(l1_loss(img1, img2), ssim(img1, img2, 11, size_average)) for training, from the fused HIP kernels
     (ops.image_loss_differentiable; csrc/image_loss.hip): img1, img2 [B, T, H, W, C] on the device, C = 1..4, both read

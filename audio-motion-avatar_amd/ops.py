@@ -1769,6 +1769,170 @@ def image_loss_differentiable(x, y):
     # needs_input_grad does not see torch.no_grad(): decide here whether the derivative maps are written at all
     return _ImageLoss.apply(x, y, x.requires_grad and torch.is_grad_enabled())
 
+
+# ------------------------------------------------------------------------------------- SMPL-X parameter term
+SMPLX_TERM_KEYS = ("betas", "global_orient", "body_pose", "left_hand_pose", "right_hand_pose", "jaw_pose", "leye_pose",
+                   "reye_pose", "expression", "transl")   # amav_smplx_terms.term[k]; 1..7 are losses.ROTATION_KEYS
+SMPLX_PART_NAMES = ("betas_mse", "betas_prior") + tuple(k + "_geo" for k in SMPLX_TERM_KEYS[1:8]) + (
+    "expression_l1", "expression_prior", "transl_smoothl1")
+SmplxTerm, SmplxTerms, SmplxGrads = (_lib.STRUCTS["amav_smplx_" + n] for n in ("term", "terms", "grads"))
+assert len(SMPLX_TERM_KEYS) == _lib.DEFINES["AMAV_SMPLX_TERMS"] and len(SMPLX_PART_NAMES) == _lib.DEFINES["AMAV_SMPLX_PARTS"]
+
+
+def _rot6d_rows(d6, what):
+    """d6 [..., 6] float32 on the device -> (tensor read in place, n, row stride): the leading axes must fold into one
+    stride and the last be dense (a [B,55,6] view of a wider buffer is); anything else is copied."""
+    _need(d6, f"{what}: d6")
+    if d6.dim() < 1 or d6.shape[-1] != 6:
+        raise AmavError(f"{what}: expected d6 [..., 6], got {tuple(d6.shape)}")
+    rows = _fold(d6, d6.dim() - 1)
+    if rows is None:
+        d6 = d6.contiguous()
+        rows = (d6.numel() // 6, 6)
+    return d6, rows[0], rows[1]
+
+
+def _fold(t, k):
+    """(frames, frame stride) when axes k.. of t are dense and axes ..k fold into one stride, else None."""
+    want = 1
+    for size, stride in zip(reversed(t.shape[k:]), reversed(t.stride()[k:])):
+        if size != 1 and stride != want:
+            return None
+        want *= size
+    lead = [(size, stride) for size, stride in zip(t.shape[:k], t.stride()[:k]) if size != 1]
+    frames = math.prod(t.shape[:k])
+    if not lead or frames == 0:
+        return frames, want
+    for (_, outer), (size, inner) in zip(lead, lead[1:]):
+        if outer != size * inner:
+            return None
+    return frames, lead[-1][1]
+
+
+def rot6d_to_axis_angle(d6):
+    """d6 [..., 6] -> axis-angle [..., 3] (contiguous): smplx_decoder.matrix_to_axis_angle(rotation_6d_to_matrix(d6))
+    branch for branch, one lane per rotation, one launch (amav_rot6d_to_axis_angle)."""
+    d6, n, stride = _rot6d_rows(d6, "rot6d_to_axis_angle")
+    aa = torch.empty(*d6.shape[:-1], 3, device=d6.device)
+    _call("amav_rot6d_to_axis_angle", n, d6.data_ptr(), stride, aa.data_ptr())
+    return aa
+
+
+def rot6d_to_axis_angle_backward(d6, grad_aa):
+    """Gradient of rot6d_to_axis_angle with respect to d6, [..., 6] contiguous, for grad_aa [..., 3]: one launch that
+    recomputes the forward from d6 (nothing is saved) and takes the forward's own branches."""
+    d6, n, stride = _rot6d_rows(d6, "rot6d_to_axis_angle_backward")
+    grad_aa = _contig(grad_aa, "rot6d_to_axis_angle_backward: grad_aa")
+    if tuple(grad_aa.shape) != (*d6.shape[:-1], 3):
+        raise AmavError(f"rot6d_to_axis_angle_backward: grad_aa {tuple(grad_aa.shape)} for d6 {tuple(d6.shape)}")
+    grad_d6 = torch.empty(d6.shape, device=d6.device)
+    _call("amav_rot6d_to_axis_angle_backward", n, d6.data_ptr(), stride, grad_aa.data_ptr(), grad_d6.data_ptr())
+    return grad_d6
+
+
+class _Rot6dToAxisAngle(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, d6):
+        ctx.save_for_backward(d6)
+        return rot6d_to_axis_angle(d6)
+
+    @staticmethod
+    def backward(ctx, grad_aa):
+        return rot6d_to_axis_angle_backward(ctx.saved_tensors[0], grad_aa.float())
+
+
+def rot6d_to_axis_angle_differentiable(d6):
+    """rot6d_to_axis_angle under autograd (what SMPLXDecoder.forward runs with AMAV_SMPLX_PARAMS=hip)."""
+    _rot6d_rows(d6, "rot6d_to_axis_angle_differentiable")
+    return _Rot6dToAxisAngle.apply(d6)
+
+
+def _smplx_terms(pred, gt, what):
+    """pred, gt: dicts over SMPLX_TERM_KEYS (a key missing from either: the term is absent) of float32 device tensors
+    of one shape per key -> (amav_smplx_terms, the tensors it points into, {key: pred shape}).  Both sides are read in
+    place where one split into (frames, dense items of a frame) fits both; otherwise they are copied."""
+    terms, keep, shapes = SmplxTerms(), [], {}
+    for k, key in enumerate(SMPLX_TERM_KEYS):
+        if key not in pred or key not in gt:
+            continue
+        p, g = _need(pred[key], f"{what}: pred[{key}]"), _need(gt[key], f"{what}: gt[{key}]")
+        if p.shape != g.shape or p.device != g.device:
+            raise AmavError(f"{what}: pred[{key}] {tuple(p.shape)} on {p.device}, gt[{key}] {tuple(g.shape)} on {g.device}")
+        width = 3 if 1 <= k <= 7 else 1
+        if width == 3 and (p.dim() < 1 or p.shape[-1] != 3):
+            raise AmavError(f"{what}: {key} {tuple(p.shape)}: the last dimension must be 3")
+        shapes[key] = p.shape
+        fit = None
+        for split in range(p.dim() - (width == 3) + 1):
+            fp, fg = _fold(p, split), _fold(g, split)
+            if fp is not None and fg is not None:
+                fit = (fp[0], math.prod(p.shape[split:]) // width, fp[1], fg[1])
+                break
+        if fit is None:
+            p, g = p.contiguous(), g.contiguous()
+            fit = (1, p.numel() // width, p.numel(), g.numel())
+        keep += [p, g]
+        terms.term[k] = SmplxTerm(p.data_ptr(), g.data_ptr(), *fit)
+    return terms, keep, shapes
+
+
+def smplx_param_loss_forward(pred, gt):
+    """parts [12] of losses.smplx_param_loss(pred, gt) in SMPLX_PART_NAMES order (the means; 0 for an absent key), by
+    amav_smplx_param_loss_forward: one launch at the training sizes, fixed-order sums, bitwise the same on every run.
+    pred[k], gt[k]: float32 device tensors of one shape, slices of the decoder's [F,55,3] included, read in place."""
+    terms, keep, _ = _smplx_terms(pred, gt, "smplx_param_loss_forward")
+    device = keep[0].device if keep else torch.device("cuda")
+    parts = torch.empty(len(SMPLX_PART_NAMES), device=device)
+    nbytes = _lib.lib().amav_smplx_param_loss_workspace_bytes(ctypes.byref(terms))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
+    _call("amav_smplx_param_loss_forward", ctypes.byref(terms), parts.data_ptr(), ws.data_ptr() if nbytes else None, nbytes)
+    return parts
+
+
+def smplx_param_loss_backward(pred, gt, grad_parts, wanted=None):
+    """{key: gradient of sum(grad_parts * parts) with respect to pred[key], contiguous, pred[key]'s shape} for the keys
+    in `wanted` (None: every present key); grad_parts [12] stays on the device.  One launch, every element written
+    once, the gates replayed from the forward's arithmetic; gt gets no gradient."""
+    terms, keep, shapes = _smplx_terms(pred, gt, "smplx_param_loss_backward")
+    grad_parts = _contig(grad_parts, "smplx_param_loss_backward: grad_parts")
+    if grad_parts.numel() != len(SMPLX_PART_NAMES):
+        raise AmavError(f"smplx_param_loss_backward: {grad_parts.numel()} gradients for {len(SMPLX_PART_NAMES)} parts")
+    grads, out = SmplxGrads(), {}
+    for k, key in enumerate(SMPLX_TERM_KEYS):
+        if key in shapes and (wanted is None or key in wanted):
+            out[key] = torch.empty(shapes[key], device=grad_parts.device)
+            grads.grad[k] = out[key].data_ptr()
+    _call("amav_smplx_param_loss_backward", ctypes.byref(terms), grad_parts.data_ptr(), ctypes.byref(grads))
+    return out
+
+
+class _SmplxParamLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, keys, *tensors):
+        pred, gt = dict(zip(keys, tensors[:len(keys)])), dict(zip(keys, tensors[len(keys):]))
+        ctx.keys = keys
+        ctx.save_for_backward(*tensors)
+        return smplx_param_loss_forward(pred, gt)
+
+    @staticmethod
+    def backward(ctx, grad_parts):
+        keys, tensors = ctx.keys, ctx.saved_tensors
+        pred, gt = dict(zip(keys, tensors[:len(keys)])), dict(zip(keys, tensors[len(keys):]))
+        wanted = [k for i, k in enumerate(keys) if ctx.needs_input_grad[1 + i]]
+        grads = smplx_param_loss_backward(pred, gt, grad_parts.float(), wanted)
+        return (None, *(grads.get(k) for k in keys), *(None for _ in keys))
+
+
+def smplx_param_loss_differentiable(pred, gt):
+    """parts [12] (SMPLX_PART_NAMES order) of losses.smplx_param_loss under autograd: one Function over every present
+    key, so whatever weights the caller puts on the parts, the backward to all pred tensors is one launch that reads
+    grad_parts on the device.  The targets must not require a gradient."""
+    keys = tuple(k for k in SMPLX_TERM_KEYS if k in pred and k in gt)
+    _smplx_terms(pred, gt, "smplx_param_loss_differentiable")
+    if torch.is_grad_enabled() and any(gt[k].requires_grad for k in keys):
+        raise AmavError("smplx_param_loss_differentiable: a target requires a gradient; only pred receives one")
+    return _SmplxParamLoss.apply(keys, *(pred[k] for k in keys), *(gt[k] for k in keys))
+
 # ---------------------------------------------------------------------------------------------- stage-1 reductions
 def cell_segments(cell_of, cells):
     """cell_of int [..., N] (cell of every point) -> (order int32 [..., N], seg int32 [..., cells + 1]): point ids

@@ -3,7 +3,8 @@
 Same module / parameter names as the reference (`mlp.{0,2,4}`, `dec_*`), so `smpl_decoder.*` checkpoint keys load.
 The three Linear+ReLU layers and nine small heads are plain library GEMMs (rocBLAS through torch); the rot6d ->
 axis-angle conversions replace pytorch3d.transforms (absent) with batched torch ops on the device, all 55 joints
-of all frames in one pass instead of the reference's nine separate conversions.
+of all frames in one pass instead of the reference's nine separate conversions.  AMAV_SMPLX_PARAMS=hip runs that pass
+as one HIP kernel (rot6d_to_axis_angle below).
 """
 import torch
 import torch.nn as nn
@@ -44,6 +45,19 @@ def matrix_to_axis_angle(m: torch.Tensor) -> torch.Tensor:
     return quat[..., 1:] / sin_half_over_angle
 
 
+def rot6d_to_axis_angle(d6: torch.Tensor) -> torch.Tensor:
+    """matrix_to_axis_angle(rotation_6d_to_matrix(d6)): the two statements above, or with AMAV_SMPLX_PARAMS=hip (read
+    per call) the same conversion as one HIP launch forward and one backward (ops.rot6d_to_axis_angle_differentiable;
+    csrc/smplx_params.hip), which needs float32 on the device."""
+    from .losses import smplx_params_path
+
+    if smplx_params_path() == "hip":
+        from . import ops
+
+        return ops.rot6d_to_axis_angle_differentiable(d6)
+    return matrix_to_axis_angle(rotation_6d_to_matrix(d6))
+
+
 class SMPLXDecoder(nn.Module):
     def __init__(self, cfg=None):
         super().__init__()
@@ -75,7 +89,7 @@ class SMPLXDecoder(nn.Module):
         # all 55 rotations in one conversion: root(1) body(21) lhand(15) rhand(15) jaw leye reye
         d6 = torch.cat([self.dec_body_root_pose(feat), self.dec_body_pose(feat), self.dec_hand_pose(feat),
                         self.dec_face_jaw_pose(feat), self.dec_leye_pose(feat), self.dec_reye_pose(feat)], dim=1)
-        aa = matrix_to_axis_angle(rotation_6d_to_matrix(d6.reshape(B, 55, 6)))
+        aa = rot6d_to_axis_angle(d6.reshape(B, 55, 6))
         return {
             "betas": self.dec_body_shape(feat),
             "transl": self.dec_transl(feat),

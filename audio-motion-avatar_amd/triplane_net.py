@@ -452,13 +452,15 @@ class TriplaneGaussianAvatar(nn.Module):
         views, and the test views from the same Gaussians (render_multi_view), and returns (total, parts) with
 
             total = l1_train + 0.1 * ssim_train + (l1_test + 0.1 * ssim_test)
-                    + 0.01 * (smplx_param_loss(pred_smpl_1, smpl_params)[0] + smplx_param_loss(pred_smpl_2, smpl_params)[0])
+                    + 0.01 * (training_smplx_term(pred_smpl_1, smpl_params) + training_smplx_term(pred_smpl_2, smpl_params))
 
         ref_images / test_images [B,T,3,H,W] in [0,1], smpl_params the ground-truth dict of [B,T,...], cam_params /
         test_cam_params the camera dicts, image_tokens [B,T,4096,image_feature_dim] (the Sapiens output, from the
         caller as for forward).  parts: l1_train, ssim_train (= 1 - ssim), l1_test, ssim_test (0 without test images),
         loss_smplx.  Call total.backward() for the gradients.  The image terms come from the fused HIP loss
         (losses.image_losses); AMAV_IMAGE_LOSS=library, read per call, keeps the library's l1_loss and ssim.
+        training_smplx_term is smplx_param_loss(...)[0], or with AMAV_SMPLX_PARAMS=hip (read per call) the fused
+        losses.smplx_param_losses.
 
         Every stage-1 parameter receives a gradient: ImageFeature.feature_reducer, the point network (fc_pos, blocks,
         fc_c) and vertex_emb through the HIP backwards of the encoder's reductions, the SMPL-X predictor (smpl_tokens,
@@ -466,7 +468,7 @@ class TriplaneGaussianAvatar(nn.Module):
         and the renderer's decoder heads.  The reference renders with the ground-truth parameters, so LBS sits outside
         the graph here.  The step runs in the module's current mode; .eval() and .train() differ only in the
         transformers' dropout, which is 0 at the reference's settings."""
-        from .losses import smplx_param_loss, training_image_terms
+        from .losses import training_image_terms, training_smplx_term
         from .renderer import render_multi_view
 
         rendered, gaussians, _, _, pred_smpl_1, pred_smpl_2, _ = self(ref_images, smpl_params, cam_params, image_tokens)
@@ -480,7 +482,7 @@ class TriplaneGaussianAvatar(nn.Module):
         else:
             parts["l1_test"] = torch.zeros((), device=rendered.device)
             parts["ssim_test"] = torch.zeros((), device=rendered.device)
-        parts["loss_smplx"] = smplx_param_loss(pred_smpl_1, smpl_params)[0] + smplx_param_loss(pred_smpl_2, smpl_params)[0]
+        parts["loss_smplx"] = training_smplx_term(pred_smpl_1, smpl_params) + training_smplx_term(pred_smpl_2, smpl_params)
         total = (parts["l1_train"] + 0.1 * parts["ssim_train"] + (parts["l1_test"] + 0.1 * parts["ssim_test"])
                  + 0.01 * parts["loss_smplx"])
         return total, parts

@@ -1631,6 +1631,66 @@ int amav_png_encode(int num_frames, int height, int width, const void *frames_de
                     uint8_t *stream_out_dev, int64_t capacity, int64_t *frame_offsets_dev, int32_t *status_dev,
                     void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * The SMPL-X parameter term of the two training steps (csrc/smplx_params.hip): the decoder's
+ * rot6d -> axis-angle conversion and losses.smplx_param_loss, one forward and one backward launch each.
+ *
+ * amav_rot6d_to_axis_angle: aa [n,3] (contiguous) = matrix_to_axis_angle(rotation_6d_to_matrix(d6)) of
+ * smplx_decoder.py, branch for branch: Gram-Schmidt with F.normalize's max(||x||, 1e-12), the four quaternion
+ * candidates of sqrt(max(., 0)), the one with the largest |q| divided by 2 max(|q|, 0.1), flipped to w >= 0,
+ * angle = 2 atan2(||xyz||, w), and xyz / (sin(angle / 2) / angle) with the series 1/2 - angle^2 / 48 below 1e-6.
+ * Row i of d6 is the six floats at d6[i * row_stride] (floats; a [B,55,6] view of a wider buffer is read in place).
+ * amav_rot6d_to_axis_angle_backward: grad_d6 [n,6] (contiguous) for grad_aa [n,3]; the forward is recomputed from d6,
+ * nothing is saved, and every branch (candidate, flip, small angle, the clamps' gates, the zero derivative of the
+ * square root of a non-positive number) is the one the forward takes on the same d6.
+ * Both refuse a negative n and NULL pointers (AMAV_ERR_INVALID_ARG, before any launch); n = 0 is AMAV_OK and no
+ * pointer is looked at.  No allocation and no host synchronisation. */
+int amav_rot6d_to_axis_angle(int n, const float *d6_dev, int64_t row_stride, float *aa_dev, void *stream);
+int amav_rot6d_to_axis_angle_backward(int n, const float *d6_dev, int64_t row_stride, const float *grad_aa_dev,
+                                      float *grad_d6_dev, void *stream);
+/* One term of the parameter loss: `frames` blocks of `per_frame` consecutive items, frame f of pred starting at
+ * pred[f * pred_stride] (floats), of gt at gt[f * gt_stride].  An item is one float for betas, expression and transl
+ * and a rotation vector of three floats for the seven rotation keys.  So body_pose = aa[:, 1:22] of the decoder's
+ * [F,55,3] (per_frame 21, pred_stride 165) and a contiguous [B,T,21,3] target (gt_stride 63) are read in place.
+ * pred = gt = NULL: the term is absent and its parts are 0; so is a term with frames = 0 or per_frame = 0. */
+#define AMAV_SMPLX_TERMS 10
+#define AMAV_SMPLX_PARTS 12
+typedef struct amav_smplx_term {
+    const float *pred, *gt;
+    int frames, per_frame;
+    int64_t pred_stride, gt_stride; /* floats */
+} amav_smplx_term;
+/* term[0] betas, term[1..7] global_orient, body_pose, left_hand_pose, right_hand_pose, jaw_pose, leye_pose, reye_pose
+ * (losses.ROTATION_KEYS), term[8] expression, term[9] transl */
+typedef struct amav_smplx_terms {
+    amav_smplx_term term[10];
+} amav_smplx_terms;
+/* grad[k]: NULL (no gradient wanted), or [frames, per_frame] items of term k, contiguous */
+typedef struct amav_smplx_grads {
+    float *grad[10];
+} amav_smplx_grads;
+/* Bytes of the forward's workspace: 0 while one workgroup does the whole sum (no term above 4096 items, which covers
+ * every training size), else twelve doubles per workgroup (16-byte aligned); 0 as well for terms the forward
+ * refuses. */
+size_t amav_smplx_param_loss_workspace_bytes(const amav_smplx_terms *terms);
+/* parts [12], the means of losses.smplx_param_loss in this order: betas_mse, betas_prior, the seven *_geo parts,
+ * expression_l1, expression_prior, transl_smoothl1.  Geodesic part: the mean over rows of
+ * acos(clamp((tr(Rp^T Rg) - 1) / 2, -0.999, 0.999)) with R = I + sin K + (1 - cos) K K of r / angle,
+ * angle = ||r + 1e-8|| (1 - cos evaluated as 2 sin^2(angle / 2)); smooth-L1 with beta = 1.  Inputs and parts are fp32;
+ * the arithmetic and the sums in between run in double (so do the conversion's above), the sums in a fixed order with
+ * no atomics: bitwise the same on every run.  workspace: NULL is fine while the query returns 0, else
+ * AMAV_ERR_WORKSPACE when it is NULL or too small. */
+int amav_smplx_param_loss_forward(const amav_smplx_terms *terms, float *parts_dev, void *workspace_dev,
+                                  size_t workspace_bytes, void *stream);
+/* grads->grad[k] = d(sum over p of grad_parts[p] * parts[p]) / d(pred of term k), every element written exactly once;
+ * grad_parts [12] is read on the device.  The gates are the forward's: the clamp passes the gradient where
+ * -0.999 <= cos <= 0.999 and nowhere else, sign(0) = 0 for the L1 part, smooth-L1 is quadratic where |d| < 1.  The
+ * targets get no gradient.  All three entry points refuse (AMAV_ERR_INVALID_ARG, before any launch) NULL terms /
+ * parts / grads, negative counts, one NULL pointer of a pair and terms beyond 2^30 - 1 floats.  No allocation and no
+ * host synchronisation. */
+int amav_smplx_param_loss_backward(const amav_smplx_terms *terms, const float *grad_parts_dev,
+                                   const amav_smplx_grads *grads, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
